@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: Mrays/s on scene.xml at 1920x1080, depth 8, 256 spp (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -11,7 +11,11 @@ load, BVH build and upload happen before the timed region (inputs resident in HB
 steps and, for N > 1, the one RCCL reduce of the HDR framebuffer (the K steps accumulate into one HDR sum).  N > 1: one process per GPU, the 8x8 pixel tiles are
 interleaved over the ranks (strong scaling: the job is fixed, `value` = all rays of the job / max-over-ranks time).
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline line (`config` included);
+--dump-outputs DIR also writes what the timed path returned after its last step (the HDR sum the K steps accumulated, and the
+ray / path counts) as DIR/*.npy.  Everything else is measured only with --full, which adds these objects to the line:
+  serial_ms_per_render  three renders issued one at a time after the timed region (N = 1)
+  extra_workloads       untimed extras, one serial render each (N = 1; --no-extra-workloads skips them)
   roofline      dominant kernel vs the two roofs it can be measured against: vector-ALU instruction issue (wave64
                 instructions x 2 cycles on a SIMD-32) and measured HBM traffic; `frac` is the larger of the two and
                 cannot exceed 1.  The per-ray instruction / byte figures come from the committed rocprofv3 --pmc passes of
@@ -20,7 +24,8 @@ Rank 0 prints ONE JSON line.  Extra objects:
                 The SURVEY.md 8(d) algorithmic bytes per ray are kept under `algorithmic` (they price LDS-served BVH
                 reads as HBM and so exceed the HBM peak: not a bound).
   cpu_baseline  the CPU oracle (this repo's restatement of the reference algorithm; the reference has no CPU
-                path) timed on the host cores on a bounded sample of the same workload (rank 0, N = 1 only)
+                path) timed on the host cores on a bounded sample of the same workload (rank 0, N = 1 only;
+                --no-cpu-baseline skips it)
 """
 import argparse
 import json
@@ -62,7 +67,36 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-workloads", action="store_true",
                     help="skip the untimed extras (Cornell box and bunny x20 at 1920x1080 x 256 spp, one serial render each)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: serial renders, the CPU baseline, the extra workloads and "
+                         "the roofline (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the HDR sum they accumulated and the ray / path counts as DIR/*.npy")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 48 << 20   # the HDR sum is written whole up to this size (1920x1080 RGBA32F: 33 MB), a fixed pixel sample above it
+
+
+def dump_outputs(out_dir, fb, rays, paths):
+    """What a caller of the timed path receives after its last step: the HDR sum (H x W x 4 float32, the K steps accumulated, as
+    mpt_read_sum returns it) and the ray / path counts of the timed steps (mpt_get_stats).  Inputs and seeds are fixed, so two
+    builds given the same arguments can be compared file for file.  Above DUMP_LIMIT_BYTES the sum is a fixed, seeded sample of
+    pixels: hdr_sum.npy holds their RGBA rows and hdr_sum_pixels.npy their row-major pixel indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = fb.cpu().numpy().astype(np.float32, copy=False)
+    H, W = img.shape[:2]
+    pix_path = os.path.join(out_dir, "hdr_sum_pixels.npy")
+    if os.path.exists(pix_path):              # (left by an earlier, larger run: it would describe another sum)
+        os.remove(pix_path)
+    if img.nbytes > DUMP_LIMIT_BYTES:
+        n = DUMP_LIMIT_BYTES // (4 * 4 + 8)
+        pix = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        np.save(pix_path, pix.astype(np.float64))
+        img = img.reshape(H * W, 4)[pix]
+    np.save(os.path.join(out_dir, "hdr_sum.npy"), img)
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([rays, paths], dtype=np.float64))
 
 
 def counter_profile(kernel, workload):
@@ -337,13 +371,6 @@ def main():
     st = ctx.stats()
     rays_local = st["rays"]
     image_mean = (fb[..., :3].double().mean(dim=(0, 1)) / (args.steps * spp)).tolist() if rank == 0 else None
-    # untimed extra (N = 1): ONE render at a time, no overlap of consecutive steps — what a single 256-spp frame takes
-    serial_ms = []
-    if world == 1:
-        for k in range(min(3, args.steps)):
-            ctx.render(sample_begin=(args.steps + k) * spp, sample_count=spp, **kw)
-            serial_ms.append(ctx.stats()["total_ms"])
-    serial_ms = sum(serial_ms) / len(serial_ms) if serial_ms else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -353,6 +380,15 @@ def main():
         rays_total, paths_total = int(r[0].item()), int(r[1].item())
     else:
         rays_total, paths_total = rays_local, st["paths"]
+    if rank == 0 and args.dump_outputs:       # (before the serial renders below, which add to the same sum)
+        dump_outputs(args.dump_outputs, fb, rays_total, paths_total)
+    # untimed extra (--full, N = 1): ONE render at a time, no overlap of consecutive steps — what a single 256-spp frame takes
+    serial_ms = []
+    if world == 1 and args.full:
+        for k in range(min(3, args.steps)):
+            ctx.render(sample_begin=(args.steps + k) * spp, sample_count=spp, **kw)
+            serial_ms.append(ctx.stats()["total_ms"])
+    serial_ms = sum(serial_ms) / len(serial_ms) if serial_ms else None
 
     if rank == 0:
         mean = image_mean
@@ -381,7 +417,7 @@ def main():
             },
         }
         n_node, n_prim, h = 7.52, 3.59, 0.405   # SURVEY.md App. C.5 (used only if the CPU leg is skipped)
-        if world == 1 and not args.no_cpu_baseline and args.cpu_spp > 0:
+        if world == 1 and args.full and not args.no_cpu_baseline and args.cpu_spp > 0:
             ref_buffers = None
             if args.bvh != "reference":          # a second CPU figure on the reference's own tree (what the reference itself would walk)
                 sc_ref = host.Scene()
@@ -391,11 +427,12 @@ def main():
                     ref_buffers = sc_ref.buffers()
             out["cpu_baseline"], (n_node, n_prim, h) = cpu_baseline(args, buffers, P, T, ref_buffers)
         b_ray = B_QUEUE + 32.0 * n_node + 52.0 * n_prim + 32.0 * h
-        out["serial_ms_per_render"] = serial_ms
-        if world == 1 and not args.no_extra_workloads:
+        if args.full:
+            out["serial_ms_per_render"] = serial_ms
+            out["config"]["serial_mrays_per_s"] = rays_local / args.steps / serial_ms / 1e3 if serial_ms else None
+        if world == 1 and args.full and not args.no_extra_workloads:
             out["extra_workloads"] = extra_workloads(ctx, capi, host, args.depth)
-        out["config"]["serial_mrays_per_s"] = rays_local / args.steps / serial_ms / 1e3 if serial_ms else None
-        if launches and kernel_ms > 0:
+        if args.full and launches and kernel_ms > 0:
             rays_per_launch = rays_local / launches
             sec_per_launch = kernel_ms * 1e-3 / launches
             workload = {"scene": os.path.basename(args.scene), "width": W, "height": H, "spp": spp, "depth": args.depth,

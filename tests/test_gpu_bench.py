@@ -1,5 +1,5 @@
-"""bench.py end to end on the GPU box: the contract line (metric / roofline / cpu_baseline objects) at N = 1 and the
-N = 2 launch path (`python -m torch.distributed.run`, one rank per process) on the single GPU of the test box.  The
+"""bench.py end to end on the GPU box: the contract line of a plain run and the outputs it dumps, the --full line (metric /
+roofline / cpu_baseline objects) at N = 1 and the N = 2 launch path (`python -m torch.distributed.run`, one rank per process) on the single GPU of the test box.  The
 2-rank run uses gloo for the reduce (two RCCL ranks cannot share one device) and both ranks render on GPU 0; it must
 produce the same image mean as the 1-rank run because the tile shards partition the pixels."""
 import json
@@ -22,7 +22,7 @@ def last_json(text):
 
 
 def test_bench_line_single_gpu():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--cpu-spp", "2"], capture_output=True,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--full", "--cpu-spp", "2"], capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
@@ -69,6 +69,32 @@ def test_bench_line_single_gpu():
     for e in ex:                    # each extra names its own counter profile, or says that none of this build is committed
         r = e["roofline"]
         assert (r["frac"] is not None and 0.0 < r["frac"] <= 1.0 and "profiles/" in r["profile"]) or r.get("profile_stale") is True or "profile_missing" in r
+
+
+def test_plain_bench_line_is_lean_and_dumps_what_the_timed_steps_computed(tmp_path):
+    """A plain run measures only the headline; --dump-outputs writes the HDR sum of the timed steps and their ray / path counts,
+    the same bit for bit from run to run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d_out = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *SMALL, "--dump-outputs", str(d_out)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = last_json(r.stdout)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+            assert key in d, key
+        for key in ("cpu_baseline", "extra_workloads", "roofline", "serial_ms_per_render"):
+            assert key not in d, key
+        assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["config"]["paths"] == 640 * 360 * 8 * 2
+        hdr, counts = np.load(d_out / "hdr_sum.npy"), np.load(d_out / "counts.npy")
+        assert hdr.dtype == np.float32 and hdr.shape == (360, 640, 4) and not (d_out / "hdr_sum_pixels.npy").exists()
+        assert counts.dtype == np.float64 and counts.tolist() == [d["config"]["rays"], d["config"]["paths"]]
+        mean = hdr[..., :3].astype(np.float64).mean(axis=(0, 1)) / (2 * 8)
+        np.testing.assert_allclose(mean, d["config"]["image_mean_rgb"], rtol=1e-9)
+        dumps.append((hdr, counts))
+    assert np.array_equal(dumps[0][0].view(np.uint32), dumps[1][0].view(np.uint32))
+    assert np.array_equal(dumps[0][1], dumps[1][1])
 
 
 def test_bench_two_ranks_share_the_gpu_and_agree_with_one_rank():

@@ -46,7 +46,7 @@ if os.path.exists(trace):
     timed = [x for x in launches if x["what"] == "timed step"]
     first = launches.index(timed[0]) if timed else 0
     ends = [launches[first - 1]["end_ms"]] + [x["end_ms"] for x in timed] if timed and first > 0 else []
-    json.dump({"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps %d --warmup %d" % (K, Wm),
+    json.dump({"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps %d --warmup %d" % (K, Wm),
                "note": "ms = End - Start of the kernel trace.  The timed steps are submitted while the launch before them is still running (mpt_render_async: "
                        "a launch is submitted as soon as the one before it is fully resident, DESIGN.md 6), and the trace's Start is the DISPATCH of the "
                        "launch, not the start of its first wave: for those launches End - Start includes the wait behind the resident kernel.  What the "
