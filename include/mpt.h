@@ -283,6 +283,51 @@ int mpt_reduce_sum(mpt_comm* comm, int root);   /* waits for the renders in flig
 int mpt_comm_destroy(mpt_comm* comm);
 const char* mpt_comm_last_error(const mpt_comm* comm);
 
+/* ---- denoiser: first-hit guide buffers + an edge-avoiding a-trous filter (Dammertz et al. 2010) --------------------------
+ * No reference counterpart (the reference presents the raw running mean, Fragment.metal:62-69).  Guide buffers: one ray per pixel
+ * through the pixel centre (mpt_draw's primary ray without jitter), traced on the device with the scene, uniforms and size of the
+ * context; they are traced again when stale (after mpt_resize, mpt_upload_scene, mpt_build_and_upload, or new uniforms whose
+ * cameraPosition, viewportU/V, firstPixelPosition or screenSize differ).  Per pixel: the first hit's albedo and distance t
+ * along the normalised ray, the shading normal facing the ray, a class (0 surface, 1 emissive material: emissionPower > 0,
+ * 2 miss) and the caller's primitive id (-1 on a miss; a miss has albedo 0, t = +inf, normal 0).  Neither the guide pass nor
+ * the filter touches the HDR sum, the frame targets or mpt_stats.
+ *
+ * The filter (tests/denoise_ref.py restates it in numpy), colour c = sum / samples (SUM) or the current mpt_draw target
+ * (FRAME); pixels of class 1 / 2 are returned bit for bit and are never taps; alpha is c's alpha.  x0 = c / max(albedo, 1e-3);
+ * level i = 0..N-1, step s = 2^i, taps q = p + s (dx, dy), dx, dy in -2..2 (dy outer), kernel h = {1, 4, 6, 4, 1} / 16:
+ *   w(q) = max(0, n_p . n_q)^sigma_normal * exp(-|t_p - t_q| / (sigma_depth * t_p * s)) * exp(-|l_p - l_q| / (sigma_luminance * 2^-i))
+ * (l = Rec. 709 luminance of level i's x; the centre's w is 1), taps outside the image or of class != 0 skipped,
+ * x_{i+1}(p) = sum h[dx] h[dy] w x_q / sum h[dx] h[dy] w; output = x_N * max(albedo, 1e-3), unclamped.  N = 0: the input.
+ * Defaults (a sigma <= 0 or iterations < 0 selects them): chosen by the sweep of profiles/r06_denoise_sweep.txt.          */
+enum { MPT_DENOISE_SUM = 0,     /* the HDR sum divided by samples                                                          */
+       MPT_DENOISE_FRAME = 1 }; /* the current mpt_draw target (the running mean)                                          */
+#define MPT_DENOISE_DEFAULT_ITERATIONS 3
+#define MPT_DENOISE_MAX_ITERATIONS 8
+#define MPT_DENOISE_DEFAULT_SIGMA_LUMINANCE 8.0f
+#define MPT_DENOISE_DEFAULT_SIGMA_NORMAL 32.0f
+#define MPT_DENOISE_DEFAULT_SIGMA_DEPTH 0.25f
+typedef struct mpt_denoise_params {
+    int32_t source;           /* MPT_DENOISE_* (mpt_denoise; mpt_denoise_image filters the colour it is given)              */
+    uint32_t samples;         /* SUM: samples per pixel the sum holds (> 0)                                                 */
+    int32_t iterations;       /* levels N, 0..MPT_DENOISE_MAX_ITERATIONS; < 0 = MPT_DENOISE_DEFAULT_ITERATIONS               */
+    float sigma_luminance;    /* <= 0: the defaults above                                                                   */
+    float sigma_normal;
+    float sigma_depth;
+} mpt_denoise_params;
+
+/* The guide buffers (traced first if stale), W*H*4 floats each: albedo_depth = (albedo rgb, t), normal_class = (normal, class);
+ * prim (W*H int32, may be NULL) = primitive ids.                                                                             */
+int mpt_read_aovs(mpt_ctx* ctx, float* albedo_depth, float* normal_class, int32_t* prim);
+/* Waits for the renders queued and in flight (reporting a failed mpt_render_async), refreshes stale guides, filters; the
+ * result stays on the device (ctx's stream) for mpt_read_denoised / mpt_denoised_buffer (RGBA32F, W*H*4 floats).            */
+int mpt_denoise(mpt_ctx* ctx, const mpt_denoise_params* params);
+int mpt_read_denoised(mpt_ctx* ctx, float* rgba_host);
+int mpt_denoised_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);
+/* The same filter kernels on caller arrays (host, W*H*4 floats each; the unit-test hook): color is c itself (source and
+ * samples are ignored), albedo_depth / normal_class as mpt_read_aovs returns them; a surface's t must be > 0.  No scene needed. */
+int mpt_denoise_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const float* albedo_depth,
+                      const float* normal_class, const mpt_denoise_params* params, float* rgba_out);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

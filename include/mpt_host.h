@@ -71,6 +71,10 @@ int mpt_renderer_read_sum(mpt_renderer* r, float* rgba);
 int mpt_renderer_clear_sum(mpt_renderer* r);
 int mpt_renderer_uniforms(mpt_renderer* r, mpt_uniforms* out);
 int mpt_renderer_stats(mpt_renderer* r, mpt_stats* out);
+/* mpt_denoise + mpt_read_denoised of what was rendered last: the FRAME source after mpt_renderer_draw, the SUM after
+ * mpt_renderer_render_batch (params->source is ignored; params->samples = 0 means the samples rendered since the sum was
+ * last cleared).  rgba: W*H*4 floats.                                                                                  */
+int mpt_renderer_denoise(mpt_renderer* r, const mpt_denoise_params* params, float* rgba);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 

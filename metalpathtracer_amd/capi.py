@@ -28,8 +28,13 @@ SYMBOLS = (
     "mpt_read_frame", "mpt_read_sum", "mpt_write_sum", "mpt_get_stats", "mpt_reset_stats", "mpt_stream", "mpt_synchronize",
     "mpt_trace_rays", "mpt_trace_rays_ordered", "mpt_accel_info", "mpt_kat_pcg", "mpt_kat_philox", "mpt_kat_sincos", "mpt_kat_rcp",
     "mpt_build_bvh", "mpt_build_and_upload", "mpt_download_bvh", "mpt_gpu_leaf_max", "mpt_build_info", "mpt_scene_digest", "mpt_comm_unique_id", "mpt_comm_create_all", "mpt_comm_create_rank", "mpt_reduce_sum", "mpt_comm_destroy",
-    "mpt_comm_last_error",
+    "mpt_comm_last_error", "mpt_read_aovs", "mpt_denoise", "mpt_read_denoised", "mpt_denoised_buffer", "mpt_denoise_image",
 )
+
+DENOISE_SUM, DENOISE_FRAME = 0, 1
+DENOISE_MAX_ITERATIONS = 8
+# include/mpt.h MPT_DENOISE_DEFAULT_* (a sigma <= 0 / iterations < 0 selects them on the device too)
+DENOISE_DEFAULTS = dict(iterations=3, sigma_luminance=8.0, sigma_normal=32.0, sigma_depth=0.25)
 
 
 class MptError(RuntimeError):
@@ -79,6 +84,17 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("source", C.c_int32), ("samples", C.c_uint32), ("iterations", C.c_int32),
+                ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
+def denoise_params(source=DENOISE_SUM, samples=0, iterations=-1, sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0):
+    """mpt_denoise_params; iterations < 0 and sigmas <= 0 mean the defaults of include/mpt.h."""
+    return DenoiseParams(int(source), int(samples), int(iterations), float(sigma_luminance), float(sigma_normal),
+                         float(sigma_depth))
 
 
 _lib = None
@@ -164,6 +180,11 @@ def load():
     L.mpt_kat_sincos.argtypes = [vp, fp, C.c_uint64, fp, fp]
     L.mpt_kat_rcp.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.mpt_async_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.mpt_read_aovs.argtypes = [vp, fp, fp, ip]
+    L.mpt_denoise.argtypes = [vp, C.POINTER(DenoiseParams)]
+    L.mpt_read_denoised.argtypes = [vp, fp]
+    L.mpt_denoised_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_denoise_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, fp, C.POINTER(DenoiseParams), fp]
     _lib = L
     return L
 
@@ -422,6 +443,43 @@ class Context:
         self._chk(self.L.mpt_accel_info(self.h, out), "mpt_accel_info")
         keys = ("ordered_ok", "nodes", "depth", "lds_nodes", "always_spheres", "reference_leaves", "lds_prims", "auto_pipeline")
         return dict(zip(keys, [int(v) for v in out]))
+
+    def read_aovs(self):
+        """First-hit guide buffers (traced on the device if stale): (albedo_depth [H,W,4], normal_class [H,W,4], prim [H,W])."""
+        ad = np.empty((self.height, self.width, 4), np.float32)
+        nc = np.empty((self.height, self.width, 4), np.float32)
+        prim = np.empty((self.height, self.width), np.int32)
+        self._chk(self.L.mpt_read_aovs(self.h, _fp(ad), _fp(nc), _ip(prim)), "mpt_read_aovs")
+        return ad, nc, prim
+
+    def denoise(self, **kw):
+        """mpt_denoise: filter the sum (source=DENOISE_SUM, samples=spp) or the draw target (DENOISE_FRAME) on the device."""
+        p = denoise_params(**kw)
+        self._chk(self.L.mpt_denoise(self.h, C.byref(p)), "mpt_denoise")
+
+    def read_denoised(self):
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._chk(self.L.mpt_read_denoised(self.h, _fp(out)), "mpt_read_denoised")
+        return out
+
+    def denoised_buffer(self):
+        """(device pointer, bytes) of the last denoise result, for zero-copy use after synchronize()."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_denoised_buffer(self.h, C.byref(p), C.byref(n)), "mpt_denoised_buffer")
+        return p.value, n.value
+
+    def denoise_image(self, color, albedo_depth, normal_class, **kw):
+        """The filter kernels on caller arrays [H,W,4] (color is filtered as given; source / samples are ignored)."""
+        c = np.ascontiguousarray(color, np.float32)
+        ad = np.ascontiguousarray(albedo_depth, np.float32)
+        nc = np.ascontiguousarray(normal_class, np.float32)
+        if c.ndim != 3 or c.shape[2] != 4 or ad.shape != c.shape or nc.shape != c.shape:
+            raise ValueError("denoise_image: color, albedo_depth and normal_class must be [H, W, 4] arrays of one shape")
+        H, W = c.shape[:2]
+        out = np.empty_like(c)
+        p = denoise_params(**kw)
+        self._chk(self.L.mpt_denoise_image(self.h, W, H, _fp(c), _fp(ad), _fp(nc), C.byref(p), _fp(out)), "mpt_denoise_image")
+        return out
 
     def kat_pcg(self, seeds):
         s = np.ascontiguousarray(seeds, np.uint32)

@@ -162,6 +162,7 @@ void Renderer::buildBuffers() {
 void Renderer::buildTextures() {
     check(mpt_resize(ctx_, static_cast<uint32_t>(Camera::screenSize.x), static_cast<uint32_t>(Camera::screenSize.y)),
           "mpt_resize");
+    sumSamples_ = 0;
 }
 
 void Renderer::recalculateViewport() {
@@ -218,6 +219,7 @@ void Renderer::draw(OffscreenView* /*view*/) {
     p.sample_count = 1;
     if (p.rng_mode == MPT_RNG_PHILOX) p.sample_begin = static_cast<uint32_t>(uniforms_.frameCount);
     check(mpt_draw(ctx_, &p), "mpt_draw");  // swaps the accumulation targets, then launches
+    lastSource_ = MPT_DENOISE_FRAME;
 }
 
 void Renderer::drawableSizeWillChange(OffscreenView* view, DrawableSize size) {
@@ -247,6 +249,8 @@ int Renderer::renderBatch(uint32_t sampleBegin, uint32_t sampleCount) {
     p.sample_count = sampleCount;
     int rc = mpt_render(ctx_, &p);
     check(rc, "mpt_render");
+    lastSource_ = MPT_DENOISE_SUM;
+    sumSamples_ += sampleCount;
     return rc;
 }
 
@@ -256,7 +260,19 @@ void Renderer::readSum(std::vector<float>& rgba) {
     check(mpt_read_sum(ctx_, rgba.data()), "mpt_read_sum");
 }
 
-void Renderer::clearSum() { check(mpt_clear_sum(ctx_), "mpt_clear_sum"); }
+void Renderer::clearSum() {
+    check(mpt_clear_sum(ctx_), "mpt_clear_sum");
+    sumSamples_ = 0;
+}
+
+void Renderer::denoise(const mpt_denoise_params& p, std::vector<float>& rgba) {
+    mpt_denoise_params q = p;
+    q.source = lastSource_;
+    if (q.source == MPT_DENOISE_SUM && q.samples == 0) q.samples = sumSamples_;
+    check(mpt_denoise(ctx_, &q), "mpt_denoise");
+    rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_denoised(ctx_, rgba.data()), "mpt_read_denoised");
+}
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     if (rgba.size() != n) throw std::runtime_error("writeSum: the array does not have the size of the frame");

@@ -58,6 +58,9 @@ public:
     void writeSum(const std::vector<float>& rgba);   // checkpoint / resume: the inverse of readSum (mpt_write_sum)
     void clearSum();
     mpt_stats stats();
+    // mpt_denoise of what was rendered last: the draw() target after draw(), the sum after renderBatch() (samples = p.samples, or
+    // when 0 the samples added since the sum was last cleared); rgba = the W*H*4 denoised floats
+    void denoise(const mpt_denoise_params& p, std::vector<float>& rgba);
 
 private:
     void check(int status, const char* where);
@@ -72,7 +75,9 @@ private:
     uint32_t hostSeed_ = 92407235u;  // R/Renderer/Renderer.cpp:32
     bool sceneUploaded_ = false;
     int buildMode_ = BUILD_REFERENCE;
-    bool deviceBuild_ = false, deviceDirty_ = false;   // BUILD_GPU: mpt_build_and_upload, no tree on the host
+    bool deviceBuild_ = false, deviceDirty_ = false;
+    int lastSource_ = MPT_DENOISE_SUM;   // what denoise() filters: the source of the last draw() / renderBatch()
+    uint32_t sumSamples_ = 0;            // samples renderBatch() added since the sum was cleared   // BUILD_GPU: mpt_build_and_upload, no tree on the host
 };
 
 }  // namespace MetalCppPathTracer

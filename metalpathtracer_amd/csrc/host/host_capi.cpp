@@ -269,6 +269,14 @@ int mpt_renderer_stats(mpt_renderer* r, mpt_stats* out) {
     if (!r || !out) return MPT_ERR_INVALID_ARG;
     return mpt_get_stats(r->r->context(), out);
 }
+int mpt_renderer_denoise(mpt_renderer* r, const mpt_denoise_params* p, float* rgba) {
+    if (!r || !p || !rgba) return MPT_ERR_INVALID_ARG;
+    std::vector<float> img;
+    GUARD({
+        r->r->denoise(*p, img);
+        std::memcpy(rgba, img.data(), img.size() * sizeof(float));
+    });
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

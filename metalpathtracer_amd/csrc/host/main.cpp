@@ -41,7 +41,9 @@ static void usage() {
         "           [--pipeline auto|ordered|wavelocal|wavefront|megakernel] [--frames N] [--device 0] [--out image.pfm|image.ppm]\n"
         "           [--camera-pos x,y,z] [--camera-dir x,y,z] [--camera-up x,y,z] [--vfov degrees]\n"
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
-        "           [--checkpoint FILE] [--resume FILE]\n"
+        "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]]\n"
+        "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
+        "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
         "                    the drop-in behaviour) or auto (default for batch renders: the tree of every scene is built on the\n"
         "                    device, mpt_build_and_upload, with leaves of <= 6 primitives below 8192 primitives and <= 2 from there\n"
@@ -107,7 +109,8 @@ static bool applyInputLine(const std::string& line, int* repeat) {
 // Replays a camera path: one draw() per frame with that frame's inputs, every frame written to outDir.  Returns the
 // number of frames, -1 on error.  Prints one JSON line per frame (camera, frameCount) for checking against the reference's
 // protocol (a camera change resets the accumulation and reseeds, R/Renderer/Renderer.cpp:255-257).
-static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& path, const std::string& outDir) {
+static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& path, const std::string& outDir,
+                          const mpt_denoise_params* dn) {
     FILE* f = std::fopen(path.c_str(), "r");
     if (!f) {
         std::fprintf(stderr, "cannot open camera path %s\n", path.c_str());
@@ -132,6 +135,7 @@ static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& p
             n = repeat;
             r.draw(&view);
             r.readFrame(&view);
+            if (dn) r.denoise(*dn, view.rgba);
             const mpt_uniforms& u = r.uniforms();
             char name[64];
             std::snprintf(name, sizeof name, "/frame_%04d.ppm", frame);
@@ -151,7 +155,7 @@ static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& p
 // scene, renders its interleaved tile shard asynchronously, and ONE ncclReduce(sum) lands the HDR sum on the first GPU.
 static int renderOnSeveralGpus(const std::string& scene, const std::string& assetRoot, const std::string& out, int width, int height,
                                int spp, const std::vector<int>& devices, int bvh, mpt_render_params prm, const float* camPos, const float* camDir,
-                               const float* camUp, float vfov) {
+                               const float* camUp, float vfov, const mpt_denoise_params* dn) {
     std::vector<std::unique_ptr<Renderer>> rs;
     mpt_comm* comm = nullptr;
     const int gpus = static_cast<int>(devices.size());
@@ -195,9 +199,16 @@ static int renderOnSeveralGpus(const std::string& scene, const std::string& asse
                     sec > 0 ? rays / sec / 1e6 : 0.0);
         if (!out.empty()) {
             std::vector<float> img;
-            rs[0]->readSum(img);
+            float scale = 1.0f / (float)spp;
+            if (dn) {   // the guide pass and the filter run on the root, over the reduced sum
+                mpt_denoise_params q = *dn;
+                q.samples = (uint32_t)spp;
+                rs[0]->denoise(q, img);
+                scale = 1.0f;
+            } else {
+                rs[0]->readSum(img);
+            }
             bool ppm = out.size() > 4 && out.substr(out.size() - 4) == ".ppm";
-            const float scale = 1.0f / (float)spp;
             if (ppm ? mpt_write_ppm(out.c_str(), img.data(), width, height, scale, 2.2f) : mpt_write_pfm(out.c_str(), img.data(), width, height, scale))
                 throw std::runtime_error("cannot write " + out);
         }
@@ -223,6 +234,10 @@ int main(int argc, char** argv) {
     prm.rng_mode = MPT_RNG_PHILOX;
     prm.shard_count = 1;
     prm.pipeline = MPT_PIPE_AUTO;
+    bool denoise = false;
+    mpt_denoise_params dnp;
+    std::memset(&dnp, 0, sizeof dnp);
+    dnp.iterations = -1;   // (defaults of include/mpt.h)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -259,6 +274,8 @@ int main(int argc, char** argv) {
         else if (a == "--out") out = next();
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
         else if (a == "--bvh") {
             const char* v = next();
             bvh = std::strcmp(v, "reference") == 0 ? Renderer::BUILD_REFERENCE
@@ -305,7 +322,7 @@ int main(int argc, char** argv) {
         if (deviceList.empty())
             for (int g = 0; g < gpus; ++g) deviceList.push_back(device + g);
         return renderOnSeveralGpus(scene, assetRoot, out, width, height, spp, deviceList, bvh, prm, havePos ? camPos : nullptr, haveDir ? camDir : nullptr,
-                                   haveUp ? camUp : nullptr, vfov);
+                                   haveUp ? camUp : nullptr, vfov, denoise ? &dnp : nullptr);
     }
     if (deviceList.size() == 1) device = deviceList[0];
     try {
@@ -322,15 +339,17 @@ int main(int argc, char** argv) {
         float scale = 1.0f;
         auto t0 = std::chrono::steady_clock::now();
         if (!cameraPath.empty()) {
-            const int n = playCameraPath(r, view, cameraPath, outDir);
+            const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr);
             if (n < 0) return 1;
             frames = n;
             r.readFrame(&view);
             img = view.rgba;
+            if (denoise) r.denoise(dnp, img);
         } else if (frames > 0) {
             for (int f = 0; f < frames; ++f) r.draw(&view);
             r.readFrame(&view);
             img = view.rgba;
+            if (denoise) r.denoise(dnp, img);
         } else {
             // checkpoint / resume of the accumulation (the reference's running mean lives in a GPU-private texture and is lost with the
             // process, R/Renderer/Renderer.cpp:236): header "MPTSUM2 W H samples seed rng depth bsdf scene-hash\n" + W * H * 4 raw floats.
@@ -374,6 +393,12 @@ int main(int argc, char** argv) {
                 }
             }
             scale = 1.0f / static_cast<float>(have + static_cast<uint32_t>(spp));
+            if (denoise) {   // the checkpoint above keeps the raw sum; the image is the denoised sum / samples
+                mpt_denoise_params q = dnp;
+                q.samples = have + static_cast<uint32_t>(spp);
+                r.denoise(q, img);
+                scale = 1.0f;
+            }
         }
         double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         mpt_stats st = r.stats();

@@ -33,6 +33,7 @@
 #include "mpt_lbvh.h"
 #include "mpt_devbuild.h"
 #include "mpt_ordered.h"
+#include "mpt_denoise.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -213,6 +214,19 @@ struct mpt_ctx {
     int wgs_per_cu = 0;  // 0 = as many as the occupancy query admits
     size_t lds_budget = 78 * 1024;  // per workgroup; two workgroups per CU share the 160 KiB
     mpt_stats stats = {};
+    // denoiser (mpt_denoise.h): the first-hit guide buffers, traced again when stale, and the filter's own buffers (W x H each,
+    // allocated by the first mpt_read_aovs / mpt_denoise after a resize)
+    float4* d_aov_ad = nullptr;     // (albedo rgb, t)
+    float4* d_aov_nc = nullptr;     // (normal rgb, class)
+    int* d_aov_prim = nullptr;      // caller's primitive id, -1 = miss
+    float4* d_dn_guide = nullptr;   // packed per-tap guide (normal, t or MPT_DN_SKIP)
+    float4* d_dn_x[2] = {nullptr, nullptr};   // ping-pong (x rgb, luminance) of the levels
+    float4* d_denoised = nullptr;
+    uint32_t dn_W = 0, dn_H = 0;    // size of those buffers
+    uint64_t guide_epoch = 1;       // bumped by every scene upload / build and every mpt_resize
+    uint64_t guide_built = 0;       // the epoch the guide buffers were traced in (0 = never)
+    float guide_cam[14] = {};       // camera fields of the uniforms they were traced with
+    bool denoised_valid = false;    // d_denoised holds the result of an mpt_denoise at the current size
 };
 
 // kernel variants: COUNT (work counters) x ALL_LDS (the whole BVH fits the LDS budget)
@@ -392,6 +406,7 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
         }
     hipFuncSetAttribute((const void*)k_trace_rays_ordered, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_trace_rays, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipFuncSetAttribute((const void*)k_dn_guide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // (the image of k_trace_rays)
     *out = ctx;
     return MPT_OK;
 }
@@ -454,6 +469,13 @@ extern "C" int mpt_destroy(mpt_ctx* ctx) {
     hipFree(ctx->d_sum_own);
     hipFree(ctx->d_pixel_seed);
     hipFree(ctx->d_tile_xy);
+    hipFree(ctx->d_aov_ad);
+    hipFree(ctx->d_aov_nc);
+    hipFree(ctx->d_aov_prim);
+    hipFree(ctx->d_dn_guide);
+    hipFree(ctx->d_dn_x[0]);
+    hipFree(ctx->d_dn_x[1]);
+    hipFree(ctx->d_denoised);
     for (Lane& L : ctx->lane) {
         hipFree(L.d_slots);
         hipFree(L.d_desc);
@@ -878,6 +900,7 @@ static int upload_scene_impl(mpt_ctx* ctx, const float* bvh, uint64_t n_nodes, c
     ctx->acc_why = !nested ? "a child box is not inside its parent's box" : !use_always ? "more than 16 spheres" : "";
     size_lds_images(ctx);
     ctx->have_scene = true;
+    ctx->guide_epoch++;
     return MPT_OK;
 }
 
@@ -913,6 +936,8 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;
+    ctx->guide_epoch++;
+    ctx->denoised_valid = false;
     return MPT_OK;
 }
 
@@ -1904,6 +1929,7 @@ static int build_and_upload_impl(mpt_ctx* ctx, const float* prims, const float* 
     ctx->acc_why = ctx->acc_ok ? "" : "more than 16 spheres";
     size_lds_images(ctx);
     ctx->have_scene = true;
+    ctx->guide_epoch++;
     if (device_ms_out) *device_ms_out = ms;
     return MPT_OK;
 }
@@ -2108,6 +2134,186 @@ extern "C" int mpt_gpu_leaf_max(uint64_t n_prims) { return gpu_leaf_max(n_prims)
 
 // Position-sensitive 64-bit digest of a device array of 32-bit words: sum over i of splitmix64(i << 32 | word[i]) (a commutative sum, so
 // the order in which the waves add is free).  What the tests compare two builds of a scene by, array by array (mpt_scene_digest).
+// ---- denoiser (mpt_denoise.h; the specification is in include/mpt.h) ---------------------------------------------------------
+struct DnSigmas {
+    int iterations;
+    float sl, sn, sz;
+};
+static int dn_resolve(mpt_ctx* ctx, const mpt_denoise_params* p, DnSigmas& r) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null denoise params");
+    if (p->iterations > MPT_DENOISE_MAX_ITERATIONS) return fail(ctx, MPT_ERR_INVALID_ARG, "denoise iterations > 8");
+    r.iterations = p->iterations < 0 ? MPT_DENOISE_DEFAULT_ITERATIONS : p->iterations;
+    r.sl = p->sigma_luminance > 0.0f ? p->sigma_luminance : MPT_DENOISE_DEFAULT_SIGMA_LUMINANCE;
+    r.sn = p->sigma_normal > 0.0f ? p->sigma_normal : MPT_DENOISE_DEFAULT_SIGMA_NORMAL;
+    r.sz = p->sigma_depth > 0.0f ? p->sigma_depth : MPT_DENOISE_DEFAULT_SIGMA_DEPTH;
+    return MPT_OK;
+}
+// N levels on `stream`: level 0 demodulates `color` / samples, level N-1 remodulates into `out`; x[2] are the ping-pong buffers.
+static int dn_filter(mpt_ctx* ctx, hipStream_t stream, uint32_t W, uint32_t H, const float4* color, float samples, const float4* ad,
+                     const float4* guide, float4* const x[2], const DnSigmas& sg, float4* out) {
+    const uint32_t n = W * H;
+    if (sg.iterations == 0) {
+        hipLaunchKernelGGL(k_dn_copy, dim3((n + 255) / 256), dim3(256), 0, stream, color, samples, n, out);
+        HIPCHK(hipGetLastError());
+        return MPT_OK;
+    }
+    const dim3 grid((W + MPT_DN_TILE - 1) / MPT_DN_TILE, (H + MPT_DN_TILE - 1) / MPT_DN_TILE);
+    for (int i = 0; i < sg.iterations; ++i) {
+        const bool first = i == 0, last = i == sg.iterations - 1;
+        DnLevel L;
+        L.color = color;
+        L.ad = ad;
+        L.guide = guide;
+        L.xin = first ? nullptr : x[(i - 1) & 1];
+        L.xout = last ? out : x[i & 1];
+        L.W = W;
+        L.H = H;
+        L.step = 1u << i;
+        L.samples = samples;
+        L.sigma_n = sg.sn;
+        L.sigma_z = sg.sz;
+        L.sigma_l = sg.sl * ldexpf(1.0f, -i);
+        const bool lds = L.step <= MPT_DN_LDS_MAX_STEP;
+        const uint32_t T = MPT_DN_TILE + 4u * L.step;
+        const void* k = lds ? dn_level_kernel<true>(first, last) : dn_level_kernel<false>(first, last);
+        void* args[] = {&L};
+        HIPCHK(hipLaunchKernel(k, grid, dim3(256), args, lds ? (size_t)T * T * 32u : 0u, stream));
+    }
+    return MPT_OK;
+}
+static int ensure_dn_buffers(mpt_ctx* ctx) {
+    if (ctx->d_denoised && ctx->dn_W == ctx->W && ctx->dn_H == ctx->H) return MPT_OK;
+    float4** bufs[] = {&ctx->d_aov_ad, &ctx->d_aov_nc, &ctx->d_dn_guide, &ctx->d_dn_x[0], &ctx->d_dn_x[1], &ctx->d_denoised};
+    for (float4** b : bufs) {
+        hipFree(*b);
+        *b = nullptr;
+    }
+    hipFree(ctx->d_aov_prim);
+    ctx->d_aov_prim = nullptr;
+    ctx->dn_W = ctx->dn_H = 0;
+    ctx->guide_built = 0;
+    ctx->denoised_valid = false;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    for (float4** b : bufs) HIPCHK(hipMalloc(b, n * 16));
+    HIPCHK(hipMalloc(&ctx->d_aov_prim, n * 4));
+    ctx->dn_W = ctx->W;
+    ctx->dn_H = ctx->H;
+    return MPT_OK;
+}
+static void guide_key(const mpt_uniforms& u, float k[14]) {
+    memcpy(k, u.cameraPosition, 12);
+    memcpy(k + 3, u.viewportU, 12);
+    memcpy(k + 6, u.viewportV, 12);
+    memcpy(k + 9, u.firstPixelPosition, 12);
+    memcpy(k + 12, u.screenSize, 8);
+}
+// The guide pass, when the guides are stale: one thread per pixel, 16 x 16 pixels per workgroup of four 8 x 8 tiles, the top of the
+// tree staged in LDS as k_trace_rays does (the reference-order walk: it returns what the closest-first walk returns).
+static int refresh_guides(mpt_ctx* ctx) {
+    if (!ctx->have_scene || !ctx->have_uniforms || !ctx->W) return fail(ctx, MPT_ERR_NOT_READY, "scene, uniforms or size not set");
+    if ((uint32_t)ctx->u.screenSize[0] != ctx->W || (uint32_t)ctx->u.screenSize[1] != ctx->H)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "uniforms.screenSize does not match mpt_resize");
+    int rc = ensure_dn_buffers(ctx);
+    if (rc) return rc;
+    float key[14];
+    guide_key(ctx->u, key);
+    if (ctx->guide_built == ctx->guide_epoch && memcmp(key, ctx->guide_cam, sizeof key) == 0) return MPT_OK;
+    const mpt_uniforms& u = ctx->u;
+    const SceneDev sc = scene_dev(ctx);
+    const dim3 grid((ctx->W + MPT_DN_TILE - 1) / MPT_DN_TILE, (ctx->H + MPT_DN_TILE - 1) / MPT_DN_TILE);
+    hipLaunchKernelGGL(k_dn_guide, grid, dim3(256), (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA,
+                       ctx->stream, sc, F3{u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2]},
+                       F3{u.firstPixelPosition[0], u.firstPixelPosition[1], u.firstPixelPosition[2]},
+                       F3{u.viewportU[0], u.viewportU[1], u.viewportU[2]}, F3{u.viewportV[0], u.viewportV[1], u.viewportV[2]},
+                       u.screenSize[0], u.screenSize[1], ctx->W, ctx->H, ctx->d_aov_ad, ctx->d_aov_nc, ctx->d_aov_prim, ctx->d_dn_guide);
+    HIPCHK(hipGetLastError());
+    ctx->guide_built = ctx->guide_epoch;
+    memcpy(ctx->guide_cam, key, sizeof key);
+    return MPT_OK;
+}
+static int read_aovs_impl(mpt_ctx* ctx, float* ad, float* nc, int32_t* prim) {
+    if (!ctx || !ad || !nc) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    int rc = wait_impl(ctx);
+    if (rc) return rc;
+    if ((rc = refresh_guides(ctx))) return rc;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    HIPCHK(hipMemcpyAsync(ad, ctx->d_aov_ad, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(nc, ctx->d_aov_nc, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (prim) HIPCHK(hipMemcpyAsync(prim, ctx->d_aov_prim, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+static int denoise_impl(mpt_ctx* ctx, const mpt_denoise_params* p) {
+    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    DnSigmas sg;
+    int rc = dn_resolve(ctx, p, sg);
+    if (rc) return rc;
+    if (p->source != MPT_DENOISE_SUM && p->source != MPT_DENOISE_FRAME) return fail(ctx, MPT_ERR_INVALID_ARG, "bad denoise source");
+    if (p->source == MPT_DENOISE_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "denoise of the sum with samples = 0");
+    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
+    if ((rc = refresh_guides(ctx))) return rc;
+    const bool sum = p->source == MPT_DENOISE_SUM;
+    float4* x[2] = {ctx->d_dn_x[0], ctx->d_dn_x[1]};
+    ctx->denoised_valid = false;
+    if ((rc = dn_filter(ctx, ctx->stream, ctx->W, ctx->H, sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target], sum ? (float)p->samples : 1.0f,
+                        ctx->d_aov_ad, ctx->d_dn_guide, x, sg, ctx->d_denoised)))
+        return rc;
+    ctx->denoised_valid = true;
+    return MPT_OK;
+}
+static int read_denoised_impl(mpt_ctx* ctx, float* out) {
+    if (!ctx || !out) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    if (!ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
+    HIPCHK(hipMemcpyAsync(out, ctx->d_denoised, (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+static int denoise_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const float* ad, const float* nc,
+                              const mpt_denoise_params* p, float* out) {
+    if (!ctx || !color || !ad || !nc || !p || !out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31))
+        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    DnSigmas sg;
+    int rc = dn_resolve(ctx, p, sg);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)W * H;
+    DevBuf d_c, d_ad, d_nc, d_g, d_x0, d_x1, d_o;
+    for (DevBuf* b : {&d_c, &d_ad, &d_nc, &d_g, &d_x0, &d_x1, &d_o}) HIPCHK(b->alloc(n * 16));
+    HIPCHK(hipMemcpyAsync(d_c.p, color, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_ad.p, ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_nc.p, nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)d_ad.p, (const float4*)d_nc.p,
+                       (uint32_t)n, (float4*)d_g.p);
+    HIPCHK(hipGetLastError());
+    float4* x[2] = {(float4*)d_x0.p, (float4*)d_x1.p};
+    if ((rc = dn_filter(ctx, ctx->stream, W, H, (const float4*)d_c.p, 1.0f, (const float4*)d_ad.p, (const float4*)d_g.p, x, sg,
+                        (float4*)d_o.p)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(out, d_o.p, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+extern "C" int mpt_read_aovs(mpt_ctx* ctx, float* albedo_depth, float* normal_class, int32_t* prim) {
+    return guarded(ctx, [&] { return read_aovs_impl(ctx, albedo_depth, normal_class, prim); });
+}
+extern "C" int mpt_denoise(mpt_ctx* ctx, const mpt_denoise_params* p) {
+    return guarded(ctx, [&] { return denoise_impl(ctx, p); });
+}
+extern "C" int mpt_read_denoised(mpt_ctx* ctx, float* rgba) {
+    return guarded(ctx, [&] { return read_denoised_impl(ctx, rgba); });
+}
+extern "C" int mpt_denoised_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
+    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
+    if (!ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
+    *p = ctx->d_denoised;
+    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 16;
+    return MPT_OK;
+}
+extern "C" int mpt_denoise_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth, const float* normal_class,
+                                 const mpt_denoise_params* p, float* out) {
+    return guarded(ctx, [&] { return denoise_image_impl(ctx, w, h, color, albedo_depth, normal_class, p, out); });
+}
+
 __global__ void k_digest(const uint32_t* w, uint64_t n_words, unsigned long long* out) {
     unsigned long long acc = 0ull;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x) {

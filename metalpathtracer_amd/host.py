@@ -23,7 +23,7 @@ SYMBOLS = (
     "mpt_renderer_drawable_size_will_change", "mpt_renderer_set_params", "mpt_renderer_draw", "mpt_renderer_input",
     "mpt_renderer_read_frame", "mpt_renderer_render_batch", "mpt_renderer_read_sum", "mpt_renderer_clear_sum",
     "mpt_renderer_uniforms", "mpt_renderer_stats", "mpt_renderer_context", "mpt_renderer_scene", "mpt_write_pfm",
-    "mpt_write_ppm",
+    "mpt_write_ppm", "mpt_renderer_denoise",
 )
 
 _lib = None
@@ -64,6 +64,7 @@ def load():
     L.mpt_renderer_clear_sum.argtypes = [vp]
     L.mpt_renderer_uniforms.argtypes = [vp, C.POINTER(capi.Uniforms)]
     L.mpt_renderer_stats.argtypes = [vp, C.POINTER(capi.Stats)]
+    L.mpt_renderer_denoise.argtypes = [vp, C.POINTER(capi.DenoiseParams), fp]
     L.mpt_renderer_context.argtypes = [vp]
     L.mpt_renderer_context.restype = vp
     L.mpt_renderer_scene.argtypes = [vp]
@@ -300,6 +301,15 @@ class Renderer:
         s = capi.Stats()
         self._chk(self.L.mpt_renderer_stats(self.h, C.byref(s)), "stats")
         return s.as_dict()
+
+    def denoise(self, **kw):
+        """mpt_renderer_denoise: the draw() target after draw(), the sum after renderBatch() (samples=0: all rendered since the
+        last clearSum()); the denoised [H, W, 4] image."""
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
+        p = capi.denoise_params(**kw)
+        self._chk(self.L.mpt_renderer_denoise(self.h, C.byref(p), _fp(out)), "denoise")
+        return out
 
     def scene(self):
         return Scene(_borrowed=self.L.mpt_renderer_scene(self.h))
