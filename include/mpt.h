@@ -106,7 +106,9 @@ typedef struct mpt_render_params {
     uint32_t flags;          /* MPT_FLAG_*                                                            */
 } mpt_render_params;
 
-enum { MPT_FLAG_COUNT_WORK = 1u }; /* also count node visits / primitive tests (slower; for tests)    */
+enum { MPT_FLAG_COUNT_WORK = 1u,   /* also count node visits / primitive tests (slower; for tests)    */
+       MPT_FLAG_MOMENTS = 2u };    /* mpt_render / mpt_render_async: also add the per-sample second moments to the
+                                      context's moments buffer (mpt_read_moments); mpt_draw ignores it                    */
 
 typedef struct mpt_stats {   /* cumulative since mpt_reset_stats                                      */
     uint64_t paths;          /* primary rays generated                                                */
@@ -327,6 +329,53 @@ int mpt_denoised_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);
  * samples are ignored), albedo_depth / normal_class as mpt_read_aovs returns them; a surface's t must be > 0.  No scene needed. */
 int mpt_denoise_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const float* albedo_depth,
                       const float* normal_class, const mpt_denoise_params* params, float* rgba_out);
+
+/* ---- adaptive sampling: per-pixel moments + per-tile early stopping -------------------------------------------------------
+ * No reference counterpart (the reference spends one sample per pixel per frame everywhere, Fragment.metal:8-72).
+ *
+ * Moments (MPT_FLAG_MOMENTS): the resolve of a render with the flag also adds, per pixel and per sample v (the clamped per-sample
+ * colour the HDR sum adds), in sample order, m2 += (v.x^2, v.y^2, v.z^2, l^2) with l = (0.2126 v.x + 0.7152 v.y) + 0.0722 v.z into
+ * a context-owned RGBA32F buffer (W*H*4 floats).  The HDR sum is bit-identical with and without the flag.  The buffer is allocated
+ * by the first render with the flag; mpt_resize and mpt_clear_sum zero it, a render without the flag leaves it as it is.
+ * mpt_write_sum, checkpoints and mpt_reduce_sum do not carry it.  mpt_read_moments: MPT_ERR_NOT_READY before mpt_resize, zeros
+ * when no render with the flag has run since the last clear.                                                                  */
+int mpt_read_moments(mpt_ctx* ctx, float* rgba_host);
+
+/* Adaptive render: renders p's 8x8 tiles in passes until each tile's noise meets a target, with b = p->sample_begin and
+ * N = p->sample_count the most samples any tile gets.  Synchronous, like mpt_render: it first waits for the renders queued and in
+ * flight (reporting a failed mpt_render_async), then clears the HDR sum (the caller's storage of mpt_set_sum_buffer included), the
+ * moments and the tile counts, and renders with MPT_FLAG_MOMENTS.
+ *   schedule: n_0 = min(min_samples, N), n_{k+1} = min(n_k + batch_samples, N); pass 0 renders samples [b, b+n_0) of every tile,
+ *             pass k+1 renders [b+n_k, b+n_{k+1}) of the tiles still active (every active tile holds n_k samples).
+ *   stopping: after each pass, in double precision from the float32 sum and moments, for every pixel inside the image of a tile
+ *             holding n samples: s = lum(sum.rgb), mean = s / n, var = max(0, (m2.w - s * mean) / (n - 1)),
+ *             err = sqrt(var / n) / max(mean, luminance_floor); lum uses the three float constants above.  The tile's error is the
+ *             maximum over its pixels; the tile stays active iff error > threshold and n < N.  A stopped tile never resumes.
+ * Afterwards mpt_read_tile_samples gives every tile's sample count; the per-pixel estimate is sum / count(tile).  Each tile holds,
+ * bit for bit, the sum a plain mpt_render of [b, b+count) produces.  mpt_get_stats: paths grows by out->samples; trace_kernel_ms,
+ * total_ms and trace_launches are the totals over the passes.  Every pipeline and BSDF mode works.
+ * MPT_ERR_INVALID_ARG, with nothing rendered: a null argument, MPT_RNG_LITERAL (its stream repeats per pixel: no variance),
+ * shard_count != 1, min_samples == 1, a negative or NaN threshold, N < 2.  MPT_ERR_NOT_READY before scene, uniforms and size.  */
+#define MPT_ADAPTIVE_DEFAULT_MIN_SAMPLES 16u
+#define MPT_ADAPTIVE_DEFAULT_BATCH 16u
+#define MPT_ADAPTIVE_DEFAULT_LUMINANCE_FLOOR 0.05f
+typedef struct mpt_adaptive_params {
+    uint32_t min_samples;     /* first pass, every tile (>= 2); 0 = MPT_ADAPTIVE_DEFAULT_MIN_SAMPLES                            */
+    uint32_t batch_samples;   /* samples per later pass (>= 1); 0 = MPT_ADAPTIVE_DEFAULT_BATCH                                  */
+    float threshold;          /* target relative standard error of a pixel's mean (>= 0; 0 = every tile to N)                   */
+    float luminance_floor;    /* <= 0: MPT_ADAPTIVE_DEFAULT_LUMINANCE_FLOOR                                                     */
+} mpt_adaptive_params;
+typedef struct mpt_adaptive_info {
+    uint64_t samples;           /* pixel samples rendered (pixels inside the image only)                                        */
+    uint32_t passes;            /* trace passes run (the first pass included)                                                   */
+    uint32_t tiles_converged;   /* tiles stopped by the threshold below N                                                       */
+    uint32_t tiles_at_max;      /* tiles that reached N = p->sample_count                                                       */
+    uint32_t _pad;
+} mpt_adaptive_info;
+int mpt_render_adaptive(mpt_ctx* ctx, const mpt_render_params* p, const mpt_adaptive_params* a, mpt_adaptive_info* out);
+/* Samples per tile of the last mpt_render_adaptive: ceil(W/8) * ceil(H/8) uint32, row-major tiles (zeros before the first one;
+ * MPT_ERR_NOT_READY before mpt_resize).                                                                                       */
+int mpt_read_tile_samples(mpt_ctx* ctx, uint32_t* counts);
 
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);

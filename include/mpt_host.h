@@ -75,6 +75,10 @@ int mpt_renderer_stats(mpt_renderer* r, mpt_stats* out);
  * mpt_renderer_render_batch (params->source is ignored; params->samples = 0 means the samples rendered since the sum was
  * last cleared).  rgba: W*H*4 floats.                                                                                  */
 int mpt_renderer_denoise(mpt_renderer* r, const mpt_denoise_params* params, float* rgba);
+/* mpt_render_adaptive with the renderer's params and uniforms: samples [sample_begin, sample_begin + max_samples) at most per tile,
+ * the counts per tile through mpt_read_tile_samples(mpt_renderer_context(r), ...).  out may not be NULL.                         */
+int mpt_renderer_render_adaptive(mpt_renderer* r, uint32_t sample_begin, uint32_t max_samples, const mpt_adaptive_params* params,
+                                 mpt_adaptive_info* out);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 

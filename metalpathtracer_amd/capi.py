@@ -17,6 +17,7 @@ PIPE_WAVEFRONT, PIPE_MEGAKERNEL, PIPE_WAVELOCAL, PIPE_ORDERED, PIPE_AUTO = 0, 1,
 REFERENCE_ORDER_PIPELINES = (PIPE_WAVEFRONT, PIPE_MEGAKERNEL, PIPE_WAVELOCAL)  # walk the BVH in the reference's own order
 DEFAULT_PIPELINE = PIPE_AUTO  # closest-first for big scenes, reference-order wave-local below 8192 primitives
 FLAG_COUNT_WORK = 1
+FLAG_MOMENTS = 2
 
 STATUS = {0: "MPT_OK", 1: "MPT_ERR_INVALID_ARG", 2: "MPT_ERR_NO_DEVICE", 3: "MPT_ERR_HIP",
           4: "MPT_ERR_BAD_SCENE", 5: "MPT_ERR_NOT_READY", 6: "MPT_ERR_OVERFLOW"}
@@ -29,12 +30,15 @@ SYMBOLS = (
     "mpt_trace_rays", "mpt_trace_rays_ordered", "mpt_accel_info", "mpt_kat_pcg", "mpt_kat_philox", "mpt_kat_sincos", "mpt_kat_rcp",
     "mpt_build_bvh", "mpt_build_and_upload", "mpt_download_bvh", "mpt_gpu_leaf_max", "mpt_build_info", "mpt_scene_digest", "mpt_comm_unique_id", "mpt_comm_create_all", "mpt_comm_create_rank", "mpt_reduce_sum", "mpt_comm_destroy",
     "mpt_comm_last_error", "mpt_read_aovs", "mpt_denoise", "mpt_read_denoised", "mpt_denoised_buffer", "mpt_denoise_image",
+    "mpt_read_moments", "mpt_render_adaptive", "mpt_read_tile_samples",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
 DENOISE_MAX_ITERATIONS = 8
 # include/mpt.h MPT_DENOISE_DEFAULT_* (a sigma <= 0 / iterations < 0 selects them on the device too)
 DENOISE_DEFAULTS = dict(iterations=3, sigma_luminance=8.0, sigma_normal=32.0, sigma_depth=0.25)
+# include/mpt.h MPT_ADAPTIVE_DEFAULT_* (0 / a floor <= 0 selects them)
+ADAPTIVE_DEFAULTS = dict(min_samples=16, batch_samples=16, luminance_floor=0.05)
 
 
 class MptError(RuntimeError):
@@ -95,6 +99,24 @@ def denoise_params(source=DENOISE_SUM, samples=0, iterations=-1, sigma_luminance
     """mpt_denoise_params; iterations < 0 and sigmas <= 0 mean the defaults of include/mpt.h."""
     return DenoiseParams(int(source), int(samples), int(iterations), float(sigma_luminance), float(sigma_normal),
                          float(sigma_depth))
+
+
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_samples", C.c_uint32), ("batch_samples", C.c_uint32), ("threshold", C.c_float),
+                ("luminance_floor", C.c_float)]
+
+
+class AdaptiveInfo(C.Structure):
+    _fields_ = [("samples", C.c_uint64), ("passes", C.c_uint32), ("tiles_converged", C.c_uint32),
+                ("tiles_at_max", C.c_uint32), ("_pad", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "_pad"}
+
+
+def expand_tile_counts(counts, H, W):
+    """(tiles_y, tiles_x) per-tile counts -> (H, W) per-pixel counts (8x8 tiles, the edge tiles cut at the image border)."""
+    return np.repeat(np.repeat(np.asarray(counts), 8, axis=0), 8, axis=1)[:H, :W]
 
 
 _lib = None
@@ -185,6 +207,9 @@ def load():
     L.mpt_read_denoised.argtypes = [vp, fp]
     L.mpt_denoised_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.mpt_denoise_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, fp, C.POINTER(DenoiseParams), fp]
+    L.mpt_read_moments.argtypes = [vp, fp]
+    L.mpt_render_adaptive.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo)]
+    L.mpt_read_tile_samples.argtypes = [vp, up]
     _lib = L
     return L
 
@@ -480,6 +505,31 @@ class Context:
         p = denoise_params(**kw)
         self._chk(self.L.mpt_denoise_image(self.h, W, H, _fp(c), _fp(ad), _fp(nc), C.byref(p), _fp(out)), "mpt_denoise_image")
         return out
+
+    def read_moments(self):
+        """Per-pixel second moments of the renders with FLAG_MOMENTS since the last clear: (sum v.x^2, v.y^2, v.z^2, lum^2) [H,W,4]."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._chk(self.L.mpt_read_moments(self.h, _fp(out)), "mpt_read_moments")
+        return out
+
+    def render_adaptive(self, threshold, min_samples=0, batch_samples=0, luminance_floor=0.0, **params):
+        """mpt_render_adaptive: sample_count (params) is the most samples a tile gets; returns the mpt_adaptive_info as a dict."""
+        p = self.params(**params)
+        a = AdaptiveParams(int(min_samples), int(batch_samples), float(threshold), float(luminance_floor))
+        info = AdaptiveInfo()
+        self._chk(self.L.mpt_render_adaptive(self.h, C.byref(p), C.byref(a), C.byref(info)), "mpt_render_adaptive")
+        return info.as_dict()
+
+    def read_tile_samples(self):
+        """Samples per 8x8 tile of the last adaptive render: (tiles_y, tiles_x) uint32."""
+        out = np.empty(((self.height + 7) // 8, (self.width + 7) // 8), np.uint32)
+        self._chk(self.L.mpt_read_tile_samples(self.h, _up(out)), "mpt_read_tile_samples")
+        return out
+
+    def read_adaptive_mean(self):
+        """The per-pixel estimate of the last adaptive render: the HDR sum divided by its tile's sample count, in float32."""
+        n = expand_tile_counts(self.read_tile_samples(), self.height, self.width).astype(np.float32)
+        return self.read_sum() / n[..., None]
 
     def kat_pcg(self, seeds):
         s = np.ascontiguousarray(seeds, np.uint32)

@@ -254,6 +254,34 @@ int Renderer::renderBatch(uint32_t sampleBegin, uint32_t sampleCount) {
     return rc;
 }
 
+mpt_adaptive_info Renderer::renderAdaptive(uint32_t sampleBegin, uint32_t maxSamples, const mpt_adaptive_params& a) {
+    uniforms_.primitiveCount = scene_->getPrimitiveCount();
+    uniforms_.triangleCount = scene_->getTriangleCount();
+    check(mpt_set_uniforms(ctx_, &uniforms_), "mpt_set_uniforms");
+    mpt_render_params p = params_;
+    p.sample_begin = sampleBegin;
+    p.sample_count = maxSamples;
+    mpt_adaptive_info info;
+    check(mpt_render_adaptive(ctx_, &p, &a, &info), "mpt_render_adaptive");
+    lastSource_ = MPT_DENOISE_SUM;
+    sumSamples_ = 0;   // (the tiles hold different counts: denoise() needs an explicit sample count)
+    return info;
+}
+
+void Renderer::readAdaptiveMean(std::vector<float>& rgba) {
+    const uint32_t W = static_cast<uint32_t>(Camera::screenSize.x), H = static_cast<uint32_t>(Camera::screenSize.y);
+    const uint32_t tilesX = (W + 7) / 8, tilesY = (H + 7) / 8;
+    std::vector<uint32_t> counts(static_cast<size_t>(tilesX) * tilesY);
+    readSum(rgba);
+    check(mpt_read_tile_samples(ctx_, counts.data()), "mpt_read_tile_samples");
+    for (uint32_t y = 0; y < H; ++y)
+        for (uint32_t x = 0; x < W; ++x) {
+            const float n = static_cast<float>(counts[static_cast<size_t>(y / 8) * tilesX + x / 8]);
+            float* v = &rgba[(static_cast<size_t>(y) * W + x) * 4];
+            for (int c = 0; c < 4; ++c) v[c] = v[c] / n;
+        }
+}
+
 void Renderer::readSum(std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     rgba.resize(n);

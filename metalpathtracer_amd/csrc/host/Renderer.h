@@ -61,6 +61,9 @@ public:
     // mpt_denoise of what was rendered last: the draw() target after draw(), the sum after renderBatch() (samples = p.samples, or
     // when 0 the samples added since the sum was last cleared); rgba = the W*H*4 denoised floats
     void denoise(const mpt_denoise_params& p, std::vector<float>& rgba);
+    // mpt_render_adaptive of [sampleBegin, sampleBegin + maxSamples) at most per tile; readAdaptiveMean = the sum / the tile's count
+    mpt_adaptive_info renderAdaptive(uint32_t sampleBegin, uint32_t maxSamples, const mpt_adaptive_params& a);
+    void readAdaptiveMean(std::vector<float>& rgba);
 
 private:
     void check(int status, const char* where);

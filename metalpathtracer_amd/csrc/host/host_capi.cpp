@@ -277,6 +277,11 @@ int mpt_renderer_denoise(mpt_renderer* r, const mpt_denoise_params* p, float* rg
         std::memcpy(rgba, img.data(), img.size() * sizeof(float));
     });
 }
+int mpt_renderer_render_adaptive(mpt_renderer* r, uint32_t sample_begin, uint32_t max_samples, const mpt_adaptive_params* p,
+                                 mpt_adaptive_info* out) {
+    if (!r || !p || !out) return MPT_ERR_INVALID_ARG;
+    GUARD({ *out = r->r->renderAdaptive(sample_begin, max_samples, *p); });
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

@@ -42,6 +42,13 @@ static void usage() {
         "           [--camera-pos x,y,z] [--camera-dir x,y,z] [--camera-up x,y,z] [--vfov degrees]\n"
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]]\n"
+        "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
+        "  --adaptive T      batch mode, adaptive sampling (mpt_render_adaptive, include/mpt.h): every 8x8 tile gets --adaptive-min\n"
+        "                    samples (default 16), then --adaptive-batch more per pass (default 16) until the relative standard error\n"
+        "                    of each of its pixels' mean luminance is <= T (luminance below --adaptive-floor, default 0.05, counts as\n"
+        "                    the floor) or it holds --spp samples.  --out gets the per-pixel mean (the sum / its tile's count; with\n"
+        "                    --denoise the denoised mean); the JSON line gains an \"adaptive\" object.  Not with --frames,\n"
+        "                    --camera-path, --gpus > 1, --rng literal, --checkpoint or --resume\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
@@ -238,6 +245,9 @@ int main(int argc, char** argv) {
     mpt_denoise_params dnp;
     std::memset(&dnp, 0, sizeof dnp);
     dnp.iterations = -1;   // (defaults of include/mpt.h)
+    bool adaptive = false;
+    mpt_adaptive_params adp;
+    std::memset(&adp, 0, sizeof adp);   // (0 = the defaults of include/mpt.h)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -276,6 +286,13 @@ int main(int argc, char** argv) {
         else if (a == "--resume") resume = next();
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
+        else if (a == "--adaptive") {
+            adaptive = true;
+            adp.threshold = static_cast<float>(std::atof(next()));
+        }
+        else if (a == "--adaptive-min") adp.min_samples = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
+        else if (a == "--adaptive-batch") adp.batch_samples = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
+        else if (a == "--adaptive-floor") adp.luminance_floor = static_cast<float>(std::atof(next()));
         else if (a == "--bvh") {
             const char* v = next();
             bvh = std::strcmp(v, "reference") == 0 ? Renderer::BUILD_REFERENCE
@@ -318,6 +335,15 @@ int main(int argc, char** argv) {
     prm.seed_lo = seed;
     if (bvh < 0) bvh = prm.rng_mode == MPT_RNG_LITERAL || frames > 0 || !cameraPath.empty() ? Renderer::BUILD_REFERENCE : Renderer::BUILD_AUTO;
     if (!deviceList.empty()) gpus = static_cast<int>(deviceList.size());
+    if (adaptive) {
+        const char* why = frames > 0 ? "--frames" : !cameraPath.empty() ? "--camera-path" : gpus > 1 ? "--gpus > 1"
+                          : prm.rng_mode == MPT_RNG_LITERAL ? "--rng literal" : !checkpoint.empty() ? "--checkpoint"
+                          : !resume.empty() ? "--resume" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: --adaptive cannot be combined with %s\n", why);
+            return 2;
+        }
+    }
     if (gpus > 1) {
         if (deviceList.empty())
             for (int g = 0; g < gpus; ++g) deviceList.push_back(device + g);
@@ -337,8 +363,27 @@ int main(int argc, char** argv) {
         r.drawableSizeWillChange(&view, DrawableSize{(double)width, (double)height});
         std::vector<float> img;
         float scale = 1.0f;
+        std::string adaptiveJson;
         auto t0 = std::chrono::steady_clock::now();
-        if (!cameraPath.empty()) {
+        if (adaptive) {
+            const mpt_adaptive_info info = r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);
+            r.readAdaptiveMean(img);
+            if (denoise) {   // the mean through the filter kernels, with the context's guides (mpt_read_aovs + mpt_denoise_image)
+                std::vector<float> ad(img.size()), nc(img.size()), dn(img.size());
+                mpt_ctx* ctx = r.context();
+                int rc = mpt_read_aovs(ctx, ad.data(), nc.data(), nullptr);
+                if (!rc) rc = mpt_denoise_image(ctx, width, height, img.data(), ad.data(), nc.data(), &dnp, dn.data());
+                if (rc) throw std::runtime_error(std::string("adaptive denoise: ") + mpt_status_string(rc) + ": " + mpt_last_error(ctx));
+                img.swap(dn);
+            }
+            const double pixels = static_cast<double>(width) * height;
+            char buf[256];
+            std::snprintf(buf, sizeof buf,
+                          ", \"adaptive\": {\"passes\": %u, \"samples\": %llu, \"tiles_converged\": %u, \"tiles_at_max\": %u, \"mean_spp\": %.4f}",
+                          info.passes, (unsigned long long)info.samples, info.tiles_converged, info.tiles_at_max,
+                          pixels > 0 ? static_cast<double>(info.samples) / pixels : 0.0);
+            adaptiveJson = buf;
+        } else if (!cameraPath.empty()) {
             const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr);
             if (n < 0) return 1;
             frames = n;
@@ -402,9 +447,9 @@ int main(int argc, char** argv) {
         }
         double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         mpt_stats st = r.stats();
-        std::printf("{\"paths\": %llu, \"rays\": %llu, \"seconds\": %.6f, \"device_ms\": %.3f, \"mrays_per_s\": %.1f}\n",
+        std::printf("{\"paths\": %llu, \"rays\": %llu, \"seconds\": %.6f, \"device_ms\": %.3f, \"mrays_per_s\": %.1f%s}\n",
                     (unsigned long long)st.paths, (unsigned long long)st.rays, sec, st.total_ms,
-                    st.total_ms > 0 ? st.rays / st.total_ms / 1e3 : 0.0);
+                    st.total_ms > 0 ? st.rays / st.total_ms / 1e3 : 0.0, adaptiveJson.c_str());
         if (!out.empty()) {
             bool ppm = out.size() > 4 && out.substr(out.size() - 4) == ".ppm";
             int rc = ppm ? mpt_write_ppm(out.c_str(), img.data(), width, height, scale, 2.2f)

@@ -34,6 +34,7 @@
 #include "mpt_devbuild.h"
 #include "mpt_ordered.h"
 #include "mpt_denoise.h"
+#include "mpt_adaptive.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -227,6 +228,16 @@ struct mpt_ctx {
     uint64_t guide_built = 0;       // the epoch the guide buffers were traced in (0 = never)
     float guide_cam[14] = {};       // camera fields of the uniforms they were traced with
     bool denoised_valid = false;    // d_denoised holds the result of an mpt_denoise at the current size
+    // adaptive sampling (mpt_adaptive.h): the moments buffer (W x H, allocated by the first render with MPT_FLAG_MOMENTS) and the
+    // tile buffers of mpt_render_adaptive (allocated by its first call after a resize); mpt_resize frees them all
+    float4* d_m2 = nullptr;
+    uint32_t* d_tile_count = nullptr;            // samples per tile, row-major
+    uint32_t* d_alist[2] = {nullptr, nullptr};   // ping-pong active tile lists (x | y << 16)
+    uint8_t* d_aflag = nullptr;                  // per list entry: the tile stays active
+    uint32_t* d_nsel = nullptr;                  // entries DeviceSelect::Flagged kept
+    void* d_sel_tmp = nullptr;                   // its temporary storage, sized once per tile count
+    size_t sel_tmp_bytes = 0;
+    uint32_t ad_tiles = 0;                       // tile count the tile buffers were allocated for
 };
 
 // kernel variants: COUNT (work counters) x ALL_LDS (the whole BVH fits the LDS budget)
@@ -455,6 +466,24 @@ static void free_queues(Lane& L) {
     L.shard_cap = 0;
 }
 
+static void free_adaptive_buffers(mpt_ctx* ctx) {
+    hipFree(ctx->d_m2);
+    hipFree(ctx->d_tile_count);
+    hipFree(ctx->d_alist[0]);
+    hipFree(ctx->d_alist[1]);
+    hipFree(ctx->d_aflag);
+    hipFree(ctx->d_nsel);
+    hipFree(ctx->d_sel_tmp);
+    ctx->d_m2 = nullptr;
+    ctx->d_tile_count = nullptr;
+    ctx->d_alist[0] = ctx->d_alist[1] = nullptr;
+    ctx->d_aflag = nullptr;
+    ctx->d_nsel = nullptr;
+    ctx->d_sel_tmp = nullptr;
+    ctx->sel_tmp_bytes = 0;
+    ctx->ad_tiles = 0;
+}
+
 extern "C" int mpt_destroy(mpt_ctx* ctx) {
     if (!ctx) return MPT_ERR_INVALID_ARG;
     stop_submit(ctx);   // (renders still queued are submitted, then the thread ends)
@@ -476,6 +505,7 @@ extern "C" int mpt_destroy(mpt_ctx* ctx) {
     hipFree(ctx->d_dn_x[0]);
     hipFree(ctx->d_dn_x[1]);
     hipFree(ctx->d_denoised);
+    free_adaptive_buffers(ctx);
     for (Lane& L : ctx->lane) {
         hipFree(L.d_slots);
         hipFree(L.d_desc);
@@ -925,6 +955,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     }
     hipFree(ctx->d_sum_own);
     ctx->d_sum_own = nullptr;
+    free_adaptive_buffers(ctx);   // (moments and tile counts of the old size: zero from here on)
     size_t bytes = (size_t)width * height * 16;
     for (int i = 0; i < 2; ++i) {
         HIPCHK(hipMalloc(&ctx->d_accum[i], bytes));
@@ -963,6 +994,7 @@ static int clear_sum_impl(mpt_ctx* ctx) {
     int wrc = wait_impl(ctx);
     if (wrc) return wrc;
     HIPCHK(hipMemsetAsync(ctx->d_sum, 0, (size_t)ctx->W * ctx->H * 16, ctx->stream));
+    if (ctx->d_m2) HIPCHK(hipMemsetAsync(ctx->d_m2, 0, (size_t)ctx->W * ctx->H * 16, ctx->stream));
     HIPCHK(hipEventRecord(ctx->ev_sum_op, ctx->stream));  // the next resolve (on either lane) is ordered behind the clear
     ctx->last_resolved = ctx->ev_sum_op;
     return MPT_OK;
@@ -1217,9 +1249,15 @@ static int tile_order_of(const mpt_ctx* ctx, const mpt_render_params* p) {
     return resolve_pipeline(ctx, p->pipeline, p->rng_mode) == MPT_PIPE_ORDERED && ordered_point(ctx, count_flag(p)) == 1 ? 3 : 0;
 }
 
-// Runs one pass of S samples/pixel over this rank's tiles; leaves the per-path results in d_slots.
+// A device list of tiles (x | y << 16) that a pass walks instead of the rank's table: mpt_render_adaptive's active tiles.
+struct TileOverride {
+    const uint32_t* tiles;
+    uint32_t n;
+};
+
+// Runs one pass of S samples/pixel over this rank's tiles (or the override's); leaves the per-path results in d_slots.
 static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t sample_begin, uint32_t S, PassParams& pp,
-                    uint32_t& n_local_tiles, bool time_kernels) {
+                    uint32_t& n_local_tiles, bool time_kernels, const TileOverride* ovr = nullptr) {
     const uint32_t tiles_x = (ctx->W + 7) / 8;
     const uint32_t nr = (uint32_t)p->shard_count, rk = (uint32_t)p->shard_rank;
     const int tile_mode = tile_order_of(ctx, p);
@@ -1227,6 +1265,7 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         int trc = ensure_tile_order(ctx, rk, nr, tile_mode, n_local_tiles);
         if (trc) return trc;
     }
+    if (ovr) n_local_tiles = ovr->n;
     const uint64_t pass_paths = (uint64_t)n_local_tiles * S * 64ull;
     if (pass_paths >= pass_path_limit(p->pipeline)) return fail(ctx, MPT_ERR_INVALID_ARG, "pass too large (internal)");
     uint32_t slots = p->slots_per_iter ? p->slots_per_iter : (16u << 20);
@@ -1258,7 +1297,7 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     pp.tiles_x = tiles_x;
     pp.S = S;
     pp.s_shift = (S & (S - 1)) == 0 ? (uint32_t)__builtin_ctz(S) : 0xFFu;
-    pp.tile_xy = ctx->d_tile_xy;
+    pp.tile_xy = ovr ? ovr->tiles : ctx->d_tile_xy;
     pp.sample_begin = sample_begin;
     pp.rank = rk;
     pp.nranks = nr;
@@ -1266,7 +1305,7 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         // while T * tiles_x < 2^32 (error term T * (tiles_x - 1) / (tiles_x * 2^32) < 1 / tiles_x); otherwise the table
         const uint64_t tiles = (uint64_t)tiles_x * ((ctx->H + 7) / 8);
         pp.tile_magic = 0u;
-        if (tile_mode == 0 && tiles_x >= 2u && tiles * tiles_x < (1ull << 32) && getenv("MPT_TILE_TABLE") == nullptr)
+        if (!ovr && tile_mode == 0 && tiles_x >= 2u && tiles * tiles_x < (1ull << 32) && getenv("MPT_TILE_TABLE") == nullptr)
             pp.tile_magic = (uint32_t)(((1ull << 32) + tiles_x - 1u) / tiles_x);
     }
     pp.sp.rng_mode = p->rng_mode;
@@ -1545,7 +1584,7 @@ static int wait_impl(mpt_ctx* ctx) {
 
 // Enqueues one render (all its passes, each followed by its resolve into the HDR sum) on the next lane and returns.
 // At most two renders are in flight: the lane is collected first if it is still busy.
-static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p) {
+static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p, const TileOverride* ovr = nullptr) {
     int rc = check_ready(ctx, p);
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
@@ -1556,10 +1595,15 @@ static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p) {
         return rc;
     Lane& L = ctx->lane[ctx->next_lane];
     if (L.in_flight && (rc = collect_lane(ctx, L))) return rc;
+    if ((p->flags & MPT_FLAG_MOMENTS) && !ctx->d_m2) {   // (first render with moments since the resize: zeroed in stream order)
+        const size_t bytes = (size_t)ctx->W * ctx->H * 16;
+        HIPCHK(hipMalloc(&ctx->d_m2, bytes));
+        HIPCHK(hipMemsetAsync(ctx->d_m2, 0, bytes, L.stream));
+    }
     HIPCHK(hipEventRecord(L.ev0, L.stream));
     ctx->next_lane ^= 1;
     const uint32_t tiles = ((ctx->W + 7) / 8) * ((ctx->H + 7) / 8);
-    const uint32_t local_tiles = (tiles + p->shard_count - 1) / p->shard_count;
+    const uint32_t local_tiles = ovr ? ovr->n : (tiles + p->shard_count - 1) / p->shard_count;
     uint32_t s_max = (uint32_t)std::max<uint64_t>(
         1, (pass_path_limit(p->pipeline) - 64) / ((uint64_t)std::max(1u, local_tiles) * 64ull));
     if (p->pipeline == MPT_PIPE_WAVEFRONT && s_max > 64) s_max = 64;
@@ -1598,7 +1642,7 @@ static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p) {
         uint32_t S = std::min(s_max, p->sample_count - done);
         PassParams pp;
         uint32_t nlt = 0;
-        rc = run_pass(ctx, L, p, p->sample_begin + done, S, pp, nlt, ctx->time_kernels);
+        rc = run_pass(ctx, L, p, p->sample_begin + done, S, pp, nlt, ctx->time_kernels, ovr);
         if (rc) return abandon(rc);
         if (nlt) {
             // sum[p] += pass total must happen in submission order on both lanes (float addition does not commute
@@ -1608,7 +1652,10 @@ static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p) {
             const uint32_t threads = nlt * 64u, wide = (threads + 255u) / 256u;
             const uint32_t narrow = (uint32_t)ctx->prop.multiProcessorCount * (uint32_t)ctx->resolve_wgs_per_cu;
             const uint32_t rgrid = !ctx->sync_render && ctx->resolve_wgs_per_cu > 0 ? std::min(wide, narrow) : wide;
-            hipLaunchKernelGGL(k_resolve_sum, dim3(rgrid), dim3(256), 0, L.stream, pp, ctx->d_sum, nlt);
+            if (p->flags & MPT_FLAG_MOMENTS)
+                hipLaunchKernelGGL(k_resolve_sum_moments, dim3(rgrid), dim3(256), 0, L.stream, pp, ctx->d_sum, ctx->d_m2, nlt);
+            else
+                hipLaunchKernelGGL(k_resolve_sum, dim3(rgrid), dim3(256), 0, L.stream, pp, ctx->d_sum, nlt);
             HIPCHK_AB(hipGetLastError());
             HIPCHK_AB(hipEventRecord(L.ev_resolved, L.stream));
             ctx->last_resolved = L.ev_resolved;
@@ -1671,6 +1718,142 @@ static int draw_impl(mpt_ctx* ctx, const mpt_render_params* p) {
     }
     if ((rc = enqueue_stats_copy(ctx, L))) return rc;
     return collect_lane(ctx, L);
+}
+
+// ---- adaptive sampling (mpt_adaptive.h; the contract is in include/mpt.h) ----------------------------------------------------
+static int read_moments_impl(mpt_ctx* ctx, float* out) {
+    if (!ctx->d_sum) return fail(ctx, MPT_ERR_NOT_READY, "mpt_resize not called");
+    int rc = wait_impl(ctx);
+    if (rc) return rc;
+    const size_t bytes = (size_t)ctx->W * ctx->H * 16;
+    if (!ctx->d_m2) {   // (no render with moments since the resize)
+        memset(out, 0, bytes);
+        return MPT_OK;
+    }
+    HIPCHK(hipMemcpyAsync(out, ctx->d_m2, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+static int read_tile_samples_impl(mpt_ctx* ctx, uint32_t* out) {
+    if (!ctx->d_sum) return fail(ctx, MPT_ERR_NOT_READY, "mpt_resize not called");
+    int rc = wait_impl(ctx);
+    if (rc) return rc;
+    const size_t n = (size_t)((ctx->W + 7) / 8) * ((ctx->H + 7) / 8);
+    if (!ctx->d_tile_count) {   // (no adaptive render since the resize)
+        memset(out, 0, n * 4);
+        return MPT_OK;
+    }
+    HIPCHK(hipMemcpyAsync(out, ctx->d_tile_count, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+static int ensure_adaptive_buffers(mpt_ctx* ctx, uint32_t tiles) {
+    if (ctx->d_tile_count && ctx->ad_tiles == tiles) return MPT_OK;
+    hipFree(ctx->d_tile_count);
+    hipFree(ctx->d_alist[0]);
+    hipFree(ctx->d_alist[1]);
+    hipFree(ctx->d_aflag);
+    hipFree(ctx->d_nsel);
+    hipFree(ctx->d_sel_tmp);
+    ctx->d_tile_count = ctx->d_alist[0] = ctx->d_alist[1] = ctx->d_nsel = nullptr;
+    ctx->d_aflag = nullptr;
+    ctx->d_sel_tmp = nullptr;
+    ctx->sel_tmp_bytes = 0;
+    ctx->ad_tiles = 0;
+    HIPCHK(hipMalloc(&ctx->d_tile_count, (size_t)tiles * 4));
+    HIPCHK(hipMalloc(&ctx->d_alist[0], (size_t)tiles * 4));
+    HIPCHK(hipMalloc(&ctx->d_alist[1], (size_t)tiles * 4));
+    HIPCHK(hipMalloc(&ctx->d_aflag, tiles));
+    HIPCHK(hipMalloc(&ctx->d_nsel, 4));
+    size_t tmp = 0;
+    HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tmp, ctx->d_alist[0], ctx->d_aflag, ctx->d_alist[1], ctx->d_nsel, (int)tiles,
+                                         ctx->stream));
+    HIPCHK(hipMalloc(&ctx->d_sel_tmp, std::max<size_t>(tmp, 16)));
+    ctx->sel_tmp_bytes = tmp;
+    ctx->ad_tiles = tiles;
+    return MPT_OK;
+}
+static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_adaptive_params* a, mpt_adaptive_info* out) {
+    const uint32_t N = p->sample_count;
+    if (p->rng_mode == MPT_RNG_LITERAL) return fail(ctx, MPT_ERR_INVALID_ARG, "adaptive render with the literal RNG (no per-sample variance)");
+    if (p->shard_count != 1) return fail(ctx, MPT_ERR_INVALID_ARG, "adaptive render with shard_count != 1");
+    if (a->min_samples == 1u || !(a->threshold >= 0.0f) || N < 2u)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "bad adaptive params (min_samples 1, threshold < 0 or NaN, or sample_count < 2)");
+    int rc = check_ready(ctx, p);
+    if (rc) return rc;
+    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async)
+    const uint32_t min_s = a->min_samples ? a->min_samples : MPT_ADAPTIVE_DEFAULT_MIN_SAMPLES;
+    const uint32_t batch = a->batch_samples ? a->batch_samples : MPT_ADAPTIVE_DEFAULT_BATCH;
+    const float floor_l = a->luminance_floor > 0.0f ? a->luminance_floor : MPT_ADAPTIVE_DEFAULT_LUMINANCE_FLOOR;
+    const uint32_t tiles_x = (ctx->W + 7) / 8, tiles_y = (ctx->H + 7) / 8, tiles = tiles_x * tiles_y;
+    if ((rc = ensure_adaptive_buffers(ctx, tiles))) return rc;
+    if ((rc = clear_sum_impl(ctx))) return rc;   // (the sum, and the moments if they exist yet: ordered before the first resolve)
+    HIPCHK(hipMemsetAsync(ctx->d_tile_count, 0, (size_t)tiles * 4, ctx->stream));
+    ctx->stats.trace_kernel_ms = 0;   // (totals over the passes, as one mpt_render reports its own)
+    ctx->stats.trace_launches = 0;
+    ctx->stats.total_ms = 0;
+    mpt_render_params q = *p;
+    q.flags |= MPT_FLAG_MOMENTS;
+    uint32_t n = 0, passes = 0, n_active = 0, cur = 0;
+    const uint32_t* list = nullptr;   // pass 0: the full tile table itself
+    for (;;) {
+        const uint32_t n_next = passes == 0 ? std::min(min_s, N) : (uint32_t)std::min<uint64_t>((uint64_t)n + batch, N);
+        q.sample_begin = p->sample_begin + n;
+        q.sample_count = n_next - n;
+        ctx->next_lane = 0;   // every pass on lane 0, whose stream is ctx->stream: the evaluation below follows its resolve in stream order
+        {
+            SyncRenderScope sync(ctx);
+            const TileOverride ovr{list, n_active};
+            rc = render_async_impl(ctx, &q, list ? &ovr : nullptr);
+        }
+        if (rc) return rc;
+        if ((rc = wait_impl(ctx))) return rc;
+        passes++;
+        n = n_next;
+        if (!list) {
+            list = ctx->d_tile_xy;   // (built by pass 0; one rank: every tile, in the table's order)
+            n_active = ctx->tile_count;
+        }
+        AdaptiveEval ev;
+        ev.list = list;
+        ev.n_list = n_active;
+        ev.sum = ctx->d_sum;
+        ev.m2 = ctx->d_m2;
+        ev.width = ctx->W;
+        ev.height = ctx->H;
+        ev.tiles_x = tiles_x;
+        ev.n = n;
+        ev.n_max = N;
+        ev.threshold = (double)a->threshold;
+        ev.luminance_floor = (double)floor_l;
+        ev.tile_count = ctx->d_tile_count;
+        ev.flag = ctx->d_aflag;
+        hipLaunchKernelGGL(k_adaptive_eval, dim3((n_active + 3u) / 4u), dim3(256), 0, ctx->stream, ev);
+        HIPCHK(hipGetLastError());
+        uint32_t* next = ctx->d_alist[cur];
+        size_t tmp = ctx->sel_tmp_bytes;
+        HIPCHK(hipcub::DeviceSelect::Flagged(ctx->d_sel_tmp, tmp, list, ctx->d_aflag, next, ctx->d_nsel, (int)n_active, ctx->stream));
+        uint32_t kept = 0;
+        HIPCHK(hipMemcpyAsync(&kept, ctx->d_nsel, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (kept == 0u) break;   // (every tile stopped: a tile at N is never flagged)
+        if (kept > n_active) return fail(ctx, MPT_ERR_HIP, "adaptive compaction kept more tiles than it was given (internal)");
+        list = next;
+        n_active = kept;
+        cur ^= 1u;
+    }
+    std::vector<uint32_t> counts(tiles);
+    HIPCHK(hipMemcpy(counts.data(), ctx->d_tile_count, (size_t)tiles * 4, hipMemcpyDeviceToHost));
+    mpt_adaptive_info info = {};
+    for (uint32_t t = 0; t < tiles; ++t) {
+        const uint32_t tx = t % tiles_x, ty = t / tiles_x;
+        const uint64_t px = (uint64_t)std::min<uint32_t>(8u, ctx->W - tx * 8u) * std::min<uint32_t>(8u, ctx->H - ty * 8u);
+        info.samples += px * counts[t];
+        (counts[t] == N ? info.tiles_at_max : info.tiles_converged)++;
+    }
+    info.passes = passes;
+    *out = info;
+    return MPT_OK;
 }
 
 // ---- unit-test entry points -----------------------------------------------------------------------------------
@@ -2096,6 +2279,18 @@ extern "C" int mpt_render(mpt_ctx* ctx, const mpt_render_params* p) {
 }
 extern "C" int mpt_render_async(mpt_ctx* ctx, const mpt_render_params* p) {
     return guarded<false>(ctx, [&] { return enqueue_render(ctx, p); });
+}
+extern "C" int mpt_render_adaptive(mpt_ctx* ctx, const mpt_render_params* p, const mpt_adaptive_params* a, mpt_adaptive_info* out) {
+    if (!ctx || !p || !a || !out) return MPT_ERR_INVALID_ARG;   // (before anything touches the context or a device)
+    return guarded(ctx, [&] { return render_adaptive_impl(ctx, p, a, out); });
+}
+extern "C" int mpt_read_moments(mpt_ctx* ctx, float* rgba_host) {
+    if (!ctx || !rgba_host) return MPT_ERR_INVALID_ARG;
+    return guarded(ctx, [&] { return read_moments_impl(ctx, rgba_host); });
+}
+extern "C" int mpt_read_tile_samples(mpt_ctx* ctx, uint32_t* counts) {
+    if (!ctx || !counts) return MPT_ERR_INVALID_ARG;
+    return guarded(ctx, [&] { return read_tile_samples_impl(ctx, counts); });
 }
 extern "C" int mpt_async_info(mpt_ctx* ctx, uint64_t out[4]) {
     if (!ctx || !out) return MPT_ERR_INVALID_ARG;

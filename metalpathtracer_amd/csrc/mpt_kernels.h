@@ -1037,6 +1037,44 @@ __global__ __launch_bounds__(256, 8) void k_resolve_sum(PassParams pp, float4* s
     }
 }
 
+// k_resolve_sum with MPT_FLAG_MOMENTS: the same HDR-sum additions in the same order (the sum is bit-identical), and beside them
+// m2[pixel] += (v.x^2, v.y^2, v.z^2, l^2) per sample, l = the luminance of dn_lum (mpt_denoise.h).  Same launch bound and footprint rule.
+__device__ __forceinline__ void add_moments(float4& m, const float4& v) {
+    const float l = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z;
+    m.x += v.x * v.x; m.y += v.y * v.y; m.z += v.z * v.z; m.w += l * l;
+}
+__global__ __launch_bounds__(256, 8) void k_resolve_sum_moments(PassParams pp, float4* sum, float4* m2, uint32_t n_local_tiles) {
+    const uint32_t n = n_local_tiles * 64u;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const uint32_t tl = i >> 6, lane = i & 63u;
+        uint32_t px, py, s0;
+        if (!path_to_pixel(pp, (tl * pp.S) * 64u + lane, px, py, s0)) continue;
+        float4 acc = sum[py * pp.width + px];
+        float4 m = m2[py * pp.width + px];
+        const uint32_t base = tl * pp.S;
+        uint32_t s = 0;
+        for (; s + 4u <= pp.S; s += 4u) {
+            const float4 v0 = load_slot(pp.slots, (base + s) * 64u + lane), v1 = load_slot(pp.slots, (base + s + 1u) * 64u + lane),
+                         v2 = load_slot(pp.slots, (base + s + 2u) * 64u + lane), v3 = load_slot(pp.slots, (base + s + 3u) * 64u + lane);
+            acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+            acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
+            acc.x += v2.x; acc.y += v2.y; acc.z += v2.z; acc.w += v2.w;
+            acc.x += v3.x; acc.y += v3.y; acc.z += v3.z; acc.w += v3.w;
+            add_moments(m, v0);
+            add_moments(m, v1);
+            add_moments(m, v2);
+            add_moments(m, v3);
+        }
+        for (; s < pp.S; ++s) {
+            const float4 v = load_slot(pp.slots, (base + s) * 64u + lane);
+            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            add_moments(m, v);
+        }
+        sum[py * pp.width + px] = acc;
+        m2[py * pp.width + px] = m;
+    }
+}
+
 // Fragment.metal:23-27,62-69 — running mean with the frameCount+1 weight and the clamp.
 __global__ void k_resolve_frame(PassParams pp, const float4* last, float4* cur, uint32_t n_local_tiles,
                                 unsigned long long frameCount) {

@@ -23,7 +23,7 @@ SYMBOLS = (
     "mpt_renderer_drawable_size_will_change", "mpt_renderer_set_params", "mpt_renderer_draw", "mpt_renderer_input",
     "mpt_renderer_read_frame", "mpt_renderer_render_batch", "mpt_renderer_read_sum", "mpt_renderer_clear_sum",
     "mpt_renderer_uniforms", "mpt_renderer_stats", "mpt_renderer_context", "mpt_renderer_scene", "mpt_write_pfm",
-    "mpt_write_ppm", "mpt_renderer_denoise",
+    "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
 )
 
 _lib = None
@@ -65,6 +65,8 @@ def load():
     L.mpt_renderer_uniforms.argtypes = [vp, C.POINTER(capi.Uniforms)]
     L.mpt_renderer_stats.argtypes = [vp, C.POINTER(capi.Stats)]
     L.mpt_renderer_denoise.argtypes = [vp, C.POINTER(capi.DenoiseParams), fp]
+    L.mpt_renderer_render_adaptive.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(capi.AdaptiveParams),
+                                               C.POINTER(capi.AdaptiveInfo)]
     L.mpt_renderer_context.argtypes = [vp]
     L.mpt_renderer_context.restype = vp
     L.mpt_renderer_scene.argtypes = [vp]
@@ -283,6 +285,21 @@ class Renderer:
 
     def renderBatch(self, sample_begin, sample_count):
         self._chk(self.L.mpt_renderer_render_batch(self.h, int(sample_begin), int(sample_count)), "renderBatch")
+
+    def renderAdaptive(self, sample_begin, max_samples, threshold, min_samples=0, batch_samples=0, luminance_floor=0.0):
+        """mpt_renderer_render_adaptive: the mpt_adaptive_info as a dict (counts per tile: capi's read_tile_samples on context())."""
+        a = capi.AdaptiveParams(int(min_samples), int(batch_samples), float(threshold), float(luminance_floor))
+        info = capi.AdaptiveInfo()
+        self._chk(self.L.mpt_renderer_render_adaptive(self.h, int(sample_begin), int(max_samples), C.byref(a), C.byref(info)),
+                  "renderAdaptive")
+        return info.as_dict()
+
+    def readTileSamples(self):
+        """Samples per 8x8 tile of the last renderAdaptive: (tiles_y, tiles_x) uint32 (mpt_read_tile_samples on the context)."""
+        out = np.empty(((self.height + 7) // 8, (self.width + 7) // 8), np.uint32)
+        ctx = self.L.mpt_renderer_context(self.h)
+        self._chk(capi.load().mpt_read_tile_samples(ctx, out.ctypes.data_as(C.POINTER(C.c_uint32))), "readTileSamples")
+        return out
 
     def readSum(self):
         out = np.empty((self.height, self.width, 4), np.float32)
