@@ -21,6 +21,7 @@
 #include "mpt_accel.h"
 #include "mpt_device.h"
 #include "mpt_lbvh.h"
+#include "mpt_own.h"
 #include "mpt_radix.h"
 
 namespace mpt_devbuild {
@@ -599,22 +600,17 @@ __global__ void k_always(Scalars* sc, float4* dprims, const float4* refleaf, flo
 }
 
 // Everything above, in order, on one stream.  Inputs: the caller's primitive and material arrays, ALREADY on the device
-// (d_prims_in: 3 float4 per primitive, d_mats_in: 2 float4 per primitive).  All outputs are hipMalloc'ed here and handed to
-// the caller (who frees them); scratch is freed on return.
+// (d_prims_in: 3 float4 per primitive, d_mats_in: 2 float4 per primitive).  All outputs are allocated here and handed to
+// the caller (who takes `block`); scratch is freed on return.
 struct Built {
     // views into `block` (ONE allocation, sized from upper bounds before the first kernel: n_out <= 2n - 1 nodes, <= n leaves, <= n + 2 wide
     // nodes, <= n materials — ~390 bytes per primitive; until round 4 nine hipMallocs of the exact sizes sat on the build's critical path)
     float4 *nodes = nullptr, *prims = nullptr, *mats = nullptr, *acc_nodes = nullptr, *refleaf = nullptr, *refbox = nullptr, *always = nullptr;
     float4* ref_bvh = nullptr;   // the same tree in the reference's buffer format (2 float4 per node) ...
     int* ref_idx = nullptr;      // ... and its primitiveIndices
-    void* block = nullptr;
-    size_t block_bytes = 0;
+    mpt_own::DevMem<> block;
     uint32_t n_nodes = 0, n_prims = 0, n_mats = 0, n_acc_nodes = 0, n_always = 0, n_ref_leaves = 0, acc_depth = 0, n_spheres = 0;
     float tri_extent = 0.0f;
-    void release() {
-        hipFree(block);
-        *this = Built{};
-    }
 };
 static size_t out_block_bytes(uint32_t n) {
     const size_t nn = 2 * (size_t)n - 1, al = 256;
@@ -625,12 +621,12 @@ static size_t out_block_bytes(uint32_t n) {
     return total;
 }
 
-// spare / spare_bytes (in, out): a device allocation the caller has no more use for — taken for the outputs if it is large enough.
+// spare (in, out): a device allocation the caller has no more use for — taken for the outputs if it is large enough.
 // mats_host (may be null): the caller's material array in host memory, NOT yet copied to d_mats_in — the copy is then made here, on the side
 // stream by a helper thread (a copy from pageable memory keeps its host thread for its whole length: 1.1 ms for the 32 MB of 1 M
 // primitives), while this thread drives the tree build on the main stream.
 static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_mats_in, const float* mats_host, uint32_t n, int leaf_max, int builder,
-                             uint32_t n_spheres_hint, Built& out, mpt_lbvh::ScratchPool* pool, void** spare, size_t* spare_bytes, bool wide_mat_sort, bool* mat_collision) {
+                             uint32_t n_spheres_hint, Built& out, mpt_lbvh::ScratchPool* pool, mpt_own::DevMem<>* spare, bool wide_mat_sort, bool* mat_collision) {
     Scratch sc(pool);
     // Two streams (round 5): the material chain (hash, sort, table: ~0.19 ms of small kernels for 1 M primitives) needs nothing of the tree until
     // the leaves are written, and the threaded tree (depths, their sort, the emission: ~0.13 ms) nothing of the own tree's collapse — each runs
@@ -654,16 +650,11 @@ static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_m
     };
     {
         const size_t need = out_block_bytes(n);
-        if (spare && *spare && *spare_bytes >= need) {
-            out.block = *spare;
-            out.block_bytes = *spare_bytes;
-            *spare = nullptr;
-            *spare_bytes = 0;
-        } else {
-            MPT_LB(hipMalloc(&out.block, need));
-            out.block_bytes = need;
-        }
-        char* q = (char*)out.block;
+        if (spare && spare->bytes() >= need)
+            out.block = std::move(*spare);
+        else
+            MPT_LB(out.block.alloc(need));
+        char* q = (char*)out.block.get();
         auto carve = [&](size_t bytes) {
             char* r = q;
             q += (bytes + 255) & ~(size_t)255;
@@ -986,18 +977,15 @@ static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_m
     return hipSuccess;
 }
 static hipError_t build(hipStream_t stream, float4* d_prims_in, float4* d_mats_in, const float* mats_host, uint32_t n, int leaf_max, int builder, uint32_t n_spheres_hint,
-                        Built& out, mpt_lbvh::ScratchPool* pool = nullptr, void** spare = nullptr, size_t* spare_bytes = nullptr) {
+                        Built& out, mpt_lbvh::ScratchPool* pool = nullptr, mpt_own::DevMem<>* spare = nullptr) {
     bool collision = false;
-    MPT_LB(build_pass(stream, d_prims_in, d_mats_in, mats_host, n, leaf_max, builder, n_spheres_hint, out, pool, spare, spare_bytes, false, &collision));
+    MPT_LB(build_pass(stream, d_prims_in, d_mats_in, mats_host, n, leaf_max, builder, n_spheres_hint, out, pool, spare, false, &collision));
     if (!collision) return hipSuccess;
     // two different materials share the upper half of their hashes (one scene in ~2^33 / materials^2): once more, sorted on all 64 bits,
-    // into the same block
-    void* block = out.block;
-    size_t bytes = out.block_bytes;
+    // into the same block (freed on return if the pass fails before it takes it)
+    mpt_own::DevMem<> block = std::move(out.block);
     out = Built{};
-    const hipError_t e = build_pass(stream, d_prims_in, d_mats_in, nullptr, n, leaf_max, builder, n_spheres_hint, out, pool, &block, &bytes, true, &collision);   // (the materials are on the device by now)
-    if (block) hipFree(block);   // (not taken: the pass failed before it got there)
-    return e;
+    return build_pass(stream, d_prims_in, d_mats_in, nullptr, n, leaf_max, builder, n_spheres_hint, out, pool, &block, true, &collision);   // (the materials are on the device by now)
 }
 
 }  // namespace mpt_devbuild

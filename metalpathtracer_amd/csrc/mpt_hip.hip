@@ -28,6 +28,7 @@
 #include "mpt.h"
 #include "mpt_accel.h"
 #include "mpt_device.h"
+#include "mpt_own.h"
 
 #include "mpt_kernels.h"
 #include "mpt_lbvh.h"
@@ -78,23 +79,30 @@ static OtBudgets default_ot_budgets() {
     return b;
 }
 
+using mpt_own::DevMem;
+using mpt_own::Event;
+using mpt_own::HostMem;
+using mpt_own::Stream;
+
 struct Lane {
-    hipStream_t stream = nullptr;
-    QueueDev q[2] = {};
-    uint32_t shard_cap = 0;
-    float4* d_slots = nullptr;
-    uint64_t slots_cap = 0;
-    PassDesc* d_desc = nullptr;
-    uint32_t* d_ctr = nullptr;
-    uint32_t* h_done = nullptr;  // pinned, device-visible
-    PassDesc* h_desc = nullptr;  // pinned copy of the pass descriptor (statistics read-back without a sync copy)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_resolved = nullptr, ev_traced = nullptr;
-    std::vector<hipEvent_t> ev_pool;
+    Stream stream;
+    DevMem<PassDesc> d_desc;
+    DevMem<uint32_t> d_ctr;
+    HostMem<uint32_t> h_done;    // pinned, device-visible
+    HostMem<PassDesc> h_desc;    // pinned copy of the pass descriptor (statistics read-back without a sync copy)
+    Event ev0, ev1, ev_resolved, ev_traced;
+    std::vector<Event> ev_pool;  // kernel-timing events (next_event)
     size_t ev_used = 0;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_timed;  // kernel-event pairs to read at collection
-    WaveRings ring = {};         // wave-local pipeline: MPT_WL_LEVELS rings of MPT_WL_RING records per wave
+    // workspace, allocated on first use and only ever grown
+    DevMem<float4> d_slots;      // per-path result slots of a pass
+    DevMem<float4> q_od[2], q_dt[2], q_tl[2];   // the wavefront pipeline's two global ray queues (QueueDev), shard_cap items per shard
+    DevMem<uint2> q_ia[2];
+    uint32_t shard_cap = 0;
+    DevMem<float4> ring_mem, ot_ring_mem;
+    WaveRings ring = {};         // wave-local pipeline: MPT_WL_LEVELS rings of MPT_WL_RING records per wave (in ring_mem)
     size_t ring_waves = 0;
-    OtRings ot_ring = {};        // ... and its rings (MPT_OT_RINGS per wave)
+    OtRings ot_ring = {};        // ... and its rings (MPT_OT_RINGS per wave, in ot_ring_mem)
     size_t ot_ring_waves = 0;
     uint32_t announced_id = 0;   // launch id of the lane's last trace kernel that announces its residency (0: none)
     bool in_flight = false;      // enqueued by mpt_render_async, not yet collected
@@ -119,7 +127,50 @@ struct Submitter {
 };
 #define MPT_ASYNC_QUEUE_MAX 64   // queued renders beyond this make mpt_render_async wait for room (back pressure, not an error)
 
-struct mpt_ctx {
+// One scene on the device, made whole by mpt_upload_scene or mpt_build_and_upload and put in place of the one before by install_scene.
+// The arrays of a built scene are views into ONE device allocation (scene_block: nine hipMallocs on the build's critical path were
+// ~0.3 ms of a 4.3 ms build); those of an uploaded scene own their allocations one by one (scene_bufs).
+struct SceneState {
+    DevMem<> scene_block;
+    std::vector<DevMem<>> scene_bufs;
+    float4* d_nodes = nullptr;
+    float4* d_prims = nullptr;
+    float4* d_mats = nullptr;
+    uint32_t n_nodes = 0, n_prims = 0, n_mats = 0, n_lds_nodes = 0, n_lds_prims = 0;
+    // the product's own tree (mpt_accel.h) for the closest-first pipeline; it shares d_prims with the threaded tree
+    float4* d_acc_nodes = nullptr;
+    float4* d_refleaf = nullptr;
+    float4* d_refbox = nullptr;       // the box of its reference leaf PER PRIMITIVE, 2 float4 each: the final check of the closest-first walk needs no look-up through the primitive
+    float4* d_always = nullptr;
+    uint32_t n_acc_nodes = 0, n_always = 0, n_ref_leaves = 0, acc_depth = 0;
+    // mpt_build_and_upload keeps its tree in the reference's buffer format on the device too (mpt_download_bvh)
+    float4* d_ref_bvh = nullptr;
+    int* d_ref_idx = nullptr;
+    uint32_t n_ref_nodes = 0;
+    uint32_t built_leaf_max = 0;     // leaf limit of that tree (mpt_build_info)
+    float tri_extent = 0.0f, acc_eps_abs = 0.0f;
+    bool acc_ok = false;             // the closest-first pipeline may be used for this scene
+    std::string acc_why;
+    hipError_t own(float4** p, size_t bytes) {   // an array of an uploaded scene
+        scene_bufs.emplace_back();
+        const hipError_t e = scene_bufs.back().alloc(bytes);
+        *p = (float4*)scene_bufs.back().get();
+        return e;
+    }
+};
+
+// mpt_render_adaptive's tile buffers, for `tiles` tiles (allocated by its first call after a resize; mpt_resize drops them)
+struct AdaptiveTiles {
+    DevMem<uint32_t> tile_count;   // samples per tile, row-major
+    DevMem<uint32_t> alist[2];     // ping-pong active tile lists (x | y << 16)
+    DevMem<uint8_t> aflag;         // per list entry: the tile stays active
+    DevMem<uint32_t> nsel;         // entries DeviceSelect::Flagged kept
+    DevMem<> sel_tmp;              // its temporary storage ...
+    size_t sel_tmp_bytes = 0;      // ... of the size it asked for
+    uint32_t tiles = 0;
+};
+
+struct mpt_ctx : SceneState {
     int device = 0;
     std::unique_ptr<Submitter> sub;      // mpt_render_async's submit thread (none until the first asynchronous render)
     uint64_t async_jobs = 0;             // renders submitted by that thread
@@ -136,22 +187,12 @@ struct mpt_ctx {
     uint32_t launch_seq = 0;             // launch ids of the trace kernels (never 0)
     Lane* last_trace_lane = nullptr;     // lane of the last trace kernel enqueued
     int lane_order = 5;                  // MPT_LANE_ORDER: bit 0 = the event chain between trace kernels, bit 2 = the residency gate for overlapping k_wavelocal renders (run_pass), bit 1 = lane 0's stream has the higher priority (no effect measured)
-    hipEvent_t ev_sum_op = nullptr;      // recorded behind mpt_clear_sum
+    Event ev_sum_op;                     // recorded behind mpt_clear_sum
     hipDeviceProp_t prop;
     std::string err;
     std::mutex err_mu;                   // writers of `err`: the caller's thread and the submit thread (set_err)
-    // scene
-    float4* d_nodes = nullptr;
-    float4* d_prims = nullptr;
-    float4* d_mats = nullptr;
-    uint32_t n_nodes = 0, n_prims = 0, n_mats = 0, n_lds_nodes = 0, n_lds_prims = 0;
+    // scene (struct SceneState)
     bool have_scene = false;
-    // the product's own tree (mpt_accel.h) for the closest-first pipeline; it shares d_prims with the threaded tree
-    float4* d_acc_nodes = nullptr;
-    float4* d_refleaf = nullptr;
-    float4* d_refbox = nullptr;       // the box of its reference leaf PER PRIMITIVE, 2 float4 each: the final check of the closest-first walk needs no look-up through the primitive
-    float4* d_always = nullptr;
-    uint32_t n_acc_nodes = 0, n_always = 0, n_ref_leaves = 0, acc_depth = 0;
     // the two operating points of the closest-first kernel (mpt_ordered.h: k_ordered<.., 5> = 5 x 256 threads per CU, k_ordered<.., 6> = 2 x 768) and
     // what each stages in LDS for the scene at hand (size_lds_images)
     struct OtPoint {
@@ -159,41 +200,29 @@ struct mpt_ctx {
     } ot_pt[2] = {{MPT_OT_THREADS, MPT_OT_WGS_PER_CU, 0, 0}, {MPT_OT6_THREADS, (MPT_OT6_WAVES * 256) / MPT_OT6_THREADS, 0, 0}};
     int ot_occ = 0;                  // MPT_OT_OCC: 5 / 6 forces an operating point, 0 = by scene size (ordered_point)
     bool tile_order_forced = false;  // MPT_TILE_ORDER was given
-    // mpt_build_and_upload keeps its tree in the reference's buffer format on the device too (mpt_download_bvh)
-    float4* d_ref_bvh = nullptr;
-    int* d_ref_idx = nullptr;
-    uint32_t n_ref_nodes = 0;
-    uint32_t built_leaf_max = 0;     // leaf limit of that tree (mpt_build_info)
     uint32_t ot_stack_depth = 8;     // LDS stack entries per lane (MPT_OT_STACK); deeper entries spill to global memory
     mpt_lbvh::ScratchPool build_pool;  // scratch chunks of the GPU builders, kept between builds (<= 2 GiB)
-    // The arrays of a scene made by mpt_build_and_upload are views into ONE device allocation (scene_block: nine hipMallocs on the
-    // build's critical path were ~0.3 ms of a 4.3 ms build); the block of the scene before is kept as the next build's (spare_block),
-    // so a rebuild allocates nothing and a failed build leaves the old scene intact.  Scenes of mpt_upload_scene own their arrays one by one.
-    void* scene_block = nullptr;
-    void* spare_block = nullptr;
-    void* in_block = nullptr;          // device staging of mpt_build_and_upload's input arrays, kept between builds
-    size_t in_block_bytes = 0;
-    size_t scene_block_bytes = 0, spare_block_bytes = 0;
+    // the block of the built scene before is kept as the next build's (install_scene), so a rebuild allocates nothing
+    DevMem<> spare_block;
+    DevMem<> in_block;                 // device staging of mpt_build_and_upload's input arrays, kept between builds
     OtBudgets ot_budgets = default_ot_budgets();
-    float tri_extent = 0.0f, acc_eps_abs = 0.0f, acc_cull_rel = 9.765625e-4f;
-    bool acc_ok = false;             // the closest-first pipeline may be used for this scene
-    std::string acc_why;
+    float acc_cull_rel = 9.765625e-4f;
     // uniforms / size
     mpt_uniforms u;
     bool have_uniforms = false;
     uint32_t W = 0, H = 0;
-    float4* d_accum[2] = {nullptr, nullptr};
+    DevMem<float4> d_accum[2];
     int cur_target = 0;
-    float4* d_sum_own = nullptr;
-    float4* d_sum = nullptr;
+    DevMem<float4> d_sum_own;
+    float4* d_sum = nullptr;             // d_sum_own, or the caller's buffer (mpt_set_sum_buffer)
     // this rank's tile processing order (x | y << 16), rebuilt when size or sharding changes
-    uint32_t* d_tile_xy = nullptr;
+    DevMem<uint32_t> d_tile_xy;
     uint32_t tile_W = 0, tile_H = 0, tile_rank = 0, tile_nranks = 0, tile_count = 0;
     int tile_mode_built = -1;   // tile order the table was built for (tile_order_of)
     int tile_order_mode = 0;  // 0 row-major top-down (measured best with guided claims: the cheap sky tiles take the
                               // large early claims, the expensive tiles the small late ones), 1 strided, 2 bottom-up
     // literal RNG seeds
-    uint32_t* d_pixel_seed = nullptr;
+    DevMem<uint32_t> d_pixel_seed;
     float seed_rs[3] = {NAN, NAN, NAN};
     uint32_t seed_W = 0, seed_H = 0;
     // launch geometry
@@ -217,27 +246,21 @@ struct mpt_ctx {
     mpt_stats stats = {};
     // denoiser (mpt_denoise.h): the first-hit guide buffers, traced again when stale, and the filter's own buffers (W x H each,
     // allocated by the first mpt_read_aovs / mpt_denoise after a resize)
-    float4* d_aov_ad = nullptr;     // (albedo rgb, t)
-    float4* d_aov_nc = nullptr;     // (normal rgb, class)
-    int* d_aov_prim = nullptr;      // caller's primitive id, -1 = miss
-    float4* d_dn_guide = nullptr;   // packed per-tap guide (normal, t or MPT_DN_SKIP)
-    float4* d_dn_x[2] = {nullptr, nullptr};   // ping-pong (x rgb, luminance) of the levels
-    float4* d_denoised = nullptr;
+    DevMem<float4> d_aov_ad;        // (albedo rgb, t)
+    DevMem<float4> d_aov_nc;        // (normal rgb, class)
+    DevMem<int> d_aov_prim;         // caller's primitive id, -1 = miss
+    DevMem<float4> d_dn_guide;      // packed per-tap guide (normal, t or MPT_DN_SKIP)
+    DevMem<float4> d_dn_x[2];       // ping-pong (x rgb, luminance) of the levels
+    DevMem<float4> d_denoised;
     uint32_t dn_W = 0, dn_H = 0;    // size of those buffers
     uint64_t guide_epoch = 1;       // bumped by every scene upload / build and every mpt_resize
     uint64_t guide_built = 0;       // the epoch the guide buffers were traced in (0 = never)
     float guide_cam[14] = {};       // camera fields of the uniforms they were traced with
     bool denoised_valid = false;    // d_denoised holds the result of an mpt_denoise at the current size
     // adaptive sampling (mpt_adaptive.h): the moments buffer (W x H, allocated by the first render with MPT_FLAG_MOMENTS) and the
-    // tile buffers of mpt_render_adaptive (allocated by its first call after a resize); mpt_resize frees them all
-    float4* d_m2 = nullptr;
-    uint32_t* d_tile_count = nullptr;            // samples per tile, row-major
-    uint32_t* d_alist[2] = {nullptr, nullptr};   // ping-pong active tile lists (x | y << 16)
-    uint8_t* d_aflag = nullptr;                  // per list entry: the tile stays active
-    uint32_t* d_nsel = nullptr;                  // entries DeviceSelect::Flagged kept
-    void* d_sel_tmp = nullptr;                   // its temporary storage, sized once per tile count
-    size_t sel_tmp_bytes = 0;
-    uint32_t ad_tiles = 0;                       // tile count the tile buffers were allocated for
+    // tile buffers of mpt_render_adaptive; mpt_resize drops both
+    DevMem<float4> d_m2;
+    AdaptiveTiles ad;
 };
 
 // kernel variants: COUNT (work counters) x ALL_LDS (the whole BVH fits the LDS budget)
@@ -307,35 +330,28 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return MPT_ERR_NO_DEVICE;
     if (device_ordinal < 0 || device_ordinal >= n) return MPT_ERR_NO_DEVICE;
-    mpt_ctx* ctx = new mpt_ctx();
+    std::unique_ptr<mpt_ctx> ctx(new mpt_ctx());   // (an early return frees what has been made so far)
     ctx->device = device_ordinal;
-    auto bail = [&](int code) {
-        mpt_destroy(ctx);
-        return code;
-    };
-    if (hipSetDevice(device_ordinal) != hipSuccess) return bail(MPT_ERR_HIP);
-    if (hipGetDeviceProperties(&ctx->prop, device_ordinal) != hipSuccess) return bail(MPT_ERR_HIP);
+    if (hipSetDevice(device_ordinal) != hipSuccess) return MPT_ERR_HIP;
+    if (hipGetDeviceProperties(&ctx->prop, device_ordinal) != hipSuccess) return MPT_ERR_HIP;
     if (const char* lo = getenv("MPT_LANE_ORDER")) ctx->lane_order = atoi(lo);
     if (const char* rw = getenv("MPT_RESOLVE_WGS")) ctx->resolve_wgs_per_cu = std::max(0, atoi(rw));
     int prio_lo = 0, prio_hi = 0;   // (numerically lower = higher priority)
     if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
     for (Lane& L : ctx->lane) {  // small per-lane state now; slots, rings and queues are allocated on first use
-        if (ctx->lane_order & 2) {
-            if (hipStreamCreateWithPriority(&L.stream, hipStreamNonBlocking, &L == &ctx->lane[0] ? prio_hi : prio_lo) != hipSuccess) return bail(MPT_ERR_HIP);
-        } else if (hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) != hipSuccess) return bail(MPT_ERR_HIP);
-        if (hipMalloc(&L.d_desc, sizeof(PassDesc)) != hipSuccess) return bail(MPT_ERR_HIP);
-        if (hipMemset(L.d_desc, 0, sizeof(PassDesc)) != hipSuccess) return bail(MPT_ERR_HIP);
-        if (hipMalloc(&L.d_ctr, MPT_CTR_WORDS * 4) != hipSuccess) return bail(MPT_ERR_HIP);
-        if (hipMemset(L.d_ctr, 0, MPT_CTR_WORDS * 4) != hipSuccess) return bail(MPT_ERR_HIP);
-        if (hipHostMalloc((void**)&L.h_done, 64, hipHostMallocMapped) != hipSuccess) return bail(MPT_ERR_HIP);
-        if (hipHostMalloc((void**)&L.h_desc, sizeof(PassDesc), hipHostMallocDefault) != hipSuccess) return bail(MPT_ERR_HIP);
-        memset((void*)L.h_done, 0, 64);   // (every word: the residency gate polls word MPT_HOST_RESIDENT against small launch ids — ADVICE r4)
-        if (hipEventCreate(&L.ev0) != hipSuccess || hipEventCreate(&L.ev1) != hipSuccess ||
-            hipEventCreate(&L.ev_resolved) != hipSuccess || hipEventCreateWithFlags(&L.ev_traced, hipEventDisableTiming) != hipSuccess)
-            return bail(MPT_ERR_HIP);
+        const int prio = &L == &ctx->lane[0] ? prio_hi : prio_lo;
+        if (((ctx->lane_order & 2) ? L.stream.create(hipStreamCreateWithPriority, hipStreamNonBlocking, prio)
+                                   : L.stream.create(hipStreamCreateWithFlags, hipStreamNonBlocking)) != hipSuccess ||
+            L.d_desc.alloc(sizeof(PassDesc)) != hipSuccess || hipMemset(L.d_desc.get(), 0, sizeof(PassDesc)) != hipSuccess ||
+            L.d_ctr.alloc(MPT_CTR_WORDS * 4) != hipSuccess || hipMemset(L.d_ctr.get(), 0, MPT_CTR_WORDS * 4) != hipSuccess ||
+            L.h_done.alloc(64, hipHostMallocMapped) != hipSuccess || L.h_desc.alloc(sizeof(PassDesc)) != hipSuccess ||
+            L.ev0.create(hipEventCreate) != hipSuccess || L.ev1.create(hipEventCreate) != hipSuccess ||
+            L.ev_resolved.create(hipEventCreate) != hipSuccess || L.ev_traced.create(hipEventCreateWithFlags, hipEventDisableTiming) != hipSuccess)
+            return MPT_ERR_HIP;
+        memset((void*)L.h_done.get(), 0, 64);   // (every word: the residency gate polls word MPT_HOST_RESIDENT against small launch ids — ADVICE r4)
     }
-    ctx->stream = ctx->lane[0].stream;
-    if (hipEventCreate(&ctx->ev_sum_op) != hipSuccess) return bail(MPT_ERR_HIP);
+    ctx->stream = ctx->lane[0].stream.get();
+    if (ctx->ev_sum_op.create(hipEventCreate) != hipSuccess) return MPT_ERR_HIP;
     const char* e;
     if ((e = getenv("MPT_WG_SIZE"))) ctx->wg_size = atoi(e);
     if ((e = getenv("MPT_WGS_PER_CU"))) ctx->wgs_per_cu = atoi(e);
@@ -418,112 +434,17 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     hipFuncSetAttribute((const void*)k_trace_rays_ordered, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_trace_rays, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_dn_guide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // (the image of k_trace_rays)
-    *out = ctx;
+    *out = ctx.release();
     return MPT_OK;
-}
-
-// Lets go of the scene's device arrays: one by one (mpt_upload_scene's), or the block they are views into (mpt_build_and_upload's), which
-// becomes the spare block of the next build if it is not larger than 1 GiB and larger than the spare there is.
-static void free_scene_buffers(mpt_ctx* ctx, bool keep_spare) {
-    if (ctx->scene_block) {
-        // (the larger of the two is the one worth keeping: a spare that is too small for the scenes being built is never taken)
-        if (keep_spare && ctx->scene_block_bytes <= ((size_t)1 << 30) && (!ctx->spare_block || ctx->scene_block_bytes > ctx->spare_block_bytes)) {
-            hipFree(ctx->spare_block);
-            ctx->spare_block = ctx->scene_block;
-            ctx->spare_block_bytes = ctx->scene_block_bytes;
-        } else {
-            hipFree(ctx->scene_block);
-        }
-        ctx->scene_block = nullptr;
-        ctx->scene_block_bytes = 0;
-    } else {
-        hipFree(ctx->d_nodes);
-        hipFree(ctx->d_prims);
-        hipFree(ctx->d_mats);
-        hipFree(ctx->d_acc_nodes);
-        hipFree(ctx->d_refbox);
-        hipFree(ctx->d_refleaf);
-        hipFree(ctx->d_always);
-        hipFree(ctx->d_ref_bvh);
-        hipFree(ctx->d_ref_idx);
-    }
-    ctx->d_nodes = ctx->d_prims = ctx->d_mats = ctx->d_acc_nodes = ctx->d_refbox = ctx->d_refleaf = ctx->d_always = ctx->d_ref_bvh = nullptr;
-    ctx->d_ref_idx = nullptr;
-}
-
-static void free_ot_rings(OtRings& r) {
-    hipFree(r.base);
-    r = OtRings{};
-}
-static void free_queues(Lane& L) {
-    for (int i = 0; i < 2; ++i) {
-        hipFree(L.q[i].od);
-        hipFree(L.q[i].dt);
-        hipFree(L.q[i].tl);
-        hipFree(L.q[i].ia);
-        L.q[i] = QueueDev{};
-    }
-    L.shard_cap = 0;
-}
-
-static void free_adaptive_buffers(mpt_ctx* ctx) {
-    hipFree(ctx->d_m2);
-    hipFree(ctx->d_tile_count);
-    hipFree(ctx->d_alist[0]);
-    hipFree(ctx->d_alist[1]);
-    hipFree(ctx->d_aflag);
-    hipFree(ctx->d_nsel);
-    hipFree(ctx->d_sel_tmp);
-    ctx->d_m2 = nullptr;
-    ctx->d_tile_count = nullptr;
-    ctx->d_alist[0] = ctx->d_alist[1] = nullptr;
-    ctx->d_aflag = nullptr;
-    ctx->d_nsel = nullptr;
-    ctx->d_sel_tmp = nullptr;
-    ctx->sel_tmp_bytes = 0;
-    ctx->ad_tiles = 0;
 }
 
 extern "C" int mpt_destroy(mpt_ctx* ctx) {
     if (!ctx) return MPT_ERR_INVALID_ARG;
     stop_submit(ctx);   // (renders still queued are submitted, then the thread ends)
     hipSetDevice(ctx->device);
-    for (Lane& L : ctx->lane)
-        if (L.stream) hipStreamSynchronize(L.stream);
-    free_scene_buffers(ctx, false);
-    hipFree(ctx->spare_block);
-    hipFree(ctx->in_block);
-    hipFree(ctx->d_accum[0]);
-    hipFree(ctx->d_accum[1]);
-    hipFree(ctx->d_sum_own);
-    hipFree(ctx->d_pixel_seed);
-    hipFree(ctx->d_tile_xy);
-    hipFree(ctx->d_aov_ad);
-    hipFree(ctx->d_aov_nc);
-    hipFree(ctx->d_aov_prim);
-    hipFree(ctx->d_dn_guide);
-    hipFree(ctx->d_dn_x[0]);
-    hipFree(ctx->d_dn_x[1]);
-    hipFree(ctx->d_denoised);
-    free_adaptive_buffers(ctx);
-    for (Lane& L : ctx->lane) {
-        hipFree(L.d_slots);
-        hipFree(L.d_desc);
-        hipFree(L.d_ctr);
-        hipFree(L.ring.base);
-        free_ot_rings(L.ot_ring);
-        free_queues(L);
-        if (L.h_done) hipHostFree(L.h_done);
-        if (L.h_desc) hipHostFree(L.h_desc);
-        if (L.ev0) hipEventDestroy(L.ev0);
-        if (L.ev1) hipEventDestroy(L.ev1);
-        if (L.ev_resolved) hipEventDestroy(L.ev_resolved);
-        if (L.ev_traced) hipEventDestroy(L.ev_traced);
-        for (auto e : L.ev_pool) hipEventDestroy(e);
-        if (L.stream) hipStreamDestroy(L.stream);
-    }
-    if (ctx->ev_sum_op) hipEventDestroy(ctx->ev_sum_op);
-    delete ctx;
+    for (Lane& L : ctx->lane)   // (nothing is freed while a kernel may still read it)
+        if (L.stream) hipStreamSynchronize(L.stream.get());
+    delete ctx;   // (and with it every resource it owns)
     return MPT_OK;
 }
 
@@ -587,14 +508,26 @@ static int ordered_point(const mpt_ctx* ctx, bool count) {
     return ctx->n_prims <= MPT_OT6_MAX_PRIMS ? 1 : 0;
 }
 
+// Puts a scene in place of the one before.  The block of a built scene it replaces becomes the next build's spare if it is not larger
+// than 1 GiB and larger than the spare there is (the larger of the two is the one worth keeping: a spare that is too small for the
+// scenes being built is never taken).
+static void install_scene(mpt_ctx* ctx, SceneState&& s) {
+    const DevMem<>& old = ctx->scene_block;
+    if (old && old.bytes() <= ((size_t)1 << 30) && (!ctx->spare_block || old.bytes() > ctx->spare_block.bytes()))
+        ctx->spare_block = std::move(ctx->scene_block);
+    static_cast<SceneState&>(*ctx) = std::move(s);
+    ctx->acc_eps_abs = ctx->tri_extent * 3.814697265625e-06f;  // 2^-18 of the largest triangle coordinate
+    size_lds_images(ctx);
+    ctx->have_scene = true;
+    ctx->guide_epoch++;
+}
+
 // the per-primitive reference-leaf boxes of an uploaded scene (k_prim_refbox, mpt_devbuild.h)
-static int make_prim_refbox(mpt_ctx* ctx) {
-    hipFree(ctx->d_refbox);
-    ctx->d_refbox = nullptr;
-    if (ctx->n_prims == 0 || ctx->d_refleaf == nullptr || ctx->n_ref_leaves == 0) return MPT_OK;
-    HIPCHK(hipMalloc(&ctx->d_refbox, (size_t)ctx->n_prims * 32));
-    hipLaunchKernelGGL(mpt_devbuild::k_prim_refbox, dim3((ctx->n_prims + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)ctx->d_prims,
-                       (const float4*)ctx->d_refleaf, ctx->n_prims, ctx->d_refbox);
+static int make_prim_refbox(mpt_ctx* ctx, SceneState& s) {
+    if (s.n_prims == 0 || s.d_refleaf == nullptr || s.n_ref_leaves == 0) return MPT_OK;
+    HIPCHK(s.own(&s.d_refbox, (size_t)s.n_prims * 32));
+    hipLaunchKernelGGL(mpt_devbuild::k_prim_refbox, dim3((s.n_prims + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)s.d_prims,
+                       (const float4*)s.d_refleaf, s.n_prims, s.d_refbox);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MPT_OK;
@@ -898,39 +831,33 @@ static int upload_scene_impl(mpt_ctx* ctx, const float* bvh, uint64_t n_nodes, c
         }
     }
 
-    free_scene_buffers(ctx, true);
-    ctx->n_ref_nodes = 0;
-    ctx->built_leaf_max = 0;
-    ctx->have_scene = false;
+    SceneState s;   // (the scene before stays in place until this one is complete)
     auto up = [&](float4** dst, const std::vector<float>& v, size_t min_floats) -> hipError_t {
-        hipError_t e = hipMalloc(dst, std::max(v.size(), min_floats) * 4);
+        hipError_t e = s.own(dst, std::max(v.size(), min_floats) * 4);
         if (e != hipSuccess || v.empty()) return e;
         return hipMemcpy(*dst, v.data(), v.size() * 4, hipMemcpyHostToDevice);
     };
-    HIPCHK(up(&ctx->d_nodes, dnodes, 8));
-    HIPCHK(up(&ctx->d_prims, dprims, 12));
-    HIPCHK(up(&ctx->d_mats, mat_table, 8));
-    HIPCHK(up(&ctx->d_acc_nodes, acc_nodes, MPT_ACCEL_NODE_FLOATS));
-    HIPCHK(up(&ctx->d_refleaf, refleaf, 8));
-    HIPCHK(up(&ctx->d_always, always, 20));
-    ctx->n_nodes = ND;
-    ctx->n_prims = (uint32_t)(dprims.size() / 12);
-    ctx->n_mats = (uint32_t)(mat_table.size() / 8);
-    ctx->n_acc_nodes = (uint32_t)(acc_nodes.size() / MPT_ACCEL_NODE_FLOATS);
-    ctx->n_always = (uint32_t)(always.size() / 20);
-    ctx->n_ref_leaves = (uint32_t)(refleaf.size() / 8);
+    HIPCHK(up(&s.d_nodes, dnodes, 8));
+    HIPCHK(up(&s.d_prims, dprims, 12));
+    HIPCHK(up(&s.d_mats, mat_table, 8));
+    HIPCHK(up(&s.d_acc_nodes, acc_nodes, MPT_ACCEL_NODE_FLOATS));
+    HIPCHK(up(&s.d_refleaf, refleaf, 8));
+    HIPCHK(up(&s.d_always, always, 20));
+    s.n_nodes = ND;
+    s.n_prims = (uint32_t)(dprims.size() / 12);
+    s.n_mats = (uint32_t)(mat_table.size() / 8);
+    s.n_acc_nodes = (uint32_t)(acc_nodes.size() / MPT_ACCEL_NODE_FLOATS);
+    s.n_always = (uint32_t)(always.size() / 20);
+    s.n_ref_leaves = (uint32_t)(refleaf.size() / 8);
     {
-        int rrc = make_prim_refbox(ctx);
+        int rrc = make_prim_refbox(ctx, s);
         if (rrc) return rrc;
     }
-    ctx->acc_depth = topo.depth;
-    ctx->tri_extent = tri_extent;
-    ctx->acc_eps_abs = tri_extent * 3.814697265625e-06f;  // 2^-18 of the largest triangle coordinate
-    ctx->acc_ok = nested && use_always;
-    ctx->acc_why = !nested ? "a child box is not inside its parent's box" : !use_always ? "more than 16 spheres" : "";
-    size_lds_images(ctx);
-    ctx->have_scene = true;
-    ctx->guide_epoch++;
+    s.acc_depth = topo.depth;
+    s.tri_extent = tri_extent;
+    s.acc_ok = nested && use_always;
+    s.acc_why = !nested ? "a child box is not inside its parent's box" : !use_always ? "more than 16 spheres" : "";
+    install_scene(ctx, std::move(s));
     return MPT_OK;
 }
 
@@ -949,21 +876,19 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
         if (wrc) return wrc;
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 2; ++i) {
-        hipFree(ctx->d_accum[i]);
-        ctx->d_accum[i] = nullptr;
+    // the buffers of the new size are made whole before they replace the old ones: a failure leaves the context as it was
+    const size_t bytes = (size_t)width * height * 16;
+    DevMem<float4> accum[2], sum;
+    for (DevMem<float4>* b : {&accum[0], &accum[1], &sum}) {
+        HIPCHK(b->alloc(bytes));
+        HIPCHK(hipMemset(b->get(), 0, bytes));
     }
-    hipFree(ctx->d_sum_own);
-    ctx->d_sum_own = nullptr;
-    free_adaptive_buffers(ctx);   // (moments and tile counts of the old size: zero from here on)
-    size_t bytes = (size_t)width * height * 16;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(hipMalloc(&ctx->d_accum[i], bytes));
-        HIPCHK(hipMemset(ctx->d_accum[i], 0, bytes));
-    }
-    HIPCHK(hipMalloc(&ctx->d_sum_own, bytes));
-    HIPCHK(hipMemset(ctx->d_sum_own, 0, bytes));
-    ctx->d_sum = ctx->d_sum_own;
+    ctx->d_accum[0] = std::move(accum[0]);
+    ctx->d_accum[1] = std::move(accum[1]);
+    ctx->d_sum_own = std::move(sum);
+    ctx->d_sum = ctx->d_sum_own.get();
+    ctx->d_m2.reset();   // (moments and tile counts of the old size: zero from here on)
+    ctx->ad = AdaptiveTiles{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;
@@ -985,7 +910,7 @@ extern "C" int mpt_set_sum_buffer(mpt_ctx* ctx, void* p) {
     if (wrc) return wrc;
     wrc = wait_impl(ctx);
     if (wrc) return wrc;
-    ctx->d_sum = p ? (float4*)p : ctx->d_sum_own;
+    ctx->d_sum = p ? (float4*)p : ctx->d_sum_own.get();
     return MPT_OK;
 }
 static int clear_sum_impl(mpt_ctx* ctx) {
@@ -994,9 +919,9 @@ static int clear_sum_impl(mpt_ctx* ctx) {
     int wrc = wait_impl(ctx);
     if (wrc) return wrc;
     HIPCHK(hipMemsetAsync(ctx->d_sum, 0, (size_t)ctx->W * ctx->H * 16, ctx->stream));
-    if (ctx->d_m2) HIPCHK(hipMemsetAsync(ctx->d_m2, 0, (size_t)ctx->W * ctx->H * 16, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->ev_sum_op, ctx->stream));  // the next resolve (on either lane) is ordered behind the clear
-    ctx->last_resolved = ctx->ev_sum_op;
+    if (ctx->d_m2) HIPCHK(hipMemsetAsync(ctx->d_m2.get(), 0, (size_t)ctx->W * ctx->H * 16, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->ev_sum_op.get(), ctx->stream));  // the next resolve (on either lane) is ordered behind the clear
+    ctx->last_resolved = ctx->ev_sum_op.get();
     return MPT_OK;
 }
 extern "C" void* mpt_stream(mpt_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
@@ -1014,7 +939,7 @@ static int read_frame_impl(mpt_ctx* ctx, float* out) {
     if (!ctx->d_accum[0]) return fail(ctx, MPT_ERR_NOT_READY, "mpt_resize not called");
     int wrc = wait_impl(ctx);
     if (wrc) return wrc;
-    HIPCHK(hipMemcpyAsync(out, ctx->d_accum[ctx->cur_target], (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->d_accum[ctx->cur_target].get(), (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MPT_OK;
 }
@@ -1112,10 +1037,8 @@ static int ensure_pixel_seeds(mpt_ctx* ctx) {
             v = v - floorf(v);
             seeds[(size_t)y * ctx->W + x] = (uint32_t)(v * 4294967296.0f);
         }
-    hipFree(ctx->d_pixel_seed);
-    ctx->d_pixel_seed = nullptr;
-    HIPCHK(hipMalloc(&ctx->d_pixel_seed, seeds.size() * 4));
-    HIPCHK(hipMemcpy(ctx->d_pixel_seed, seeds.data(), seeds.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx->d_pixel_seed.alloc(seeds.size() * 4));
+    HIPCHK(hipMemcpy(ctx->d_pixel_seed.get(), seeds.data(), seeds.size() * 4, hipMemcpyHostToDevice));
     memcpy(ctx->seed_rs, rs, 12);
     ctx->seed_W = ctx->W;
     ctx->seed_H = ctx->H;
@@ -1173,10 +1096,8 @@ static int ensure_tile_order(mpt_ctx* ctx, uint32_t rank, uint32_t nranks, int m
             for (uint32_t j = 0; j < n_g; ++j) xy[(size_t)j * MPT_NGROUP + g] = stripe[j];
         }
     }
-    hipFree(ctx->d_tile_xy);
-    ctx->d_tile_xy = nullptr;
-    HIPCHK(hipMalloc(&ctx->d_tile_xy, xy.size() * 4));
-    HIPCHK(hipMemcpy(ctx->d_tile_xy, xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
+    HIPCHK(ctx->d_tile_xy.alloc(xy.size() * 4));
+    HIPCHK(hipMemcpy(ctx->d_tile_xy.get(), xy.data(), xy.size() * 4, hipMemcpyHostToDevice));
     ctx->tile_W = ctx->W;
     ctx->tile_H = ctx->H;
     ctx->tile_rank = rank;
@@ -1190,23 +1111,17 @@ static int ensure_tile_order(mpt_ctx* ctx, uint32_t rank, uint32_t nranks, int m
 static int ensure_workspace(mpt_ctx* ctx, Lane& L, uint32_t slots_items, uint64_t pass_paths, bool need_queues) {
     uint32_t cap = ((slots_items + MPT_NSHARD - 1) / MPT_NSHARD + 2) * 64u;
     if (need_queues && cap > L.shard_cap) {
-        free_queues(L);
+        L.shard_cap = 0;
         size_t n = (size_t)cap * MPT_NSHARD;
         for (int i = 0; i < 2; ++i) {
-            HIPCHK(hipMalloc(&L.q[i].od, n * 16));
-            HIPCHK(hipMalloc(&L.q[i].dt, n * 16));
-            HIPCHK(hipMalloc(&L.q[i].tl, n * 16));
-            HIPCHK(hipMalloc(&L.q[i].ia, n * 8));
+            HIPCHK(L.q_od[i].alloc(n * 16));
+            HIPCHK(L.q_dt[i].alloc(n * 16));
+            HIPCHK(L.q_tl[i].alloc(n * 16));
+            HIPCHK(L.q_ia[i].alloc(n * 8));
         }
         L.shard_cap = cap;
     }
-    if (pass_paths > L.slots_cap) {
-        hipFree(L.d_slots);
-        L.d_slots = nullptr;
-        L.slots_cap = 0;
-        HIPCHK(hipMalloc(&L.d_slots, pass_paths * 16));
-        L.slots_cap = pass_paths;
-    }
+    if (pass_paths * 16 > L.d_slots.bytes()) HIPCHK(L.d_slots.alloc(pass_paths * 16));
     return MPT_OK;
 }
 
@@ -1255,6 +1170,18 @@ struct TileOverride {
     uint32_t n;
 };
 
+// The next of the lane's kernel-timing events (the pool grows as a render needs them; collect_lane hands them all back).
+static hipError_t next_event(Lane& L, hipEvent_t* e) {
+    if (L.ev_used == L.ev_pool.size()) {
+        Event ev;
+        const hipError_t r = ev.create(hipEventCreate);
+        if (r != hipSuccess) return r;
+        L.ev_pool.push_back(std::move(ev));
+    }
+    *e = L.ev_pool[L.ev_used++].get();
+    return hipSuccess;
+}
+
 // Runs one pass of S samples/pixel over this rank's tiles (or the override's); leaves the per-path results in d_slots.
 static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t sample_begin, uint32_t S, PassParams& pp,
                     uint32_t& n_local_tiles, bool time_kernels, const TileOverride* ovr = nullptr) {
@@ -1278,13 +1205,12 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
 
     const int pipeline = resolve_pipeline(ctx, p->pipeline, p->rng_mode);
     pp.scene = scene_dev(ctx);
-    pp.q[0] = L.q[0];
-    pp.q[1] = L.q[1];
+    for (int i = 0; i < 2; ++i) pp.q[i] = QueueDev{L.q_od[i].get(), L.q_dt[i].get(), L.q_tl[i].get(), L.q_ia[i].get()};
     pp.shard_cap = L.shard_cap;
-    pp.desc = L.d_desc;
-    pp.ctr = L.d_ctr;
-    pp.slots = L.d_slots;
-    pp.pixel_seed = ctx->d_pixel_seed;
+    pp.desc = L.d_desc.get();
+    pp.ctr = L.d_ctr.get();
+    pp.slots = L.d_slots.get();
+    pp.pixel_seed = ctx->d_pixel_seed.get();
     const mpt_uniforms& u = ctx->u;
     pp.cam = F3{u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2]};
     pp.first = F3{u.firstPixelPosition[0], u.firstPixelPosition[1], u.firstPixelPosition[2]};
@@ -1297,7 +1223,7 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     pp.tiles_x = tiles_x;
     pp.S = S;
     pp.s_shift = (S & (S - 1)) == 0 ? (uint32_t)__builtin_ctz(S) : 0xFFu;
-    pp.tile_xy = ovr ? ovr->tiles : ctx->d_tile_xy;
+    pp.tile_xy = ovr ? ovr->tiles : ctx->d_tile_xy.get();
     pp.sample_begin = sample_begin;
     pp.rank = rk;
     pp.nranks = nr;
@@ -1315,12 +1241,12 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     pp.sp.seed_hi = p->seed_hi;
     pp.sp.primitive_count = (uint32_t)std::min<uint64_t>(u.primitiveCount, 0xFFFFFFFFull);
     uint32_t* dev_done = nullptr;
-    HIPCHK(hipHostGetDevicePointer((void**)&dev_done, L.h_done, 0));
+    HIPCHK(hipHostGetDevicePointer((void**)&dev_done, L.h_done.get(), 0));
     pp.host_done = dev_done;
 
     if (pass_paths == 0) return MPT_OK;
     // test mode: poison the per-path result slots so that a path that is lost shows up as NaN in the image
-    if (count_flag(p)) HIPCHK(hipMemsetAsync(L.d_slots, 0xFF, pass_paths * 16, L.stream));
+    if (count_flag(p)) HIPCHK(hipMemsetAsync(L.d_slots.get(), 0xFF, pass_paths * 16, L.stream.get()));
 
     size_t lds = (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA;
     int per_cu = 0;
@@ -1353,8 +1279,8 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     if (getenv("MPT_DEBUG_LAUNCH")) fprintf(stderr, "[mpt] pipeline %d: %d workgroups of %d per CU, %zu B of LDS each\n", pipeline, per_cu, wg, lds);
     if (ctx->wgs_per_cu > 0 && per_cu > ctx->wgs_per_cu) per_cu = ctx->wgs_per_cu;
     const int grid = ctx->prop.multiProcessorCount * per_cu;
-    hipStream_t st = L.stream;
-    *L.h_done = 0;
+    hipStream_t st = L.stream.get();
+    *L.h_done.get() = 0;
     // Trace kernels are persistent and sized for the whole chip: two of them must never be DISPATCHED side by side (each would hold
     // half of the workgroup slots for its whole life — measured: 21.7 ms per 256-spp step instead of 16.8), and which of two pending
     // launches the hardware starts is not ours to choose.  Two ways to keep them apart:
@@ -1370,10 +1296,10 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         Lane& O = *ctx->last_trace_lane;
         bool resident = false;
         if (O.announced_id != 0u) {
-            const volatile uint32_t* flag = (const volatile uint32_t*)O.h_done + MPT_HOST_RESIDENT;
+            const volatile uint32_t* flag = (const volatile uint32_t*)O.h_done.get() + MPT_HOST_RESIDENT;
             const auto t0 = std::chrono::steady_clock::now();
             for (;;) {
-                if (*flag == O.announced_id || hipEventQuery(O.ev_traced) == hipSuccess) {   // resident (or even finished)
+                if (*flag == O.announced_id || hipEventQuery(O.ev_traced.get()) == hipSuccess) {   // resident (or even finished)
                     resident = true;
                     break;
                 }
@@ -1384,38 +1310,31 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         }
         need_chain = !resident;
     }
-    if (need_chain && ctx->last_traced && ctx->last_traced != L.ev_traced) HIPCHK(hipStreamWaitEvent(st, ctx->last_traced, 0));
+    if (need_chain && ctx->last_traced && ctx->last_traced != L.ev_traced.get()) HIPCHK(hipStreamWaitEvent(st, ctx->last_traced, 0));
     pp.launch_id = 0u;
     if (pipeline == MPT_PIPE_WAVELOCAL || pipeline == MPT_PIPE_ORDERED) {
         if (++ctx->launch_seq == 0u) ctx->launch_seq = 1u;
         pp.launch_id = ctx->launch_seq;
     }
     L.announced_id = pp.launch_id;
-    hipLaunchKernelGGL(k_begin_pass, dim3(1), dim3(64), 0, st, L.d_desc, L.d_ctr, (uint32_t)pass_paths, slots_items,
+    hipLaunchKernelGGL(k_begin_pass, dim3(1), dim3(64), 0, st, L.d_desc.get(), L.d_ctr.get(), (uint32_t)pass_paths, slots_items,
                        (volatile uint32_t*)dev_done, pipeline == MPT_PIPE_WAVEFRONT ? 0 : 1);
     if (pipeline != MPT_PIPE_WAVEFRONT) {
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (time_kernels) {  // events from the context's pool; they are read after the ONE sync of mpt_render / mpt_draw
-            while (L.ev_pool.size() < L.ev_used + 2) {
-                hipEvent_t e;
-                HIPCHK(hipEventCreate(&e));
-                L.ev_pool.push_back(e);
-            }
-            e0 = L.ev_pool[L.ev_used++];
-            e1 = L.ev_pool[L.ev_used++];
+        if (time_kernels) {  // events from the lane's pool; they are read after the ONE sync of mpt_render / mpt_draw
+            HIPCHK(next_event(L, &e0));
+            HIPCHK(next_event(L, &e1));
             HIPCHK(hipEventRecord(e0, st));
         }
         if (pipeline == MPT_PIPE_WAVELOCAL || pipeline == MPT_PIPE_ORDERED) {
             const size_t waves = (size_t)grid * (wg / 64);
             if (pipeline == MPT_PIPE_WAVELOCAL && waves > L.ring_waves) {
-                WaveRings& r = L.ring;
-                hipFree(r.base);
-                r = WaveRings{};
+                L.ring = WaveRings{};
                 L.ring_waves = 0;
                 const size_t n = waves * MPT_WL_LEVELS * MPT_WL_RING;
                 if (n >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "too many waves for the ring index (internal)");
-                HIPCHK(hipMalloc(&r.base, 5 * n * 16 + waves * 128 + 1024));  // five arrays + room for the MPT_DEBUG_WAVE_TIMES records
-                r.n = (uint32_t)n;
+                HIPCHK(L.ring_mem.alloc(5 * n * 16 + waves * 128 + 1024));  // five arrays + room for the MPT_DEBUG_WAVE_TIMES records
+                L.ring = WaveRings{L.ring_mem.get(), (uint32_t)n};
                 L.ring_waves = waves;
             }
             uint32_t wl_block = ctx->wl_block, wl_min = ctx->wl_min, wl_div = ctx->wl_div;
@@ -1425,13 +1344,12 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
             }
             if (pipeline == MPT_PIPE_ORDERED) {
                 if (waves > L.ot_ring_waves) {
-                    free_ot_rings(L.ot_ring);
+                    L.ot_ring = OtRings{};
                     L.ot_ring_waves = 0;
                     const size_t n = waves * MPT_OT_RINGS * MPT_WL_RING;
                     if (n >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "too many waves for the ring index (internal)");
-                    OtRings& r = L.ot_ring;
-                    HIPCHK(hipMalloc(&r.base, MPT_OT_RING_ARRAYS * n * 16));
-                    r.n = (uint32_t)n;
+                    HIPCHK(L.ot_ring_mem.alloc(MPT_OT_RING_ARRAYS * n * 16));
+                    L.ot_ring = OtRings{L.ot_ring_mem.get(), (uint32_t)n};
                     L.ot_ring_waves = waves;
                 }
                 void* args[] = {(void*)&pp, (void*)&accel, (void*)&L.ot_ring, (void*)&ctx->ot_budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div};
@@ -1449,24 +1367,14 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
             L.pending_timed.emplace_back(e0, e1);
         }
         if (ctx->lane_order & 5) {   // (always, unless MPT_LANE_ORDER=0)
-            HIPCHK(hipEventRecord(L.ev_traced, st));
-            ctx->last_traced = L.ev_traced;
+            HIPCHK(hipEventRecord(L.ev_traced.get(), st));
+            ctx->last_traced = L.ev_traced.get();
             ctx->last_trace_lane = &L;
         }
         ctx->stats.iterations += 1;
         return MPT_OK;
     }
     // wavefront: enqueue iterations in batches; the device publishes `done` to pinned host memory
-    std::vector<hipEvent_t>& pool = L.ev_pool;
-    size_t& ev_used = L.ev_used;
-    auto get_event = [&]() -> hipEvent_t {
-        if (ev_used == pool.size()) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-            pool.push_back(e);
-        }
-        return pool[ev_used++];
-    };
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
     uint32_t parity = 0;
     uint64_t launched = 0;
@@ -1481,9 +1389,8 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         for (uint64_t b = 0; b < batch; ++b) {
             hipEvent_t e0 = nullptr, e1 = nullptr;
             if (time_kernels) {
-                e0 = get_event();
-                e1 = get_event();
-                if (!e0 || !e1) return fail(ctx, MPT_ERR_HIP, "hipEventCreate failed");
+                HIPCHK(next_event(L, &e0));
+                HIPCHK(next_event(L, &e1));
                 HIPCHK(hipEventRecord(e0, st));
             }
             {
@@ -1494,13 +1401,13 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
                 HIPCHK(hipEventRecord(e1, st));
                 timed.emplace_back(e0, e1);
             }
-            hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, L.d_desc, L.d_ctr, (volatile uint32_t*)dev_done);
+            hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, L.d_desc.get(), L.d_ctr.get(), (volatile uint32_t*)dev_done);
             parity ^= 1u;
             launched++;
         }
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
-        uint32_t flag = *(volatile uint32_t*)L.h_done;
+        uint32_t flag = *(volatile uint32_t*)L.h_done.get();
         if (flag & 2u) return fail(ctx, MPT_ERR_OVERFLOW, "ray queue overflow");
         if (flag & 1u) break;
         if (launched > hard_cap) return fail(ctx, MPT_ERR_HIP, "pass did not drain (internal)");
@@ -1508,7 +1415,7 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     }
     {
         PassDesc hd;
-        HIPCHK(hipMemcpy(&hd, L.d_desc, sizeof hd, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&hd, L.d_desc.get(), sizeof hd, hipMemcpyDeviceToHost));
         // only the iterations that had work count as launches of the dominant kernel
         const uint64_t real = hd.iterations;
         for (size_t i = 0; i < timed.size() && i < real; ++i) {
@@ -1526,16 +1433,16 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
 // Statistics: the pass descriptor of a lane is copied to pinned memory behind the lane's last kernel
 // (enqueue_stats_copy); collect_lane waits for the lane ONCE and reads the copy and the kernel-event pairs.
 static int enqueue_stats_copy(mpt_ctx* ctx, Lane& L) {
-    HIPCHK(hipMemcpyAsync(L.h_desc, L.d_desc, sizeof(PassDesc), hipMemcpyDeviceToHost, L.stream));
-    HIPCHK(hipMemsetAsync(&L.d_desc->paths, 0, MPT_DESC_COUNTERS * sizeof(unsigned long long), L.stream));
-    HIPCHK(hipMemsetAsync(&L.d_desc->overflow, 0, 4, L.stream));
+    HIPCHK(hipMemcpyAsync(L.h_desc.get(), L.d_desc.get(), sizeof(PassDesc), hipMemcpyDeviceToHost, L.stream.get()));
+    HIPCHK(hipMemsetAsync(&L.d_desc.get()->paths, 0, MPT_DESC_COUNTERS * sizeof(unsigned long long), L.stream.get()));
+    HIPCHK(hipMemsetAsync(&L.d_desc.get()->overflow, 0, 4, L.stream.get()));
     return MPT_OK;
 }
 
 static int collect_lane(mpt_ctx* ctx, Lane& L) {
-    HIPCHK(hipStreamSynchronize(L.stream));
+    HIPCHK(hipStreamSynchronize(L.stream.get()));
     L.in_flight = false;
-    const PassDesc& hd = *L.h_desc;
+    const PassDesc& hd = *L.h_desc.get();
     // duration of the trace kernels: what the persistent kernels stamped themselves (first workgroup's start to last wave's end on the
     // 100 MHz clock, note_wave_exit) — the event pairs of overlapping renders include the time a launch waits behind the running kernel
     float ev_ms = 0;
@@ -1550,7 +1457,7 @@ static int collect_lane(mpt_ctx* ctx, Lane& L) {
     L.ev_used = 0;
     if (L.timed) {
         float ms = 0;
-        HIPCHK(hipEventElapsedTime(&ms, L.ev0, L.ev1));
+        HIPCHK(hipEventElapsedTime(&ms, L.ev0.get(), L.ev1.get()));
         ctx->stats.total_ms += ms;
         L.timed = false;
     }
@@ -1597,11 +1504,31 @@ static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p, const Til
     if (L.in_flight && (rc = collect_lane(ctx, L))) return rc;
     if ((p->flags & MPT_FLAG_MOMENTS) && !ctx->d_m2) {   // (first render with moments since the resize: zeroed in stream order)
         const size_t bytes = (size_t)ctx->W * ctx->H * 16;
-        HIPCHK(hipMalloc(&ctx->d_m2, bytes));
-        HIPCHK(hipMemsetAsync(ctx->d_m2, 0, bytes, L.stream));
+        HIPCHK(ctx->d_m2.alloc(bytes));
+        HIPCHK(hipMemsetAsync(ctx->d_m2.get(), 0, bytes, L.stream.get()));
     }
-    HIPCHK(hipEventRecord(L.ev0, L.stream));
+    HIPCHK(hipEventRecord(L.ev0.get(), L.stream.get()));
     ctx->next_lane ^= 1;
+    // from here on, a render that does not get enqueued whole (a HIP error, or a host exception that guarded() turns into a status):
+    // drain what it has enqueued, forget its event pairs and give the lane back, so that the next render starts from a clean lane
+    // (the HDR sum may hold some of this render's passes: the caller clears it)
+    struct Abandon {
+        mpt_ctx* ctx;
+        Lane& L;
+        bool enqueued = false;
+        ~Abandon() {
+            if (enqueued) return;
+            // (the statistics copy that normally clears them never runs for an abandoned render)
+            hipMemsetAsync(&L.d_desc.get()->paths, 0, MPT_DESC_COUNTERS * sizeof(unsigned long long), L.stream.get());
+            hipMemsetAsync(&L.d_desc.get()->overflow, 0, 4, L.stream.get());
+            hipStreamSynchronize(L.stream.get());
+            L.pending_timed.clear();
+            L.ev_used = 0;
+            L.timed = false;
+            L.in_flight = false;
+            ctx->next_lane ^= 1;
+        }
+    } abandon{ctx, L};
     const uint32_t tiles = ((ctx->W + 7) / 8) * ((ctx->H + 7) / 8);
     const uint32_t local_tiles = ovr ? ovr->n : (tiles + p->shard_count - 1) / p->shard_count;
     uint32_t s_max = (uint32_t)std::max<uint64_t>(
@@ -1615,60 +1542,38 @@ static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p, const Til
     }
     const char* e = getenv("MPT_PASS_SPP");
     if (e && atoi(e) > 0) s_max = std::min<uint32_t>(s_max, (uint32_t)atoi(e));
-    // a render that fails half way: drain what it has enqueued, forget its event pairs and give the lane back, so that
-    // the next render starts from a clean lane (the HDR sum may hold some of this render's passes: the caller clears it)
-    auto abandon = [&](int code) {
-        // (the statistics copy that normally clears them never runs for an abandoned render)
-        hipMemsetAsync(&L.d_desc->paths, 0, MPT_DESC_COUNTERS * sizeof(unsigned long long), L.stream);
-        hipMemsetAsync(&L.d_desc->overflow, 0, 4, L.stream);
-        hipStreamSynchronize(L.stream);
-        L.pending_timed.clear();
-        L.ev_used = 0;
-        L.timed = false;
-        L.in_flight = false;
-        ctx->next_lane ^= 1;
-        return code;
-    };
-#define HIPCHK_AB(call)                                                                     \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            set_err(ctx, std::string(#call) + ": " + hipGetErrorString(e_));                \
-            return abandon(MPT_ERR_HIP);                                                    \
-        }                                                                                   \
-    } while (0)
     uint32_t done = 0;
     while (done < p->sample_count) {
         uint32_t S = std::min(s_max, p->sample_count - done);
         PassParams pp;
         uint32_t nlt = 0;
         rc = run_pass(ctx, L, p, p->sample_begin + done, S, pp, nlt, ctx->time_kernels, ovr);
-        if (rc) return abandon(rc);
+        if (rc) return rc;
         if (nlt) {
             // sum[p] += pass total must happen in submission order on both lanes (float addition does not commute
             // bit for bit): this resolve waits for the previous one, wherever it ran
-            if (ctx->last_resolved) HIPCHK_AB(hipStreamWaitEvent(L.stream, ctx->last_resolved, 0));
+            if (ctx->last_resolved) HIPCHK(hipStreamWaitEvent(L.stream.get(), ctx->last_resolved, 0));
             // beside the other lane's trace kernel: a footprint that fits next to it on every CU (k_resolve_sum); alone: the whole chip
             const uint32_t threads = nlt * 64u, wide = (threads + 255u) / 256u;
             const uint32_t narrow = (uint32_t)ctx->prop.multiProcessorCount * (uint32_t)ctx->resolve_wgs_per_cu;
             const uint32_t rgrid = !ctx->sync_render && ctx->resolve_wgs_per_cu > 0 ? std::min(wide, narrow) : wide;
             if (p->flags & MPT_FLAG_MOMENTS)
-                hipLaunchKernelGGL(k_resolve_sum_moments, dim3(rgrid), dim3(256), 0, L.stream, pp, ctx->d_sum, ctx->d_m2, nlt);
+                hipLaunchKernelGGL(k_resolve_sum_moments, dim3(rgrid), dim3(256), 0, L.stream.get(), pp, ctx->d_sum, ctx->d_m2.get(), nlt);
             else
-                hipLaunchKernelGGL(k_resolve_sum, dim3(rgrid), dim3(256), 0, L.stream, pp, ctx->d_sum, nlt);
-            HIPCHK_AB(hipGetLastError());
-            HIPCHK_AB(hipEventRecord(L.ev_resolved, L.stream));
-            ctx->last_resolved = L.ev_resolved;
+                hipLaunchKernelGGL(k_resolve_sum, dim3(rgrid), dim3(256), 0, L.stream.get(), pp, ctx->d_sum, nlt);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(L.ev_resolved.get(), L.stream.get()));
+            ctx->last_resolved = L.ev_resolved.get();
         }
         done += S;
         // the next pass reuses the lane's slot buffer and descriptor: in-stream order is enough, no host sync here
     }
-    HIPCHK_AB(hipEventRecord(L.ev1, L.stream));
+    HIPCHK(hipEventRecord(L.ev1.get(), L.stream.get()));
     L.timed = true;
-    if ((rc = enqueue_stats_copy(ctx, L))) return abandon(rc);
+    if ((rc = enqueue_stats_copy(ctx, L))) return rc;
     L.in_flight = true;
+    abandon.enqueued = true;
     return MPT_OK;
-#undef HIPCHK_AB
 }
 
 // "Nothing else is in flight and nothing will be submitted behind this render": the trace kernel may be the variant that fills the
@@ -1711,8 +1616,8 @@ static int draw_impl(mpt_ctx* ctx, const mpt_render_params* p) {
     if (rc) return rc;
     if (nlt) {
         uint32_t threads = nlt * 64u;
-        hipLaunchKernelGGL(k_resolve_frame, dim3((threads + 255) / 256), dim3(256), 0, L.stream, pp,
-                           (const float4*)ctx->d_accum[ctx->cur_target ^ 1], ctx->d_accum[ctx->cur_target], nlt,
+        hipLaunchKernelGGL(k_resolve_frame, dim3((threads + 255) / 256), dim3(256), 0, L.stream.get(), pp,
+                           (const float4*)ctx->d_accum[ctx->cur_target ^ 1].get(), ctx->d_accum[ctx->cur_target].get(), nlt,
                            (unsigned long long)ctx->u.frameCount);
         HIPCHK(hipGetLastError());
     }
@@ -1730,7 +1635,7 @@ static int read_moments_impl(mpt_ctx* ctx, float* out) {
         memset(out, 0, bytes);
         return MPT_OK;
     }
-    HIPCHK(hipMemcpyAsync(out, ctx->d_m2, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->d_m2.get(), bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MPT_OK;
 }
@@ -1739,38 +1644,29 @@ static int read_tile_samples_impl(mpt_ctx* ctx, uint32_t* out) {
     int rc = wait_impl(ctx);
     if (rc) return rc;
     const size_t n = (size_t)((ctx->W + 7) / 8) * ((ctx->H + 7) / 8);
-    if (!ctx->d_tile_count) {   // (no adaptive render since the resize)
+    if (!ctx->ad.tile_count) {   // (no adaptive render since the resize)
         memset(out, 0, n * 4);
         return MPT_OK;
     }
-    HIPCHK(hipMemcpyAsync(out, ctx->d_tile_count, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->ad.tile_count.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MPT_OK;
 }
 static int ensure_adaptive_buffers(mpt_ctx* ctx, uint32_t tiles) {
-    if (ctx->d_tile_count && ctx->ad_tiles == tiles) return MPT_OK;
-    hipFree(ctx->d_tile_count);
-    hipFree(ctx->d_alist[0]);
-    hipFree(ctx->d_alist[1]);
-    hipFree(ctx->d_aflag);
-    hipFree(ctx->d_nsel);
-    hipFree(ctx->d_sel_tmp);
-    ctx->d_tile_count = ctx->d_alist[0] = ctx->d_alist[1] = ctx->d_nsel = nullptr;
-    ctx->d_aflag = nullptr;
-    ctx->d_sel_tmp = nullptr;
-    ctx->sel_tmp_bytes = 0;
-    ctx->ad_tiles = 0;
-    HIPCHK(hipMalloc(&ctx->d_tile_count, (size_t)tiles * 4));
-    HIPCHK(hipMalloc(&ctx->d_alist[0], (size_t)tiles * 4));
-    HIPCHK(hipMalloc(&ctx->d_alist[1], (size_t)tiles * 4));
-    HIPCHK(hipMalloc(&ctx->d_aflag, tiles));
-    HIPCHK(hipMalloc(&ctx->d_nsel, 4));
+    AdaptiveTiles& a = ctx->ad;
+    if (a.tile_count && a.tiles == tiles) return MPT_OK;
+    a = AdaptiveTiles{};
+    HIPCHK(a.tile_count.alloc((size_t)tiles * 4));
+    HIPCHK(a.alist[0].alloc((size_t)tiles * 4));
+    HIPCHK(a.alist[1].alloc((size_t)tiles * 4));
+    HIPCHK(a.aflag.alloc(tiles));
+    HIPCHK(a.nsel.alloc(4));
     size_t tmp = 0;
-    HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tmp, ctx->d_alist[0], ctx->d_aflag, ctx->d_alist[1], ctx->d_nsel, (int)tiles,
+    HIPCHK(hipcub::DeviceSelect::Flagged(nullptr, tmp, a.alist[0].get(), a.aflag.get(), a.alist[1].get(), a.nsel.get(), (int)tiles,
                                          ctx->stream));
-    HIPCHK(hipMalloc(&ctx->d_sel_tmp, std::max<size_t>(tmp, 16)));
-    ctx->sel_tmp_bytes = tmp;
-    ctx->ad_tiles = tiles;
+    HIPCHK(a.sel_tmp.alloc(std::max<size_t>(tmp, 16)));
+    a.sel_tmp_bytes = tmp;
+    a.tiles = tiles;
     return MPT_OK;
 }
 static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_adaptive_params* a, mpt_adaptive_info* out) {
@@ -1788,7 +1684,7 @@ static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const 
     const uint32_t tiles_x = (ctx->W + 7) / 8, tiles_y = (ctx->H + 7) / 8, tiles = tiles_x * tiles_y;
     if ((rc = ensure_adaptive_buffers(ctx, tiles))) return rc;
     if ((rc = clear_sum_impl(ctx))) return rc;   // (the sum, and the moments if they exist yet: ordered before the first resolve)
-    HIPCHK(hipMemsetAsync(ctx->d_tile_count, 0, (size_t)tiles * 4, ctx->stream));
+    HIPCHK(hipMemsetAsync(ctx->ad.tile_count.get(), 0, (size_t)tiles * 4, ctx->stream));
     ctx->stats.trace_kernel_ms = 0;   // (totals over the passes, as one mpt_render reports its own)
     ctx->stats.trace_launches = 0;
     ctx->stats.total_ms = 0;
@@ -1811,14 +1707,14 @@ static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const 
         passes++;
         n = n_next;
         if (!list) {
-            list = ctx->d_tile_xy;   // (built by pass 0; one rank: every tile, in the table's order)
+            list = ctx->d_tile_xy.get();   // (built by pass 0; one rank: every tile, in the table's order)
             n_active = ctx->tile_count;
         }
         AdaptiveEval ev;
         ev.list = list;
         ev.n_list = n_active;
         ev.sum = ctx->d_sum;
-        ev.m2 = ctx->d_m2;
+        ev.m2 = ctx->d_m2.get();
         ev.width = ctx->W;
         ev.height = ctx->H;
         ev.tiles_x = tiles_x;
@@ -1826,15 +1722,15 @@ static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const 
         ev.n_max = N;
         ev.threshold = (double)a->threshold;
         ev.luminance_floor = (double)floor_l;
-        ev.tile_count = ctx->d_tile_count;
-        ev.flag = ctx->d_aflag;
+        ev.tile_count = ctx->ad.tile_count.get();
+        ev.flag = ctx->ad.aflag.get();
         hipLaunchKernelGGL(k_adaptive_eval, dim3((n_active + 3u) / 4u), dim3(256), 0, ctx->stream, ev);
         HIPCHK(hipGetLastError());
-        uint32_t* next = ctx->d_alist[cur];
-        size_t tmp = ctx->sel_tmp_bytes;
-        HIPCHK(hipcub::DeviceSelect::Flagged(ctx->d_sel_tmp, tmp, list, ctx->d_aflag, next, ctx->d_nsel, (int)n_active, ctx->stream));
+        uint32_t* next = ctx->ad.alist[cur].get();
+        size_t tmp = ctx->ad.sel_tmp_bytes;
+        HIPCHK(hipcub::DeviceSelect::Flagged(ctx->ad.sel_tmp.get(), tmp, list, ctx->ad.aflag.get(), next, ctx->ad.nsel.get(), (int)n_active, ctx->stream));
         uint32_t kept = 0;
-        HIPCHK(hipMemcpyAsync(&kept, ctx->d_nsel, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(&kept, ctx->ad.nsel.get(), 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         if (kept == 0u) break;   // (every tile stopped: a tile at N is never flagged)
         if (kept > n_active) return fail(ctx, MPT_ERR_HIP, "adaptive compaction kept more tiles than it was given (internal)");
@@ -1843,7 +1739,7 @@ static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const 
         cur ^= 1u;
     }
     std::vector<uint32_t> counts(tiles);
-    HIPCHK(hipMemcpy(counts.data(), ctx->d_tile_count, (size_t)tiles * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(counts.data(), ctx->ad.tile_count.get(), (size_t)tiles * 4, hipMemcpyDeviceToHost));
     mpt_adaptive_info info = {};
     for (uint32_t t = 0; t < tiles; ++t) {
         const uint32_t tx = t % tiles_x, ty = t / tiles_x;
@@ -1857,41 +1753,30 @@ static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const 
 }
 
 // ---- unit-test entry points -----------------------------------------------------------------------------------
-namespace {
-struct DevBuf {  // temporary device buffer, freed on every exit path
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-};
-}  // namespace
 static int trace_rays_impl(mpt_ctx* ctx, const float* o, const float* d, uint64_t n, float* t_out,
                               int32_t* prim_out, float* normal_out, int32_t* front_out) {
     if (!ctx || !o || !d || !t_out || !prim_out || !normal_out || !front_out || n == 0 || n > (1ull << 30))
         return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
     if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
     HIPCHK(hipSetDevice(ctx->device));
-    DevBuf d_o, d_d, d_t, d_n, d_p, d_f;
+    DevMem<> d_o, d_d, d_t, d_n, d_p, d_f;
     HIPCHK(d_o.alloc(n * 12));
     HIPCHK(d_d.alloc(n * 12));
     HIPCHK(d_t.alloc(n * 4));
     HIPCHK(d_n.alloc(n * 12));
     HIPCHK(d_p.alloc(n * 4));
     HIPCHK(d_f.alloc(n * 4));
-    HIPCHK(hipMemcpy(d_o.p, o, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_d.p, d, n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
     SceneDev sc = scene_dev(ctx);
     hipLaunchKernelGGL(k_trace_rays, dim3((uint32_t)((n + 255) / 256)), dim3(256), (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA,
-                       ctx->stream, sc, (const float*)d_o.p, (const float*)d_d.p, (uint32_t)n, (float*)d_t.p, (int*)d_p.p, (float*)d_n.p, (int*)d_f.p);
+                       ctx->stream, sc, (const float*)d_o.get(), (const float*)d_d.get(), (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(), (float*)d_n.get(), (int*)d_f.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(t_out, d_t.p, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(prim_out, d_p.p, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(normal_out, d_n.p, n * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(front_out, d_f.p, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t_out, d_t.get(), n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(prim_out, d_p.get(), n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(normal_out, d_n.get(), n * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(front_out, d_f.get(), n * 4, hipMemcpyDeviceToHost));
     return MPT_OK;
 }
 
@@ -1902,7 +1787,7 @@ static int trace_rays_ordered_impl(mpt_ctx* ctx, const float* o, const float* d,
     if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
     if (!ctx->acc_ok) return fail(ctx, MPT_ERR_BAD_SCENE, "closest-first walk unavailable for this scene: " + ctx->acc_why);
     HIPCHK(hipSetDevice(ctx->device));
-    DevBuf d_o, d_d, d_t, d_n, d_p, d_f, d_g;
+    DevMem<> d_o, d_d, d_t, d_n, d_p, d_f, d_g;
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
     HIPCHK(d_o.alloc(n * 12));
     HIPCHK(d_d.alloc(n * 12));
@@ -1911,21 +1796,21 @@ static int trace_rays_ordered_impl(mpt_ctx* ctx, const float* o, const float* d,
     HIPCHK(d_p.alloc(n * 4));
     HIPCHK(d_f.alloc(n * 4));
     HIPCHK(d_g.alloc(n * 4));
-    HIPCHK(hipMemcpy(d_o.p, o, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_d.p, d, n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
     SceneDev sc;
     AccelDev ac;
     const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the five-wave operating point's image: workgroups of 256)
     if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-    hipLaunchKernelGGL(k_trace_rays_ordered, dim3(blocks), dim3(256), lds, ctx->stream, sc, ac, (const float*)d_o.p, (const float*)d_d.p,
-                       (uint32_t)n, (float*)d_t.p, (int*)d_p.p, (float*)d_n.p, (int*)d_f.p, (uint32_t*)d_g.p);
+    hipLaunchKernelGGL(k_trace_rays_ordered, dim3(blocks), dim3(256), lds, ctx->stream, sc, ac, (const float*)d_o.get(), (const float*)d_d.get(),
+                       (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(), (float*)d_n.get(), (int*)d_f.get(), (uint32_t*)d_g.get());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(t_out, d_t.p, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(prim_out, d_p.p, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(normal_out, d_n.p, n * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(front_out, d_f.p, n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(flags_out, d_g.p, n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t_out, d_t.get(), n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(prim_out, d_p.get(), n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(normal_out, d_n.get(), n * 12, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(front_out, d_f.get(), n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(flags_out, d_g.get(), n * 4, hipMemcpyDeviceToHost));
     return MPT_OK;
 }
 
@@ -1933,16 +1818,16 @@ template <typename F>
 static int kat_run(mpt_ctx* ctx, const void* const* in, const size_t* in_bytes, int n_in, void* const* out,
                    const size_t* out_bytes, int n_out, F launch) {
     HIPCHK(hipSetDevice(ctx->device));
-    std::vector<DevBuf> bi(n_in), bo(n_out);
+    std::vector<DevMem<>> bi(n_in), bo(n_out);
     std::vector<void*> di(n_in), dout(n_out);
     for (int i = 0; i < n_in; ++i) {
         HIPCHK(bi[i].alloc(in_bytes[i]));
-        di[i] = bi[i].p;
+        di[i] = bi[i].get();
         HIPCHK(hipMemcpy(di[i], in[i], in_bytes[i], hipMemcpyHostToDevice));
     }
     for (int i = 0; i < n_out; ++i) {
         HIPCHK(bo[i].alloc(out_bytes[i]));
-        dout[i] = bo[i].p;
+        dout[i] = bo[i].get();
     }
     launch(di, dout);
     HIPCHK(hipGetLastError());
@@ -2034,85 +1919,54 @@ static int build_and_upload_impl(mpt_ctx* ctx, const float* prims, const float* 
         n_spheres = 0;
         for (uint32_t i = 0; i < n; ++i) n_spheres += (int)prims[12 * (size_t)i + 3] != 1 ? 1u : 0u;
     }
-    // the staging buffer of the inputs is kept between builds (<= 1 GiB): two hipMallocs and two hipFrees of 80 MB were 0.3 ms of the call
+    // the staging buffer of the inputs is kept between builds (<= 1 GiB; a larger one goes when the call ends): allocating and freeing
+    // two buffers of 80 MB per build was 0.3 ms of the call
     const size_t in_bytes = (size_t)n * 80;
-    if (ctx->in_block_bytes < in_bytes) {
-        hipFree(ctx->in_block);
-        ctx->in_block = nullptr;
-        ctx->in_block_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->in_block, in_bytes));
-        ctx->in_block_bytes = in_bytes;
-    }
-    struct InBuf {
-        void* p;
-    } d_p{ctx->in_block}, d_m{(char*)ctx->in_block + (size_t)n * 48};
-    struct InRelease {   // (a buffer too large to keep goes when the call ends)
-        mpt_ctx* c;
-        ~InRelease() {
-            if (c->in_block_bytes > ((size_t)1 << 30)) {
-                hipFree(c->in_block);
-                c->in_block = nullptr;
-                c->in_block_bytes = 0;
-            }
-        }
-    } in_release{ctx};
-    HIPCHK(hipMemcpyAsync(d_p.p, prims, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream));
+    DevMem<> too_large;
+    DevMem<>& in = in_bytes <= ((size_t)1 << 30) ? ctx->in_block : too_large;
+    if (in.bytes() < in_bytes) HIPCHK(in.alloc(in_bytes));
+    float4* const d_p = (float4*)in.get();
+    float4* const d_m = (float4*)((char*)in.get() + (size_t)n * 48);
+    HIPCHK(hipMemcpyAsync(d_p, prims, (size_t)n * 48, hipMemcpyHostToDevice, ctx->stream));
     const int leaf_max = gpu_leaf_max(n);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        hipEventDestroy(e0);
-        return fail(ctx, MPT_ERR_HIP, "hipEventCreate failed");
-    }
-    hipEventRecord(e0, ctx->stream);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventCreate));
+    HIPCHK(e1.create(hipEventCreate));
+    hipEventRecord(e0.get(), ctx->stream);
     mpt_devbuild::Built b;
     // (the materials are copied by the build itself, on its second stream, beside the tree build: mpt_devbuild.h build_pass)
-    hipError_t e = mpt_devbuild::build(ctx->stream, (float4*)d_p.p, (float4*)d_m.p, mats, n, leaf_max, gpu_builder(), n_spheres, b, &ctx->build_pool, &ctx->spare_block,
-                                       &ctx->spare_block_bytes);
-    if (e == hipSuccess) e = hipEventRecord(e1, ctx->stream);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    hipError_t e = mpt_devbuild::build(ctx->stream, d_p, d_m, mats, n, leaf_max, gpu_builder(), n_spheres, b, &ctx->build_pool, &ctx->spare_block);
+    if (e == hipSuccess) e = hipEventRecord(e1.get(), ctx->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(e1.get());
     float ms = 0.0f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (e != hipSuccess) {
-        b.release();
-        return fail(ctx, MPT_ERR_HIP, std::string("GPU BVH build: ") + hipGetErrorString(e));
-    }
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0.get(), e1.get());
+    if (e != hipSuccess) return fail(ctx, MPT_ERR_HIP, std::string("GPU BVH build: ") + hipGetErrorString(e));
     if (n_spheres == 0xFFFFFFFFu) n_spheres = b.n_spheres;
-    if (b.n_spheres != n_spheres) {
-        b.release();
-        return fail(ctx, MPT_ERR_HIP, "GPU BVH build: sphere count mismatch (internal)");
-    }
-    free_scene_buffers(ctx, true);   // (the old scene's block becomes the next build's)
-    ctx->scene_block = b.block;
-    ctx->scene_block_bytes = b.block_bytes;
-    ctx->d_nodes = b.nodes;
-    ctx->d_prims = b.prims;
-    ctx->d_mats = b.mats;
-    ctx->d_acc_nodes = b.acc_nodes;
-    ctx->n_acc_nodes = b.n_acc_nodes;
-    ctx->d_refleaf = b.refleaf;
-    ctx->d_refbox = b.refbox;
-    ctx->d_always = b.always;
-    ctx->d_ref_bvh = b.ref_bvh;
-    ctx->d_ref_idx = b.ref_idx;
-    ctx->n_ref_nodes = b.n_nodes;
-    ctx->built_leaf_max = (uint32_t)leaf_max;
-    ctx->n_nodes = b.n_nodes;
-    ctx->n_prims = b.n_prims;
-    ctx->n_mats = b.n_mats;
-    ctx->n_acc_nodes = b.n_acc_nodes;
-    ctx->n_always = b.n_always;
-    ctx->n_ref_leaves = b.n_ref_leaves;
-    ctx->acc_depth = b.acc_depth;
-    ctx->tri_extent = b.tri_extent;
-    ctx->acc_eps_abs = b.tri_extent * 3.814697265625e-06f;  // 2^-18 of the largest triangle coordinate
-    ctx->acc_ok = n_spheres <= MPT_ACCEL_MAX_ALWAYS;        // (parent boxes are unions of child boxes: nested by construction)
-    ctx->acc_why = ctx->acc_ok ? "" : "more than 16 spheres";
-    size_lds_images(ctx);
-    ctx->have_scene = true;
-    ctx->guide_epoch++;
+    if (b.n_spheres != n_spheres) return fail(ctx, MPT_ERR_HIP, "GPU BVH build: sphere count mismatch (internal)");
+    SceneState s;
+    s.scene_block = std::move(b.block);
+    s.d_nodes = b.nodes;
+    s.d_prims = b.prims;
+    s.d_mats = b.mats;
+    s.d_acc_nodes = b.acc_nodes;
+    s.d_refleaf = b.refleaf;
+    s.d_refbox = b.refbox;
+    s.d_always = b.always;
+    s.d_ref_bvh = b.ref_bvh;
+    s.d_ref_idx = b.ref_idx;
+    s.n_ref_nodes = b.n_nodes;
+    s.built_leaf_max = (uint32_t)leaf_max;
+    s.n_nodes = b.n_nodes;
+    s.n_prims = b.n_prims;
+    s.n_mats = b.n_mats;
+    s.n_acc_nodes = b.n_acc_nodes;
+    s.n_always = b.n_always;
+    s.n_ref_leaves = b.n_ref_leaves;
+    s.acc_depth = b.acc_depth;
+    s.tri_extent = b.tri_extent;
+    s.acc_ok = n_spheres <= MPT_ACCEL_MAX_ALWAYS;        // (parent boxes are unions of child boxes: nested by construction)
+    s.acc_why = s.acc_ok ? "" : "more than 16 spheres";
+    install_scene(ctx, std::move(s));   // (the old scene's block becomes the next build's)
     if (device_ms_out) *device_ms_out = ms;
     return MPT_OK;
 }
@@ -2265,8 +2119,8 @@ static int write_sum_impl(mpt_ctx* ctx, const float* in) {
     int wrc = wait_impl(ctx);
     if (wrc) return wrc;
     HIPCHK(hipMemcpyAsync(ctx->d_sum, in, (size_t)ctx->W * ctx->H * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->ev_sum_op, ctx->stream));   // the next resolve (on either lane) is ordered behind the upload
-    ctx->last_resolved = ctx->ev_sum_op;
+    HIPCHK(hipEventRecord(ctx->ev_sum_op.get(), ctx->stream));   // the next resolve (on either lane) is ordered behind the upload
+    ctx->last_resolved = ctx->ev_sum_op.get();
     HIPCHK(hipStreamSynchronize(ctx->stream));             // (the host array may be freed on return)
     return MPT_OK;
 }
@@ -2378,19 +2232,13 @@ static int dn_filter(mpt_ctx* ctx, hipStream_t stream, uint32_t W, uint32_t H, c
 }
 static int ensure_dn_buffers(mpt_ctx* ctx) {
     if (ctx->d_denoised && ctx->dn_W == ctx->W && ctx->dn_H == ctx->H) return MPT_OK;
-    float4** bufs[] = {&ctx->d_aov_ad, &ctx->d_aov_nc, &ctx->d_dn_guide, &ctx->d_dn_x[0], &ctx->d_dn_x[1], &ctx->d_denoised};
-    for (float4** b : bufs) {
-        hipFree(*b);
-        *b = nullptr;
-    }
-    hipFree(ctx->d_aov_prim);
-    ctx->d_aov_prim = nullptr;
     ctx->dn_W = ctx->dn_H = 0;
     ctx->guide_built = 0;
     ctx->denoised_valid = false;
     const size_t n = (size_t)ctx->W * ctx->H;
-    for (float4** b : bufs) HIPCHK(hipMalloc(b, n * 16));
-    HIPCHK(hipMalloc(&ctx->d_aov_prim, n * 4));
+    for (DevMem<float4>* b : {&ctx->d_aov_ad, &ctx->d_aov_nc, &ctx->d_dn_guide, &ctx->d_dn_x[0], &ctx->d_dn_x[1], &ctx->d_denoised})
+        HIPCHK(b->alloc(n * 16));
+    HIPCHK(ctx->d_aov_prim.alloc(n * 4));
     ctx->dn_W = ctx->W;
     ctx->dn_H = ctx->H;
     return MPT_OK;
@@ -2420,7 +2268,8 @@ static int refresh_guides(mpt_ctx* ctx) {
                        ctx->stream, sc, F3{u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2]},
                        F3{u.firstPixelPosition[0], u.firstPixelPosition[1], u.firstPixelPosition[2]},
                        F3{u.viewportU[0], u.viewportU[1], u.viewportU[2]}, F3{u.viewportV[0], u.viewportV[1], u.viewportV[2]},
-                       u.screenSize[0], u.screenSize[1], ctx->W, ctx->H, ctx->d_aov_ad, ctx->d_aov_nc, ctx->d_aov_prim, ctx->d_dn_guide);
+                       u.screenSize[0], u.screenSize[1], ctx->W, ctx->H, ctx->d_aov_ad.get(), ctx->d_aov_nc.get(), ctx->d_aov_prim.get(),
+                       ctx->d_dn_guide.get());
     HIPCHK(hipGetLastError());
     ctx->guide_built = ctx->guide_epoch;
     memcpy(ctx->guide_cam, key, sizeof key);
@@ -2432,9 +2281,9 @@ static int read_aovs_impl(mpt_ctx* ctx, float* ad, float* nc, int32_t* prim) {
     if (rc) return rc;
     if ((rc = refresh_guides(ctx))) return rc;
     const size_t n = (size_t)ctx->W * ctx->H;
-    HIPCHK(hipMemcpyAsync(ad, ctx->d_aov_ad, n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(nc, ctx->d_aov_nc, n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (prim) HIPCHK(hipMemcpyAsync(prim, ctx->d_aov_prim, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(ad, ctx->d_aov_ad.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(nc, ctx->d_aov_nc.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (prim) HIPCHK(hipMemcpyAsync(prim, ctx->d_aov_prim.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MPT_OK;
 }
@@ -2448,10 +2297,10 @@ static int denoise_impl(mpt_ctx* ctx, const mpt_denoise_params* p) {
     if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
     if ((rc = refresh_guides(ctx))) return rc;
     const bool sum = p->source == MPT_DENOISE_SUM;
-    float4* x[2] = {ctx->d_dn_x[0], ctx->d_dn_x[1]};
+    float4* x[2] = {ctx->d_dn_x[0].get(), ctx->d_dn_x[1].get()};
     ctx->denoised_valid = false;
-    if ((rc = dn_filter(ctx, ctx->stream, ctx->W, ctx->H, sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target], sum ? (float)p->samples : 1.0f,
-                        ctx->d_aov_ad, ctx->d_dn_guide, x, sg, ctx->d_denoised)))
+    if ((rc = dn_filter(ctx, ctx->stream, ctx->W, ctx->H, sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target].get(), sum ? (float)p->samples : 1.0f,
+                        ctx->d_aov_ad.get(), ctx->d_dn_guide.get(), x, sg, ctx->d_denoised.get())))
         return rc;
     ctx->denoised_valid = true;
     return MPT_OK;
@@ -2459,7 +2308,7 @@ static int denoise_impl(mpt_ctx* ctx, const mpt_denoise_params* p) {
 static int read_denoised_impl(mpt_ctx* ctx, float* out) {
     if (!ctx || !out) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
     if (!ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
-    HIPCHK(hipMemcpyAsync(out, ctx->d_denoised, (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, ctx->d_denoised.get(), (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MPT_OK;
 }
@@ -2472,19 +2321,19 @@ static int denoise_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float*
     if (rc) return rc;
     HIPCHK(hipSetDevice(ctx->device));
     const size_t n = (size_t)W * H;
-    DevBuf d_c, d_ad, d_nc, d_g, d_x0, d_x1, d_o;
-    for (DevBuf* b : {&d_c, &d_ad, &d_nc, &d_g, &d_x0, &d_x1, &d_o}) HIPCHK(b->alloc(n * 16));
-    HIPCHK(hipMemcpyAsync(d_c.p, color, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_ad.p, ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_nc.p, nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)d_ad.p, (const float4*)d_nc.p,
-                       (uint32_t)n, (float4*)d_g.p);
+    DevMem<> d_c, d_ad, d_nc, d_g, d_x0, d_x1, d_o;
+    for (DevMem<>* b : {&d_c, &d_ad, &d_nc, &d_g, &d_x0, &d_x1, &d_o}) HIPCHK(b->alloc(n * 16));
+    HIPCHK(hipMemcpyAsync(d_c.get(), color, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)d_ad.get(), (const float4*)d_nc.get(),
+                       (uint32_t)n, (float4*)d_g.get());
     HIPCHK(hipGetLastError());
-    float4* x[2] = {(float4*)d_x0.p, (float4*)d_x1.p};
-    if ((rc = dn_filter(ctx, ctx->stream, W, H, (const float4*)d_c.p, 1.0f, (const float4*)d_ad.p, (const float4*)d_g.p, x, sg,
-                        (float4*)d_o.p)))
+    float4* x[2] = {(float4*)d_x0.get(), (float4*)d_x1.get()};
+    if ((rc = dn_filter(ctx, ctx->stream, W, H, (const float4*)d_c.get(), 1.0f, (const float4*)d_ad.get(), (const float4*)d_g.get(), x, sg,
+                        (float4*)d_o.get())))
         return rc;
-    HIPCHK(hipMemcpyAsync(out, d_o.p, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out, d_o.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return MPT_OK;
 }
@@ -2500,7 +2349,7 @@ extern "C" int mpt_read_denoised(mpt_ctx* ctx, float* rgba) {
 extern "C" int mpt_denoised_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
     if (!ctx || !p) return MPT_ERR_INVALID_ARG;
     if (!ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
-    *p = ctx->d_denoised;
+    *p = ctx->d_denoised.get();
     if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 16;
     return MPT_OK;
 }
@@ -2531,16 +2380,16 @@ extern "C" int mpt_scene_digest(mpt_ctx* ctx, uint64_t out[16]) {
             {ctx->d_acc_nodes, (uint64_t)ctx->n_acc_nodes * MPT_OT_NODE_STRIDE * 4}, {ctx->d_refleaf, (uint64_t)ctx->n_ref_leaves * 8},
             {ctx->d_refbox, ctx->d_refbox ? (uint64_t)ctx->n_prims * 8 : 0u}, {ctx->d_always, (uint64_t)ctx->n_always * 20},
             {ctx->d_ref_bvh, built ? (uint64_t)ctx->n_ref_nodes * 8 : 0u}, {ctx->d_ref_idx, built ? (uint64_t)ctx->n_prims : 0u}};
-        DevBuf d;
+        DevMem<> d;
         HIPCHK(d.alloc(16 * 8));
-        HIPCHK(hipMemsetAsync(d.p, 0, 16 * 8, ctx->stream));
+        HIPCHK(hipMemsetAsync(d.get(), 0, 16 * 8, ctx->stream));
         for (int k = 0; k < 9; ++k)
             if (a[k].p && a[k].words) {
                 const uint32_t g = (uint32_t)std::min<uint64_t>((a[k].words + 255) / 256, 2048);
-                hipLaunchKernelGGL(k_digest, dim3(g), dim3(256), 0, ctx->stream, (const uint32_t*)a[k].p, a[k].words, (unsigned long long*)d.p + k);
+                hipLaunchKernelGGL(k_digest, dim3(g), dim3(256), 0, ctx->stream, (const uint32_t*)a[k].p, a[k].words, (unsigned long long*)d.get() + k);
             }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out, d.p, 16 * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(out, d.get(), 16 * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         const uint64_t counts[7] = {ctx->n_nodes, ctx->n_prims, ctx->n_mats, ctx->n_acc_nodes, ctx->n_ref_leaves, ctx->n_always, ctx->acc_depth};
         for (int k = 0; k < 7; ++k) out[9 + k] = counts[k];

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "mpt_own.h"
 #include "mpt_sah.h"
 
 #define MPT_LBVH_LEAF_MAX 8u   // what the reference's builder allows (R/Scene/Scene.h:223) and a device leaf record holds twice over
@@ -772,30 +773,20 @@ static hipError_t build(hipStream_t stream, const float* prims, uint32_t n, int 
     MPT_LB(sc.alloc(&d_bvh, 2 * (2 * (size_t)n - 1)));
     MPT_LB(sc.alloc(&d_idx, n));
     MPT_LB(hipMemcpyAsync(d_prims, prims, (size_t)n * 48, hipMemcpyHostToDevice, stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    MPT_LB(hipEventCreate(&e0));
-    hipError_t rc = hipEventCreate(&e1);
-    if (rc != hipSuccess) {
-        hipEventDestroy(e0);
-        return rc;
-    }
-    auto body = [&]() -> hipError_t {
-        MPT_LB(hipEventRecord(e0, stream));
-        Radix R;
-        MPT_LB(build_radix(stream, sc, d_prims, n, leaf_max, builder, R));
-        MPT_LB(emit_reference_format(stream, R, d_bvh, d_idx));
-        MPT_LB(hipEventRecord(e1, stream));
-        MPT_LB(hipStreamSynchronize(stream));
-        MPT_LB(hipMemcpy(bvh_out, d_bvh, (size_t)R.n_out * 32, hipMemcpyDeviceToHost));
-        MPT_LB(hipMemcpy(prim_idx_out, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
-        *n_nodes_out = R.n_out;
-        if (ms_out) MPT_LB(hipEventElapsedTime(ms_out, e0, e1));
-        return hipSuccess;
-    };
-    rc = body();
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    return rc;
+    mpt_own::Event e0, e1;
+    MPT_LB(e0.create(hipEventCreate));
+    MPT_LB(e1.create(hipEventCreate));
+    MPT_LB(hipEventRecord(e0.get(), stream));
+    Radix R;
+    MPT_LB(build_radix(stream, sc, d_prims, n, leaf_max, builder, R));
+    MPT_LB(emit_reference_format(stream, R, d_bvh, d_idx));
+    MPT_LB(hipEventRecord(e1.get(), stream));
+    MPT_LB(hipStreamSynchronize(stream));
+    MPT_LB(hipMemcpy(bvh_out, d_bvh, (size_t)R.n_out * 32, hipMemcpyDeviceToHost));
+    MPT_LB(hipMemcpy(prim_idx_out, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost));
+    *n_nodes_out = R.n_out;
+    if (ms_out) MPT_LB(hipEventElapsedTime(ms_out, e0.get(), e1.get()));
+    return hipSuccess;
 }
 
 }  // namespace mpt_lbvh

@@ -751,3 +751,45 @@ def test_checkpoint_and_resume_of_the_accumulation(gpu_ctx, tmp_path):
     for other_run in (["--scene", scene_path("cornell.xml")], ["--bsdf", "scatter"]):   # ... and so is one of another scene or material model
         r = subprocess.run(base + ["--spp", "3", "--resume", c] + other_run, capture_output=True, text=True)
         assert r.returncode != 0 and "another scene, size, seed" in r.stderr, r.stderr
+
+
+def test_destroy_with_everything_live():
+    """mpt_destroy of a context that holds every kind of resource at once: a spare scene block (two builds), the moments, the
+    denoiser's buffers, the adaptive tile buffers and two renders still in flight (no mpt_wait).  Three times in one process; a
+    context made afterwards renders bit for bit what one made before did."""
+    from metalpathtracer_amd import capi, host
+    W, H = 96, 64
+    kw = dict(rng_mode=capi.RNG_PHILOX, max_depth=8, seed=(3, 1))
+
+    def make():
+        ctx = capi.Context(0)
+        sc = host.Scene()
+        st, log = host.SceneLoader.LoadSceneFromXML(scene_path("cornell.xml"), sc)
+        assert st == 0, log
+        _, prims, mats, _ = host.make_ready(ctx, sc, host.BVH_DEVICE)
+        ctx.resize(W, H)
+        ctx.set_uniforms(host.make_uniforms(W, H, sc.getPrimitiveCount(), sc.getTriangleCount(), cam=CORNELL_CAM))
+        return ctx, prims, mats
+
+    def image(ctx):
+        ctx.clear_sum()
+        ctx.render(sample_count=4, **kw)
+        return ctx.read_sum()
+
+    ctx, _, _ = make()
+    before = image(ctx)
+    ctx.close()
+    for _ in range(3):
+        ctx, prims, mats = make()
+        ctx.build_and_upload(prims, mats)                        # the first build's block becomes the spare
+        ctx.render(sample_count=2, flags=capi.FLAG_MOMENTS, **kw)
+        ctx.denoise(source=capi.DENOISE_SUM, samples=2)
+        ctx.render_adaptive(0.05, sample_count=8, **kw)
+        ctx.render_async(sample_begin=0, sample_count=2, **kw)
+        ctx.render_async(sample_begin=2, sample_count=2, **kw)
+        ctx.close()
+    ctx, _, _ = make()
+    after = image(ctx)
+    ctx.close()
+    assert before[..., 3].max() > 0
+    np.testing.assert_array_equal(before.view(np.uint32), after.view(np.uint32))
