@@ -377,6 +377,72 @@ int mpt_render_adaptive(mpt_ctx* ctx, const mpt_render_params* p, const mpt_adap
  * MPT_ERR_NOT_READY before mpt_resize).                                                                                       */
 int mpt_read_tile_samples(mpt_ctx* ctx, uint32_t* counts);
 
+/* ---- temporal accumulation: the history follows the camera ----------------------------------------------------------------------
+ * No reference counterpart (the reference restarts its running mean on every camera change, Renderer.cpp:255-257).
+ *
+ * State per context: a history image (RGBA32F; rgb = accumulated radiance, a = history length n, a float >= 1), the history guide
+ * of the frame it belongs to (per pixel: the ray-facing normal and the hit distance t of mpt_read_aovs, t = +inf for a miss) and
+ * that frame's camera (cameraPosition, viewportU/V, firstPixelPosition, screenSize: the fourteen floats that make guides stale).
+ * Two of each, ping-pong.  Allocated by the first mpt_temporal_accumulate; dropped by mpt_resize, mpt_upload_scene,
+ * mpt_build_and_upload and mpt_temporal_reset.  mpt_clear_sum does not touch it.
+ *
+ * mpt_temporal_accumulate waits for the renders queued and in flight (reporting a failed mpt_render_async), refreshes stale guides,
+ * then for every pixel p of the current frame, c = sum / samples (SUM) or the current mpt_draw target (FRAME), (cam, first, vu, vv)
+ * the current camera, primes marking the history's camera.  All arithmetic is float32, one IEEE operation at a time in the order
+ * written; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; |r| = sqrt(dot(r, r)) (tests/temporal_ref.py restates it in numpy):
+ *   1. d = the pixel-centre direction of the guide pass: dv = (first + ((px + 0.5) / W) vu + ((py + 0.5) / H) vv) - cam,
+ *      d = dv * (1 / sqrt(dot(dv, dv))).  For a hit (class 0 or 1): r = (cam + t_p * d) - cam'.  For a miss: r = d (a miss
+ *      reprojects by direction only).
+ *   2. nn = cross(vu', vv'); fc = first' - cam'; s = dot(fc, nn) / dot(r, nn).  No history unless s > 0 and s is finite.
+ *   3. q = s * r - fc; u = dot(q, vu') / dot(vu', vu'); v = dot(q, vv') / dot(vv', vv') (the viewport vectors are orthogonal);
+ *      fx = u * W - 0.5, fy = v * H - 0.5.  No history unless -1 <= fx < W and -1 <= fy < H.  x0 = floor(fx), y0 = floor(fy),
+ *      ax = fx - x0, ay = fy - y0.
+ *   4. Four taps (x0 + i, y0 + j), j outer, i inner, weight (i ? ax : 1 - ax) * (j ? ay : 1 - ay).  A tap counts iff it is inside
+ *      the image and, for a hit p: the tap is a hit, |t_q - |r|| <= depth_tolerance * |r|, and dot(n_p, n_q) >= normal_threshold;
+ *      for a miss p: the tap is a miss.
+ *   5. sw = sum of the counted weights, in tap order.  If !(sw >= min_weight): out = (c.rgb, 1) — c's bits — and the pixel counts as
+ *      reset.  Otherwise h = (sum w * hist.rgb) / sw, m = (sum w * hist.a) / sw, n = min(m + 1, max_history),
+ *      out = (h + (c.rgb - h) / n, n).
+ *   6. Same camera: when the fourteen camera floats equal the history's bit for bit, the only tap is p itself with weight 1 and no
+ *      test (a float reprojection of an unmoved camera lands up to 1e-4 pixel off the centre and would blur a little more every
+ *      frame; with this rule a still camera gives the plain running mean).
+ *   7. No history at all (first call, after a reset or a drop): every pixel is reset.
+ * The new history guide is the current guide.  pixels_reprojected + pixels_reset = W * H.  The stage reads the HDR sum or the frame
+ * target and writes neither; mpt_stats is untouched.
+ * MPT_ERR_INVALID_ARG, with nothing changed: null params, a bad source, SUM with samples = 0, a NaN tolerance.  MPT_ERR_NOT_READY
+ * before scene, uniforms and size, and from mpt_read_temporal / mpt_temporal_buffer / mpt_denoise_temporal while there is no history.
+ * Defaults: chosen by the sweep of profiles/r07_temporal_sweep.txt.                                                               */
+#define MPT_TEMPORAL_DEFAULT_MAX_HISTORY 32u
+#define MPT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE 0.05f
+#define MPT_TEMPORAL_DEFAULT_NORMAL_THRESHOLD 0.5f
+#define MPT_TEMPORAL_DEFAULT_MIN_WEIGHT 0.05f
+typedef struct mpt_temporal_params {
+    int32_t source;            /* MPT_DENOISE_SUM (sum / samples) or MPT_DENOISE_FRAME: this frame's colour c                        */
+    uint32_t samples;          /* SUM: samples the sum holds (> 0)                                                                  */
+    uint32_t max_history;      /* cap of n; 0 = MPT_TEMPORAL_DEFAULT_MAX_HISTORY                                                    */
+    float depth_tolerance;     /* relative; <= 0 = default                                                                          */
+    float normal_threshold;    /* least n_p . n_q of a tap; <= 0 = default                                                          */
+    float min_weight;          /* least sum of valid tap weights; <= 0 = default                                                    */
+} mpt_temporal_params;
+typedef struct mpt_temporal_info {
+    uint64_t pixels_reprojected, pixels_reset;
+} mpt_temporal_info;
+
+int mpt_temporal_accumulate(mpt_ctx* ctx, const mpt_temporal_params* params, mpt_temporal_info* out /* may be NULL */);
+int mpt_read_temporal(mpt_ctx* ctx, float* rgba_host);                 /* rgb = accumulated colour, a = n (W*H*4 floats)             */
+int mpt_temporal_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);
+int mpt_temporal_reset(mpt_ctx* ctx);
+/* The a-trous filter of mpt_denoise over the history's rgb with the current guides, into the denoised buffer (mpt_read_denoised);
+ * source / samples of the params are ignored; alpha = n.                                                                          */
+int mpt_denoise_temporal(mpt_ctx* ctx, const mpt_denoise_params* params);
+/* The same kernels on caller arrays (host, W*H*4 floats each; the unit-test hook, no scene needed): color is c itself (source and
+ * samples are ignored), the guides as mpt_read_aovs returns them, the cameras as uniforms (W, H stand for screenSize in the
+ * arithmetic).  history_prev = NULL: no history (the three other *_prev arguments are ignored).                                   */
+int mpt_temporal_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const float* albedo_depth_cur,
+                       const float* normal_class_cur, const mpt_uniforms* cam_cur, const float* history_prev,
+                       const float* albedo_depth_prev, const float* normal_class_prev, const mpt_uniforms* cam_prev,
+                       const mpt_temporal_params* params, float* history_out, mpt_temporal_info* out /* may be NULL */);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

@@ -79,6 +79,15 @@ int mpt_renderer_denoise(mpt_renderer* r, const mpt_denoise_params* params, floa
  * the counts per tile through mpt_read_tile_samples(mpt_renderer_context(r), ...).  out may not be NULL.                         */
 int mpt_renderer_render_adaptive(mpt_renderer* r, uint32_t sample_begin, uint32_t max_samples, const mpt_adaptive_params* params,
                                  mpt_adaptive_info* out);
+/* One frame of temporal accumulation (mpt_temporal_accumulate, include/mpt.h): consumes the pending input as mpt_renderer_draw does,
+ * clears the sum, renders samples_per_frame philox samples starting at frame * samples_per_frame — the frame counter is never reset
+ * by camera motion, so no two frames share samples — and blends them into the history reprojected from the previous frame's camera.
+ * params (may be NULL: keep the renderer's, initially the defaults): max_history and the tolerances; source / samples are ignored.
+ * out may be NULL.  mpt_renderer_read_temporal: the history (rgb, a = its length); mpt_renderer_denoise_temporal:
+ * mpt_denoise_temporal + mpt_read_denoised.  rgba: W*H*4 floats.                                                                  */
+int mpt_renderer_draw_temporal(mpt_renderer* r, uint32_t samples_per_frame, const mpt_temporal_params* params, mpt_temporal_info* out);
+int mpt_renderer_read_temporal(mpt_renderer* r, float* rgba);
+int mpt_renderer_denoise_temporal(mpt_renderer* r, const mpt_denoise_params* params, float* rgba);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 

@@ -31,6 +31,8 @@ SYMBOLS = (
     "mpt_build_bvh", "mpt_build_and_upload", "mpt_download_bvh", "mpt_gpu_leaf_max", "mpt_build_info", "mpt_scene_digest", "mpt_comm_unique_id", "mpt_comm_create_all", "mpt_comm_create_rank", "mpt_reduce_sum", "mpt_comm_destroy",
     "mpt_comm_last_error", "mpt_read_aovs", "mpt_denoise", "mpt_read_denoised", "mpt_denoised_buffer", "mpt_denoise_image",
     "mpt_read_moments", "mpt_render_adaptive", "mpt_read_tile_samples",
+    "mpt_temporal_accumulate", "mpt_read_temporal", "mpt_temporal_buffer", "mpt_temporal_reset", "mpt_denoise_temporal",
+    "mpt_temporal_image",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
@@ -39,6 +41,8 @@ DENOISE_MAX_ITERATIONS = 8
 DENOISE_DEFAULTS = dict(iterations=3, sigma_luminance=8.0, sigma_normal=32.0, sigma_depth=0.25)
 # include/mpt.h MPT_ADAPTIVE_DEFAULT_* (0 / a floor <= 0 selects them)
 ADAPTIVE_DEFAULTS = dict(min_samples=16, batch_samples=16, luminance_floor=0.05)
+# include/mpt.h MPT_TEMPORAL_DEFAULT_* (0 / a tolerance <= 0 selects them)
+TEMPORAL_DEFAULTS = dict(max_history=32, depth_tolerance=0.05, normal_threshold=0.5, min_weight=0.05)
 
 
 class MptError(RuntimeError):
@@ -112,6 +116,24 @@ class AdaptiveInfo(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "_pad"}
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("source", C.c_int32), ("samples", C.c_uint32), ("max_history", C.c_uint32),
+                ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("min_weight", C.c_float)]
+
+
+class TemporalInfo(C.Structure):
+    _fields_ = [("pixels_reprojected", C.c_uint64), ("pixels_reset", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def temporal_params(source=DENOISE_SUM, samples=0, max_history=0, depth_tolerance=0.0, normal_threshold=0.0, min_weight=0.0):
+    """mpt_temporal_params; max_history = 0 and tolerances <= 0 mean the defaults of include/mpt.h."""
+    return TemporalParams(int(source), int(samples), int(max_history), float(depth_tolerance), float(normal_threshold),
+                          float(min_weight))
 
 
 def expand_tile_counts(counts, H, W):
@@ -210,6 +232,13 @@ def load():
     L.mpt_read_moments.argtypes = [vp, fp]
     L.mpt_render_adaptive.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo)]
     L.mpt_read_tile_samples.argtypes = [vp, up]
+    L.mpt_temporal_accumulate.argtypes = [vp, C.POINTER(TemporalParams), C.POINTER(TemporalInfo)]
+    L.mpt_read_temporal.argtypes = [vp, fp]
+    L.mpt_temporal_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_temporal_reset.argtypes = [vp]
+    L.mpt_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams)]
+    L.mpt_temporal_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, fp, C.POINTER(Uniforms), fp, fp, fp, C.POINTER(Uniforms),
+                                     C.POINTER(TemporalParams), fp, C.POINTER(TemporalInfo)]
     _lib = L
     return L
 
@@ -530,6 +559,61 @@ class Context:
         """The per-pixel estimate of the last adaptive render: the HDR sum divided by its tile's sample count, in float32."""
         n = expand_tile_counts(self.read_tile_samples(), self.height, self.width).astype(np.float32)
         return self.read_sum() / n[..., None]
+
+    def temporal_accumulate(self, **kw):
+        """mpt_temporal_accumulate: blend this frame's colour (source=DENOISE_SUM, samples=spp, or DENOISE_FRAME) into the history
+        reprojected from the previous camera; returns the mpt_temporal_info as a dict."""
+        p = temporal_params(**kw)
+        info = TemporalInfo()
+        self._chk(self.L.mpt_temporal_accumulate(self.h, C.byref(p), C.byref(info)), "mpt_temporal_accumulate")
+        return info.as_dict()
+
+    def read_temporal(self):
+        """The history: rgb = accumulated colour, a = history length n, [H,W,4]."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._chk(self.L.mpt_read_temporal(self.h, _fp(out)), "mpt_read_temporal")
+        return out
+
+    def temporal_buffer(self):
+        """(device pointer, bytes) of the history, for zero-copy use after synchronize()."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_temporal_buffer(self.h, C.byref(p), C.byref(n)), "mpt_temporal_buffer")
+        return p.value, n.value
+
+    def temporal_reset(self):
+        self._chk(self.L.mpt_temporal_reset(self.h), "mpt_temporal_reset")
+
+    def denoise_temporal(self, **kw):
+        """mpt_denoise_temporal: the a-trous filter over the history with the current guides (read_denoised has the result)."""
+        p = denoise_params(**kw)
+        self._chk(self.L.mpt_denoise_temporal(self.h, C.byref(p)), "mpt_denoise_temporal")
+
+    def temporal_image(self, color, albedo_depth, normal_class, cam, history=None, albedo_depth_prev=None, normal_class_prev=None,
+                       cam_prev=None, **kw):
+        """The temporal kernels on caller arrays [H,W,4] with the two cameras as Uniforms; history=None: no history.
+        Returns (new history [H,W,4], info dict)."""
+        c = np.ascontiguousarray(color, np.float32)
+        ad = np.ascontiguousarray(albedo_depth, np.float32)
+        nc = np.ascontiguousarray(normal_class, np.float32)
+        if c.ndim != 3 or c.shape[2] != 4 or ad.shape != c.shape or nc.shape != c.shape:
+            raise ValueError("temporal_image: color, albedo_depth and normal_class must be [H, W, 4] arrays of one shape")
+        H, W = c.shape[:2]
+        null = C.POINTER(C.c_float)()
+        hp = adp = ncp = null
+        camp = None
+        if history is not None:
+            h = np.ascontiguousarray(history, np.float32)
+            a2 = np.ascontiguousarray(albedo_depth_prev, np.float32)
+            n2 = np.ascontiguousarray(normal_class_prev, np.float32)
+            if h.shape != c.shape or a2.shape != c.shape or n2.shape != c.shape or cam_prev is None:
+                raise ValueError("temporal_image: the history, its guides and its camera go together, in the shape of color")
+            hp, adp, ncp, camp = _fp(h), _fp(a2), _fp(n2), C.byref(cam_prev)
+        out = np.empty_like(c)
+        p = temporal_params(**kw)
+        info = TemporalInfo()
+        self._chk(self.L.mpt_temporal_image(self.h, W, H, _fp(c), _fp(ad), _fp(nc), C.byref(cam), hp, adp, ncp, camp, C.byref(p),
+                                            _fp(out), C.byref(info)), "mpt_temporal_image")
+        return out, info.as_dict()
 
     def kat_pcg(self, seeds):
         s = np.ascontiguousarray(seeds, np.uint32)

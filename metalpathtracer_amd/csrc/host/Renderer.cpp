@@ -282,6 +282,32 @@ void Renderer::readAdaptiveMean(std::vector<float>& rgba) {
         }
 }
 
+mpt_temporal_info Renderer::drawTemporal(OffscreenView* /*view*/, uint32_t samplesPerFrame) {
+    if (samplesPerFrame == 0) throw std::runtime_error("drawTemporal: samplesPerFrame = 0");
+    if (params_.rng_mode != MPT_RNG_PHILOX) throw std::runtime_error("drawTemporal: needs MPT_RNG_PHILOX (the literal stream repeats per pixel)");
+    updateCamera();
+    clearSum();
+    renderBatch(temporalFrame_ * samplesPerFrame, samplesPerFrame);
+    ++temporalFrame_;
+    mpt_temporal_params p = temporal_;
+    p.source = MPT_DENOISE_SUM;
+    p.samples = samplesPerFrame;
+    mpt_temporal_info info;
+    check(mpt_temporal_accumulate(ctx_, &p, &info), "mpt_temporal_accumulate");
+    return info;
+}
+
+void Renderer::readTemporal(std::vector<float>& rgba) {
+    rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_temporal(ctx_, rgba.data()), "mpt_read_temporal");
+}
+
+void Renderer::denoiseTemporal(const mpt_denoise_params& p, std::vector<float>& rgba) {
+    check(mpt_denoise_temporal(ctx_, &p), "mpt_denoise_temporal");
+    rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_denoised(ctx_, rgba.data()), "mpt_read_denoised");
+}
+
 void Renderer::readSum(std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     rgba.resize(n);

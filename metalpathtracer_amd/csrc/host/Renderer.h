@@ -64,6 +64,13 @@ public:
     // mpt_render_adaptive of [sampleBegin, sampleBegin + maxSamples) at most per tile; readAdaptiveMean = the sum / the tile's count
     mpt_adaptive_info renderAdaptive(uint32_t sampleBegin, uint32_t maxSamples, const mpt_adaptive_params& a);
     void readAdaptiveMean(std::vector<float>& rgba);
+    // Temporal accumulation (mpt_temporal_accumulate, include/mpt.h): updateCamera(), then the sum is cleared, samplesPerFrame philox
+    // samples starting at frame * samplesPerFrame are rendered — the frame counter is never reset by camera motion, so no two frames
+    // share samples — and blended into the history reprojected from the previous frame's camera.  draw() is unchanged.
+    mpt_temporal_info drawTemporal(OffscreenView* view, uint32_t samplesPerFrame);
+    void setTemporalParams(const mpt_temporal_params& p) { temporal_ = p; }
+    void readTemporal(std::vector<float>& rgba);                                        // the history: rgb, a = its length
+    void denoiseTemporal(const mpt_denoise_params& p, std::vector<float>& rgba);        // mpt_denoise_temporal + mpt_read_denoised
 
 private:
     void check(int status, const char* where);
@@ -79,6 +86,8 @@ private:
     bool sceneUploaded_ = false;
     int buildMode_ = BUILD_REFERENCE;
     bool deviceBuild_ = false, deviceDirty_ = false;
+    mpt_temporal_params temporal_ = {};  // zeros: the defaults of include/mpt.h
+    uint32_t temporalFrame_ = 0;         // frames drawTemporal() has drawn
     int lastSource_ = MPT_DENOISE_SUM;   // what denoise() filters: the source of the last draw() / renderBatch()
     uint32_t sumSamples_ = 0;            // samples renderBatch() added since the sum was cleared   // BUILD_GPU: mpt_build_and_upload, no tree on the host
 };

@@ -282,6 +282,26 @@ int mpt_renderer_render_adaptive(mpt_renderer* r, uint32_t sample_begin, uint32_
     if (!r || !p || !out) return MPT_ERR_INVALID_ARG;
     GUARD({ *out = r->r->renderAdaptive(sample_begin, max_samples, *p); });
 }
+int mpt_renderer_draw_temporal(mpt_renderer* r, uint32_t samples_per_frame, const mpt_temporal_params* p, mpt_temporal_info* out) {
+    if (!r || samples_per_frame == 0) return MPT_ERR_INVALID_ARG;
+    GUARD({
+        if (p) r->r->setTemporalParams(*p);
+        const mpt_temporal_info info = r->r->drawTemporal(nullptr, samples_per_frame);
+        if (out) *out = info;
+    });
+}
+int mpt_renderer_read_temporal(mpt_renderer* r, float* rgba) {
+    if (!r || !rgba) return MPT_ERR_INVALID_ARG;
+    return mpt_read_temporal(r->r->context(), rgba);
+}
+int mpt_renderer_denoise_temporal(mpt_renderer* r, const mpt_denoise_params* p, float* rgba) {
+    if (!r || !p || !rgba) return MPT_ERR_INVALID_ARG;
+    std::vector<float> img;
+    GUARD({
+        r->r->denoiseTemporal(*p, img);
+        std::memcpy(rgba, img.data(), img.size() * sizeof(float));
+    });
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

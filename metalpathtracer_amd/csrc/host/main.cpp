@@ -43,6 +43,12 @@ static void usage() {
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]]\n"
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
+        "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
+        "  --temporal        with --camera-path: every frame renders --temporal-spp fresh philox samples (default 1) and blends them\n"
+        "                    into the image accumulated so far, reprojected from the previous camera (mpt_temporal_accumulate,\n"
+        "                    include/mpt.h; the history is at most --temporal-history frames long, default 32); the frame written is\n"
+        "                    the history (with --denoise: mpt_denoise_temporal's); the per-frame JSON line gains \"reprojected\" and\n"
+        "                    \"reset\".  Not with --rng literal, --gpus > 1, --adaptive, --checkpoint or --resume\n"
         "  --adaptive T      batch mode, adaptive sampling (mpt_render_adaptive, include/mpt.h): every 8x8 tile gets --adaptive-min\n"
         "                    samples (default 16), then --adaptive-batch more per pass (default 16) until the relative standard error\n"
         "                    of each of its pixels' mean luminance is <= T (luminance below --adaptive-floor, default 0.05, counts as\n"
@@ -117,7 +123,7 @@ static bool applyInputLine(const std::string& line, int* repeat) {
 // number of frames, -1 on error.  Prints one JSON line per frame (camera, frameCount) for checking against the reference's
 // protocol (a camera change resets the accumulation and reseeds, R/Renderer/Renderer.cpp:255-257).
 static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& path, const std::string& outDir,
-                          const mpt_denoise_params* dn) {
+                          const mpt_denoise_params* dn, uint32_t temporalSpp = 0) {
     FILE* f = std::fopen(path.c_str(), "r");
     if (!f) {
         std::fprintf(stderr, "cannot open camera path %s\n", path.c_str());
@@ -140,17 +146,28 @@ static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& p
                 return -1;
             }
             n = repeat;
-            r.draw(&view);
-            r.readFrame(&view);
-            if (dn) r.denoise(*dn, view.rgba);
+            mpt_temporal_info ti = {};
+            if (temporalSpp) {   // --temporal: the frame is the history (or the filtered history)
+                ti = r.drawTemporal(&view, temporalSpp);
+                if (dn) r.denoiseTemporal(*dn, view.rgba);
+                else r.readTemporal(view.rgba);
+            } else {
+                r.draw(&view);
+                r.readFrame(&view);
+                if (dn) r.denoise(*dn, view.rgba);
+            }
             const mpt_uniforms& u = r.uniforms();
             char name[64];
             std::snprintf(name, sizeof name, "/frame_%04d.ppm", frame);
             if (mpt_write_ppm((outDir + name).c_str(), view.rgba.data(), (int)view.width, (int)view.height, 1.0f, 2.2f))
                 std::fprintf(stderr, "cannot write %s%s\n", outDir.c_str(), name);
-            std::printf("{\"frame\": %d, \"frameCount\": %llu, \"camera\": [%.9g, %.9g, %.9g], \"forward\": [%.9g, %.9g, %.9g], \"vfov\": %.9g}\n",
+            char temporalJson[96] = "";
+            if (temporalSpp)
+                std::snprintf(temporalJson, sizeof temporalJson, ", \"reprojected\": %llu, \"reset\": %llu", (unsigned long long)ti.pixels_reprojected,
+                              (unsigned long long)ti.pixels_reset);
+            std::printf("{\"frame\": %d, \"frameCount\": %llu, \"camera\": [%.9g, %.9g, %.9g], \"forward\": [%.9g, %.9g, %.9g], \"vfov\": %.9g%s}\n",
                         frame, (unsigned long long)u.frameCount, u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2],
-                        Camera::forward.x, Camera::forward.y, Camera::forward.z, Camera::verticalFov);
+                        Camera::forward.x, Camera::forward.y, Camera::forward.z, Camera::verticalFov, temporalJson);
             ++frame;
         }
     }
@@ -245,6 +262,9 @@ int main(int argc, char** argv) {
     mpt_denoise_params dnp;
     std::memset(&dnp, 0, sizeof dnp);
     dnp.iterations = -1;   // (defaults of include/mpt.h)
+    bool temporal = false;
+    mpt_temporal_params tpp = {};
+    uint32_t temporalSpp = 1;
     bool adaptive = false;
     mpt_adaptive_params adp;
     std::memset(&adp, 0, sizeof adp);   // (0 = the defaults of include/mpt.h)
@@ -290,6 +310,9 @@ int main(int argc, char** argv) {
             adaptive = true;
             adp.threshold = static_cast<float>(std::atof(next()));
         }
+        else if (a == "--temporal") temporal = true;
+        else if (a == "--temporal-history") tpp.max_history = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
+        else if (a == "--temporal-spp") temporalSpp = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--adaptive-min") adp.min_samples = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--adaptive-batch") adp.batch_samples = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--adaptive-floor") adp.luminance_floor = static_cast<float>(std::atof(next()));
@@ -344,6 +367,15 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (temporal) {
+        const char* why = cameraPath.empty() ? "a run without --camera-path" : prm.rng_mode == MPT_RNG_LITERAL ? "--rng literal" : gpus > 1 ? "--gpus > 1"
+                          : adaptive ? "--adaptive" : !checkpoint.empty() ? "--checkpoint" : !resume.empty() ? "--resume"
+                          : temporalSpp == 0 ? "--temporal-spp 0" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: --temporal cannot be combined with %s\n", why);
+            return 2;
+        }
+    }
     if (gpus > 1) {
         if (deviceList.empty())
             for (int g = 0; g < gpus; ++g) deviceList.push_back(device + g);
@@ -384,12 +416,19 @@ int main(int argc, char** argv) {
                           pixels > 0 ? static_cast<double>(info.samples) / pixels : 0.0);
             adaptiveJson = buf;
         } else if (!cameraPath.empty()) {
-            const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr);
+            if (temporal) r.setTemporalParams(tpp);
+            const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr, temporal ? temporalSpp : 0u);
             if (n < 0) return 1;
             frames = n;
-            r.readFrame(&view);
-            img = view.rgba;
-            if (denoise) r.denoise(dnp, img);
+            if (temporal) {   // --out gets what the last frame got: the history, or the filtered history
+                if (denoise) r.denoiseTemporal(dnp, view.rgba);
+                else r.readTemporal(view.rgba);
+                img = view.rgba;
+            } else {
+                r.readFrame(&view);
+                img = view.rgba;
+                if (denoise) r.denoise(dnp, img);
+            }
         } else if (frames > 0) {
             for (int f = 0; f < frames; ++f) r.draw(&view);
             r.readFrame(&view);

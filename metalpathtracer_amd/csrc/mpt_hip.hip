@@ -35,6 +35,7 @@
 #include "mpt_devbuild.h"
 #include "mpt_ordered.h"
 #include "mpt_denoise.h"
+#include "mpt_temporal.h"
 #include "mpt_adaptive.h"
 
 // =====================================================================================================
@@ -170,6 +171,19 @@ struct AdaptiveTiles {
     uint32_t tiles = 0;
 };
 
+// Temporal accumulation (mpt_temporal.h): the history, the guide of the frame it belongs to and that frame's camera, ping-pong.
+// Allocated by the first mpt_temporal_accumulate; valid while `epoch` is the context's guide_epoch (every scene call and mpt_resize
+// bump that one); mpt_resize and mpt_temporal_reset let go of the buffers.
+struct TemporalState {
+    DevMem<float4> hist[2];        // (accumulated rgb, history length n)
+    DevMem<float4> guide[2];       // (normal facing the ray, t; t = +inf for a miss)
+    DevMem<unsigned long long> n_reset;
+    uint32_t W = 0, H = 0;         // size of those buffers
+    int cur = 0;                   // which of the two holds the history
+    uint64_t epoch = 0;            // the guide_epoch the history was written in (0 = no history)
+    float cam[14] = {};            // guide_key of the history's frame
+};
+
 struct mpt_ctx : SceneState {
     int device = 0;
     std::unique_ptr<Submitter> sub;      // mpt_render_async's submit thread (none until the first asynchronous render)
@@ -261,6 +275,7 @@ struct mpt_ctx : SceneState {
     // tile buffers of mpt_render_adaptive; mpt_resize drops both
     DevMem<float4> d_m2;
     AdaptiveTiles ad;
+    TemporalState tp;
 };
 
 // kernel variants: COUNT (work counters) x ALL_LDS (the whole BVH fits the LDS budget)
@@ -889,6 +904,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->d_sum = ctx->d_sum_own.get();
     ctx->d_m2.reset();   // (moments and tile counts of the old size: zero from here on)
     ctx->ad = AdaptiveTiles{};
+    ctx->tp = TemporalState{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;
@@ -2356,6 +2372,217 @@ extern "C" int mpt_denoised_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
 extern "C" int mpt_denoise_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth, const float* normal_class,
                                  const mpt_denoise_params* p, float* out) {
     return guarded(ctx, [&] { return denoise_image_impl(ctx, w, h, color, albedo_depth, normal_class, p, out); });
+}
+
+// ---- temporal accumulation (mpt_temporal.h; the specification is in include/mpt.h) ---------------------------------------------
+struct TpResolved {
+    float max_history, depth_tol, normal_thr, min_weight;
+};
+static int tp_resolve(mpt_ctx* ctx, const mpt_temporal_params* p, bool use_source, TpResolved& r) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null temporal params");
+    if (use_source) {
+        if (p->source != MPT_DENOISE_SUM && p->source != MPT_DENOISE_FRAME) return fail(ctx, MPT_ERR_INVALID_ARG, "bad temporal source");
+        if (p->source == MPT_DENOISE_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "temporal accumulation of the sum with samples = 0");
+    }
+    if (p->depth_tolerance != p->depth_tolerance || p->normal_threshold != p->normal_threshold || p->min_weight != p->min_weight)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "a temporal tolerance is NaN");
+    r.max_history = (float)(p->max_history ? p->max_history : MPT_TEMPORAL_DEFAULT_MAX_HISTORY);
+    r.depth_tol = p->depth_tolerance > 0.0f ? p->depth_tolerance : MPT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE;
+    r.normal_thr = p->normal_threshold > 0.0f ? p->normal_threshold : MPT_TEMPORAL_DEFAULT_NORMAL_THRESHOLD;
+    r.min_weight = p->min_weight > 0.0f ? p->min_weight : MPT_TEMPORAL_DEFAULT_MIN_WEIGHT;
+    return MPT_OK;
+}
+// The per-frame constants of k_tp_reproject from the two cameras' guide_key (cam, vu, vv, first, screen size), by the expressions of
+// include/mpt.h in float32, and the launch.  key_h = nullptr: no history.  Returns the number of pixels reset in *n_reset_out.
+static int tp_launch(mpt_ctx* ctx, TpFrame T, const float key[14], const float* key_h, const TpResolved& r, uint64_t* n_reset_out) {
+    T.fW = (float)T.W;
+    T.fH = (float)T.H;
+    T.cam = F3{key[0], key[1], key[2]};
+    T.vu = F3{key[3], key[4], key[5]};
+    T.vv = F3{key[6], key[7], key[8]};
+    T.first = F3{key[9], key[10], key[11]};
+    T.depth_tol = r.depth_tol;
+    T.normal_thr = r.normal_thr;
+    T.min_weight = r.min_weight;
+    T.max_history = r.max_history;
+    int mode = MPT_TP_NONE;
+    if (key_h) {
+        mode = memcmp(key, key_h, 14 * sizeof(float)) == 0 ? MPT_TP_SAME : MPT_TP_MOVED;
+        T.cam_h = F3{key_h[0], key_h[1], key_h[2]};
+        T.vu_h = F3{key_h[3], key_h[4], key_h[5]};
+        T.vv_h = F3{key_h[6], key_h[7], key_h[8]};
+        const F3 a = T.vu_h, b = T.vv_h;
+        T.nn = F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+        T.fc = F3{key_h[9] - key_h[0], key_h[10] - key_h[1], key_h[11] - key_h[2]};
+        T.fcnn = tp_dot(T.fc, T.nn);
+        T.uu = tp_dot(T.vu_h, T.vu_h);
+        T.vvl = tp_dot(T.vv_h, T.vv_h);
+    }
+    HIPCHK(hipMemsetAsync(T.n_reset, 0, 8, ctx->stream));
+    const dim3 grid((T.W + MPT_DN_TILE - 1) / MPT_DN_TILE, (T.H + MPT_DN_TILE - 1) / MPT_DN_TILE);
+    void* args[] = {&T};
+    HIPCHK(hipLaunchKernel(tp_kernel(mode), grid, dim3(256), args, 0, ctx->stream));
+    unsigned long long n = 0;
+    HIPCHK(hipMemcpyAsync(&n, T.n_reset, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *n_reset_out = n;
+    return MPT_OK;
+}
+static bool tp_have_history(const mpt_ctx* ctx) {
+    return ctx->tp.epoch != 0 && ctx->tp.epoch == ctx->guide_epoch && ctx->tp.W == ctx->W && ctx->tp.H == ctx->H && ctx->tp.hist[ctx->tp.cur];
+}
+static int temporal_accumulate_impl(mpt_ctx* ctx, const mpt_temporal_params* p, mpt_temporal_info* out) {
+    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    TpResolved r;
+    int rc = tp_resolve(ctx, p, true, r);
+    if (rc) return rc;
+    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
+    if ((rc = refresh_guides(ctx))) return rc;
+    TemporalState& tp = ctx->tp;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    const bool have = tp_have_history(ctx);
+    if (!tp.hist[0] || tp.W != ctx->W || tp.H != ctx->H) {
+        tp.W = tp.H = 0;
+        tp.epoch = 0;
+        for (DevMem<float4>* b : {&tp.hist[0], &tp.hist[1], &tp.guide[0], &tp.guide[1]}) HIPCHK(b->alloc(n * 16));
+        HIPCHK(tp.n_reset.alloc(8));
+        tp.W = ctx->W;
+        tp.H = ctx->H;
+        tp.cur = 0;
+    }
+    const bool sum = p->source == MPT_DENOISE_SUM;
+    const int nxt = tp.cur ^ 1;
+    TpFrame T = {};
+    T.color = sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target].get();
+    T.samples = sum ? (float)p->samples : 1.0f;
+    T.ad = ctx->d_aov_ad.get();
+    T.nc = ctx->d_aov_nc.get();
+    T.hist_in = tp.hist[tp.cur].get();
+    T.guide_in = tp.guide[tp.cur].get();
+    T.hist_out = tp.hist[nxt].get();
+    T.guide_out = tp.guide[nxt].get();
+    T.n_reset = tp.n_reset.get();
+    T.W = ctx->W;
+    T.H = ctx->H;
+    float key[14];
+    guide_key(ctx->u, key);
+    uint64_t n_reset = 0;
+    tp.epoch = 0;   // (no history if the launch fails)
+    if ((rc = tp_launch(ctx, T, key, have ? tp.cam : nullptr, r, &n_reset))) return rc;
+    tp.cur = nxt;
+    tp.epoch = ctx->guide_epoch;
+    memcpy(tp.cam, key, sizeof key);
+    if (out) {
+        out->pixels_reset = n_reset;
+        out->pixels_reprojected = (uint64_t)n - n_reset;
+    }
+    return MPT_OK;
+}
+static int temporal_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const float* ad, const float* nc, const mpt_uniforms* cam,
+                               const float* hist_h, const float* ad_h, const float* nc_h, const mpt_uniforms* cam_h,
+                               const mpt_temporal_params* p, float* hist_out, mpt_temporal_info* out) {
+    if (!ctx || !color || !ad || !nc || !cam || !p || !hist_out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31))
+        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    if (hist_h && (!ad_h || !nc_h || !cam_h)) return fail(ctx, MPT_ERR_INVALID_ARG, "a history without its guides or camera");
+    TpResolved r;
+    int rc = tp_resolve(ctx, p, false, r);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)W * H;
+    DevMem<> d_c, d_ad, d_nc, d_h, d_adh, d_nch, d_gh, d_o, d_go;
+    DevMem<unsigned long long> d_cnt;
+    for (DevMem<>* b : {&d_c, &d_ad, &d_nc, &d_o, &d_go}) HIPCHK(b->alloc(n * 16));
+    HIPCHK(d_cnt.alloc(8));
+    HIPCHK(hipMemcpyAsync(d_c.get(), color, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    float key[14], key_h[14];
+    guide_key(*cam, key);
+    if (hist_h) {
+        for (DevMem<>* b : {&d_h, &d_adh, &d_nch, &d_gh}) HIPCHK(b->alloc(n * 16));
+        HIPCHK(hipMemcpyAsync(d_h.get(), hist_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_adh.get(), ad_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_nch.get(), nc_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_tp_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)d_adh.get(),
+                           (const float4*)d_nch.get(), (uint32_t)n, (float4*)d_gh.get());
+        HIPCHK(hipGetLastError());
+        guide_key(*cam_h, key_h);
+    }
+    TpFrame T = {};
+    T.color = (const float4*)d_c.get();
+    T.samples = 1.0f;
+    T.ad = (const float4*)d_ad.get();
+    T.nc = (const float4*)d_nc.get();
+    T.hist_in = (const float4*)d_h.get();
+    T.guide_in = (const float4*)d_gh.get();
+    T.hist_out = (float4*)d_o.get();
+    T.guide_out = (float4*)d_go.get();
+    T.n_reset = d_cnt.get();
+    T.W = W;
+    T.H = H;
+    uint64_t n_reset = 0;
+    if ((rc = tp_launch(ctx, T, key, hist_h ? key_h : nullptr, r, &n_reset))) return rc;
+    HIPCHK(hipMemcpyAsync(hist_out, d_o.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (out) {
+        out->pixels_reset = n_reset;
+        out->pixels_reprojected = (uint64_t)n - n_reset;
+    }
+    return MPT_OK;
+}
+static int denoise_temporal_impl(mpt_ctx* ctx, const mpt_denoise_params* p) {
+    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    DnSigmas sg;
+    int rc = dn_resolve(ctx, p, sg);
+    if (rc) return rc;
+    if (!tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
+    if ((rc = wait_impl(ctx))) return rc;
+    if ((rc = refresh_guides(ctx))) return rc;
+    float4* x[2] = {ctx->d_dn_x[0].get(), ctx->d_dn_x[1].get()};
+    ctx->denoised_valid = false;
+    if ((rc = dn_filter(ctx, ctx->stream, ctx->W, ctx->H, ctx->tp.hist[ctx->tp.cur].get(), 1.0f, ctx->d_aov_ad.get(), ctx->d_dn_guide.get(), x, sg,
+                        ctx->d_denoised.get())))
+        return rc;
+    ctx->denoised_valid = true;
+    return MPT_OK;
+}
+extern "C" int mpt_temporal_accumulate(mpt_ctx* ctx, const mpt_temporal_params* p, mpt_temporal_info* out) {
+    return guarded(ctx, [&] { return temporal_accumulate_impl(ctx, p, out); });
+}
+extern "C" int mpt_read_temporal(mpt_ctx* ctx, float* rgba) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx || !rgba) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+        if (!tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
+        HIPCHK(hipMemcpyAsync(rgba, ctx->tp.hist[ctx->tp.cur].get(), (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_temporal_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
+    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
+    if (!tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
+    *p = ctx->tp.hist[ctx->tp.cur].get();
+    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 16;
+    return MPT_OK;
+}
+extern "C" int mpt_temporal_reset(mpt_ctx* ctx) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx) return MPT_ERR_INVALID_ARG;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        ctx->tp = TemporalState{};
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_denoise_temporal(mpt_ctx* ctx, const mpt_denoise_params* p) {
+    return guarded(ctx, [&] { return denoise_temporal_impl(ctx, p); });
+}
+extern "C" int mpt_temporal_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth_cur, const float* normal_class_cur,
+                                  const mpt_uniforms* cam_cur, const float* history_prev, const float* albedo_depth_prev, const float* normal_class_prev,
+                                  const mpt_uniforms* cam_prev, const mpt_temporal_params* p, float* history_out, mpt_temporal_info* out) {
+    return guarded(ctx, [&] {
+        return temporal_image_impl(ctx, w, h, color, albedo_depth_cur, normal_class_cur, cam_cur, history_prev, albedo_depth_prev, normal_class_prev,
+                                   cam_prev, p, history_out, out);
+    });
 }
 
 __global__ void k_digest(const uint32_t* w, uint64_t n_words, unsigned long long* out) {

@@ -24,6 +24,7 @@ SYMBOLS = (
     "mpt_renderer_read_frame", "mpt_renderer_render_batch", "mpt_renderer_read_sum", "mpt_renderer_clear_sum",
     "mpt_renderer_uniforms", "mpt_renderer_stats", "mpt_renderer_context", "mpt_renderer_scene", "mpt_write_pfm",
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
+    "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
 )
 
 _lib = None
@@ -67,6 +68,9 @@ def load():
     L.mpt_renderer_denoise.argtypes = [vp, C.POINTER(capi.DenoiseParams), fp]
     L.mpt_renderer_render_adaptive.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(capi.AdaptiveParams),
                                                C.POINTER(capi.AdaptiveInfo)]
+    L.mpt_renderer_draw_temporal.argtypes = [vp, C.c_uint32, C.POINTER(capi.TemporalParams), C.POINTER(capi.TemporalInfo)]
+    L.mpt_renderer_read_temporal.argtypes = [vp, fp]
+    L.mpt_renderer_denoise_temporal.argtypes = [vp, C.POINTER(capi.DenoiseParams), fp]
     L.mpt_renderer_context.argtypes = [vp]
     L.mpt_renderer_context.restype = vp
     L.mpt_renderer_scene.argtypes = [vp]
@@ -326,6 +330,29 @@ class Renderer:
         out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
         p = capi.denoise_params(**kw)
         self._chk(self.L.mpt_renderer_denoise(self.h, C.byref(p), _fp(out)), "denoise")
+        return out
+
+    def drawTemporal(self, samples_per_frame=1, **kw):
+        """mpt_renderer_draw_temporal: one frame of temporal accumulation with the pending input(); kw: max_history, depth_tolerance,
+        normal_threshold, min_weight (none: keep the renderer's).  Returns the mpt_temporal_info as a dict."""
+        p = capi.temporal_params(**kw) if kw else None
+        info = capi.TemporalInfo()
+        self._chk(self.L.mpt_renderer_draw_temporal(self.h, int(samples_per_frame), C.byref(p) if p is not None else None,
+                                                    C.byref(info)), "drawTemporal")
+        return info.as_dict()
+
+    def readTemporal(self):
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
+        self._chk(self.L.mpt_renderer_read_temporal(self.h, _fp(out)), "readTemporal")
+        return out
+
+    def denoiseTemporal(self, **kw):
+        """mpt_renderer_denoise_temporal: the a-trous filter over the history with the current guides; the [H, W, 4] image."""
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
+        p = capi.denoise_params(**kw)
+        self._chk(self.L.mpt_renderer_denoise_temporal(self.h, C.byref(p), _fp(out)), "denoiseTemporal")
         return out
 
     def scene(self):
