@@ -443,6 +443,90 @@ int mpt_temporal_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const floa
                        const float* albedo_depth_prev, const float* normal_class_prev, const mpt_uniforms* cam_prev,
                        const mpt_temporal_params* params, float* history_out, mpt_temporal_info* out /* may be NULL */);
 
+/* ---- SVGF: temporal luminance moments and a variance-guided a-trous filter -----------------------------------------------------
+ * No reference counterpart.  After Schied et al. 2017, with the departures written below.
+ *
+ * State per context, two of each (ping-pong), with the lifetime of the temporal history — allocated by the first
+ * mpt_svgf_accumulate; dropped by mpt_resize, mpt_upload_scene, mpt_build_and_upload and mpt_svgf_reset; untouched by mpt_clear_sum —
+ * and independent of it: this stage neither reads nor writes the mpt_temporal_* history.
+ *   illumination history (X.rgb, n), RGBA32F: for a surface pixel (class 0) X is demodulated (divided by the albedo), for an emitter
+ *     or a miss it is the radiance itself; n = history length, a float >= 1;
+ *   moments history (M1, M2): first and second moment of the luminance of the per-frame x below, two floats;
+ *   history guide, 16 bytes: (ray-facing normal, t) with the pixel's class in t: t for a surface, -t for an emitter (a hit distance
+ *     is > 0), +inf for a miss;
+ *   the fourteen camera floats of the history's frame.
+ *
+ * mpt_svgf_accumulate waits for the renders queued and in flight (reporting a failed mpt_render_async), refreshes stale guides, then
+ * runs three steps.  All arithmetic float32, one IEEE operation at a time in the order written; dot as in the temporal section;
+ * lum(x) = (0.2126 x.r + 0.7152 x.g) + 0.0722 x.b.  c = sum / samples (SUM) or the current mpt_draw target (FRAME);
+ * a = max(albedo, 1e-3) per channel for a surface pixel, a = 1 for classes 1 / 2; x = c.rgb / a; l = lum(x).
+ *
+ * A. Temporal step (only + - * / sqrt floor and comparisons: tests/svgf_ref.py agrees bit for bit).  Every pixel is accumulated, sky
+ *    and emitters too.  Reprojection as steps 1-4 and 6 of mpt_temporal_accumulate (hit rule for classes 0 and 1, miss rule for
+ *    class 2; a history tap's distance is |t_q|) with one more condition on a tap of a hit: the history pixel has the class of p, so
+ *    that demodulated and plain values never mix.  Sums over the counted taps, in tap order: sx (rgb), sm1, sm2, sn, sw.
+ *    !(sw >= min_weight) or no history: reset — X = x, M1 = l, M2 = l * l, n = 1.  Otherwise h = sx / sw, m1 = sm1 / sw,
+ *    m2 = sm2 / sw, m = sn / sw, n = min(m + 1, max_history), X = h + (x - h) / n, M1 = m1 + (l - m1) / n,
+ *    M2 = m2 + (l * l - m2) / n.  pixels_reprojected + pixels_reset = W * H.
+ * B. Variance of the accumulated mean, V_0; surface pixels only (0 for classes 1 / 2).  n >= 4: V = max(0, M2 - M1 * M1) / n.
+ *    Otherwise a 7 x 7 window of this frame's (M1, M2): taps q = p + (dx, dy), dy outer, both from -3 to 3, the centre in its
+ *    place; taps outside the image or of class != 0 skipped; w = wn * wz with wn = pow(max(0, dot(n_p, n_q)), sigma_normal),
+ *    wz = exp(-|t_p - t_q| / (sigma_depth * t_p)), the centre's w = 1; S1 = sum w * M1_q, S2 = sum w * M2_q, Sw = sum w;
+ *    e1 = S1 / Sw; V = max(0, S2 / Sw - e1 * e1) / n.  Dividing by n departs from the paper, which filters with the per-sample
+ *    variance: with the variance of the MEAN the filter closes as the history grows, and a disoccluded pixel gets a wide one.
+ * C. N a-trous levels over (x_i.rgb, V_i), x_0 = X, V_0 as above; level i, s = 2^i, the 5 x 5 taps and the kernel h of mpt_denoise
+ *    (dy outer; taps outside the image or of class != 0 skipped).  g_p = the 3 x 3 binomial mean of V_i over the ADJACENT pixels
+ *    (not +-s): k = k3[dx] * k3[dy], k3 = {1/4, 1/2, 1/4}, dy outer, g_p = (sum k * V_q) / (sum k) over the taps not skipped.
+ *    wl = exp(-|lum(x_p) - lum(x_q)| / (sigma_luminance * sqrt(g_p) + MPT_SVGF_EPSILON));
+ *    wz = exp(-|t_p - t_q| / ((sigma_depth * t_p) * s)); w = (h[dx] * h[dy]) * ((wn * wz) * wl), the centre's w = h[0]^2 exactly.
+ *    x_{i+1} = (sum w * x_q) / (sum w); V_{i+1} = (sum (w * w) * V_q) / ((sum w) * (sum w)).
+ * Output (mpt_read_svgf, mpt_svgf_buffer): (x_N * a, n) for a surface pixel; (X, n) — the accumulated radiance, unfiltered, never a
+ * tap — for classes 1 / 2; N = 0 gives X * a.  Feedback (feedback != 0 and N >= 1): the illumination history kept for the next
+ * frame is x_1.rgb for surface pixels (n unchanged); the moments are never filtered.
+ * mpt_read_svgf_state: the illumination history as kept for the next frame, and (M1, M2, V_0, 0).
+ * The stage reads the HDR sum or the frame target and writes neither; mpt_stats is untouched; the a-trous buffers are its own, so
+ * an mpt_denoise result stays readable.
+ * MPT_ERR_INVALID_ARG, with nothing changed: null params, a bad source, SUM with samples = 0, a NaN tolerance or sigma, iterations
+ * above MPT_DENOISE_MAX_ITERATIONS.  MPT_ERR_NOT_READY before scene, uniforms and size, and from mpt_read_svgf / mpt_svgf_buffer /
+ * mpt_read_svgf_state while there is no state.  Defaults: chosen from the sweep of profiles/r08_svgf_sweep.txt; step A's are the
+ * MPT_TEMPORAL_DEFAULT_*.                                                                                                         */
+#define MPT_SVGF_EPSILON 1e-4f
+#define MPT_SVGF_DEFAULT_ITERATIONS 2
+#define MPT_SVGF_DEFAULT_SIGMA_LUMINANCE 2.0f
+#define MPT_SVGF_DEFAULT_SIGMA_NORMAL 32.0f
+#define MPT_SVGF_DEFAULT_SIGMA_DEPTH 0.25f
+#define MPT_SVGF_DEFAULT_FEEDBACK 0
+typedef struct mpt_svgf_params {
+    int32_t source;            /* MPT_DENOISE_SUM (sum / samples) or MPT_DENOISE_FRAME: this frame's colour c                        */
+    uint32_t samples;          /* SUM: samples the sum holds (> 0)                                                                  */
+    uint32_t max_history;      /* step A, as mpt_temporal_params: 0 = MPT_TEMPORAL_DEFAULT_MAX_HISTORY                              */
+    float depth_tolerance;     /* <= 0 = MPT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE                                                       */
+    float normal_threshold;    /* <= 0 = MPT_TEMPORAL_DEFAULT_NORMAL_THRESHOLD                                                      */
+    float min_weight;          /* <= 0 = MPT_TEMPORAL_DEFAULT_MIN_WEIGHT                                                            */
+    int32_t iterations;        /* levels N, 0..MPT_DENOISE_MAX_ITERATIONS; < 0 = MPT_SVGF_DEFAULT_ITERATIONS                        */
+    float sigma_luminance;     /* in standard deviations of the accumulated mean; <= 0 = MPT_SVGF_DEFAULT_SIGMA_LUMINANCE           */
+    float sigma_normal;        /* <= 0 = MPT_SVGF_DEFAULT_SIGMA_NORMAL                                                              */
+    float sigma_depth;         /* <= 0 = MPT_SVGF_DEFAULT_SIGMA_DEPTH                                                               */
+    int32_t feedback;          /* != 0: x_1 becomes the illumination history; < 0 = MPT_SVGF_DEFAULT_FEEDBACK                       */
+} mpt_svgf_params;
+typedef struct mpt_svgf_info {
+    uint64_t pixels_reprojected, pixels_reset;
+} mpt_svgf_info;
+
+int mpt_svgf_accumulate(mpt_ctx* ctx, const mpt_svgf_params* params, mpt_svgf_info* out /* may be NULL */);
+int mpt_read_svgf(mpt_ctx* ctx, float* rgba_host);                     /* the filtered frame: rgb, a = n (W*H*4 floats)             */
+int mpt_svgf_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);
+int mpt_read_svgf_state(mpt_ctx* ctx, float* history /* W*H*4 */, float* moments_variance /* W*H*4: M1, M2, V_0, 0 */);
+int mpt_svgf_reset(mpt_ctx* ctx);
+/* The same kernels on caller arrays (host; the unit-test hook, no scene needed): color is c itself (source and samples are ignored),
+ * the guides as mpt_read_aovs returns them, the cameras as uniforms, W*H*4 floats each except moments_prev (W*H*2: M1, M2).
+ * history_prev = NULL: no history (the other *_prev arguments are ignored).  The three outputs may each be NULL.                  */
+int mpt_svgf_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const float* albedo_depth_cur,
+                   const float* normal_class_cur, const mpt_uniforms* cam_cur, const float* history_prev, const float* moments_prev,
+                   const float* albedo_depth_prev, const float* normal_class_prev, const mpt_uniforms* cam_prev,
+                   const mpt_svgf_params* params, float* history_out, float* moments_variance_out, float* filtered_out,
+                   mpt_svgf_info* out /* may be NULL */);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

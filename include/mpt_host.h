@@ -88,6 +88,12 @@ int mpt_renderer_render_adaptive(mpt_renderer* r, uint32_t sample_begin, uint32_
 int mpt_renderer_draw_temporal(mpt_renderer* r, uint32_t samples_per_frame, const mpt_temporal_params* params, mpt_temporal_info* out);
 int mpt_renderer_read_temporal(mpt_renderer* r, float* rgba);
 int mpt_renderer_denoise_temporal(mpt_renderer* r, const mpt_denoise_params* params, float* rgba);
+/* One frame of SVGF (mpt_svgf_accumulate, include/mpt.h), with the frame numbering of mpt_renderer_draw_temporal (the two share the
+ * counter: samples frame * samples_per_frame onwards, never reset by camera motion).  params (may be NULL: keep the renderer's,
+ * initially the defaults): everything but source / samples, which are ignored.  out may be NULL.  mpt_renderer_read_svgf: the
+ * filtered frame (rgb, a = the history length), W*H*4 floats.                                                                    */
+int mpt_renderer_draw_svgf(mpt_renderer* r, uint32_t samples_per_frame, const mpt_svgf_params* params, mpt_svgf_info* out);
+int mpt_renderer_read_svgf(mpt_renderer* r, float* rgba);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 

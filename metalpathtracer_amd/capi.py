@@ -33,6 +33,7 @@ SYMBOLS = (
     "mpt_read_moments", "mpt_render_adaptive", "mpt_read_tile_samples",
     "mpt_temporal_accumulate", "mpt_read_temporal", "mpt_temporal_buffer", "mpt_temporal_reset", "mpt_denoise_temporal",
     "mpt_temporal_image",
+    "mpt_svgf_accumulate", "mpt_read_svgf", "mpt_svgf_buffer", "mpt_read_svgf_state", "mpt_svgf_reset", "mpt_svgf_image",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
@@ -43,6 +44,9 @@ DENOISE_DEFAULTS = dict(iterations=3, sigma_luminance=8.0, sigma_normal=32.0, si
 ADAPTIVE_DEFAULTS = dict(min_samples=16, batch_samples=16, luminance_floor=0.05)
 # include/mpt.h MPT_TEMPORAL_DEFAULT_* (0 / a tolerance <= 0 selects them)
 TEMPORAL_DEFAULTS = dict(max_history=32, depth_tolerance=0.05, normal_threshold=0.5, min_weight=0.05)
+# include/mpt.h MPT_SVGF_DEFAULT_* (iterations / feedback < 0 and a sigma <= 0 select them; step A's are the TEMPORAL_DEFAULTS)
+SVGF_DEFAULTS = dict(iterations=2, sigma_luminance=2.0, sigma_normal=32.0, sigma_depth=0.25, feedback=0)
+SVGF_EPSILON = 1e-4
 
 
 class MptError(RuntimeError):
@@ -134,6 +138,27 @@ def temporal_params(source=DENOISE_SUM, samples=0, max_history=0, depth_toleranc
     """mpt_temporal_params; max_history = 0 and tolerances <= 0 mean the defaults of include/mpt.h."""
     return TemporalParams(int(source), int(samples), int(max_history), float(depth_tolerance), float(normal_threshold),
                           float(min_weight))
+
+
+class SvgfParams(C.Structure):
+    _fields_ = [("source", C.c_int32), ("samples", C.c_uint32), ("max_history", C.c_uint32),
+                ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("min_weight", C.c_float),
+                ("iterations", C.c_int32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("feedback", C.c_int32)]
+
+
+class SvgfInfo(C.Structure):
+    _fields_ = [("pixels_reprojected", C.c_uint64), ("pixels_reset", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def svgf_params(source=DENOISE_SUM, samples=0, max_history=0, depth_tolerance=0.0, normal_threshold=0.0, min_weight=0.0, iterations=-1,
+                sigma_luminance=0.0, sigma_normal=0.0, sigma_depth=0.0, feedback=-1):
+    """mpt_svgf_params; 0 / <= 0 / < 0 mean the defaults of include/mpt.h."""
+    return SvgfParams(int(source), int(samples), int(max_history), float(depth_tolerance), float(normal_threshold), float(min_weight),
+                      int(iterations), float(sigma_luminance), float(sigma_normal), float(sigma_depth), int(feedback))
 
 
 def expand_tile_counts(counts, H, W):
@@ -239,6 +264,13 @@ def load():
     L.mpt_denoise_temporal.argtypes = [vp, C.POINTER(DenoiseParams)]
     L.mpt_temporal_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, fp, C.POINTER(Uniforms), fp, fp, fp, C.POINTER(Uniforms),
                                      C.POINTER(TemporalParams), fp, C.POINTER(TemporalInfo)]
+    L.mpt_svgf_accumulate.argtypes = [vp, C.POINTER(SvgfParams), C.POINTER(SvgfInfo)]
+    L.mpt_read_svgf.argtypes = [vp, fp]
+    L.mpt_svgf_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_read_svgf_state.argtypes = [vp, fp, fp]
+    L.mpt_svgf_reset.argtypes = [vp]
+    L.mpt_svgf_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, fp, C.POINTER(Uniforms), fp, fp, fp, fp, C.POINTER(Uniforms),
+                                 C.POINTER(SvgfParams), fp, fp, fp, C.POINTER(SvgfInfo)]
     _lib = L
     return L
 
@@ -614,6 +646,64 @@ class Context:
         self._chk(self.L.mpt_temporal_image(self.h, W, H, _fp(c), _fp(ad), _fp(nc), C.byref(cam), hp, adp, ncp, camp, C.byref(p),
                                             _fp(out), C.byref(info)), "mpt_temporal_image")
         return out, info.as_dict()
+
+    def svgf_accumulate(self, **kw):
+        """mpt_svgf_accumulate: step A (reproject the illumination and its moments, blend this frame in), step B (variance) and the
+        variance-guided a-trous levels; returns the mpt_svgf_info as a dict.  read_svgf() has the frame."""
+        p = svgf_params(**kw)
+        info = SvgfInfo()
+        self._chk(self.L.mpt_svgf_accumulate(self.h, C.byref(p), C.byref(info)), "mpt_svgf_accumulate")
+        return info.as_dict()
+
+    def read_svgf(self):
+        """The filtered frame: rgb, a = history length n, [H,W,4]."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._chk(self.L.mpt_read_svgf(self.h, _fp(out)), "mpt_read_svgf")
+        return out
+
+    def svgf_buffer(self):
+        """(device pointer, bytes) of the filtered frame, for zero-copy use after synchronize()."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_svgf_buffer(self.h, C.byref(p), C.byref(n)), "mpt_svgf_buffer")
+        return p.value, n.value
+
+    def read_svgf_state(self):
+        """(illumination history (X, n) [H,W,4], (M1, M2, V_0, 0) [H,W,4])."""
+        h = np.empty((self.height, self.width, 4), np.float32)
+        mv = np.empty((self.height, self.width, 4), np.float32)
+        self._chk(self.L.mpt_read_svgf_state(self.h, _fp(h), _fp(mv)), "mpt_read_svgf_state")
+        return h, mv
+
+    def svgf_reset(self):
+        self._chk(self.L.mpt_svgf_reset(self.h), "mpt_svgf_reset")
+
+    def svgf_image(self, color, albedo_depth, normal_class, cam, history=None, moments=None, albedo_depth_prev=None,
+                   normal_class_prev=None, cam_prev=None, **kw):
+        """The SVGF kernels on caller arrays [H,W,4] (moments [H,W,2]) with the two cameras as Uniforms; history=None: no history.
+        Returns (history [H,W,4], (M1, M2, V_0, 0) [H,W,4], filtered frame [H,W,4], info dict)."""
+        c = np.ascontiguousarray(color, np.float32)
+        ad = np.ascontiguousarray(albedo_depth, np.float32)
+        nc = np.ascontiguousarray(normal_class, np.float32)
+        if c.ndim != 3 or c.shape[2] != 4 or ad.shape != c.shape or nc.shape != c.shape:
+            raise ValueError("svgf_image: color, albedo_depth and normal_class must be [H, W, 4] arrays of one shape")
+        H, W = c.shape[:2]
+        null = C.POINTER(C.c_float)()
+        hp = mp = adp = ncp = null
+        camp = None
+        if history is not None:
+            h = np.ascontiguousarray(history, np.float32)
+            m = np.ascontiguousarray(moments, np.float32)
+            a2 = np.ascontiguousarray(albedo_depth_prev, np.float32)
+            n2 = np.ascontiguousarray(normal_class_prev, np.float32)
+            if h.shape != c.shape or m.shape != (H, W, 2) or a2.shape != c.shape or n2.shape != c.shape or cam_prev is None:
+                raise ValueError("svgf_image: the history, its moments [H, W, 2], its guides and its camera go together")
+            hp, mp, adp, ncp, camp = _fp(h), _fp(m), _fp(a2), _fp(n2), C.byref(cam_prev)
+        ho, mv, out = np.empty_like(c), np.empty_like(c), np.empty_like(c)
+        p = svgf_params(**kw)
+        info = SvgfInfo()
+        self._chk(self.L.mpt_svgf_image(self.h, W, H, _fp(c), _fp(ad), _fp(nc), C.byref(cam), hp, mp, adp, ncp, camp, C.byref(p),
+                                        _fp(ho), _fp(mv), _fp(out), C.byref(info)), "mpt_svgf_image")
+        return ho, mv, out, info.as_dict()
 
     def kat_pcg(self, seeds):
         s = np.ascontiguousarray(seeds, np.uint32)

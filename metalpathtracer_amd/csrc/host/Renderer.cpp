@@ -308,6 +308,26 @@ void Renderer::denoiseTemporal(const mpt_denoise_params& p, std::vector<float>& 
     check(mpt_read_denoised(ctx_, rgba.data()), "mpt_read_denoised");
 }
 
+mpt_svgf_info Renderer::drawSvgf(OffscreenView* /*view*/, uint32_t samplesPerFrame) {
+    if (samplesPerFrame == 0) throw std::runtime_error("drawSvgf: samplesPerFrame = 0");
+    if (params_.rng_mode != MPT_RNG_PHILOX) throw std::runtime_error("drawSvgf: needs MPT_RNG_PHILOX (the literal stream repeats per pixel)");
+    updateCamera();
+    clearSum();
+    renderBatch(temporalFrame_ * samplesPerFrame, samplesPerFrame);
+    ++temporalFrame_;
+    mpt_svgf_params p = svgf_;
+    p.source = MPT_DENOISE_SUM;
+    p.samples = samplesPerFrame;
+    mpt_svgf_info info;
+    check(mpt_svgf_accumulate(ctx_, &p, &info), "mpt_svgf_accumulate");
+    return info;
+}
+
+void Renderer::readSvgf(std::vector<float>& rgba) {
+    rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_svgf(ctx_, rgba.data()), "mpt_read_svgf");
+}
+
 void Renderer::readSum(std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     rgba.resize(n);

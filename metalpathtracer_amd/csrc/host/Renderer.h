@@ -71,6 +71,10 @@ public:
     void setTemporalParams(const mpt_temporal_params& p) { temporal_ = p; }
     void readTemporal(std::vector<float>& rgba);                                        // the history: rgb, a = its length
     void denoiseTemporal(const mpt_denoise_params& p, std::vector<float>& rgba);        // mpt_denoise_temporal + mpt_read_denoised
+    // SVGF (mpt_svgf_accumulate, include/mpt.h): drawTemporal's frame protocol and frame counter; the frame is readSvgf()'s.
+    mpt_svgf_info drawSvgf(OffscreenView* view, uint32_t samplesPerFrame);
+    void setSvgfParams(const mpt_svgf_params& p) { svgf_ = p; }
+    void readSvgf(std::vector<float>& rgba);                                            // the filtered frame: rgb, a = the history length
 
 private:
     void check(int status, const char* where);
@@ -87,7 +91,8 @@ private:
     int buildMode_ = BUILD_REFERENCE;
     bool deviceBuild_ = false, deviceDirty_ = false;
     mpt_temporal_params temporal_ = {};  // zeros: the defaults of include/mpt.h
-    uint32_t temporalFrame_ = 0;         // frames drawTemporal() has drawn
+    uint32_t temporalFrame_ = 0;         // frames drawTemporal() and drawSvgf() have drawn
+    mpt_svgf_params svgf_ = {0, 0, 0, 0.0f, 0.0f, 0.0f, -1, 0.0f, 0.0f, 0.0f, -1};   // the defaults of include/mpt.h
     int lastSource_ = MPT_DENOISE_SUM;   // what denoise() filters: the source of the last draw() / renderBatch()
     uint32_t sumSamples_ = 0;            // samples renderBatch() added since the sum was cleared   // BUILD_GPU: mpt_build_and_upload, no tree on the host
 };

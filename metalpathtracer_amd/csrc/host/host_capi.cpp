@@ -302,6 +302,18 @@ int mpt_renderer_denoise_temporal(mpt_renderer* r, const mpt_denoise_params* p, 
         std::memcpy(rgba, img.data(), img.size() * sizeof(float));
     });
 }
+int mpt_renderer_draw_svgf(mpt_renderer* r, uint32_t samples_per_frame, const mpt_svgf_params* p, mpt_svgf_info* out) {
+    if (!r || samples_per_frame == 0) return MPT_ERR_INVALID_ARG;
+    GUARD({
+        if (p) r->r->setSvgfParams(*p);
+        const mpt_svgf_info info = r->r->drawSvgf(nullptr, samples_per_frame);
+        if (out) *out = info;
+    });
+}
+int mpt_renderer_read_svgf(mpt_renderer* r, float* rgba) {
+    if (!r || !rgba) return MPT_ERR_INVALID_ARG;
+    return mpt_read_svgf(r->r->context(), rgba);
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

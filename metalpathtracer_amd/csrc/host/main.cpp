@@ -44,6 +44,13 @@ static void usage() {
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]]\n"
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
+        "           [--svgf [--svgf-iterations N] [--temporal-history N] [--temporal-spp K]]\n"
+        "  --svgf            with --camera-path: as --temporal, but what is accumulated is the illumination (the colour divided by the\n"
+        "                    first hit's albedo) with the moments of its luminance, and every frame written is that history through\n"
+        "                    --svgf-iterations a-trous levels (default 2) whose luminance stop is each pixel's own variance\n"
+        "                    (mpt_svgf_accumulate, include/mpt.h): converged pixels keep their detail, disoccluded ones are filtered\n"
+        "                    wide; the per-frame JSON line gains \"reprojected\" and \"reset\".  Not with --temporal, --denoise,\n"
+        "                    --rng literal, --gpus > 1, --adaptive, --checkpoint or --resume\n"
         "  --temporal        with --camera-path: every frame renders --temporal-spp fresh philox samples (default 1) and blends them\n"
         "                    into the image accumulated so far, reprojected from the previous camera (mpt_temporal_accumulate,\n"
         "                    include/mpt.h; the history is at most --temporal-history frames long, default 32); the frame written is\n"
@@ -123,7 +130,7 @@ static bool applyInputLine(const std::string& line, int* repeat) {
 // number of frames, -1 on error.  Prints one JSON line per frame (camera, frameCount) for checking against the reference's
 // protocol (a camera change resets the accumulation and reseeds, R/Renderer/Renderer.cpp:255-257).
 static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& path, const std::string& outDir,
-                          const mpt_denoise_params* dn, uint32_t temporalSpp = 0) {
+                          const mpt_denoise_params* dn, uint32_t temporalSpp = 0, bool svgf = false) {
     FILE* f = std::fopen(path.c_str(), "r");
     if (!f) {
         std::fprintf(stderr, "cannot open camera path %s\n", path.c_str());
@@ -147,7 +154,12 @@ static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& p
             }
             n = repeat;
             mpt_temporal_info ti = {};
-            if (temporalSpp) {   // --temporal: the frame is the history (or the filtered history)
+            if (temporalSpp && svgf) {   // --svgf: the frame is the variance-filtered history
+                const mpt_svgf_info si = r.drawSvgf(&view, temporalSpp);
+                ti.pixels_reprojected = si.pixels_reprojected;
+                ti.pixels_reset = si.pixels_reset;
+                r.readSvgf(view.rgba);
+            } else if (temporalSpp) {   // --temporal: the frame is the history (or the filtered history)
                 ti = r.drawTemporal(&view, temporalSpp);
                 if (dn) r.denoiseTemporal(*dn, view.rgba);
                 else r.readTemporal(view.rgba);
@@ -265,6 +277,9 @@ int main(int argc, char** argv) {
     bool temporal = false;
     mpt_temporal_params tpp = {};
     uint32_t temporalSpp = 1;
+    bool svgf = false;
+    int svgfIterations = -1;   // (the default of include/mpt.h)
+    bool haveSvgfIterations = false;
     bool adaptive = false;
     mpt_adaptive_params adp;
     std::memset(&adp, 0, sizeof adp);   // (0 = the defaults of include/mpt.h)
@@ -311,6 +326,11 @@ int main(int argc, char** argv) {
             adp.threshold = static_cast<float>(std::atof(next()));
         }
         else if (a == "--temporal") temporal = true;
+        else if (a == "--svgf") svgf = true;
+        else if (a == "--svgf-iterations") {
+            svgfIterations = std::atoi(next());
+            haveSvgfIterations = true;
+        }
         else if (a == "--temporal-history") tpp.max_history = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--temporal-spp") temporalSpp = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--adaptive-min") adp.min_samples = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
@@ -376,6 +396,20 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    if (svgf) {
+        // (--adaptive first: it needs a run without --camera-path, which --svgf cannot be)
+        const char* why = adaptive ? "--adaptive" : cameraPath.empty() ? "a run without --camera-path" : temporal ? "--temporal"
+                          : denoise ? "--denoise" : prm.rng_mode == MPT_RNG_LITERAL ? "--rng literal" : gpus > 1 ? "--gpus > 1"
+                          : !checkpoint.empty() ? "--checkpoint" : !resume.empty() ? "--resume" : temporalSpp == 0 ? "--temporal-spp 0" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: --svgf cannot be combined with %s\n", why);
+            return 2;
+        }
+        if (haveSvgfIterations && (svgfIterations < 0 || svgfIterations > MPT_DENOISE_MAX_ITERATIONS)) {
+            std::fprintf(stderr, "mpt_render: --svgf-iterations must be between 0 and %d\n", MPT_DENOISE_MAX_ITERATIONS);
+            return 2;
+        }
+    }
     if (gpus > 1) {
         if (deviceList.empty())
             for (int g = 0; g < gpus; ++g) deviceList.push_back(device + g);
@@ -417,10 +451,17 @@ int main(int argc, char** argv) {
             adaptiveJson = buf;
         } else if (!cameraPath.empty()) {
             if (temporal) r.setTemporalParams(tpp);
-            const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr, temporal ? temporalSpp : 0u);
+            if (svgf) {
+                mpt_svgf_params sp = {0, 0, tpp.max_history, 0.0f, 0.0f, 0.0f, haveSvgfIterations ? svgfIterations : -1, 0.0f, 0.0f, 0.0f, -1};
+                r.setSvgfParams(sp);
+            }
+            const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr, temporal || svgf ? temporalSpp : 0u, svgf);
             if (n < 0) return 1;
             frames = n;
-            if (temporal) {   // --out gets what the last frame got: the history, or the filtered history
+            if (svgf) {   // --out gets what the last frame got
+                r.readSvgf(view.rgba);
+                img = view.rgba;
+            } else if (temporal) {   // --out gets what the last frame got: the history, or the filtered history
                 if (denoise) r.denoiseTemporal(dnp, view.rgba);
                 else r.readTemporal(view.rgba);
                 img = view.rgba;

@@ -36,6 +36,7 @@
 #include "mpt_ordered.h"
 #include "mpt_denoise.h"
 #include "mpt_temporal.h"
+#include "mpt_svgf.h"
 #include "mpt_adaptive.h"
 
 // =====================================================================================================
@@ -184,6 +185,22 @@ struct TemporalState {
     float cam[14] = {};            // guide_key of the history's frame
 };
 
+// SVGF (mpt_svgf.h): the demodulated illumination history, its luminance moments, the guide of the frame they belong to and that
+// frame's camera, ping-pong, with the lifetime rules of TemporalState and independent of it.  The a-trous buffers are this
+// owner's too (not the denoiser's d_dn_x): an mpt_denoise result survives an mpt_svgf_accumulate and the other way round.
+struct SvgfState {
+    DevMem<float4> hist[2];        // (X rgb, history length n)
+    DevMem<float2> mom[2];         // (M1, M2) of the luminance
+    DevMem<float4> guide[2];       // (normal facing the ray, t / -t / +inf by class)
+    DevMem<float4> xv[3];          // (x, V): [0] = (X, V_0), kept for mpt_read_svgf_state; [1], [2] the ping-pong of the levels
+    DevMem<float4> out;            // the filtered frame
+    DevMem<unsigned long long> n_reset;
+    uint32_t W = 0, H = 0;
+    int cur = 0;
+    uint64_t epoch = 0;            // the guide_epoch the state was written in (0 = none)
+    float cam[14] = {};
+};
+
 struct mpt_ctx : SceneState {
     int device = 0;
     std::unique_ptr<Submitter> sub;      // mpt_render_async's submit thread (none until the first asynchronous render)
@@ -276,6 +293,7 @@ struct mpt_ctx : SceneState {
     DevMem<float4> d_m2;
     AdaptiveTiles ad;
     TemporalState tp;
+    SvgfState sv;
 };
 
 // kernel variants: COUNT (work counters) x ALL_LDS (the whole BVH fits the LDS budget)
@@ -905,6 +923,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->d_m2.reset();   // (moments and tile counts of the old size: zero from here on)
     ctx->ad = AdaptiveTiles{};
     ctx->tp = TemporalState{};
+    ctx->sv = SvgfState{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;
@@ -2394,7 +2413,8 @@ static int tp_resolve(mpt_ctx* ctx, const mpt_temporal_params* p, bool use_sourc
 }
 // The per-frame constants of k_tp_reproject from the two cameras' guide_key (cam, vu, vv, first, screen size), by the expressions of
 // include/mpt.h in float32, and the launch.  key_h = nullptr: no history.  Returns the number of pixels reset in *n_reset_out.
-static int tp_launch(mpt_ctx* ctx, TpFrame T, const float key[14], const float* key_h, const TpResolved& r, uint64_t* n_reset_out) {
+template <class Frame>
+static int tp_frame_constants(Frame& T, const float key[14], const float* key_h, const TpResolved& r) {
     T.fW = (float)T.W;
     T.fH = (float)T.H;
     T.cam = F3{key[0], key[1], key[2]};
@@ -2418,6 +2438,10 @@ static int tp_launch(mpt_ctx* ctx, TpFrame T, const float key[14], const float* 
         T.uu = tp_dot(T.vu_h, T.vu_h);
         T.vvl = tp_dot(T.vv_h, T.vv_h);
     }
+    return mode;
+}
+static int tp_launch(mpt_ctx* ctx, TpFrame T, const float key[14], const float* key_h, const TpResolved& r, uint64_t* n_reset_out) {
+    const int mode = tp_frame_constants(T, key, key_h, r);
     HIPCHK(hipMemsetAsync(T.n_reset, 0, 8, ctx->stream));
     const dim3 grid((T.W + MPT_DN_TILE - 1) / MPT_DN_TILE, (T.H + MPT_DN_TILE - 1) / MPT_DN_TILE);
     void* args[] = {&T};
@@ -2582,6 +2606,263 @@ extern "C" int mpt_temporal_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const fl
     return guarded(ctx, [&] {
         return temporal_image_impl(ctx, w, h, color, albedo_depth_cur, normal_class_cur, cam_cur, history_prev, albedo_depth_prev, normal_class_prev,
                                    cam_prev, p, history_out, out);
+    });
+}
+
+// ---- SVGF (mpt_svgf.h; the specification is in include/mpt.h) -------------------------------------------------------------------
+struct SvResolved {
+    TpResolved tp;
+    int iterations, feedback;
+    float sl, sn, sz;
+};
+static int sv_resolve(mpt_ctx* ctx, const mpt_svgf_params* p, bool use_source, SvResolved& r) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null svgf params");
+    if (use_source) {
+        if (p->source != MPT_DENOISE_SUM && p->source != MPT_DENOISE_FRAME) return fail(ctx, MPT_ERR_INVALID_ARG, "bad svgf source");
+        if (p->source == MPT_DENOISE_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "svgf accumulation of the sum with samples = 0");
+    }
+    if (p->depth_tolerance != p->depth_tolerance || p->normal_threshold != p->normal_threshold || p->min_weight != p->min_weight)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "an svgf tolerance is NaN");
+    const mpt_temporal_params t = {p->source, p->samples, p->max_history, p->depth_tolerance, p->normal_threshold, p->min_weight};
+    const int rc = tp_resolve(ctx, &t, false, r.tp);   // (checked above: only the defaults of step A are taken from it)
+    if (rc) return rc;
+    if (p->sigma_luminance != p->sigma_luminance || p->sigma_normal != p->sigma_normal || p->sigma_depth != p->sigma_depth)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "an svgf sigma is NaN");
+    if (p->iterations > MPT_DENOISE_MAX_ITERATIONS) return fail(ctx, MPT_ERR_INVALID_ARG, "svgf iterations > 8");
+    r.iterations = p->iterations < 0 ? MPT_SVGF_DEFAULT_ITERATIONS : p->iterations;
+    r.sl = p->sigma_luminance > 0.0f ? p->sigma_luminance : MPT_SVGF_DEFAULT_SIGMA_LUMINANCE;
+    r.sn = p->sigma_normal > 0.0f ? p->sigma_normal : MPT_SVGF_DEFAULT_SIGMA_NORMAL;
+    r.sz = p->sigma_depth > 0.0f ? p->sigma_depth : MPT_SVGF_DEFAULT_SIGMA_DEPTH;
+    r.feedback = p->feedback < 0 ? MPT_SVGF_DEFAULT_FEEDBACK : p->feedback != 0;
+    return MPT_OK;
+}
+// Steps A, B, C on the stream, then one wait for the reset count.  T: the buffers of step A (its hist_out / mom_out are what B and C
+// read); dn_guide: the denoiser's packed guide of the current frame; xv[0] = (X, V_0), xv[1], xv[2] the ping-pong; out: the frame.
+static int sv_run(mpt_ctx* ctx, SvFrame T, const float4* dn_guide, float4* const xv[3], float4* out, const float key[14], const float* key_h,
+                  const SvResolved& r, uint64_t* n_reset_out) {
+    const int mode = tp_frame_constants(T, key, key_h, r.tp);
+    const uint32_t W = T.W, H = T.H, n = W * H;
+    HIPCHK(hipMemsetAsync(T.n_reset, 0, 8, ctx->stream));
+    const dim3 grid((W + MPT_DN_TILE - 1) / MPT_DN_TILE, (H + MPT_DN_TILE - 1) / MPT_DN_TILE);
+    {
+        void* args[] = {&T};
+        HIPCHK(hipLaunchKernel(sv_reproject_kernel(mode), grid, dim3(256), args, 0, ctx->stream));
+    }
+    SvVariance S = {T.hist_out, T.mom_out, dn_guide, xv[0], W, H, r.sn, r.sz};
+    hipLaunchKernelGGL(k_sv_variance, grid, dim3(256), 0, ctx->stream, S);
+    HIPCHK(hipGetLastError());
+    if (r.iterations == 0) {
+        hipLaunchKernelGGL(k_sv_modulate, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)T.hist_out, T.ad, dn_guide, n, out);
+        HIPCHK(hipGetLastError());
+    }
+    for (int i = 0; i < r.iterations; ++i) {
+        const bool last = i == r.iterations - 1;
+        SvLevel L;
+        L.xin = i == 0 ? xv[0] : xv[1 + ((i - 1) & 1)];
+        L.guide = dn_guide;
+        L.ad = T.ad;
+        L.hist = T.hist_out;
+        L.xout = last ? out : xv[1 + (i & 1)];
+        L.feedback = i == 0 && r.feedback ? T.hist_out : nullptr;
+        L.W = W;
+        L.H = H;
+        L.step = 1u << i;
+        L.sigma_n = r.sn;
+        L.sigma_z = r.sz;
+        L.sigma_l = r.sl;
+        const bool lds = L.step <= MPT_DN_LDS_MAX_STEP;
+        const uint32_t Tl = MPT_DN_TILE + 4u * L.step;
+        const void* k = lds ? sv_level_kernel<true>(last) : sv_level_kernel<false>(last);
+        void* args[] = {&L};
+        HIPCHK(hipLaunchKernel(k, grid, dim3(256), args, lds ? (size_t)Tl * Tl * 32u : 0u, ctx->stream));
+    }
+    unsigned long long cnt = 0;
+    HIPCHK(hipMemcpyAsync(&cnt, T.n_reset, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    *n_reset_out = cnt;
+    return MPT_OK;
+}
+static bool sv_have_state(const mpt_ctx* ctx) {
+    return ctx->sv.epoch != 0 && ctx->sv.epoch == ctx->guide_epoch && ctx->sv.W == ctx->W && ctx->sv.H == ctx->H && ctx->sv.hist[ctx->sv.cur];
+}
+static int svgf_accumulate_impl(mpt_ctx* ctx, const mpt_svgf_params* p, mpt_svgf_info* out) {
+    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    SvResolved r;
+    int rc = sv_resolve(ctx, p, true, r);
+    if (rc) return rc;
+    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
+    if ((rc = refresh_guides(ctx))) return rc;
+    SvgfState& sv = ctx->sv;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    const bool have = sv_have_state(ctx);
+    if (!sv.hist[0] || sv.W != ctx->W || sv.H != ctx->H) {
+        sv.W = sv.H = 0;
+        sv.epoch = 0;
+        for (DevMem<float4>* b : {&sv.hist[0], &sv.hist[1], &sv.guide[0], &sv.guide[1], &sv.xv[0], &sv.xv[1], &sv.xv[2], &sv.out}) HIPCHK(b->alloc(n * 16));
+        for (DevMem<float2>* b : {&sv.mom[0], &sv.mom[1]}) HIPCHK(b->alloc(n * 8));
+        HIPCHK(sv.n_reset.alloc(8));
+        sv.W = ctx->W;
+        sv.H = ctx->H;
+        sv.cur = 0;
+    }
+    const bool sum = p->source == MPT_DENOISE_SUM;
+    const int nxt = sv.cur ^ 1;
+    SvFrame T = {};
+    T.color = sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target].get();
+    T.samples = sum ? (float)p->samples : 1.0f;
+    T.ad = ctx->d_aov_ad.get();
+    T.nc = ctx->d_aov_nc.get();
+    T.hist_in = sv.hist[sv.cur].get();
+    T.mom_in = sv.mom[sv.cur].get();
+    T.guide_in = sv.guide[sv.cur].get();
+    T.hist_out = sv.hist[nxt].get();
+    T.mom_out = sv.mom[nxt].get();
+    T.guide_out = sv.guide[nxt].get();
+    T.n_reset = sv.n_reset.get();
+    T.W = ctx->W;
+    T.H = ctx->H;
+    float key[14];
+    guide_key(ctx->u, key);
+    float4* xv[3] = {sv.xv[0].get(), sv.xv[1].get(), sv.xv[2].get()};
+    uint64_t n_reset = 0;
+    sv.epoch = 0;   // (no state if a launch fails)
+    if ((rc = sv_run(ctx, T, ctx->d_dn_guide.get(), xv, sv.out.get(), key, have ? sv.cam : nullptr, r, &n_reset))) return rc;
+    sv.cur = nxt;
+    sv.epoch = ctx->guide_epoch;
+    memcpy(sv.cam, key, sizeof key);
+    if (out) {
+        out->pixels_reset = n_reset;
+        out->pixels_reprojected = (uint64_t)n - n_reset;
+    }
+    return MPT_OK;
+}
+// (M1, M2) and (X, V_0) of the device -> the (M1, M2, V_0, 0) the readers return
+static void sv_moments_variance(const std::vector<float>& mom, const std::vector<float>& xv, size_t n, float* out) {
+    for (size_t i = 0; i < n; ++i) {
+        out[4 * i + 0] = mom[2 * i];
+        out[4 * i + 1] = mom[2 * i + 1];
+        out[4 * i + 2] = xv[4 * i + 3];
+        out[4 * i + 3] = 0.0f;
+    }
+}
+static int svgf_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const float* ad, const float* nc, const mpt_uniforms* cam,
+                           const float* hist_h, const float* mom_h, const float* ad_h, const float* nc_h, const mpt_uniforms* cam_h,
+                           const mpt_svgf_params* p, float* hist_out, float* mv_out, float* filtered_out, mpt_svgf_info* out) {
+    if (!ctx || !color || !ad || !nc || !cam || !p || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31))
+        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    if (hist_h && (!mom_h || !ad_h || !nc_h || !cam_h)) return fail(ctx, MPT_ERR_INVALID_ARG, "a history without its moments, guides or camera");
+    SvResolved r;
+    int rc = sv_resolve(ctx, p, false, r);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)W * H;
+    DevMem<> d_c, d_ad, d_nc, d_g, d_h, d_m, d_adh, d_nch, d_gh, d_ho, d_mo, d_go, d_x0, d_x1, d_x2, d_o;
+    DevMem<unsigned long long> d_cnt;
+    for (DevMem<>* b : {&d_c, &d_ad, &d_nc, &d_g, &d_ho, &d_go, &d_x0, &d_x1, &d_x2, &d_o}) HIPCHK(b->alloc(n * 16));
+    HIPCHK(d_mo.alloc(n * 8));
+    HIPCHK(d_cnt.alloc(8));
+    HIPCHK(hipMemcpyAsync(d_c.get(), color, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    const dim3 lin((uint32_t)((n + 255) / 256));
+    hipLaunchKernelGGL(k_dn_pack, lin, dim3(256), 0, ctx->stream, (const float4*)d_ad.get(), (const float4*)d_nc.get(), (uint32_t)n, (float4*)d_g.get());
+    HIPCHK(hipGetLastError());
+    float key[14], key_h[14];
+    guide_key(*cam, key);
+    if (hist_h) {
+        for (DevMem<>* b : {&d_h, &d_adh, &d_nch, &d_gh}) HIPCHK(b->alloc(n * 16));
+        HIPCHK(d_m.alloc(n * 8));
+        HIPCHK(hipMemcpyAsync(d_h.get(), hist_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_m.get(), mom_h, n * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_adh.get(), ad_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
+        HIPCHK(hipMemcpyAsync(d_nch.get(), nc_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_sv_pack, lin, dim3(256), 0, ctx->stream, (const float4*)d_adh.get(), (const float4*)d_nch.get(), (uint32_t)n,
+                           (float4*)d_gh.get());
+        HIPCHK(hipGetLastError());
+        guide_key(*cam_h, key_h);
+    }
+    SvFrame T = {};
+    T.color = (const float4*)d_c.get();
+    T.samples = 1.0f;
+    T.ad = (const float4*)d_ad.get();
+    T.nc = (const float4*)d_nc.get();
+    T.hist_in = (const float4*)d_h.get();
+    T.mom_in = (const float2*)d_m.get();
+    T.guide_in = (const float4*)d_gh.get();
+    T.hist_out = (float4*)d_ho.get();
+    T.mom_out = (float2*)d_mo.get();
+    T.guide_out = (float4*)d_go.get();
+    T.n_reset = d_cnt.get();
+    T.W = W;
+    T.H = H;
+    float4* xv[3] = {(float4*)d_x0.get(), (float4*)d_x1.get(), (float4*)d_x2.get()};
+    uint64_t n_reset = 0;
+    if ((rc = sv_run(ctx, T, (const float4*)d_g.get(), xv, (float4*)d_o.get(), key, hist_h ? key_h : nullptr, r, &n_reset))) return rc;
+    if (hist_out) HIPCHK(hipMemcpyAsync(hist_out, d_ho.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (filtered_out) HIPCHK(hipMemcpyAsync(filtered_out, d_o.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<float> mom, x0;
+    if (mv_out) {
+        mom.resize(n * 2);
+        x0.resize(n * 4);
+        HIPCHK(hipMemcpyAsync(mom.data(), d_mo.get(), n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(x0.data(), d_x0.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (mv_out) sv_moments_variance(mom, x0, n, mv_out);
+    if (out) {
+        out->pixels_reset = n_reset;
+        out->pixels_reprojected = (uint64_t)n - n_reset;
+    }
+    return MPT_OK;
+}
+extern "C" int mpt_svgf_accumulate(mpt_ctx* ctx, const mpt_svgf_params* p, mpt_svgf_info* out) {
+    return guarded(ctx, [&] { return svgf_accumulate_impl(ctx, p, out); });
+}
+extern "C" int mpt_read_svgf(mpt_ctx* ctx, float* rgba) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx || !rgba) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+        if (!sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
+        HIPCHK(hipMemcpyAsync(rgba, ctx->sv.out.get(), (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_svgf_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
+    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
+    if (!sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
+    *p = ctx->sv.out.get();
+    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 16;
+    return MPT_OK;
+}
+extern "C" int mpt_read_svgf_state(mpt_ctx* ctx, float* history, float* moments_variance) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx || !history || !moments_variance) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+        if (!sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
+        const size_t n = (size_t)ctx->W * ctx->H;
+        std::vector<float> mom(n * 2), x0(n * 4);
+        HIPCHK(hipMemcpyAsync(history, ctx->sv.hist[ctx->sv.cur].get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(mom.data(), ctx->sv.mom[ctx->sv.cur].get(), n * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(x0.data(), ctx->sv.xv[0].get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        sv_moments_variance(mom, x0, n, moments_variance);
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_svgf_reset(mpt_ctx* ctx) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx) return MPT_ERR_INVALID_ARG;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        ctx->sv = SvgfState{};
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_svgf_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth_cur, const float* normal_class_cur,
+                              const mpt_uniforms* cam_cur, const float* history_prev, const float* moments_prev, const float* albedo_depth_prev,
+                              const float* normal_class_prev, const mpt_uniforms* cam_prev, const mpt_svgf_params* p, float* history_out,
+                              float* moments_variance_out, float* filtered_out, mpt_svgf_info* out) {
+    return guarded(ctx, [&] {
+        return svgf_image_impl(ctx, w, h, color, albedo_depth_cur, normal_class_cur, cam_cur, history_prev, moments_prev, albedo_depth_prev,
+                               normal_class_prev, cam_prev, p, history_out, moments_variance_out, filtered_out, out);
     });
 }
 

@@ -25,6 +25,7 @@ SYMBOLS = (
     "mpt_renderer_uniforms", "mpt_renderer_stats", "mpt_renderer_context", "mpt_renderer_scene", "mpt_write_pfm",
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
+    "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf",
 )
 
 _lib = None
@@ -71,6 +72,8 @@ def load():
     L.mpt_renderer_draw_temporal.argtypes = [vp, C.c_uint32, C.POINTER(capi.TemporalParams), C.POINTER(capi.TemporalInfo)]
     L.mpt_renderer_read_temporal.argtypes = [vp, fp]
     L.mpt_renderer_denoise_temporal.argtypes = [vp, C.POINTER(capi.DenoiseParams), fp]
+    L.mpt_renderer_draw_svgf.argtypes = [vp, C.c_uint32, C.POINTER(capi.SvgfParams), C.POINTER(capi.SvgfInfo)]
+    L.mpt_renderer_read_svgf.argtypes = [vp, fp]
     L.mpt_renderer_context.argtypes = [vp]
     L.mpt_renderer_context.restype = vp
     L.mpt_renderer_scene.argtypes = [vp]
@@ -353,6 +356,21 @@ class Renderer:
         out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
         p = capi.denoise_params(**kw)
         self._chk(self.L.mpt_renderer_denoise_temporal(self.h, C.byref(p), _fp(out)), "denoiseTemporal")
+        return out
+
+    def drawSvgf(self, samples_per_frame=1, **kw):
+        """mpt_renderer_draw_svgf: one frame of SVGF with the pending input(); kw: the fields of mpt_svgf_params but source / samples
+        (none: keep the renderer's).  Returns the mpt_svgf_info as a dict; readSvgf() has the frame."""
+        p = capi.svgf_params(**kw) if kw else None
+        info = capi.SvgfInfo()
+        self._chk(self.L.mpt_renderer_draw_svgf(self.h, int(samples_per_frame), C.byref(p) if p is not None else None, C.byref(info)),
+                  "drawSvgf")
+        return info.as_dict()
+
+    def readSvgf(self):
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
+        self._chk(self.L.mpt_renderer_read_svgf(self.h, _fp(out)), "readSvgf")
         return out
 
     def scene(self):
