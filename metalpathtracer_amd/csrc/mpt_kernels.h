@@ -632,6 +632,21 @@ struct WaveBudgets {
 #ifndef MPT_WL_WAVES_N
 #define MPT_WL_WAVES_N 6
 #endif
+// Carried hits (MPT_WL_CARRY, default on).  Ring 0 is a stack and a ring-0 step pops its newest records, so whenever the step after
+// a hit push is a ring-0 step the records just written are read straight back: 48-64 bytes to the fabric (stores are not absorbed
+// by L2) and a dependent load of the same bytes at the head of the next step, for rays that never left the wave.  With the carry
+// the hits of a step stay in the lanes that found them when the next step is known to be a ring-0 step — no ring >= 1 holds a full
+// wave and ring 0 plus these hits does — and that step pops only the 64 - k records it still needs, into the lanes that carry
+// nothing.  "Push k, pop the top 64" and "keep k, pop the top 64 - k" give a step the same 64 rays and leave the same records
+// behind; only the lane a ray sits in differs, and nothing a path computes depends on its lane: every step of the schedule, every
+// count and every slot value stay what they were.  -DMPT_WL_CARRY=0 pushes every hit.  A first-in-first-out ring pops the OLDEST
+// records, so the identity does not hold there.
+#ifndef MPT_WL_CARRY
+#define MPT_WL_CARRY 1
+#endif
+#if MPT_WL_CARRY && defined(MPT_WL_FIFO)
+#error "MPT_WL_CARRY needs ring 0 to be a stack: build MPT_WL_FIFO with -DMPT_WL_CARRY=0"
+#endif
 #define MPT_WL_THREADS(ALL_LDS) MPT_WL_THREADS_N
 #define MPT_WL_WAVES(ALL_LDS) MPT_WL_WAVES_N
 template <bool COUNT, bool ALL_LDS>
@@ -704,6 +719,16 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
     float uvx_cached = 0.0f, uvy_cached = 0.0f;   // pixel_uv of this lane's pixel in the cached tile
     uint32_t n_rays = 0, n_paths = 0;
     WorkCount wc = {};
+#if MPT_WL_CARRY
+    // the hits the previous step kept in its lanes (the lane mask is this flag's ballot).  What those lanes hold is the step's own
+    // `ps`, `best_t` and `best_prim`, which therefore live across the loop's back edge: every step replaces them in every lane that
+    // carries nothing, so they occupy no register the walk did not need anyway and nothing is copied.  (A separate copy, written
+    // when a carry happens, lives through primary steps and their walk: 9-13 VGPRs of scratch.)
+    bool kept = false;
+    PathState ps = {};
+    float best_t = INFINITY;
+    int best_prim = -1;
+#endif
 #ifdef MPT_DEBUG_WAVE_TIMES
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
     unsigned long long t_exh = 0ull, t_claim = 0ull, dbg_steps = 0ull, dbg_left = 0ull, dbg_blk = 0ull;
@@ -713,9 +738,17 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         MPT_TIC(tic_);
         // ---- step choice: deepest ring with a full wave of rays; else new paths; else drain ----------------------
         int level = -1;  // -1 = primary step
+#if MPT_WL_CARRY
+        const unsigned long long carry = __ballot(kept);   // ring 0 counts with the hits its last step kept: a carry always leads to level 0
+        if (cnt[0] + (uint32_t)__popcll(carry) >= 64u) level = 0;
+#pragma unroll
+        for (int k = (int)MPT_WL_LEVELS - 1; k >= 1; --k)
+            if (level <= 0 && cnt[k] >= 64u) level = k;   // (never with a carry: the carry rule saw every ring >= 1 below 64)
+#else
 #pragma unroll
         for (int k = (int)MPT_WL_LEVELS - 1; k >= 0; --k)
             if (level < 0 && cnt[k] >= 64u) level = k;
+#endif
         if (level < 0) {
             if (!exhausted && cur == end) {
                 // Guided self-scheduling of path ids.  The pass's tiles are dealt to MPT_NGROUP interleaved ranges,
@@ -792,17 +825,27 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         if (!exhausted) dbg_steps += 1ull << (12u * (uint32_t)(level + 1));  // field 0 = primary steps
 #endif
         MPT_TOC(reg_select, tic_);
+#if MPT_WL_CARRY
+        // a lane that carries a hit holds what a push and a pop of its record would have left there (ring_push_hit / ring_pop_hit):
+        // the ray in `ps`, and t and the primitive behind the record's masks
+        float hit_t = __uint_as_float(__float_as_uint(best_t) & 0x7FFFFFFFu);
+        int hit_prim = (int)((uint32_t)best_prim & 0x07FFFFFFu);
+        ps.bounce &= 31u;
+        best_t = INFINITY;
+        best_prim = -1;
+#else
         PathState ps;
+        float best_t = INFINITY;
+        int best_prim = -1;
+        float hit_t = 0.0f;
+        int hit_prim = -1;
+#endif
         PathRngDev g;
         bool valid = false;
         uint32_t node = 0;
-        float best_t = INFINITY;
-        int best_prim = -1;
         uint32_t budget = 0xFFFFFFFFu, min_active = 0u;
         bool fresh = false;  // this lane starts a new closest-hit query (primary ray or ring-0 record)
-        bool need_shade = false;   // this lane popped a hit from ring 0
-        float hit_t = 0.0f;
-        int hit_prim = -1;
+        bool need_shade = false;   // this lane popped a hit from ring 0 (or carries one)
         if (level < 0) {
             fresh = true;
             // 64 new paths = one 8x8 pixel tile at one sample index: everything about the tile is wave-uniform, and its
@@ -823,7 +866,8 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 tile_cached = tl;
                 tile_xy_cached = (uint32_t)__builtin_amdgcn_readfirstlane((int)pp.tile_xy[tl]);
             }
-            ps.path = pchunk * 64u + lane;
+            PathState np;   // (every lane's ray is replaced, also in the lanes outside the image, which hold none: nothing of the step before stays live)
+            np.path = pchunk * 64u + lane;
             const uint32_t px = (tile_xy_cached & 0xFFFFu) * 8u + (lane & 7u), py = (tile_xy_cached >> 16) * 8u + (lane >> 3);
             CamView cv;
             {
@@ -837,28 +881,38 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             }
             if (new_tile) pixel_uv(cv, px, py, uvx_cached, uvy_cached);
             if (px < pp.width && py < pp.height) {
-                gen_primary(pp, cv, px, py, uvx_cached, uvy_cached, pp.sample_begin + sidx, ps, g);
+                gen_primary(pp, cv, px, py, uvx_cached, uvy_cached, pp.sample_begin + sidx, np, g);
                 valid = true;
-                n_paths++;
             }
+            n_paths += (uint32_t)__popcll(__ballot(valid));
+            ps = np;
         } else {
             // lanes -> ring records.  Normal step: 64 records of ring `level`.  Merged drain step: up to 64 records
             // taken from all rings, deepest first (lane ranges [lo_k, lo_k + take_k) per ring).
             uint32_t my_ring = 0, my_off = 0;
             bool take = false;
             uint32_t assigned = 0;
+#if MPT_WL_CARRY
+            // after a carry (always a ring-0 step) only the lanes that carry nothing pop: 64 - popcount(carry) records, the top of the
+            // stack, indexed by a lane's rank among those lanes (= lane when nothing is carried)
+            const uint32_t slot = wave_rank(~carry), room = 64u - (uint32_t)__popcll(carry);
+            const bool empty = !kept;
+#else
+            const uint32_t slot = lane, room = 64u;
+            const bool empty = true;
+#endif
 #pragma unroll
             for (int k = (int)MPT_WL_LEVELS - 1; k >= 0; --k) {
                 const bool use = (level == (int)MPT_WL_LEVELS) || (level == k);
                 uint32_t tk = use ? cnt[k] : 0u;
-                tk = tk < 64u - assigned ? tk : 64u - assigned;
-                if (lane >= assigned && lane < assigned + tk) {
+                tk = tk < room - assigned ? tk : room - assigned;
+                if (empty && slot >= assigned && slot < assigned + tk) {
                     take = true;
                     my_ring = (uint32_t)k;
 #ifdef MPT_WL_FIFO
-                    my_off = (head[k] + (lane - assigned)) & M;
+                    my_off = (head[k] + (slot - assigned)) & M;
 #else
-                    my_off = cnt[k] - tk + (lane - assigned);  // newest records first: they are still in L2
+                    my_off = cnt[k] - tk + (slot - assigned);  // newest records first: they are still in L2
 #endif
                 }
                 (void)k;
@@ -891,6 +945,13 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 }
                 valid = true;
             }
+#if MPT_WL_CARRY
+            if (kept) {   // a carried hit: its ray, t and primitive are in place
+                need_shade = true;
+                fresh = true;
+                valid = true;
+            }
+#endif
         }
         // ---- the hits popped from ring 0 are shaded first — all 64 lanes of a ring-0 step — and leave their bounce rays in `ps` ------
         if (need_shade) {
@@ -915,6 +976,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
 #ifdef MPT_DEBUG_WAVE_TIMES
         const WorkCount wc0 = wc;
 #endif
+        n_rays += (uint32_t)__popcll(__ballot(valid && fresh));  // a resumed query was counted when it started
         if (valid) {
             bool done;
             if (budgeted)
@@ -923,7 +985,6 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             else
                 done = closest_hit_resume<COUNT, ALL_LDS, false>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
                                                                 0xFFFFFFFFu, wc);
-            if (fresh) n_rays++;  // a resumed query was counted when it started
             MPT_TOC(reg_trace, tic_);
 #ifdef MPT_DEBUG_WAVE_TIMES
             if (COUNT) {  // per-level divergence diagnostics: [level + 1][steps, box trips, box lane work, prim trips, prim lane work]
@@ -952,13 +1013,6 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         }
         MPT_TOC(reg_shade, tic_);
         const unsigned long long am = __ballot(alive), pm = __ballot(parked);
-        if (am != 0ull) {  // survivors are fresh rays -> ring 0
-            if (alive) {
-                const uint32_t at = wbase + ((head[0] + cnt[0] + wave_rank(am)) & M);
-                ring_push_hit(ring, at, ps, best_t, (uint32_t)best_prim);
-            }
-            cnt[0] += (uint32_t)__popcll(am);
-        }
         if (pm != 0ull) {  // unfinished queries -> next ring, with their traversal state (only from budgeted steps)
             uint32_t h = 0, c = 0;
 #pragma unroll
@@ -975,6 +1029,44 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
 #pragma unroll
             for (int k = 1; k < (int)MPT_WL_LEVELS; ++k)
                 if (k == park_ring) cnt[k] = c + (uint32_t)__popcll(pm);
+        }
+        // survivors are fresh rays -> ring 0 (after the parked rays, whose ring count the carry rule reads)
+#if MPT_WL_CARRY
+        // ... unless the next step is a ring-0 step anyway — no ring >= 1 holds a full wave, ring 0 with these hits does: then they stay
+        // where they are and that step pops the rest
+        bool keep = cnt[0] + (uint32_t)__popcll(am) >= 64u;
+#pragma unroll
+        for (int k = 1; k < (int)MPT_WL_LEVELS; ++k) keep = keep && cnt[k] < 64u;
+        kept = keep && alive;
+#else
+        const bool keep = false;
+#endif
+#ifdef MPT_DEBUG_WAVE_TIMES
+        if (COUNT && (am | pm) != 0ull) {
+            // rows 15 and 14 of the per-step-kind block, the ring traffic by record: row 15 = hits (carried, pushed, carried with light,
+            // pushed with light, steps that carried, steps that pushed), row 14 = parked rays (records, with light, steps)
+            unsigned long long* rt = (unsigned long long*)(ring.tv() + (size_t)n_waves * MPT_WL_LEVELS * MPT_WL_RING) + 16ull * n_waves + 8ull * 14ull;
+            const unsigned long long lit_a = __ballot(alive && ring_has_light(ps)), lit_p = __ballot(parked && ring_has_light(ps));
+            if (lane == 0u) {
+                if (am != 0ull) {
+                    atomicAdd(rt + 8 + (keep ? 0 : 1), (unsigned long long)__popcll(am));
+                    atomicAdd(rt + 8 + (keep ? 2 : 3), (unsigned long long)__popcll(lit_a));
+                    atomicAdd(rt + 8 + (keep ? 4 : 5), 1ull);
+                }
+                if (pm != 0ull) {
+                    atomicAdd(rt + 0, (unsigned long long)__popcll(pm));
+                    atomicAdd(rt + 1, (unsigned long long)__popcll(lit_p));
+                    atomicAdd(rt + 2, 1ull);
+                }
+            }
+        }
+#endif
+        if (am != 0ull && !keep) {
+            if (alive) {
+                const uint32_t at = wbase + ((head[0] + cnt[0] + wave_rank(am)) & M);
+                ring_push_hit(ring, at, ps, best_t, (uint32_t)best_prim);
+            }
+            cnt[0] += (uint32_t)__popcll(am);
         }
         uint32_t worst = 0;
 #pragma unroll
@@ -1003,7 +1095,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
     }
 #endif
     MPT_CLOCK_END();
-    flush_stats<COUNT>(pp.desc, n_rays, n_paths, wc);
+    flush_stats<COUNT>(pp.desc, lane == 0u ? n_rays : 0u, lane == 0u ? n_paths : 0u, wc);
     note_wave_exit(pp);
 }
 

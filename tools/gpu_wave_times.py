@@ -76,6 +76,22 @@ if flags:
         print("  %-8s steps %9d  rays/step %5.1f  done %5.1f %%  box trips %7.1f util %4.1f %%  prim trips %6.1f util %4.1f %%  cost share %4.1f %%  box slots waiting with a leaf %4.1f %%" % (
             nm, st_, rays / st_, 100 * dn / max(1, rays), bt / st_, 100 * bw / max(1, 64 * bt), pt / st_, 100 * pw / max(1, 64 * pt),
             100 * (bt * 26 + pt * 70) / tot, 100 * wl / max(1, 64 * bt)))
+    # rows 15 and 14 of the block, the ring traffic by record: hits that stayed in their lanes for the ring-0 step that followed
+    # (MPT_WL_CARRY) against hits pushed to ring 0, and the rays parked in ring 1; a record is 48 bytes, 16 more if the path has
+    # gathered light, 16 more (the walk state) for a parked ray
+    carried, pushed, carried_lit, pushed_lit, carry_steps, push_steps = lv[15, :6]
+    parked, parked_lit, park_steps = lv[14, :3]
+    if carried + pushed > 0:
+        J["ring_traffic"] = {"hits_carried": carried, "hits_pushed": pushed, "carried_pct": 100 * carried / (carried + pushed),
+                             "hits_carried_with_light": carried_lit, "hits_pushed_with_light": pushed_lit,
+                             "steps_that_carried": carry_steps, "steps_that_pushed": push_steps,
+                             "parked": parked, "parked_with_light": parked_lit, "steps_that_parked": park_steps,
+                             "bytes_not_written_by_the_carry": 48 * carried + 16 * carried_lit,
+                             "bytes_pushed": 48 * (pushed + parked) + 16 * (pushed_lit + parked_lit) + 16 * parked}
+        print("ring-0 hits: %d carried in their lanes (%d with light, %d steps), %d pushed (%d with light, %d steps): %.1f %% carried" % (
+            carried, carried_lit, carry_steps, pushed, pushed_lit, push_steps, 100 * carried / (carried + pushed)))
+        print("parked rays: %d (%d with light, %d steps);  record bytes the carry did not write %.3f GB, record bytes pushed %.3f GB" % (
+            parked, parked_lit, park_steps, J["ring_traffic"]["bytes_not_written_by_the_carry"] / 1e9, J["ring_traffic"]["bytes_pushed"] / 1e9))
 
 out = os.environ.get("JSON_OUT")
 if out:
