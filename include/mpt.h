@@ -527,6 +527,84 @@ int mpt_svgf_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* c
                    const mpt_svgf_params* params, float* history_out, float* moments_variance_out, float* filtered_out,
                    mpt_svgf_info* out /* may be NULL */);
 
+/* ---- display: auto-exposure, tone curve, exact 8-bit encoding --------------------------------------------------------------------
+ * No reference counterpart (the reference hands its float target to the drawable, Renderer.cpp:303-307).  The last step between a
+ * rendered frame and a picture, on the device: W*H RGBA8 words instead of W*H*4 floats come back to the host.
+ *
+ * State per context: the display buffer (one word per pixel), the 256-bin histogram of the last call with auto_exposure, and the auto
+ * scale kept for the next call.  Allocated by the first mpt_display; dropped by mpt_resize, mpt_upload_scene and mpt_build_and_upload;
+ * mpt_display_reset forgets only the kept auto scale.  mpt_clear_sum does not touch it.
+ *
+ * mpt_display waits for the renders queued and in flight (reporting a failed mpt_render_async), then for every pixel with c the source's
+ * colour (MPT_DISPLAY_*).  All arithmetic is float32, one IEEE operation at a time in the order written;
+ * lum(c) = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b; no pow, exp or log runs on the device (tests/display_ref.py restates it in numpy and
+ * agrees bit for bit):
+ *   A. Histogram (only with auto_exposure).  l = lum(c.rgb), before any exposure.  A pixel is counted iff l > 0 and l < +inf.  With
+ *      e = float_bits(l) >> 21 its bin is b = min(max(e, 380), 635) - 380: 256 bins, four per octave, from 2^-32 to 2^32; smaller
+ *      values fall in bin 0, larger ones in bin 255.  The lower edge of bin b is E_b = bits_to_float((b + 380) << 21).  Counts are
+ *      uint32; pixels_counted = N, their sum.
+ *   B. Exposure.  N = 0: auto_scale = 1, key_bin = 0xFFFFFFFF.  Otherwise key_bin = the smallest b with cum(b) * 100 >= N * percentile
+ *      in 64-bit integers (cum = the inclusive prefix sum); target = key / E_key_bin; if the context keeps a previous auto scale p and
+ *      0 < adaptation < 1: auto_scale = p + (target - p) * adaptation, otherwise auto_scale = target.  The new auto scale is kept for
+ *      the next call.  Without auto_exposure: auto_scale = 1, key_bin = 0xFFFFFFFF, pixels_counted = 0 and the kept state is untouched.
+ *      scale = exposure * auto_scale.
+ *   C. Tone curve, per channel: x = c_ch * scale; v = x > 0 ? x : 0 (a NaN becomes 0); v = min(v, 65504).
+ *      CLAMP: y = v.  REINHARD: y = (v * (1 + v / (white * white))) / (1 + v).
+ *      ACES (Narkowicz's fit): y = (v * (2.51f * v + 0.03f)) / (v * (2.43f * v + 0.59f) + 0.14f).
+ *      A pixel is clipped iff any of its three y is >= 1 (pixels_clipped counts them).  Then y = min(y, 1).
+ *   D. Encoding: code = |{k in 1..255 : T[k] <= y}|, T[k] = the float32 nearest to f^-1((k - 0.5) / 255) — the correctly rounded
+ *      round(255 f(y)) without a transcendental.  SRGB: f^-1(s) = s <= 0.04045 ? s / 12.92 : ((s + 0.055) / 1.055)^2.4; GAMMA22:
+ *      f^-1(s) = s^2.2 (what mpt_write_ppm's pow(v, 1 / 2.2) * 255 + 0.5, truncated, means); LINEAR: f^-1(s) = s.  The three tables are
+ *      computed once in float64 by tools/make_display_table.py and committed (mpt_display_table.h); mpt_display_table returns them,
+ *      out[k - 1] = T[k].  Output word: r | g << 8 | b << 16 | 255 << 24.
+ * The stage reads its source and writes none of: the HDR sum, the frame targets, the moments, the denoised buffer, the temporal and
+ * SVGF state, mpt_stats.  It needs a size but no scene.
+ * MPT_ERR_INVALID_ARG, with nothing changed: null params, a bad source, tone or transfer, SUM with samples = 0, percentile > 100, a NaN
+ * in any float field.  MPT_ERR_NOT_READY before mpt_resize and for a source that does not exist yet (no denoised result, no temporal or
+ * SVGF history, no adaptive render), and from mpt_read_display / mpt_display_buffer / mpt_read_display_histogram before the first
+ * mpt_display.  Defaults: conventional values, not swept.                                                                            */
+enum { MPT_DISPLAY_SUM = 0,       /* HDR sum / samples (IEEE division by (float)samples per channel, as the denoiser's c)              */
+       MPT_DISPLAY_FRAME = 1,     /* the current mpt_draw target                                                                      */
+       MPT_DISPLAY_DENOISED = 2,  /* what mpt_read_denoised returns (mpt_denoise / mpt_denoise_temporal)                              */
+       MPT_DISPLAY_TEMPORAL = 3,  /* rgb of the mpt_temporal_* history                                                                */
+       MPT_DISPLAY_SVGF = 4,      /* rgb of mpt_read_svgf                                                                             */
+       MPT_DISPLAY_ADAPTIVE = 5 };/* HDR sum / (float)count(tile) of the last mpt_render_adaptive, the tile of pixel (x, y) being
+                                     (y / 8) * ceil(W / 8) + x / 8; a count of 0 gives 0                                              */
+enum { MPT_TONE_CLAMP = 0, MPT_TONE_REINHARD = 1, MPT_TONE_ACES = 2 };
+enum { MPT_TRANSFER_SRGB = 0, MPT_TRANSFER_GAMMA22 = 1, MPT_TRANSFER_LINEAR = 2 };
+#define MPT_DISPLAY_DEFAULT_WHITE 4.0f
+#define MPT_DISPLAY_DEFAULT_PERCENTILE 50u
+#define MPT_DISPLAY_DEFAULT_KEY 0.18f
+typedef struct mpt_display_params {
+    int32_t source;            /* MPT_DISPLAY_* (mpt_display; mpt_display_image presents the colour it is given)                     */
+    uint32_t samples;          /* SUM: samples per pixel the sum holds (> 0)                                                         */
+    int32_t tone;              /* MPT_TONE_*                                                                                         */
+    int32_t transfer;          /* MPT_TRANSFER_*                                                                                     */
+    float exposure;            /* linear multiplier; <= 0 selects 1                                                                  */
+    float white;               /* REINHARD's white point; <= 0 selects MPT_DISPLAY_DEFAULT_WHITE                                     */
+    int32_t auto_exposure;     /* != 0: multiply by the histogram's scale (steps A, B)                                               */
+    uint32_t percentile;       /* 1..100; 0 selects MPT_DISPLAY_DEFAULT_PERCENTILE                                                   */
+    float key;                 /* the value the key bin's lower edge is mapped to; <= 0 selects MPT_DISPLAY_DEFAULT_KEY              */
+    float adaptation;          /* (0, 1): share of the way to the target taken per call; <= 0 or >= 1: no smoothing                  */
+} mpt_display_params;
+typedef struct mpt_display_info {
+    float scale, auto_scale;   /* scale = exposure * auto_scale, as used                                                             */
+    uint32_t key_bin, _pad;    /* 0xFFFFFFFF when nothing was counted or auto_exposure is off                                        */
+    uint64_t pixels_counted, pixels_clipped;
+} mpt_display_info;
+
+int mpt_display(mpt_ctx* ctx, const mpt_display_params* params, mpt_display_info* out /* may be NULL */);
+int mpt_read_display(mpt_ctx* ctx, uint8_t* rgba8_host);               /* W*H*4 bytes (r, g, b, 255), row-major, top-left origin     */
+int mpt_display_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);
+int mpt_read_display_histogram(mpt_ctx* ctx, uint32_t out[256]);       /* of the last call with auto_exposure (zeros before one)     */
+int mpt_display_reset(mpt_ctx* ctx);                                   /* forgets the kept auto scale: the next call is unsmoothed   */
+int mpt_display_table(int transfer, float out[255]);                   /* a pure function (no context)                               */
+/* The same kernels on a caller array (host, W*H*4 floats; the unit-test hook, no scene and no size needed): color is c itself (source
+ * and samples are ignored); prev_auto_scale = NULL: no kept auto scale; the context's own display state is neither read nor written.
+ * histogram_out (256 uint32, may be NULL): this call's histogram, zeros without auto_exposure.  out may be NULL.                     */
+int mpt_display_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const mpt_display_params* params,
+                      const float* prev_auto_scale, uint8_t* rgba8_out, uint32_t* histogram_out, mpt_display_info* out);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

@@ -94,12 +94,17 @@ int mpt_renderer_denoise_temporal(mpt_renderer* r, const mpt_denoise_params* par
  * filtered frame (rgb, a = the history length), W*H*4 floats.                                                                    */
 int mpt_renderer_draw_svgf(mpt_renderer* r, uint32_t samples_per_frame, const mpt_svgf_params* params, mpt_svgf_info* out);
 int mpt_renderer_read_svgf(mpt_renderer* r, float* rgba);
+/* mpt_display + mpt_read_display (include/mpt.h) of params->source as given; for MPT_DISPLAY_SUM, params->samples = 0 means the
+ * samples rendered since the sum was last cleared.  rgba8: W*H*4 bytes.  out may be NULL.                                        */
+int mpt_renderer_display(mpt_renderer* r, const mpt_display_params* params, uint8_t* rgba8, mpt_display_info* out);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 
 /* Image output (the reference has none).  rgba: W*H*4 floats, top-left origin; value = rgba * scale. */
 int mpt_write_pfm(const char* path, const float* rgba, uint32_t width, uint32_t height, float scale);
 int mpt_write_ppm(const char* path, const float* rgba, uint32_t width, uint32_t height, float scale, float gamma);
+/* The same file from finished bytes (mpt_read_display: W*H*4, r g b 255): writes r, g, b and does no arithmetic. */
+int mpt_write_ppm8(const char* path, const uint8_t* rgba8, uint32_t width, uint32_t height);
 
 #ifdef __cplusplus
 }

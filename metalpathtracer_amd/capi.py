@@ -34,6 +34,8 @@ SYMBOLS = (
     "mpt_temporal_accumulate", "mpt_read_temporal", "mpt_temporal_buffer", "mpt_temporal_reset", "mpt_denoise_temporal",
     "mpt_temporal_image",
     "mpt_svgf_accumulate", "mpt_read_svgf", "mpt_svgf_buffer", "mpt_read_svgf_state", "mpt_svgf_reset", "mpt_svgf_image",
+    "mpt_display", "mpt_read_display", "mpt_display_buffer", "mpt_read_display_histogram", "mpt_display_reset", "mpt_display_table",
+    "mpt_display_image",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
@@ -47,6 +49,12 @@ TEMPORAL_DEFAULTS = dict(max_history=32, depth_tolerance=0.05, normal_threshold=
 # include/mpt.h MPT_SVGF_DEFAULT_* (iterations / feedback < 0 and a sigma <= 0 select them; step A's are the TEMPORAL_DEFAULTS)
 SVGF_DEFAULTS = dict(iterations=2, sigma_luminance=2.0, sigma_normal=32.0, sigma_depth=0.25, feedback=0)
 SVGF_EPSILON = 1e-4
+DISPLAY_SUM, DISPLAY_FRAME, DISPLAY_DENOISED, DISPLAY_TEMPORAL, DISPLAY_SVGF, DISPLAY_ADAPTIVE = 0, 1, 2, 3, 4, 5
+TONE_CLAMP, TONE_REINHARD, TONE_ACES = 0, 1, 2
+TRANSFER_SRGB, TRANSFER_GAMMA22, TRANSFER_LINEAR = 0, 1, 2
+# include/mpt.h MPT_DISPLAY_DEFAULT_* (a value <= 0 / percentile 0 selects them; exposure <= 0 selects 1)
+DISPLAY_DEFAULTS = dict(white=4.0, percentile=50, key=0.18)
+DISPLAY_NO_BIN = 0xFFFFFFFF
 
 
 class MptError(RuntimeError):
@@ -161,6 +169,41 @@ def svgf_params(source=DENOISE_SUM, samples=0, max_history=0, depth_tolerance=0.
                       int(iterations), float(sigma_luminance), float(sigma_normal), float(sigma_depth), int(feedback))
 
 
+class DisplayParams(C.Structure):
+    _fields_ = [("source", C.c_int32), ("samples", C.c_uint32), ("tone", C.c_int32), ("transfer", C.c_int32),
+                ("exposure", C.c_float), ("white", C.c_float), ("auto_exposure", C.c_int32), ("percentile", C.c_uint32),
+                ("key", C.c_float), ("adaptation", C.c_float)]
+
+
+class DisplayInfo(C.Structure):
+    _fields_ = [("scale", C.c_float), ("auto_scale", C.c_float), ("key_bin", C.c_uint32), ("_pad", C.c_uint32),
+                ("pixels_counted", C.c_uint64), ("pixels_clipped", C.c_uint64)]
+
+    def as_dict(self):
+        """scale / auto_scale as numpy float32 (their bits matter to the tests), the rest as int."""
+        return dict(scale=np.float32(self.scale), auto_scale=np.float32(self.auto_scale), key_bin=int(self.key_bin),
+                    pixels_counted=int(self.pixels_counted), pixels_clipped=int(self.pixels_clipped))
+
+
+assert C.sizeof(DisplayParams) == 40 and C.sizeof(DisplayInfo) == 32
+
+
+def display_params(source=DISPLAY_SUM, samples=0, tone=TONE_CLAMP, transfer=TRANSFER_SRGB, exposure=0.0, white=0.0, auto_exposure=False,
+                   percentile=0, key=0.0, adaptation=0.0):
+    """mpt_display_params; exposure / white / key <= 0 and percentile = 0 mean the defaults of include/mpt.h."""
+    return DisplayParams(int(source), int(samples), int(tone), int(transfer), float(exposure), float(white), int(bool(auto_exposure)),
+                         int(percentile), float(key), float(adaptation))
+
+
+def display_table(transfer):
+    """mpt_display_table: the 255 float32 thresholds T[1..255] of a transfer function (index k - 1); needs no context."""
+    out = np.empty(255, np.float32)
+    rc = load().mpt_display_table(int(transfer), _fp(out))
+    if rc:
+        raise MptError(rc, "mpt_display_table")
+    return out
+
+
 def expand_tile_counts(counts, H, W):
     """(tiles_y, tiles_x) per-tile counts -> (H, W) per-pixel counts (8x8 tiles, the edge tiles cut at the image border)."""
     return np.repeat(np.repeat(np.asarray(counts), 8, axis=0), 8, axis=1)[:H, :W]
@@ -271,6 +314,14 @@ def load():
     L.mpt_svgf_reset.argtypes = [vp]
     L.mpt_svgf_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, fp, C.POINTER(Uniforms), fp, fp, fp, fp, C.POINTER(Uniforms),
                                  C.POINTER(SvgfParams), fp, fp, fp, C.POINTER(SvgfInfo)]
+    u8p = C.POINTER(C.c_uint8)
+    L.mpt_display.argtypes = [vp, C.POINTER(DisplayParams), C.POINTER(DisplayInfo)]
+    L.mpt_read_display.argtypes = [vp, u8p]
+    L.mpt_display_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_read_display_histogram.argtypes = [vp, up]
+    L.mpt_display_reset.argtypes = [vp]
+    L.mpt_display_table.argtypes = [C.c_int, fp]
+    L.mpt_display_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, C.POINTER(DisplayParams), fp, u8p, up, C.POINTER(DisplayInfo)]
     _lib = L
     return L
 
@@ -704,6 +755,51 @@ class Context:
         self._chk(self.L.mpt_svgf_image(self.h, W, H, _fp(c), _fp(ad), _fp(nc), C.byref(cam), hp, mp, adp, ncp, camp, C.byref(p),
                                         _fp(ho), _fp(mv), _fp(out), C.byref(info)), "mpt_svgf_image")
         return ho, mv, out, info.as_dict()
+
+    def display(self, **kw):
+        """mpt_display: exposure, tone curve and 8-bit encoding of a source on the device; returns the mpt_display_info as a dict.
+        read_display() has the bytes."""
+        p = display_params(**kw)
+        info = DisplayInfo()
+        self._chk(self.L.mpt_display(self.h, C.byref(p), C.byref(info)), "mpt_display")
+        return info.as_dict()
+
+    def read_display(self):
+        """The finished frame: [H, W, 4] uint8 (r, g, b, 255)."""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._chk(self.L.mpt_read_display(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8))), "mpt_read_display")
+        return out
+
+    def display_buffer(self):
+        """(device pointer, bytes) of the finished frame, for zero-copy use after synchronize()."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_display_buffer(self.h, C.byref(p), C.byref(n)), "mpt_display_buffer")
+        return p.value, n.value
+
+    def read_display_histogram(self):
+        """The 256 luminance bins of the last display() with auto_exposure."""
+        out = np.empty(256, np.uint32)
+        self._chk(self.L.mpt_read_display_histogram(self.h, _up(out)), "mpt_read_display_histogram")
+        return out
+
+    def display_reset(self):
+        self._chk(self.L.mpt_display_reset(self.h), "mpt_display_reset")
+
+    def display_image(self, color, prev_auto_scale=None, **kw):
+        """The display kernels on a caller array [H,W,4] (source / samples are ignored); prev_auto_scale: the auto scale kept from an
+        earlier call, or None.  Returns (bytes [H,W,4] uint8, histogram [256] uint32, info dict)."""
+        c = np.ascontiguousarray(color, np.float32)
+        if c.ndim != 3 or c.shape[2] != 4:
+            raise ValueError("display_image: color must be an [H, W, 4] array")
+        H, W = c.shape[:2]
+        out = np.empty((H, W, 4), np.uint8)
+        hist = np.empty(256, np.uint32)
+        prev = None if prev_auto_scale is None else C.byref(C.c_float(float(prev_auto_scale)))
+        p = display_params(**kw)
+        info = DisplayInfo()
+        self._chk(self.L.mpt_display_image(self.h, W, H, _fp(c), C.byref(p), prev, out.ctypes.data_as(C.POINTER(C.c_uint8)), _up(hist),
+                                           C.byref(info)), "mpt_display_image")
+        return out, hist, info.as_dict()
 
     def kat_pcg(self, seeds):
         s = np.ascontiguousarray(seeds, np.uint32)

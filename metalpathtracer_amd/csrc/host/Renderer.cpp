@@ -347,6 +347,15 @@ void Renderer::denoise(const mpt_denoise_params& p, std::vector<float>& rgba) {
     rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
     check(mpt_read_denoised(ctx_, rgba.data()), "mpt_read_denoised");
 }
+mpt_display_info Renderer::display(const mpt_display_params& p, std::vector<uint8_t>& rgba8) {
+    mpt_display_params q = p;
+    if (q.source == MPT_DISPLAY_SUM && q.samples == 0) q.samples = sumSamples_;
+    mpt_display_info info;
+    check(mpt_display(ctx_, &q, &info), "mpt_display");
+    rgba8.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_display(ctx_, rgba8.data()), "mpt_read_display");
+    return info;
+}
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     if (rgba.size() != n) throw std::runtime_error("writeSum: the array does not have the size of the frame");

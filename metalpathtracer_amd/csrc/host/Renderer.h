@@ -75,6 +75,9 @@ public:
     mpt_svgf_info drawSvgf(OffscreenView* view, uint32_t samplesPerFrame);
     void setSvgfParams(const mpt_svgf_params& p) { svgf_ = p; }
     void readSvgf(std::vector<float>& rgba);                                            // the filtered frame: rgb, a = the history length
+    // mpt_display + mpt_read_display of p.source as given (MPT_DISPLAY_SUM with samples = 0: the samples added since the sum was last
+    // cleared); rgba8 = the W*H*4 finished bytes
+    mpt_display_info display(const mpt_display_params& p, std::vector<uint8_t>& rgba8);
 
 private:
     void check(int status, const char* where);

@@ -314,6 +314,15 @@ int mpt_renderer_read_svgf(mpt_renderer* r, float* rgba) {
     if (!r || !rgba) return MPT_ERR_INVALID_ARG;
     return mpt_read_svgf(r->r->context(), rgba);
 }
+int mpt_renderer_display(mpt_renderer* r, const mpt_display_params* p, uint8_t* rgba8, mpt_display_info* out) {
+    if (!r || !p || !rgba8) return MPT_ERR_INVALID_ARG;
+    std::vector<uint8_t> img;
+    GUARD({
+        const mpt_display_info info = r->r->display(*p, img);
+        std::memcpy(rgba8, img.data(), img.size());
+        if (out) *out = info;
+    });
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;
@@ -352,6 +361,21 @@ int mpt_write_ppm(const char* path, const float* rgba, uint32_t width, uint32_t 
                 v = std::pow(v, inv);
                 row[3 * x + c] = static_cast<unsigned char>(v * 255.0f + 0.5f);
             }
+        std::fwrite(row.data(), 1, row.size(), f);
+    }
+    std::fclose(f);
+    return MPT_OK;
+}
+int mpt_write_ppm8(const char* path, const uint8_t* rgba8, uint32_t width, uint32_t height) {
+    if (!path || !rgba8 || !width || !height) return MPT_ERR_INVALID_ARG;
+    FILE* f = std::fopen(path, "wb");
+    if (!f) return MPT_ERR_INVALID_ARG;
+    std::fprintf(f, "P6\n%u %u\n255\n", width, height);
+    std::vector<unsigned char> row(static_cast<size_t>(width) * 3);
+    for (uint32_t y = 0; y < height; ++y) {
+        const uint8_t* src = rgba8 + 4 * static_cast<size_t>(y) * width;
+        for (uint32_t x = 0; x < width; ++x)
+            for (int c = 0; c < 3; ++c) row[3 * x + c] = src[4 * x + c];
         std::fwrite(row.data(), 1, row.size(), f);
     }
     std::fclose(f);

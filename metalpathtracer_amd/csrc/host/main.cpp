@@ -1,6 +1,7 @@
 // main.cpp — mpt_render: headless command-line front end of the host Renderer.
 // (The reference's main.cpp starts an NSApplication + MTKView, R/main.cpp:15-28; that shell is out of scope.)
 #include <cctype>
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +46,17 @@ static void usage() {
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
         "           [--svgf [--svgf-iterations N] [--temporal-history N] [--temporal-spp K]]\n"
+        "           [--tonemap clamp|reinhard|aces] [--transfer srgb|gamma22|linear] [--exposure EV] [--white W]\n"
+        "           [--auto-exposure [--key K] [--percentile P] [--adaptation A]]\n"
+        "  --tonemap, --transfer, --exposure, --white, --auto-exposure\n"
+        "                    any of them: every .ppm written (--out and the frames of --camera-path) is made on the device by\n"
+        "                    mpt_display (include/mpt.h) — exposure 2^EV (times the histogram's scale with --auto-exposure: the\n"
+        "                    --percentile P luminance, default 50, goes to --key K, default 0.18, smoothed over the frames of a\n"
+        "                    camera path by --adaptation A in (0, 1)), the tone curve (default clamp; reinhard with white point\n"
+        "                    --white W, default 4; aces) and the transfer function (default srgb) — from what the mode in effect\n"
+        "                    produces: the sum, the denoised, adaptive, temporal or SVGF result, the frame protocol's target, with\n"
+        "                    --gpus N the root's reduced sum; only W*H*4 bytes come back.  The JSON line of a camera-path frame gains\n"
+        "                    \"scale\", \"key_bin\" and \"clipped\".  Not with a .pfm --out.  Without them nothing changes\n"
         "  --svgf            with --camera-path: as --temporal, but what is accumulated is the illumination (the colour divided by the\n"
         "                    first hit's albedo) with the moments of its luminance, and every frame written is that history through\n"
         "                    --svgf-iterations a-trous levels (default 2) whose luminance stop is each pixel's own variance\n"
@@ -126,11 +138,37 @@ static bool applyInputLine(const std::string& line, int* repeat) {
     return true;
 }
 
+// The display flags (--tonemap ...): a .ppm is written from mpt_display's bytes instead of the float read-back.
+struct DisplayOut {
+    mpt_display_params params;      // tone, transfer, exposure ...: source and samples are set per call
+    std::vector<uint8_t> rgba8;     // the last frame presented
+    mpt_display_info info = {};
+};
+static void present(Renderer& r, DisplayOut& d, int source, uint32_t samples = 0) {
+    mpt_display_params q = d.params;
+    q.source = source;
+    q.samples = samples;
+    d.info = r.display(q, d.rgba8);
+}
+// mpt_denoise / mpt_denoise_temporal without the read-back: the result stays on the device for MPT_DISPLAY_DENOISED
+static void denoiseOnDevice(Renderer& r, const mpt_denoise_params& dn, int source, uint32_t samples, bool temporal = false) {
+    mpt_denoise_params q = dn;
+    q.source = source;
+    q.samples = samples;
+    const int rc = temporal ? mpt_denoise_temporal(r.context(), &q) : mpt_denoise(r.context(), &q);
+    if (rc) throw std::runtime_error(std::string("denoise: ") + mpt_status_string(rc) + ": " + mpt_last_error(r.context()));
+}
+static double msSince(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 // Replays a camera path: one draw() per frame with that frame's inputs, every frame written to outDir.  Returns the
 // number of frames, -1 on error.  Prints one JSON line per frame (camera, frameCount) for checking against the reference's
 // protocol (a camera change resets the accumulation and reseeds, R/Renderer/Renderer.cpp:255-257).
 static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& path, const std::string& outDir,
-                          const mpt_denoise_params* dn, uint32_t temporalSpp = 0, bool svgf = false) {
+                          const mpt_denoise_params* dn, uint32_t temporalSpp = 0, bool svgf = false, DisplayOut* dp = nullptr) {
+    const char* ft = std::getenv("MPT_FRAME_TIMES");   // 1: the JSON line gains the host's milliseconds around render / read-back / file write
+    const bool frameTimes = ft && std::atoi(ft);
     FILE* f = std::fopen(path.c_str(), "r");
     if (!f) {
         std::fprintf(stderr, "cannot open camera path %s\n", path.c_str());
@@ -154,29 +192,53 @@ static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& p
             }
             n = repeat;
             mpt_temporal_info ti = {};
+            auto t0 = std::chrono::steady_clock::now();
+            double renderMs = 0.0;
             if (temporalSpp && svgf) {   // --svgf: the frame is the variance-filtered history
                 const mpt_svgf_info si = r.drawSvgf(&view, temporalSpp);
                 ti.pixels_reprojected = si.pixels_reprojected;
                 ti.pixels_reset = si.pixels_reset;
-                r.readSvgf(view.rgba);
+                renderMs = msSince(t0);
+                if (dp) present(r, *dp, MPT_DISPLAY_SVGF);
+                else r.readSvgf(view.rgba);
             } else if (temporalSpp) {   // --temporal: the frame is the history (or the filtered history)
                 ti = r.drawTemporal(&view, temporalSpp);
-                if (dn) r.denoiseTemporal(*dn, view.rgba);
+                if (dn && dp) denoiseOnDevice(r, *dn, MPT_DENOISE_SUM, 0, true);
+                renderMs = msSince(t0);
+                if (dp) present(r, *dp, dn ? MPT_DISPLAY_DENOISED : MPT_DISPLAY_TEMPORAL);
+                else if (dn) r.denoiseTemporal(*dn, view.rgba);
                 else r.readTemporal(view.rgba);
             } else {
                 r.draw(&view);
-                r.readFrame(&view);
-                if (dn) r.denoise(*dn, view.rgba);
+                if (dn && dp) denoiseOnDevice(r, *dn, MPT_DENOISE_FRAME, 0);
+                renderMs = msSince(t0);
+                if (dp) {
+                    present(r, *dp, dn ? MPT_DISPLAY_DENOISED : MPT_DISPLAY_FRAME);
+                } else {
+                    r.readFrame(&view);
+                    if (dn) r.denoise(*dn, view.rgba);
+                }
             }
+            const double readMs = msSince(t0) - renderMs;   // the float read-back, or mpt_display + its W*H*4 bytes
             const mpt_uniforms& u = r.uniforms();
             char name[64];
             std::snprintf(name, sizeof name, "/frame_%04d.ppm", frame);
-            if (mpt_write_ppm((outDir + name).c_str(), view.rgba.data(), (int)view.width, (int)view.height, 1.0f, 2.2f))
+            if (dp ? mpt_write_ppm8((outDir + name).c_str(), dp->rgba8.data(), view.width, view.height)
+                   : mpt_write_ppm((outDir + name).c_str(), view.rgba.data(), (int)view.width, (int)view.height, 1.0f, 2.2f))
                 std::fprintf(stderr, "cannot write %s%s\n", outDir.c_str(), name);
-            char temporalJson[96] = "";
+            const double writeMs = msSince(t0) - renderMs - readMs;   // without the display flags: the conversion and the file
+            char temporalJson[320] = "";
+            size_t tj = 0;
             if (temporalSpp)
-                std::snprintf(temporalJson, sizeof temporalJson, ", \"reprojected\": %llu, \"reset\": %llu", (unsigned long long)ti.pixels_reprojected,
-                              (unsigned long long)ti.pixels_reset);
+                tj += std::snprintf(temporalJson + tj, sizeof temporalJson - tj, ", \"reprojected\": %llu, \"reset\": %llu",
+                                    (unsigned long long)ti.pixels_reprojected, (unsigned long long)ti.pixels_reset);
+            if (dp)
+                tj += std::snprintf(temporalJson + tj, sizeof temporalJson - tj, ", \"scale\": %.9g, \"key_bin\": %lld, \"clipped\": %llu",
+                                    dp->info.scale, dp->info.key_bin == 0xFFFFFFFFu ? -1ll : (long long)dp->info.key_bin,
+                                    (unsigned long long)dp->info.pixels_clipped);
+            if (frameTimes)
+                tj += std::snprintf(temporalJson + tj, sizeof temporalJson - tj, ", \"ms\": {\"render\": %.3f, \"read\": %.3f, \"write\": %.3f}",
+                                    renderMs, readMs, writeMs);
             std::printf("{\"frame\": %d, \"frameCount\": %llu, \"camera\": [%.9g, %.9g, %.9g], \"forward\": [%.9g, %.9g, %.9g], \"vfov\": %.9g%s}\n",
                         frame, (unsigned long long)u.frameCount, u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2],
                         Camera::forward.x, Camera::forward.y, Camera::forward.z, Camera::verticalFov, temporalJson);
@@ -191,7 +253,7 @@ static int playCameraPath(Renderer& r, OffscreenView& view, const std::string& p
 // scene, renders its interleaved tile shard asynchronously, and ONE ncclReduce(sum) lands the HDR sum on the first GPU.
 static int renderOnSeveralGpus(const std::string& scene, const std::string& assetRoot, const std::string& out, int width, int height,
                                int spp, const std::vector<int>& devices, int bvh, mpt_render_params prm, const float* camPos, const float* camDir,
-                               const float* camUp, float vfov, const mpt_denoise_params* dn) {
+                               const float* camUp, float vfov, const mpt_denoise_params* dn, DisplayOut* dp) {
     std::vector<std::unique_ptr<Renderer>> rs;
     mpt_comm* comm = nullptr;
     const int gpus = static_cast<int>(devices.size());
@@ -233,7 +295,11 @@ static int renderOnSeveralGpus(const std::string& scene, const std::string& asse
         }
         std::printf("{\"gpus\": %d, \"paths\": %llu, \"rays\": %llu, \"seconds\": %.6f, \"mrays_per_s\": %.1f}\n", gpus, paths, rays, sec,
                     sec > 0 ? rays / sec / 1e6 : 0.0);
-        if (!out.empty()) {
+        if (!out.empty() && dp) {   // exposure, tone curve and encoding on the root too, over the reduced sum (or its denoised mean)
+            if (dn) denoiseOnDevice(*rs[0], *dn, MPT_DENOISE_SUM, (uint32_t)spp);
+            present(*rs[0], *dp, dn ? MPT_DISPLAY_DENOISED : MPT_DISPLAY_SUM, (uint32_t)spp);
+            if (mpt_write_ppm8(out.c_str(), dp->rgba8.data(), width, height)) throw std::runtime_error("cannot write " + out);
+        } else if (!out.empty()) {
             std::vector<float> img;
             float scale = 1.0f / (float)spp;
             if (dn) {   // the guide pass and the filter run on the root, over the reduced sum
@@ -283,6 +349,9 @@ int main(int argc, char** argv) {
     bool adaptive = false;
     mpt_adaptive_params adp;
     std::memset(&adp, 0, sizeof adp);   // (0 = the defaults of include/mpt.h)
+    bool display = false;   // a display flag was given: .ppm files come from mpt_display
+    DisplayOut shown;
+    std::memset(&shown.params, 0, sizeof shown.params);   // (clamp, srgb, and 0 = the defaults of include/mpt.h)
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -333,6 +402,34 @@ int main(int argc, char** argv) {
         }
         else if (a == "--temporal-history") tpp.max_history = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--temporal-spp") temporalSpp = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
+        else if (a == "--tonemap" || a == "--transfer") {
+            static const char* const names[2][3] = {{"clamp", "reinhard", "aces"}, {"srgb", "gamma22", "linear"}};
+            const int which = a == "--transfer";
+            const char* v = next();
+            int k = 0;
+            while (k < 3 && std::strcmp(v, names[which][k]) != 0) ++k;
+            if (k == 3) {
+                usage();
+                return 2;
+            }
+            (which ? shown.params.transfer : shown.params.tone) = k;
+            display = true;
+        }
+        else if (a == "--exposure") {
+            shown.params.exposure = exp2f(static_cast<float>(std::atof(next())));
+            display = true;
+        }
+        else if (a == "--white") {
+            shown.params.white = static_cast<float>(std::atof(next()));
+            display = true;
+        }
+        else if (a == "--auto-exposure") {
+            shown.params.auto_exposure = 1;
+            display = true;
+        }
+        else if (a == "--key") shown.params.key = static_cast<float>(std::atof(next()));
+        else if (a == "--percentile") shown.params.percentile = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
+        else if (a == "--adaptation") shown.params.adaptation = static_cast<float>(std::atof(next()));
         else if (a == "--adaptive-min") adp.min_samples = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--adaptive-batch") adp.batch_samples = static_cast<uint32_t>(std::strtoul(next(), nullptr, 10));
         else if (a == "--adaptive-floor") adp.luminance_floor = static_cast<float>(std::atof(next()));
@@ -378,6 +475,15 @@ int main(int argc, char** argv) {
     prm.seed_lo = seed;
     if (bvh < 0) bvh = prm.rng_mode == MPT_RNG_LITERAL || frames > 0 || !cameraPath.empty() ? Renderer::BUILD_REFERENCE : Renderer::BUILD_AUTO;
     if (!deviceList.empty()) gpus = static_cast<int>(deviceList.size());
+    const bool outPpm = out.size() > 4 && out.substr(out.size() - 4) == ".ppm";
+    if (display && !out.empty() && !outPpm) {
+        std::fprintf(stderr, "mpt_render: the display flags (--tonemap, --transfer, --exposure, --white, --auto-exposure) need a .ppm --out\n");
+        return 2;
+    }
+    if (!display && (shown.params.key != 0.0f || shown.params.percentile != 0u || shown.params.adaptation != 0.0f)) {
+        std::fprintf(stderr, "mpt_render: --key, --percentile and --adaptation go with --auto-exposure\n");
+        return 2;
+    }
     if (adaptive) {
         const char* why = frames > 0 ? "--frames" : !cameraPath.empty() ? "--camera-path" : gpus > 1 ? "--gpus > 1"
                           : prm.rng_mode == MPT_RNG_LITERAL ? "--rng literal" : !checkpoint.empty() ? "--checkpoint"
@@ -414,7 +520,7 @@ int main(int argc, char** argv) {
         if (deviceList.empty())
             for (int g = 0; g < gpus; ++g) deviceList.push_back(device + g);
         return renderOnSeveralGpus(scene, assetRoot, out, width, height, spp, deviceList, bvh, prm, havePos ? camPos : nullptr, haveDir ? camDir : nullptr,
-                                   haveUp ? camUp : nullptr, vfov, denoise ? &dnp : nullptr);
+                                   haveUp ? camUp : nullptr, vfov, denoise ? &dnp : nullptr, display ? &shown : nullptr);
     }
     if (deviceList.size() == 1) device = deviceList[0];
     try {
@@ -433,7 +539,8 @@ int main(int argc, char** argv) {
         auto t0 = std::chrono::steady_clock::now();
         if (adaptive) {
             const mpt_adaptive_info info = r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);
-            r.readAdaptiveMean(img);
+            if (!display || denoise) r.readAdaptiveMean(img);
+            if (display && !denoise) present(r, shown, MPT_DISPLAY_ADAPTIVE);
             if (denoise) {   // the mean through the filter kernels, with the context's guides (mpt_read_aovs + mpt_denoise_image)
                 std::vector<float> ad(img.size()), nc(img.size()), dn(img.size());
                 mpt_ctx* ctx = r.context();
@@ -441,6 +548,11 @@ int main(int argc, char** argv) {
                 if (!rc) rc = mpt_denoise_image(ctx, width, height, img.data(), ad.data(), nc.data(), &dnp, dn.data());
                 if (rc) throw std::runtime_error(std::string("adaptive denoise: ") + mpt_status_string(rc) + ": " + mpt_last_error(ctx));
                 img.swap(dn);
+                if (display) {   // (that mean is on the host: the display kernels take it from there)
+                    shown.rgba8.resize(static_cast<size_t>(width) * height * 4);
+                    rc = mpt_display_image(ctx, width, height, img.data(), &shown.params, nullptr, shown.rgba8.data(), nullptr, &shown.info);
+                    if (rc) throw std::runtime_error(std::string("adaptive display: ") + mpt_status_string(rc) + ": " + mpt_last_error(ctx));
+                }
             }
             const double pixels = static_cast<double>(width) * height;
             char buf[256];
@@ -455,10 +567,13 @@ int main(int argc, char** argv) {
                 mpt_svgf_params sp = {0, 0, tpp.max_history, 0.0f, 0.0f, 0.0f, haveSvgfIterations ? svgfIterations : -1, 0.0f, 0.0f, 0.0f, -1};
                 r.setSvgfParams(sp);
             }
-            const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr, temporal || svgf ? temporalSpp : 0u, svgf);
+            const int n = playCameraPath(r, view, cameraPath, outDir, denoise ? &dnp : nullptr, temporal || svgf ? temporalSpp : 0u, svgf,
+                                         display ? &shown : nullptr);
             if (n < 0) return 1;
             frames = n;
-            if (svgf) {   // --out gets what the last frame got
+            if (display) {
+                // --out gets what the last frame got: its bytes, which `shown` still holds
+            } else if (svgf) {   // --out gets what the last frame got
                 r.readSvgf(view.rgba);
                 img = view.rgba;
             } else if (temporal) {   // --out gets what the last frame got: the history, or the filtered history
@@ -472,9 +587,14 @@ int main(int argc, char** argv) {
             }
         } else if (frames > 0) {
             for (int f = 0; f < frames; ++f) r.draw(&view);
-            r.readFrame(&view);
-            img = view.rgba;
-            if (denoise) r.denoise(dnp, img);
+            if (display) {
+                if (denoise) denoiseOnDevice(r, dnp, MPT_DENOISE_FRAME, 0);
+                present(r, shown, denoise ? MPT_DISPLAY_DENOISED : MPT_DISPLAY_FRAME);
+            } else {
+                r.readFrame(&view);
+                img = view.rgba;
+                if (denoise) r.denoise(dnp, img);
+            }
         } else {
             // checkpoint / resume of the accumulation (the reference's running mean lives in a GPU-private texture and is lost with the
             // process, R/Renderer/Renderer.cpp:236): header "MPTSUM2 W H samples seed rng depth bsdf scene-hash\n" + W * H * 4 raw floats.
@@ -504,7 +624,7 @@ int main(int argc, char** argv) {
                 r.writeSum(sum);
             }
             r.renderBatch(have, static_cast<uint32_t>(spp));
-            r.readSum(img);
+            if (!display || !checkpoint.empty()) r.readSum(img);
             if (!checkpoint.empty()) {
                 const std::string tmp = checkpoint + ".tmp";
                 FILE* f = std::fopen(tmp.c_str(), "wb");
@@ -518,7 +638,10 @@ int main(int argc, char** argv) {
                 }
             }
             scale = 1.0f / static_cast<float>(have + static_cast<uint32_t>(spp));
-            if (denoise) {   // the checkpoint above keeps the raw sum; the image is the denoised sum / samples
+            if (display) {
+                if (denoise) denoiseOnDevice(r, dnp, MPT_DENOISE_SUM, have + static_cast<uint32_t>(spp));
+                present(r, shown, denoise ? MPT_DISPLAY_DENOISED : MPT_DISPLAY_SUM, have + static_cast<uint32_t>(spp));
+            } else if (denoise) {   // the checkpoint above keeps the raw sum; the image is the denoised sum / samples
                 mpt_denoise_params q = dnp;
                 q.samples = have + static_cast<uint32_t>(spp);
                 r.denoise(q, img);
@@ -531,9 +654,10 @@ int main(int argc, char** argv) {
                     (unsigned long long)st.paths, (unsigned long long)st.rays, sec, st.total_ms,
                     st.total_ms > 0 ? st.rays / st.total_ms / 1e3 : 0.0, adaptiveJson.c_str());
         if (!out.empty()) {
-            bool ppm = out.size() > 4 && out.substr(out.size() - 4) == ".ppm";
-            int rc = ppm ? mpt_write_ppm(out.c_str(), img.data(), width, height, scale, 2.2f)
-                         : mpt_write_pfm(out.c_str(), img.data(), width, height, scale);
+            int rc = display && shown.rgba8.empty() ? MPT_ERR_NOT_READY   // (a camera path without a frame)
+                     : display ? mpt_write_ppm8(out.c_str(), shown.rgba8.data(), width, height)
+                     : outPpm  ? mpt_write_ppm(out.c_str(), img.data(), width, height, scale, 2.2f)
+                               : mpt_write_pfm(out.c_str(), img.data(), width, height, scale);
             if (rc) {
                 std::fprintf(stderr, "cannot write %s\n", out.c_str());
                 return 1;

@@ -38,6 +38,7 @@
 #include "mpt_temporal.h"
 #include "mpt_svgf.h"
 #include "mpt_adaptive.h"
+#include "mpt_display.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -201,6 +202,19 @@ struct SvgfState {
     float cam[14] = {};
 };
 
+// The display stage (mpt_display.h): the RGBA8 frame, the luminance histogram of the last call with auto_exposure, the result block
+// (DpState: the mpt_display_info of the last call and the auto scale kept for the next one) and the three threshold tables.
+// Allocated by the first mpt_display; valid while `epoch` is the context's guide_epoch, as TemporalState; mpt_resize lets go of it.
+struct DisplayState {
+    DevMem<uint32_t> out;          // W * H words: r | g << 8 | b << 16 | 255 << 24
+    DevMem<uint32_t> hist;         // MPT_DP_BINS counts
+    DevMem<DpState> st;
+    DevMem<float> tables;          // MPT_DISPLAY_TABLE
+    uint32_t W = 0, H = 0;
+    uint64_t epoch = 0;            // the guide_epoch the buffers were made in (0 = none)
+    bool shown = false;            // `out` holds a frame
+};
+
 struct mpt_ctx : SceneState {
     int device = 0;
     std::unique_ptr<Submitter> sub;      // mpt_render_async's submit thread (none until the first asynchronous render)
@@ -294,6 +308,9 @@ struct mpt_ctx : SceneState {
     AdaptiveTiles ad;
     TemporalState tp;
     SvgfState sv;
+    DisplayState dp;
+    int dp_px = 4;                  // MPT_DISPLAY_PX: pixels per thread of k_dp_present, 1 or 4 (the same bytes)
+    bool dp_hist_agg = true;        // MPT_DISPLAY_HIST=plain: k_dp_histogram without the aggregation within the wave
 };
 
 // kernel variants: COUNT (work counters) x ALL_LDS (the whole BVH fits the LDS budget)
@@ -391,6 +408,8 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     if ((e = getenv("MPT_LDS_BYTES"))) ctx->lds_budget = (size_t)atol(e);
     ctx->time_kernels = !((e = getenv("MPT_NO_KERNEL_EVENTS")) && atoi(e));
     if ((e = getenv("MPT_WL_BLOCK")) && atoi(e) >= 64) ctx->wl_block = (uint32_t)atoi(e) & ~63u;
+    if ((e = getenv("MPT_DISPLAY_PX")) && (atoi(e) == 1 || atoi(e) == 4)) ctx->dp_px = atoi(e);
+    if ((e = getenv("MPT_DISPLAY_HIST"))) ctx->dp_hist_agg = strcmp(e, "plain") != 0;
     if ((e = getenv("MPT_BUDGETS"))) {  // e.g. "8,20,50,125": box-test trips per step of ring 0, 1, ... (the last ring has none)
         unsigned prev = 4;
         const char* q = e;
@@ -924,6 +943,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->ad = AdaptiveTiles{};
     ctx->tp = TemporalState{};
     ctx->sv = SvgfState{};
+    ctx->dp = DisplayState{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;
@@ -2864,6 +2884,201 @@ extern "C" int mpt_svgf_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float*
         return svgf_image_impl(ctx, w, h, color, albedo_depth_cur, normal_class_cur, cam_cur, history_prev, moments_prev, albedo_depth_prev,
                                normal_class_prev, cam_prev, p, history_out, moments_variance_out, filtered_out, out);
     });
+}
+
+// ---- display (mpt_display.h; the specification is in include/mpt.h) --------------------------------------------------------------
+static_assert(sizeof(mpt_display_info) == 32 && offsetof(DpState, kept) == 32, "DpState begins with mpt_display_info");
+struct DpResolved {
+    DpExposure E;
+    float ww;   // REINHARD's white * white
+};
+static int dp_resolve(mpt_ctx* ctx, const mpt_display_params* p, bool use_source, DpResolved& r) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null display params");
+    if (use_source) {
+        if (p->source < MPT_DISPLAY_SUM || p->source > MPT_DISPLAY_ADAPTIVE) return fail(ctx, MPT_ERR_INVALID_ARG, "bad display source");
+        if (p->source == MPT_DISPLAY_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "display of the sum with samples = 0");
+    }
+    if (p->tone < MPT_TONE_CLAMP || p->tone > MPT_TONE_ACES) return fail(ctx, MPT_ERR_INVALID_ARG, "bad tone curve");
+    if (p->transfer < MPT_TRANSFER_SRGB || p->transfer > MPT_TRANSFER_LINEAR) return fail(ctx, MPT_ERR_INVALID_ARG, "bad transfer function");
+    if (p->percentile > 100u) return fail(ctx, MPT_ERR_INVALID_ARG, "display percentile above 100");
+    if (p->exposure != p->exposure || p->white != p->white || p->key != p->key || p->adaptation != p->adaptation)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "a display parameter is NaN");
+    const float white = p->white > 0.0f ? p->white : 4.0f;
+    r.ww = white * white;
+    r.E.exposure = p->exposure > 0.0f ? p->exposure : 1.0f;
+    r.E.key = p->key > 0.0f ? p->key : 0.18f;
+    r.E.adaptation = p->adaptation > 0.0f && p->adaptation < 1.0f ? p->adaptation : 0.0f;
+    r.E.percentile = p->percentile ? p->percentile : 50u;
+    r.E.auto_exposure = p->auto_exposure != 0;
+    return MPT_OK;
+}
+// histogram (auto-exposure only) -> exposure -> present, back to back on the context's stream; the host reads the 32-byte result once
+static int dp_run(mpt_ctx* ctx, DpSource S, int src_kind, const mpt_display_params* p, const DpResolved& r, uint32_t* hist, DpState* st,
+                  const float* tables, uint32_t* out_words, mpt_display_info* info) {
+    if (r.E.auto_exposure) {
+        HIPCHK(hipMemsetAsync(hist, 0, MPT_DP_BINS * 4, ctx->stream));
+        const uint32_t blocks = std::min<uint32_t>((S.n + 255u) / 256u, (uint32_t)std::max(1, ctx->prop.multiProcessorCount) * 8u);
+        void* args[] = {&S, &hist};
+        HIPCHK(hipLaunchKernel(dp_histogram_kernel(src_kind, ctx->dp_hist_agg), dim3(blocks), dim3(256), args, 0, ctx->stream));
+    }
+    DpExposure E = r.E;
+    hipLaunchKernelGGL(k_dp_exposure, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)hist, E, st);
+    HIPCHK(hipGetLastError());
+    DpTone P = {tables + (size_t)p->transfer * 255, r.ww};
+    const uint32_t per_block = 256u * (uint32_t)ctx->dp_px;
+    void* args[] = {&S, &P, &st, &out_words};
+    HIPCHK(hipLaunchKernel(dp_present_kernel(src_kind, p->tone, ctx->dp_px), dim3((S.n + per_block - 1u) / per_block), dim3(256), args, 0, ctx->stream));
+    mpt_display_info got = {};
+    HIPCHK(hipMemcpyAsync(&got, st, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (info) *info = got;
+    return MPT_OK;
+}
+static bool dp_have_state(const mpt_ctx* ctx) {
+    return ctx->dp.epoch != 0 && ctx->dp.epoch == ctx->guide_epoch && ctx->dp.W == ctx->W && ctx->dp.H == ctx->H && ctx->dp.out;
+}
+static int dp_upload_tables(mpt_ctx* ctx, DevMem<float>& tables) {
+    HIPCHK(tables.alloc(sizeof MPT_DISPLAY_TABLE));
+    HIPCHK(hipMemcpy(tables.get(), MPT_DISPLAY_TABLE, sizeof MPT_DISPLAY_TABLE, hipMemcpyHostToDevice));
+    return MPT_OK;
+}
+static int display_impl(mpt_ctx* ctx, const mpt_display_params* p, mpt_display_info* out) {
+    if (!ctx) return MPT_ERR_INVALID_ARG;
+    DpResolved r;
+    int rc = dp_resolve(ctx, p, true, r);
+    if (rc) return rc;
+    if (!ctx->d_sum) return fail(ctx, MPT_ERR_NOT_READY, "mpt_resize not called");
+    if (p->source == MPT_DISPLAY_DENOISED && !ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
+    if (p->source == MPT_DISPLAY_TEMPORAL && !tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
+    if (p->source == MPT_DISPLAY_SVGF && !sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
+    if (p->source == MPT_DISPLAY_ADAPTIVE && !ctx->ad.tile_count) return fail(ctx, MPT_ERR_NOT_READY, "no adaptive render at this size");
+    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint32_t n = ctx->W * ctx->H;
+    if (!dp_have_state(ctx)) {   // the first call, or the first after a scene call: the buffers are made whole before they replace the old ones
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        DisplayState d;
+        HIPCHK(d.out.alloc(((size_t)n * 4 + 15) & ~(size_t)15));
+        HIPCHK(d.hist.alloc(MPT_DP_BINS * 4));
+        HIPCHK(d.st.alloc(sizeof(DpState)));
+        HIPCHK(hipMemset(d.hist.get(), 0, MPT_DP_BINS * 4));
+        HIPCHK(hipMemset(d.st.get(), 0, sizeof(DpState)));
+        if ((rc = dp_upload_tables(ctx, d.tables))) return rc;
+        d.W = ctx->W;
+        d.H = ctx->H;
+        d.epoch = ctx->guide_epoch;
+        ctx->dp = std::move(d);
+    }
+    DisplayState& dp = ctx->dp;
+    DpSource S = {};
+    S.n = n;
+    S.W = ctx->W;
+    S.tiles_x = (ctx->W + 7) / 8;
+    S.samples = 1.0f;
+    int kind = MPT_DP_SRC_RAW;
+    switch (p->source) {
+    case MPT_DISPLAY_SUM:
+        S.color = ctx->d_sum;
+        S.samples = (float)p->samples;
+        kind = MPT_DP_SRC_DIV;
+        break;
+    case MPT_DISPLAY_FRAME: S.color = ctx->d_accum[ctx->cur_target].get(); break;
+    case MPT_DISPLAY_DENOISED: S.color = ctx->d_denoised.get(); break;
+    case MPT_DISPLAY_TEMPORAL: S.color = ctx->tp.hist[ctx->tp.cur].get(); break;
+    case MPT_DISPLAY_SVGF: S.color = ctx->sv.out.get(); break;
+    default:
+        S.color = ctx->d_sum;
+        S.tile_count = ctx->ad.tile_count.get();
+        kind = MPT_DP_SRC_TILE;
+        break;
+    }
+    dp.shown = false;
+    if ((rc = dp_run(ctx, S, kind, p, r, dp.hist.get(), dp.st.get(), dp.tables.get(), dp.out.get(), out))) return rc;
+    dp.shown = true;
+    return MPT_OK;
+}
+static int display_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const mpt_display_params* p, const float* prev_auto_scale,
+                              uint8_t* rgba8_out, uint32_t* histogram_out, mpt_display_info* out) {
+    if (!ctx || !color || !rgba8_out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    DpResolved r;
+    int rc = dp_resolve(ctx, p, false, r);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const uint32_t n = W * H;
+    DevMem<float4> d_c;
+    DevMem<uint32_t> d_o, d_h;
+    DevMem<DpState> d_st;
+    DevMem<float> d_t;
+    HIPCHK(d_c.alloc((size_t)n * 16));
+    HIPCHK(d_o.alloc(((size_t)n * 4 + 15) & ~(size_t)15));
+    HIPCHK(d_h.alloc(MPT_DP_BINS * 4));
+    HIPCHK(d_st.alloc(sizeof(DpState)));
+    if ((rc = dp_upload_tables(ctx, d_t))) return rc;
+    DpState st0 = {};
+    if (prev_auto_scale) {
+        st0.kept = *prev_auto_scale;
+        st0.have_kept = 1;
+    }
+    HIPCHK(hipMemcpyAsync(d_c.get(), color, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_st.get(), &st0, sizeof st0, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemsetAsync(d_h.get(), 0, MPT_DP_BINS * 4, ctx->stream));
+    DpSource S = {};
+    S.color = d_c.get();
+    S.n = n;
+    S.W = W;
+    S.tiles_x = (W + 7) / 8;
+    S.samples = 1.0f;
+    if ((rc = dp_run(ctx, S, MPT_DP_SRC_RAW, p, r, d_h.get(), d_st.get(), d_t.get(), d_o.get(), out))) return rc;
+    HIPCHK(hipMemcpyAsync(rgba8_out, d_o.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (histogram_out) HIPCHK(hipMemcpyAsync(histogram_out, d_h.get(), MPT_DP_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+extern "C" int mpt_display(mpt_ctx* ctx, const mpt_display_params* p, mpt_display_info* out) {
+    return guarded(ctx, [&] { return display_impl(ctx, p, out); });
+}
+extern "C" int mpt_read_display(mpt_ctx* ctx, uint8_t* rgba8) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx || !rgba8) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+        if (!dp_have_state(ctx) || !ctx->dp.shown) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_display result");
+        HIPCHK(hipMemcpyAsync(rgba8, ctx->dp.out.get(), (size_t)ctx->W * ctx->H * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_display_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
+    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
+    if (!dp_have_state(ctx) || !ctx->dp.shown) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_display result");
+    *p = ctx->dp.out.get();
+    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 4;
+    return MPT_OK;
+}
+extern "C" int mpt_read_display_histogram(mpt_ctx* ctx, uint32_t out[256]) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx || !out) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+        if (!dp_have_state(ctx) || !ctx->dp.shown) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_display result");
+        HIPCHK(hipMemcpyAsync(out, ctx->dp.hist.get(), MPT_DP_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_display_reset(mpt_ctx* ctx) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx) return MPT_ERR_INVALID_ARG;
+        if (!dp_have_state(ctx)) return MPT_OK;   // (nothing kept)
+        HIPCHK(hipMemsetAsync((char*)ctx->dp.st.get() + offsetof(DpState, kept), 0, sizeof(DpState) - offsetof(DpState, kept), ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_display_table(int transfer, float out[255]) {
+    if (!out || transfer < MPT_TRANSFER_SRGB || transfer > MPT_TRANSFER_LINEAR) return MPT_ERR_INVALID_ARG;
+    memcpy(out, MPT_DISPLAY_TABLE[transfer], sizeof MPT_DISPLAY_TABLE[transfer]);
+    return MPT_OK;
+}
+extern "C" int mpt_display_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const mpt_display_params* p,
+                                 const float* prev_auto_scale, uint8_t* rgba8_out, uint32_t* histogram_out, mpt_display_info* out) {
+    return guarded(ctx, [&] { return display_image_impl(ctx, width, height, color, p, prev_auto_scale, rgba8_out, histogram_out, out); });
 }
 
 __global__ void k_digest(const uint32_t* w, uint64_t n_words, unsigned long long* out) {

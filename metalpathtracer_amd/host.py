@@ -25,7 +25,7 @@ SYMBOLS = (
     "mpt_renderer_uniforms", "mpt_renderer_stats", "mpt_renderer_context", "mpt_renderer_scene", "mpt_write_pfm",
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
-    "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf",
+    "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
 )
 
 _lib = None
@@ -80,6 +80,8 @@ def load():
     L.mpt_renderer_scene.restype = vp
     L.mpt_write_pfm.argtypes = [C.c_char_p, fp, C.c_uint32, C.c_uint32, C.c_float]
     L.mpt_write_ppm.argtypes = [C.c_char_p, fp, C.c_uint32, C.c_uint32, C.c_float, C.c_float]
+    L.mpt_renderer_display.argtypes = [vp, C.POINTER(capi.DisplayParams), C.POINTER(C.c_uint8), C.POINTER(capi.DisplayInfo)]
+    L.mpt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
     _lib = L
     return L
 
@@ -373,6 +375,16 @@ class Renderer:
         self._chk(self.L.mpt_renderer_read_svgf(self.h, _fp(out)), "readSvgf")
         return out
 
+    def display(self, **kw):
+        """mpt_renderer_display: mpt_display + mpt_read_display of `source` (DISPLAY_SUM with samples=0: all rendered since the last
+        clearSum()).  Returns (bytes [H, W, 4] uint8, the mpt_display_info as a dict)."""
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.uint8)
+        p = capi.display_params(**kw)
+        info = capi.DisplayInfo()
+        self._chk(self.L.mpt_renderer_display(self.h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)), "display")
+        return out, info.as_dict()
+
     def scene(self):
         return Scene(_borrowed=self.L.mpt_renderer_scene(self.h))
 
@@ -385,3 +397,9 @@ def write_pfm(path, rgba, scale=1.0):
 def write_ppm(path, rgba, scale=1.0, gamma=2.2):
     a = np.ascontiguousarray(rgba, np.float32)
     return load().mpt_write_ppm(path.encode(), _fp(a), a.shape[1], a.shape[0], float(scale), float(gamma))
+
+
+def write_ppm8(path, rgba8):
+    """mpt_write_ppm8: the r, g, b of finished bytes [H, W, 4] uint8 (Context.read_display) as a binary PPM; no arithmetic."""
+    a = np.ascontiguousarray(rgba8, np.uint8)
+    return load().mpt_write_ppm8(path.encode(), a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0])
