@@ -605,6 +605,72 @@ int mpt_display_table(int transfer, float out[255]);                   /* a pure
 int mpt_display_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const mpt_display_params* params,
                       const float* prev_auto_scale, uint8_t* rgba8_out, uint32_t* histogram_out, mpt_display_info* out);
 
+/* ---- shadow rays: occlusion queries and ambient occlusion ---------------------------------------------------------------------------
+ * No reference counterpart (every ray of the reference is a closest-hit ray, PathTracing.h:75-204).
+ *
+ * Any hit.  A ray (o, d) with the limit tmax is OCCLUDED iff the reference's walk, started with best t = tmax instead of +inf, accepts
+ * any primitive: the same slab test (tMin = 1e-4, tMax = best t), the same sphere and triangle tests, acceptance t > 1e-4 && t < best t.
+ * !(tmax > 1e-4) (a NaN included) and a direction with a NaN component are "not occluded"; tmax = +inf asks for any hit at all.
+ * With the same tree, "occluded" implies that mpt_trace_rays returns t < tmax, exactly.  The converse fails only for the reference's
+ * known artefact — a hit whose computed t lies in front of its own leaf's slab entry — when tmax falls between the two.
+ * MPT_WALK_REFERENCE walks the threaded reference-order tree, MPT_WALK_OWN the product's own 4-wide tree (children culled beyond
+ * tmax * (1 + 2^-10) + eps_abs, primitives tested with the reference's exact tests, no final check: for that artefact it answers by
+ * the primitive test alone); rays the closest-first walk hands to the reference-order walk for their direction or origin (flag 1), or
+ * whose stack overflows (flag 8), are answered by the reference-order walk.  OWN on a scene whose mpt_accel_info out[0] is 0 is
+ * REFERENCE; MPT_WALK_AUTO is OWN where mpt_accel_info out[7] is MPT_PIPE_ORDERED and REFERENCE elsewhere.
+ * mpt_trace_occluded is the sibling of mpt_trace_rays: host arrays, at most 2^22 rays per call, tmax per ray (NULL = +inf for all),
+ * occluded_out one byte per ray (0 / 1), flags_out (may be NULL) as mpt_trace_rays_ordered's (0 for every ray of the REFERENCE walk).
+ * MPT_ERR_INVALID_ARG for a null pointer, n_rays = 0 or a bad walk; MPT_ERR_NOT_READY without a scene.  Touches neither mpt_stats nor
+ * the sum.                                                                                                                          */
+enum { MPT_WALK_REFERENCE = 0, MPT_WALK_OWN = 1, MPT_WALK_AUTO = 2 };
+int mpt_trace_occluded(mpt_ctx* ctx, const float* origins, const float* directions, const float* tmax, uint64_t n_rays, int32_t walk,
+                       uint8_t* occluded_out, uint32_t* flags_out);
+
+/* Measurement hook: the closest-hit and the any-hit kernel of either tree on the SAME rays (uploaded once; at most 2^22), launched in
+ * turn — warmup untimed rounds, then reps (1..1000) rounds — with a pair of HIP events around every launch.  ms_out[4 * r + k], k = 0
+ * closest hit in reference order (what mpt_trace_rays launches), 1 any hit in reference order, 2 closest hit through the own tree (what
+ * mpt_trace_rays_ordered launches), 3 any hit through the own tree; 2 and 3 are 0 where mpt_accel_info out[0] is 0.  No result is returned. */
+int mpt_time_trace(mpt_ctx* ctx, const float* origins, const float* directions, const float* tmax, uint64_t n_rays, uint32_t warmup,
+                   uint32_t reps, double* ms_out);
+
+/* Ambient occlusion over the first-hit guide buffers (float32, one IEEE operation at a time, dot and normalize as the guide pass:
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, normalize(v) = v * (1 / sqrt(dot(v, v))); tests/ao_ref.py restates it in numpy).
+ * Every pixel of the (refreshed) guide buffers has a class, a ray-facing normal n and a hit distance t; dc is the pixel-centre direction
+ * of step 1 of mpt_temporal_accumulate.  Class 1 and 2: ao = 1, occluded = 0, no ray is traced.  Class 0:
+ *   P = cam + t * dc,  o = P + 0.0001f * n   (the origin the bounce ray leaves from)
+ *   for sample s in [sample_begin, sample_begin + sample_count):
+ *     r = philox4x32_10(counter = (py * W + px, s, 0xFFFFFFFE, 0), key = (seed_lo, seed_hi))   — word 2 = 0xFFFFFFFE is taken by no
+ *         bounce and not by the pixel jitter (0xFFFFFFFF)
+ *     uz = u01(r.x), uphi = u01(r.y), z = 2 uz - 1, (sn, cs) = sincos_2pi(uphi), rr = sqrt(1 - z * z)
+ *     dir = normalize(n + (rr * cs, rr * sn, z))       (the Lambert direction of PathTracing.h:252-254 as mpt_render draws it)
+ *     the sample is occluded iff any-hit(o, dir, radius > 0 ? radius : +inf)
+ *   occluded = the count, ao = (float)(N - count) / (float)N.
+ * One lane per (pixel, sample); a pixel's count is a ballot and a popcount over its lanes (no atomics), so the result does not depend on
+ * how lanes are mapped.  The pass waits for queued renders, refreshes the guides if stale and writes none of: the HDR sum, the frame
+ * targets, the moments, the denoised buffer, the temporal, SVGF and display state, mpt_stats.  Its result is dropped by mpt_resize,
+ * mpt_upload_scene and mpt_build_and_upload.
+ * MPT_ERR_INVALID_ARG, with nothing changed: null params, sample_count 0 or > MPT_AO_MAX_SAMPLES, a NaN radius, a bad walk.
+ * MPT_ERR_NOT_READY before scene, uniforms and size, and from mpt_read_ao / mpt_ao_buffer before the first pass.                      */
+#define MPT_AO_MAX_SAMPLES 1024u
+typedef struct mpt_ao_params {
+    uint32_t sample_begin, sample_count;   /* sample_count: 1..MPT_AO_MAX_SAMPLES                                                      */
+    float radius;                          /* <= 0: +inf                                                                               */
+    uint32_t seed_lo, seed_hi;
+    int32_t walk;                          /* MPT_WALK_*                                                                               */
+} mpt_ao_params;
+typedef struct mpt_ao_info {
+    uint64_t pixels_surface, rays, rays_occluded;
+    double device_ms;                      /* HIP-event time of the pass (a guide refresh not included)                                */
+} mpt_ao_info;
+int mpt_ambient_occlusion(mpt_ctx* ctx, const mpt_ao_params* params, mpt_ao_info* out /* may be NULL */);
+int mpt_read_ao(mpt_ctx* ctx, float* ao_host /* W*H */, uint32_t* occluded_host /* W*H, may be NULL */);
+int mpt_ao_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);    /* the W*H floats of ao                                        */
+/* The same kernel on caller guides (host arrays as mpt_read_aovs returns them; the unit-test hook: it needs a scene but no size and
+ * neither reads nor writes context state).  Of cam_uniforms only cameraPosition, viewportU, viewportV and firstPixelPosition are read.
+ * occluded_out may be NULL.                                                                                                          */
+int mpt_ao_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* albedo_depth, const float* normal_class,
+                 const mpt_uniforms* cam_uniforms, const mpt_ao_params* params, float* ao_out, uint32_t* occluded_out);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

@@ -97,6 +97,9 @@ int mpt_renderer_read_svgf(mpt_renderer* r, float* rgba);
 /* mpt_display + mpt_read_display (include/mpt.h) of params->source as given; for MPT_DISPLAY_SUM, params->samples = 0 means the
  * samples rendered since the sum was last cleared.  rgba8: W*H*4 bytes.  out may be NULL.                                        */
 int mpt_renderer_display(mpt_renderer* r, const mpt_display_params* params, uint8_t* rgba8, mpt_display_info* out);
+/* mpt_ambient_occlusion + mpt_read_ao (include/mpt.h) for the renderer's camera: `samples` shadow rays per surface pixel numbered from
+ * 0, keyed by the render parameters' seed, radius <= 0 = no limit, MPT_WALK_AUTO.  ao: W*H floats (1 = open).  out may be NULL.     */
+int mpt_renderer_ambient_occlusion(mpt_renderer* r, uint32_t samples, float radius, float* ao, mpt_ao_info* out);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 

@@ -36,6 +36,7 @@ SYMBOLS = (
     "mpt_svgf_accumulate", "mpt_read_svgf", "mpt_svgf_buffer", "mpt_read_svgf_state", "mpt_svgf_reset", "mpt_svgf_image",
     "mpt_display", "mpt_read_display", "mpt_display_buffer", "mpt_read_display_histogram", "mpt_display_reset", "mpt_display_table",
     "mpt_display_image",
+    "mpt_trace_occluded", "mpt_time_trace", "mpt_ambient_occlusion", "mpt_read_ao", "mpt_ao_buffer", "mpt_ao_image",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
@@ -55,6 +56,8 @@ TRANSFER_SRGB, TRANSFER_GAMMA22, TRANSFER_LINEAR = 0, 1, 2
 # include/mpt.h MPT_DISPLAY_DEFAULT_* (a value <= 0 / percentile 0 selects them; exposure <= 0 selects 1)
 DISPLAY_DEFAULTS = dict(white=4.0, percentile=50, key=0.18)
 DISPLAY_NO_BIN = 0xFFFFFFFF
+WALK_REFERENCE, WALK_OWN, WALK_AUTO = 0, 1, 2
+AO_MAX_SAMPLES = 1024
 
 
 class MptError(RuntimeError):
@@ -195,6 +198,23 @@ def display_params(source=DISPLAY_SUM, samples=0, tone=TONE_CLAMP, transfer=TRAN
                          int(percentile), float(key), float(adaptation))
 
 
+class AoParams(C.Structure):
+    _fields_ = [("sample_begin", C.c_uint32), ("sample_count", C.c_uint32), ("radius", C.c_float), ("seed_lo", C.c_uint32),
+                ("seed_hi", C.c_uint32), ("walk", C.c_int32)]
+
+
+class AoInfo(C.Structure):
+    _fields_ = [("pixels_surface", C.c_uint64), ("rays", C.c_uint64), ("rays_occluded", C.c_uint64), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def ao_params(samples=16, radius=0.0, sample_begin=0, seed=(0, 0), walk=WALK_AUTO):
+    """mpt_ao_params: `samples` rays per surface pixel, numbered from sample_begin; radius <= 0 means no limit."""
+    return AoParams(int(sample_begin), int(samples), float(radius), int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF, int(walk))
+
+
 def display_table(transfer):
     """mpt_display_table: the 255 float32 thresholds T[1..255] of a transfer function (index k - 1); needs no context."""
     out = np.empty(255, np.float32)
@@ -322,6 +342,12 @@ def load():
     L.mpt_display_reset.argtypes = [vp]
     L.mpt_display_table.argtypes = [C.c_int, fp]
     L.mpt_display_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, C.POINTER(DisplayParams), fp, u8p, up, C.POINTER(DisplayInfo)]
+    L.mpt_trace_occluded.argtypes = [vp, fp, fp, fp, C.c_uint64, C.c_int32, u8p, up]
+    L.mpt_time_trace.argtypes = [vp, fp, fp, fp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
+    L.mpt_ambient_occlusion.argtypes = [vp, C.POINTER(AoParams), C.POINTER(AoInfo)]
+    L.mpt_read_ao.argtypes = [vp, fp, up]
+    L.mpt_ao_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_ao_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(AoParams), fp, up]
     _lib = L
     return L
 
@@ -530,6 +556,63 @@ class Context:
         self._chk(self.L.mpt_trace_rays_ordered(self.h, _fp(o), _fp(d), n, _fp(t), _ip(prim), _fp(nrm), _ip(front),
                                                 _up(flags)), "mpt_trace_rays_ordered")
         return t, prim, nrm, front, flags
+
+    def trace_occluded(self, origins, directions, tmax=None, walk=WALK_AUTO):
+        """mpt_trace_occluded: is anything in the way before tmax (per ray; None = no limit)?  Returns (occluded [n] bool,
+        flags [n] uint32 as trace_rays_ordered's)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        t = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        occ = np.empty(n, np.uint8)
+        flags = np.empty(n, np.uint32)
+        self._chk(self.L.mpt_trace_occluded(self.h, _fp(o), _fp(d), None if t is None else _fp(t), n, int(walk),
+                                            occ.ctypes.data_as(C.POINTER(C.c_uint8)), _up(flags)), "mpt_trace_occluded")
+        return occ.astype(bool), flags
+
+    def time_trace(self, origins, directions, tmax=None, warmup=3, reps=20):
+        """mpt_time_trace: HIP-event ms per launch, [reps, 4] = (closest reference, any-hit reference, closest own, any-hit own)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        t = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        ms = np.zeros((int(reps), 4), np.float64)
+        self._chk(self.L.mpt_time_trace(self.h, _fp(o), _fp(d), None if t is None else _fp(t), n, int(warmup), int(reps),
+                                        ms.ctypes.data_as(C.POINTER(C.c_double))), "mpt_time_trace")
+        return ms
+
+    def ambient_occlusion(self, **kw):
+        """mpt_ambient_occlusion over the context's guide buffers (ao_params' keywords); returns the info dict."""
+        p = ao_params(**kw)
+        info = AoInfo()
+        self._chk(self.L.mpt_ambient_occlusion(self.h, C.byref(p), C.byref(info)), "mpt_ambient_occlusion")
+        return info.as_dict()
+
+    def read_ao(self):
+        """(ao [H,W] float32, occluded [H,W] uint32) of the last ambient_occlusion."""
+        ao = np.empty((self.height, self.width), np.float32)
+        occ = np.empty((self.height, self.width), np.uint32)
+        self._chk(self.L.mpt_read_ao(self.h, _fp(ao), _up(occ)), "mpt_read_ao")
+        return ao, occ
+
+    def ao_buffer(self):
+        """(device pointer, bytes) of the last ambient_occlusion's ao image (float32, W * H)."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_ao_buffer(self.h, C.byref(p), C.byref(n)), "mpt_ao_buffer")
+        return p.value, n.value
+
+    def ao_image(self, albedo_depth, normal_class, cam, **kw):
+        """The AO kernel on caller guides [H,W,4] with the camera of `cam` (Uniforms); needs a scene, touches no context state."""
+        ad = np.ascontiguousarray(albedo_depth, np.float32)
+        nc = np.ascontiguousarray(normal_class, np.float32)
+        if ad.ndim != 3 or ad.shape[2] != 4 or nc.shape != ad.shape:
+            raise ValueError("ao_image: albedo_depth and normal_class must be [H, W, 4] arrays of one shape")
+        H, W = ad.shape[:2]
+        ao = np.empty((H, W), np.float32)
+        occ = np.empty((H, W), np.uint32)
+        p = ao_params(**kw)
+        self._chk(self.L.mpt_ao_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), C.byref(p), _fp(ao), _up(occ)), "mpt_ao_image")
+        return ao, occ
 
     def build_bvh(self, prims):
         """GPU LBVH over the packed primitive array (12 floats each) -> (bvh [N, 8] f32, prim_idx [P] i32, device ms)."""

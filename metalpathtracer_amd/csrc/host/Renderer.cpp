@@ -356,6 +356,19 @@ mpt_display_info Renderer::display(const mpt_display_params& p, std::vector<uint
     check(mpt_read_display(ctx_, rgba8.data()), "mpt_read_display");
     return info;
 }
+mpt_ao_info Renderer::renderAmbientOcclusion(uint32_t samples, float radius) {
+    uniforms_.primitiveCount = scene_->getPrimitiveCount();
+    uniforms_.triangleCount = scene_->getTriangleCount();
+    check(mpt_set_uniforms(ctx_, &uniforms_), "mpt_set_uniforms");
+    const mpt_ao_params p = {0u, samples, radius, params_.seed_lo, params_.seed_hi, MPT_WALK_AUTO};
+    mpt_ao_info info;
+    check(mpt_ambient_occlusion(ctx_, &p, &info), "mpt_ambient_occlusion");
+    return info;
+}
+void Renderer::readAmbientOcclusion(std::vector<float>& ao) {
+    ao.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y));
+    check(mpt_read_ao(ctx_, ao.data(), nullptr), "mpt_read_ao");
+}
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     if (rgba.size() != n) throw std::runtime_error("writeSum: the array does not have the size of the frame");

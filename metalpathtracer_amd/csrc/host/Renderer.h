@@ -78,6 +78,11 @@ public:
     // mpt_display + mpt_read_display of p.source as given (MPT_DISPLAY_SUM with samples = 0: the samples added since the sum was last
     // cleared); rgba8 = the W*H*4 finished bytes
     mpt_display_info display(const mpt_display_params& p, std::vector<uint8_t>& rgba8);
+    // mpt_ambient_occlusion over the first-hit guides of the current camera: `samples` shadow rays per surface pixel, numbered from 0,
+    // keyed by the render parameters' seed, no farther than `radius` (<= 0: no limit), through MPT_WALK_AUTO; readAmbientOcclusion =
+    // the W*H floats of ao (1 = open)
+    mpt_ao_info renderAmbientOcclusion(uint32_t samples, float radius);
+    void readAmbientOcclusion(std::vector<float>& ao);
 
 private:
     void check(int status, const char* where);

@@ -323,6 +323,16 @@ int mpt_renderer_display(mpt_renderer* r, const mpt_display_params* p, uint8_t* 
         if (out) *out = info;
     });
 }
+int mpt_renderer_ambient_occlusion(mpt_renderer* r, uint32_t samples, float radius, float* ao, mpt_ao_info* out) {
+    if (!r || !ao) return MPT_ERR_INVALID_ARG;
+    std::vector<float> img;
+    GUARD({
+        const mpt_ao_info info = r->r->renderAmbientOcclusion(samples, radius);
+        r->r->readAmbientOcclusion(img);
+        std::memcpy(ao, img.data(), img.size() * sizeof(float));
+        if (out) *out = info;
+    });
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

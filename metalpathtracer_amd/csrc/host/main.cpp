@@ -42,7 +42,7 @@ static void usage() {
         "           [--pipeline auto|ordered|wavelocal|wavefront|megakernel] [--frames N] [--device 0] [--out image.pfm|image.ppm]\n"
         "           [--camera-pos x,y,z] [--camera-dir x,y,z] [--camera-up x,y,z] [--vfov degrees]\n"
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
-        "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]]\n"
+        "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]] [--ao N [--ao-radius R]]\n"
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
         "           [--svgf [--svgf-iterations N] [--temporal-history N] [--temporal-spp K]]\n"
@@ -74,6 +74,11 @@ static void usage() {
         "                    the floor) or it holds --spp samples.  --out gets the per-pixel mean (the sum / its tile's count; with\n"
         "                    --denoise the denoised mean); the JSON line gains an \"adaptive\" object.  Not with --frames,\n"
         "                    --camera-path, --gpus > 1, --rng literal, --checkpoint or --resume\n"
+        "  --ao N            write ambient occlusion instead of the radiance to --out (a .ppm): N shadow rays per surface pixel of the\n"
+        "                    first hits (mpt_ambient_occlusion, include/mpt.h), no farther than --ao-radius R (default: no limit); grey,\n"
+        "                    1 = open, through the same .ppm writer; the JSON line gains an \"ao\" object.  Nothing is path traced.\n"
+        "                    Only with a plain run: not with --frames, --camera-path, --gpus > 1, --adaptive, --denoise, the display\n"
+        "                    flags, --checkpoint or --resume\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
@@ -349,6 +354,10 @@ int main(int argc, char** argv) {
     bool adaptive = false;
     mpt_adaptive_params adp;
     std::memset(&adp, 0, sizeof adp);   // (0 = the defaults of include/mpt.h)
+    int ao = 0;             // --ao N: shadow rays per surface pixel (0 = none)
+    bool haveAo = false;    // --ao was given (with whatever count: 0 is refused, not ignored)
+    float aoRadius = 0.0f;
+    bool haveAoRadius = false;
     bool display = false;   // a display flag was given: .ppm files come from mpt_display
     DisplayOut shown;
     std::memset(&shown.params, 0, sizeof shown.params);   // (clamp, srgb, and 0 = the defaults of include/mpt.h)
@@ -389,6 +398,14 @@ int main(int argc, char** argv) {
         else if (a == "--checkpoint") checkpoint = next();
         else if (a == "--resume") resume = next();
         else if (a == "--denoise") denoise = true;
+        else if (a == "--ao") {
+            ao = std::atoi(next());
+            haveAo = true;
+        }
+        else if (a == "--ao-radius") {
+            aoRadius = static_cast<float>(std::atof(next()));
+            haveAoRadius = true;
+        }
         else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
         else if (a == "--adaptive") {
             adaptive = true;
@@ -484,6 +501,16 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "mpt_render: --key, --percentile and --adaptation go with --auto-exposure\n");
         return 2;
     }
+    if (haveAo || haveAoRadius) {
+        const char* why = ao < 1 || ao > static_cast<int>(MPT_AO_MAX_SAMPLES) ? "a sample count outside 1..1024" : !outPpm ? "an --out that is no .ppm"
+                          : frames > 0 ? "--frames" : !cameraPath.empty() ? "--camera-path" : gpus > 1 ? "--gpus > 1" : adaptive ? "--adaptive"
+                          : denoise ? "--denoise" : display ? "the display flags" : temporal ? "--temporal" : svgf ? "--svgf"
+                          : !checkpoint.empty() ? "--checkpoint" : !resume.empty() ? "--resume" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: --ao cannot be combined with %s\n", why);
+            return 2;
+        }
+    }
     if (adaptive) {
         const char* why = frames > 0 ? "--frames" : !cameraPath.empty() ? "--camera-path" : gpus > 1 ? "--gpus > 1"
                           : prm.rng_mode == MPT_RNG_LITERAL ? "--rng literal" : !checkpoint.empty() ? "--checkpoint"
@@ -537,7 +564,21 @@ int main(int argc, char** argv) {
         float scale = 1.0f;
         std::string adaptiveJson;
         auto t0 = std::chrono::steady_clock::now();
-        if (adaptive) {
+        if (ao > 0) {   // grey (ao, ao, ao, 1) through the writer the radiance goes through
+            const mpt_ao_info info = r.renderAmbientOcclusion(static_cast<uint32_t>(ao), aoRadius);
+            std::vector<float> a;
+            r.readAmbientOcclusion(a);
+            img.resize(a.size() * 4);
+            for (size_t k = 0; k < a.size(); ++k) {
+                img[4 * k] = img[4 * k + 1] = img[4 * k + 2] = a[k];
+                img[4 * k + 3] = 1.0f;
+            }
+            char buf[256];
+            std::snprintf(buf, sizeof buf, ", \"ao\": {\"samples\": %d, \"radius\": %.9g, \"pixels_surface\": %llu, \"rays\": %llu, \"rays_occluded\": %llu, \"device_ms\": %.3f}",
+                          ao, static_cast<double>(aoRadius), (unsigned long long)info.pixels_surface, (unsigned long long)info.rays,
+                          (unsigned long long)info.rays_occluded, info.device_ms);
+            adaptiveJson = buf;
+        } else if (adaptive) {
             const mpt_adaptive_info info = r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);
             if (!display || denoise) r.readAdaptiveMean(img);
             if (display && !denoise) present(r, shown, MPT_DISPLAY_ADAPTIVE);

@@ -39,6 +39,8 @@
 #include "mpt_svgf.h"
 #include "mpt_adaptive.h"
 #include "mpt_display.h"
+#include "mpt_anyhit.h"
+#include "mpt_ao.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -215,6 +217,14 @@ struct DisplayState {
     bool shown = false;            // `out` holds a frame
 };
 
+// Ambient occlusion (mpt_ao.h): the result of the last mpt_ambient_occlusion and the two totals of its info.  Allocated by the first
+// pass; valid while `epoch` is the context's guide_epoch, as TemporalState; mpt_resize and the scene calls let go of it.
+struct AoState {
+    DevMem<float> out;             // AoPass::out: W * H floats of ao, W * H counts, the two totals
+    uint32_t W = 0, H = 0;
+    uint64_t epoch = 0;            // the guide_epoch the result was written in (0 = none)
+};
+
 struct mpt_ctx : SceneState {
     int device = 0;
     std::unique_ptr<Submitter> sub;      // mpt_render_async's submit thread (none until the first asynchronous render)
@@ -309,6 +319,7 @@ struct mpt_ctx : SceneState {
     TemporalState tp;
     SvgfState sv;
     DisplayState dp;
+    AoState ao;
     int dp_px = 4;                  // MPT_DISPLAY_PX: pixels per thread of k_dp_present, 1 or 4 (the same bytes)
     bool dp_hist_agg = true;        // MPT_DISPLAY_HIST=plain: k_dp_histogram without the aggregation within the wave
 };
@@ -486,6 +497,9 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     hipFuncSetAttribute((const void*)k_trace_rays_ordered, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_trace_rays, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_dn_guide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // (the image of k_trace_rays)
+    for (const void* k : {(const void*)k_occluded_ref<false>, (const void*)k_occluded_ref<true>, (const void*)k_occluded_own, (const void*)k_ao<MPT_AO_REF>,
+                          (const void*)k_ao<MPT_AO_REF_ALL_LDS>, (const void*)k_ao<MPT_AO_OWN>})
+        hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = ctx.release();
     return MPT_OK;
 }
@@ -572,6 +586,7 @@ static void install_scene(mpt_ctx* ctx, SceneState&& s) {
     size_lds_images(ctx);
     ctx->have_scene = true;
     ctx->guide_epoch++;
+    ctx->ao = AoState{};   // (an AO result belongs to the scene it was traced in)
 }
 
 // the per-primitive reference-leaf boxes of an uploaded scene (k_prim_refbox, mpt_devbuild.h)
@@ -944,6 +959,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->tp = TemporalState{};
     ctx->sv = SvgfState{};
     ctx->dp = DisplayState{};
+    ctx->ao = AoState{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;
@@ -2411,6 +2427,265 @@ extern "C" int mpt_denoised_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
 extern "C" int mpt_denoise_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth, const float* normal_class,
                                  const mpt_denoise_params* p, float* out) {
     return guarded(ctx, [&] { return denoise_image_impl(ctx, w, h, color, albedo_depth, normal_class, p, out); });
+}
+
+// ---- shadow rays (mpt_anyhit.h, mpt_ao.h; the specification is in include/mpt.h) ----------------------------------------------------
+// MPT_WALK_* -> does the own tree answer?  (-1: a bad value)
+static int resolve_walk(const mpt_ctx* ctx, int32_t walk) {
+    if (walk == MPT_WALK_REFERENCE) return 0;
+    if (walk == MPT_WALK_OWN) return ctx->acc_ok ? 1 : 0;
+    if (walk == MPT_WALK_AUTO) return resolve_pipeline(ctx, MPT_PIPE_AUTO) == MPT_PIPE_ORDERED ? 1 : 0;
+    return -1;
+}
+static bool walk_valid(int32_t walk) { return walk == MPT_WALK_REFERENCE || walk == MPT_WALK_OWN || walk == MPT_WALK_AUTO; }
+static size_t ref_lds_bytes(const mpt_ctx* ctx) { return (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA; }
+
+static int trace_occluded_impl(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, int32_t walk, uint8_t* occ_out,
+                               uint32_t* flags_out) {
+    if (!ctx || !o || !d || !occ_out || n == 0 || n > (1ull << 22) || !walk_valid(walk))
+        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument (at most 2^22 rays per call, walk = MPT_WALK_*)");
+    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
+    HIPCHK(hipSetDevice(ctx->device));
+    const bool own = resolve_walk(ctx, walk) == 1;
+    DevMem<> d_o, d_d, d_t, d_occ, d_g;
+    HIPCHK(d_o.alloc(n * 12));
+    HIPCHK(d_d.alloc(n * 12));
+    HIPCHK(d_occ.alloc(n));
+    HIPCHK(d_g.alloc(n * 4));
+    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
+    if (tmax) {
+        HIPCHK(d_t.alloc(n * 4));
+        HIPCHK(hipMemcpy(d_t.get(), tmax, n * 4, hipMemcpyHostToDevice));
+    }
+    const uint32_t blocks = (uint32_t)((n + 255) / 256);
+    if (own) {
+        SceneDev sc;
+        AccelDev ac;
+        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the image of k_trace_rays_ordered: workgroups of 256)
+        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+        hipLaunchKernelGGL(k_occluded_own, dim3(blocks), dim3(256), lds, ctx->stream, sc, ac, (const float*)d_o.get(), (const float*)d_d.get(),
+                           (const float*)d_t.get(), (uint32_t)n, (uint8_t*)d_occ.get(), (uint32_t*)d_g.get());
+    } else {
+        HIPCHK(hipMemsetAsync(d_g.get(), 0, n * 4, ctx->stream));
+        const SceneDev sc = scene_dev(ctx);
+        if (ctx->n_lds_nodes == ctx->n_nodes)
+            hipLaunchKernelGGL(k_occluded_ref<true>, dim3(blocks), dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, (const float*)d_o.get(), (const float*)d_d.get(),
+                               (const float*)d_t.get(), (uint32_t)n, (uint8_t*)d_occ.get());
+        else
+            hipLaunchKernelGGL(k_occluded_ref<false>, dim3(blocks), dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, (const float*)d_o.get(), (const float*)d_d.get(),
+                               (const float*)d_t.get(), (uint32_t)n, (uint8_t*)d_occ.get());
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(occ_out, d_occ.get(), n, hipMemcpyDeviceToHost));
+    if (flags_out) HIPCHK(hipMemcpy(flags_out, d_g.get(), n * 4, hipMemcpyDeviceToHost));
+    return MPT_OK;
+}
+
+// Measurement hook (tools/ao_timing.py): the four one-ray-per-lane kernels on the SAME rays, uploaded once, launched in turn — closest hit
+// in reference order (k_trace_rays), any hit in reference order, closest hit through the own tree (k_trace_rays_ordered), any hit through
+// the own tree — `warmup` untimed rounds, then `reps` rounds with a pair of HIP events around every launch.
+static int time_trace_impl(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, uint32_t warmup, uint32_t reps, double* ms_out) {
+    if (!ctx || !o || !d || !ms_out || n == 0 || n > (1ull << 22) || reps == 0 || reps > 1000u || warmup > 1000u)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument (at most 2^22 rays, 1..1000 repetitions)");
+    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
+    HIPCHK(hipSetDevice(ctx->device));
+    DevMem<> d_o, d_d, d_tm, d_t, d_n, d_p, d_f, d_g, d_occ;
+    for (DevMem<>* b : {&d_o, &d_d, &d_n}) HIPCHK(b->alloc(n * 12));
+    for (DevMem<>* b : {&d_t, &d_p, &d_f, &d_g, &d_occ}) HIPCHK(b->alloc(n * 4));
+    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
+    if (tmax) {
+        HIPCHK(d_tm.alloc(n * 4));
+        HIPCHK(hipMemcpy(d_tm.get(), tmax, n * 4, hipMemcpyHostToDevice));
+    }
+    const SceneDev sc = scene_dev(ctx);
+    SceneDev osc = sc;
+    AccelDev ac = {};
+    size_t olds = 0;
+    if (ctx->acc_ok) {
+        olds = ordered_views(ctx, 0, ctx->ot_stack_depth, osc, ac);
+        if (!ordered_layout_ok(osc, ac, 256u, olds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+    }
+    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
+    const float *po = (const float*)d_o.get(), *pd = (const float*)d_d.get(), *pt = (const float*)d_tm.get();
+    const bool all_lds = ctx->n_lds_nodes == ctx->n_nodes;
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventCreate));
+    HIPCHK(e1.create(hipEventCreate));
+    for (uint32_t r = 0; r < warmup + reps; ++r)
+        for (int kind = 0; kind < 4; ++kind) {
+            double* slot = r >= warmup ? ms_out + 4 * (size_t)(r - warmup) + kind : nullptr;
+            if (kind >= 2 && !ctx->acc_ok) {
+                if (slot) *slot = 0.0;
+                continue;
+            }
+            HIPCHK(hipEventRecord(e0.get(), ctx->stream));
+            if (kind == 0)
+                hipLaunchKernelGGL(k_trace_rays, grid, block, ref_lds_bytes(ctx), ctx->stream, sc, po, pd, (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(),
+                                   (float*)d_n.get(), (int*)d_f.get());
+            else if (kind == 1 && all_lds)
+                hipLaunchKernelGGL(k_occluded_ref<true>, grid, block, ref_lds_bytes(ctx), ctx->stream, sc, po, pd, pt, (uint32_t)n, (uint8_t*)d_occ.get());
+            else if (kind == 1)
+                hipLaunchKernelGGL(k_occluded_ref<false>, grid, block, ref_lds_bytes(ctx), ctx->stream, sc, po, pd, pt, (uint32_t)n, (uint8_t*)d_occ.get());
+            else if (kind == 2)
+                hipLaunchKernelGGL(k_trace_rays_ordered, grid, block, olds, ctx->stream, osc, ac, po, pd, (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(),
+                                   (float*)d_n.get(), (int*)d_f.get(), (uint32_t*)d_g.get());
+            else
+                hipLaunchKernelGGL(k_occluded_own, grid, block, olds, ctx->stream, osc, ac, po, pd, pt, (uint32_t)n, (uint8_t*)d_occ.get(), (uint32_t*)d_g.get());
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(e1.get(), ctx->stream));
+            HIPCHK(hipEventSynchronize(e1.get()));
+            float ms = 0.0f;
+            HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
+            if (slot) *slot = (double)ms;
+        }
+    return MPT_OK;
+}
+
+static int ao_check(mpt_ctx* ctx, const mpt_ao_params* p) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null ambient-occlusion params");
+    if (p->sample_count == 0 || p->sample_count > MPT_AO_MAX_SAMPLES) return fail(ctx, MPT_ERR_INVALID_ARG, "ambient occlusion: sample_count outside 1..1024");
+    if (p->radius != p->radius) return fail(ctx, MPT_ERR_INVALID_ARG, "ambient occlusion: the radius is NaN");
+    if (!walk_valid(p->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "ambient occlusion: bad walk");
+    return MPT_OK;
+}
+// One pass on ctx->stream over guides on the device; `key`: cam, vu, vv, first as guide_key lays them out; out: ao_out_bytes(W * H).
+static int ao_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad, const float4* nc, const float key[12], const mpt_ao_params* p, float* out) {
+    AoPass P = {};
+    P.ad = ad;
+    P.nc = nc;
+    P.out = out;
+    P.n_pixels = W * H;
+    HIPCHK(hipMemsetAsync(P.totals(), 0, 16, ctx->stream));
+    P.cam = F3{key[0], key[1], key[2]};
+    P.vu = F3{key[3], key[4], key[5]};
+    P.vv = F3{key[6], key[7], key[8]};
+    P.first = F3{key[9], key[10], key[11]};
+    P.fW = (float)W;
+    P.fH = (float)H;
+    P.W = W;
+    P.H = H;
+    P.sample_begin = p->sample_begin;
+    P.sample_count = p->sample_count;
+    uint32_t gl = 0;
+    while (gl < 6u && (2u << gl) <= p->sample_count) ++gl;   // min(N, 64) rounded down to a power of two
+    P.group_log2 = gl;
+    P.tmax = p->radius > 0.0f ? p->radius : INFINITY;
+    P.seed_lo = p->seed_lo;
+    P.seed_hi = p->seed_hi;
+    const dim3 grid((W + MPT_DN_TILE - 1) / MPT_DN_TILE, (H + MPT_DN_TILE - 1) / MPT_DN_TILE);
+    SceneDev sc = scene_dev(ctx);
+    AccelDev ac = {};
+    if (resolve_walk(ctx, p->walk) == 1) {
+        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);
+        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+        hipLaunchKernelGGL(k_ao<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
+    } else if (ctx->n_lds_nodes == ctx->n_nodes) {
+        hipLaunchKernelGGL(k_ao<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+    } else {
+        hipLaunchKernelGGL(k_ao<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+    }
+    HIPCHK(hipGetLastError());
+    return MPT_OK;
+}
+static size_t ao_out_bytes(size_t n_pixels) { return n_pixels * 8 + 16; }
+static bool ao_have(const mpt_ctx* ctx) {
+    return ctx->ao.epoch != 0 && ctx->ao.epoch == ctx->guide_epoch && ctx->ao.W == ctx->W && ctx->ao.H == ctx->H && ctx->ao.out;
+}
+static int ambient_occlusion_impl(mpt_ctx* ctx, const mpt_ao_params* p, mpt_ao_info* out) {
+    if (!ctx) return MPT_ERR_INVALID_ARG;
+    int rc = ao_check(ctx, p);
+    if (rc) return rc;
+    if ((rc = wait_impl(ctx))) return rc;
+    if ((rc = refresh_guides(ctx))) return rc;
+    AoState& a = ctx->ao;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    if (!a.out || a.W != ctx->W || a.H != ctx->H) {
+        a = AoState{};
+        HIPCHK(a.out.alloc(ao_out_bytes(n)));
+        a.W = ctx->W;
+        a.H = ctx->H;
+    }
+    a.epoch = 0;
+    float key[14];
+    guide_key(ctx->u, key);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventCreate));
+    HIPCHK(e1.create(hipEventCreate));
+    HIPCHK(hipEventRecord(e0.get(), ctx->stream));
+    if ((rc = ao_launch(ctx, ctx->W, ctx->H, ctx->d_aov_ad.get(), ctx->d_aov_nc.get(), key, p, a.out.get()))) return rc;
+    HIPCHK(hipEventRecord(e1.get(), ctx->stream));
+    unsigned long long totals[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(totals, a.out.get() + 2 * n, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    a.epoch = ctx->guide_epoch;
+    if (out) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
+        out->pixels_surface = totals[0];
+        out->rays = totals[0] * p->sample_count;
+        out->rays_occluded = totals[1];
+        out->device_ms = (double)ms;
+    }
+    return MPT_OK;
+}
+static int read_ao_impl(mpt_ctx* ctx, float* ao, uint32_t* occluded) {
+    if (!ctx || !ao) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    if (!ao_have(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_ambient_occlusion result for this scene and size");
+    const size_t n = (size_t)ctx->W * ctx->H;
+    HIPCHK(hipMemcpyAsync(ao, ctx->ao.out.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (occluded) HIPCHK(hipMemcpyAsync(occluded, ctx->ao.out.get() + n, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+static int ao_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* ad, const float* nc, const mpt_uniforms* cam, const mpt_ao_params* p,
+                         float* ao_out, uint32_t* occ_out) {
+    if (!ctx || !ad || !nc || !cam || !ao_out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    int rc = ao_check(ctx, p);
+    if (rc) return rc;
+    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)W * H;
+    DevMem<> d_ad, d_nc;
+    DevMem<float> d_out;
+    HIPCHK(d_ad.alloc(n * 16));
+    HIPCHK(d_nc.alloc(n * 16));
+    HIPCHK(d_out.alloc(ao_out_bytes(n)));
+    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
+    float key[14];
+    guide_key(*cam, key);
+    if ((rc = ao_launch(ctx, W, H, (const float4*)d_ad.get(), (const float4*)d_nc.get(), key, p, d_out.get()))) return rc;
+    HIPCHK(hipMemcpyAsync(ao_out, d_out.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (occ_out) HIPCHK(hipMemcpyAsync(occ_out, d_out.get() + n, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+extern "C" int mpt_trace_occluded(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, int32_t walk, uint8_t* occluded_out,
+                                  uint32_t* flags_out) {
+    return guarded(ctx, [&] { return trace_occluded_impl(ctx, o, d, tmax, n, walk, occluded_out, flags_out); });
+}
+extern "C" int mpt_time_trace(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, uint32_t warmup, uint32_t reps, double* ms_out) {
+    return guarded(ctx, [&] { return time_trace_impl(ctx, o, d, tmax, n, warmup, reps, ms_out); });
+}
+extern "C" int mpt_ambient_occlusion(mpt_ctx* ctx, const mpt_ao_params* p, mpt_ao_info* out) {
+    return guarded(ctx, [&] { return ambient_occlusion_impl(ctx, p, out); });
+}
+extern "C" int mpt_read_ao(mpt_ctx* ctx, float* ao, uint32_t* occluded) {
+    return guarded(ctx, [&] { return read_ao_impl(ctx, ao, occluded); });
+}
+extern "C" int mpt_ao_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
+    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
+    if (!ao_have(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_ambient_occlusion result for this scene and size");
+    *p = ctx->ao.out.get();
+    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 4;
+    return MPT_OK;
+}
+extern "C" int mpt_ao_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* albedo_depth, const float* normal_class, const mpt_uniforms* cam,
+                            const mpt_ao_params* p, float* ao_out, uint32_t* occluded_out) {
+    return guarded(ctx, [&] { return ao_image_impl(ctx, w, h, albedo_depth, normal_class, cam, p, ao_out, occluded_out); });
 }
 
 // ---- temporal accumulation (mpt_temporal.h; the specification is in include/mpt.h) ---------------------------------------------

@@ -26,6 +26,7 @@ SYMBOLS = (
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
+    "mpt_renderer_ambient_occlusion",
 )
 
 _lib = None
@@ -82,6 +83,7 @@ def load():
     L.mpt_write_ppm.argtypes = [C.c_char_p, fp, C.c_uint32, C.c_uint32, C.c_float, C.c_float]
     L.mpt_renderer_display.argtypes = [vp, C.POINTER(capi.DisplayParams), C.POINTER(C.c_uint8), C.POINTER(capi.DisplayInfo)]
     L.mpt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
+    L.mpt_renderer_ambient_occlusion.argtypes = [vp, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(capi.AoInfo)]
     _lib = L
     return L
 
@@ -383,6 +385,15 @@ class Renderer:
         p = capi.display_params(**kw)
         info = capi.DisplayInfo()
         self._chk(self.L.mpt_renderer_display(self.h, C.byref(p), out.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(info)), "display")
+        return out, info.as_dict()
+
+    def renderAmbientOcclusion(self, samples, radius=0.0):
+        """mpt_renderer_ambient_occlusion: `samples` shadow rays per surface pixel of the current camera's first hits, no farther than
+        `radius` (<= 0: no limit).  Returns (ao [H, W] float32, 1 = open; the mpt_ao_info as a dict)."""
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0])), np.float32)
+        info = capi.AoInfo()
+        self._chk(self.L.mpt_renderer_ambient_occlusion(self.h, int(samples), float(radius), _fp(out), C.byref(info)), "renderAmbientOcclusion")
         return out, info.as_dict()
 
     def scene(self):
