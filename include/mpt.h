@@ -612,7 +612,8 @@ int mpt_display_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float
  * any primitive: the same slab test (tMin = 1e-4, tMax = best t), the same sphere and triangle tests, acceptance t > 1e-4 && t < best t.
  * !(tmax > 1e-4) (a NaN included) and a direction with a NaN component are "not occluded"; tmax = +inf asks for any hit at all.
  * With the same tree, "occluded" implies that mpt_trace_rays returns t < tmax, exactly.  The converse fails only for the reference's
- * known artefact — a hit whose computed t lies in front of its own leaf's slab entry — when tmax falls between the two.
+ * known artefact — a hit whose computed t lies in front of its own leaf's slab entry — when tmax falls between the two, and, with
+ * tmax within a rounding of t (one ulp above it, say), for a leaf whose slab entry rounds to >= tmax: hi > lo fails, the hit is not seen.
  * MPT_WALK_REFERENCE walks the threaded reference-order tree, MPT_WALK_OWN the product's own 4-wide tree (children culled beyond
  * tmax * (1 + 2^-10) + eps_abs, primitives tested with the reference's exact tests, no final check: for that artefact it answers by
  * the primitive test alone); rays the closest-first walk hands to the reference-order walk for their direction or origin (flag 1), or

@@ -18,6 +18,9 @@
 //   t < tmax  =>  occluded, EXCEPT the reference's known artefact: a hit whose computed t lies in front of its own leaf's slab entry
 //       (mpt_ordered.h:13-25: the r = 10^4 ground sphere, slivers seen along their plane) with tmax between the two.  The closest-hit
 //       walk enters that leaf with best t = +inf and accepts; this walk, with best t = tmax, is turned away at the leaf's box.
+//       The same happens by one rounding when tmax is within an ulp or so of t: the slab entry of the hit's leaf (or of a box above
+//       it) rounds to >= tmax, `hi > lo` fails and the hit below tmax is not seen (1-2 rays in 2048 on sliver scenes at
+//       tmax = nextafter(t); tests/anyhit_ref.py restates the walk by brute force and tests/test_gpu_anyhit_exact.py holds both walks to it).
 // The own tree reaches the same leaves another way (padded boxes, reciprocal arithmetic, spheres on the always list), culls with the
 // closest-first walk's margin around tmax and tests primitives with the reference's exact tests, so it accepts what the reference
 // accepts; it has no final check, so for the artefact above it answers by the primitive test alone ("occluded").

@@ -1,7 +1,10 @@
 """GPU tests of mpt_trace_occluded: both any-hit walks against the oracle's closest hit.  For every ray "occluded" must equal t* < tmax
 (t* = the oracle's closest t): 0 mismatches.  A ray that is occluded with t* >= tmax breaks the exact direction of include/mpt.h and
 is a bug, always; one with t* < tmax that is not occluded would be the reference's artefact (a hit in front of its own leaf's slab
-entry, tmax between the two) and is reported with the ray — the limits used here keep tmax away from t* so that it cannot occur."""
+entry, tmax between the two) or, with tmax within a rounding of t*, a leaf whose slab entry rounds to >= tmax although its hit lies
+below (seen at tmax = nextafter(t*) and at 1.001 t* on sliver scenes), and is reported with the ray — the limits and scenes used here
+keep tmax away from t* so that neither occurs.  tests/test_gpu_anyhit_exact.py puts the limit AT t* and checks both walks exactly,
+against a brute-force restatement of the any-hit walk itself (tests/anyhit_ref.py)."""
 import ctypes as C
 
 import numpy as np
