@@ -175,38 +175,51 @@ struct AdaptiveTiles {
     uint32_t tiles = 0;
 };
 
-// Temporal accumulation (mpt_temporal.h): the history, the guide of the frame it belongs to and that frame's camera, ping-pong.
-// Allocated by the first mpt_temporal_accumulate; valid while `epoch` is the context's guide_epoch (every scene call and mpt_resize
-// bump that one); mpt_resize and mpt_temporal_reset let go of the buffers.
-struct TemporalState {
+// The state of the post-processing stages (mpt_post.h drives them).  Each is valid while its `epoch` is the context's guide_epoch
+// (every scene call and mpt_resize bump that one) and its W x H the context's size; mpt_resize lets go of all of them.
+//
+// The first-hit guide buffers of the current frame (k_dn_guide, mpt_denoise.h), traced again when stale; every stage reads them.
+// Allocated, with DenoiseState, by the first stage call after a resize.
+struct GuideState {
+    DevMem<float4> ad;             // (albedo rgb, t)
+    DevMem<float4> nc;             // (normal rgb, class)
+    DevMem<int> prim;              // caller's primitive id, -1 = miss
+    DevMem<float4> packed;         // packed per-tap guide (normal, t or MPT_DN_SKIP)
+    uint32_t W = 0, H = 0;         // size of those buffers and of DenoiseState's
+    uint64_t built = 0;            // the guide_epoch the guides were traced in (0 = never)
+    float cam[14] = {};            // guide_key of the uniforms they were traced with
+};
+// The denoiser's own buffers (mpt_denoise.h)
+struct DenoiseState {
+    DevMem<float4> x[2];           // ping-pong (x rgb, luminance) of the levels
+    DevMem<float4> out;
+    bool valid = false;            // `out` holds the result of an mpt_denoise at the current size
+};
+
+// A reprojected history: the accumulated frame, the guide of the frame it belongs to and that frame's camera, ping-pong.  Temporal
+// accumulation (mpt_temporal.h) keeps exactly this.  Allocated by the first accumulate call; mpt_temporal_reset / mpt_svgf_reset let go of it.
+struct History {
     DevMem<float4> hist[2];        // (accumulated rgb, history length n)
-    DevMem<float4> guide[2];       // (normal facing the ray, t; t = +inf for a miss)
+    DevMem<float4> guide[2];       // (normal facing the ray, t; SVGF: t / -t by class; +inf for a miss)
     DevMem<unsigned long long> n_reset;
     uint32_t W = 0, H = 0;         // size of those buffers
     int cur = 0;                   // which of the two holds the history
     uint64_t epoch = 0;            // the guide_epoch the history was written in (0 = no history)
     float cam[14] = {};            // guide_key of the history's frame
 };
+using TemporalState = History;
 
-// SVGF (mpt_svgf.h): the demodulated illumination history, its luminance moments, the guide of the frame they belong to and that
-// frame's camera, ping-pong, with the lifetime rules of TemporalState and independent of it.  The a-trous buffers are this
-// owner's too (not the denoiser's d_dn_x): an mpt_denoise result survives an mpt_svgf_accumulate and the other way round.
-struct SvgfState {
-    DevMem<float4> hist[2];        // (X rgb, history length n)
+// SVGF (mpt_svgf.h): the demodulated illumination history with its luminance moments, independent of TemporalState.  The a-trous
+// buffers are this owner's too (not DenoiseState's): an mpt_denoise result survives an mpt_svgf_accumulate and the other way round.
+struct SvgfState : History {
     DevMem<float2> mom[2];         // (M1, M2) of the luminance
-    DevMem<float4> guide[2];       // (normal facing the ray, t / -t / +inf by class)
     DevMem<float4> xv[3];          // (x, V): [0] = (X, V_0), kept for mpt_read_svgf_state; [1], [2] the ping-pong of the levels
     DevMem<float4> out;            // the filtered frame
-    DevMem<unsigned long long> n_reset;
-    uint32_t W = 0, H = 0;
-    int cur = 0;
-    uint64_t epoch = 0;            // the guide_epoch the state was written in (0 = none)
-    float cam[14] = {};
 };
 
 // The display stage (mpt_display.h): the RGBA8 frame, the luminance histogram of the last call with auto_exposure, the result block
 // (DpState: the mpt_display_info of the last call and the auto scale kept for the next one) and the three threshold tables.
-// Allocated by the first mpt_display; valid while `epoch` is the context's guide_epoch, as TemporalState; mpt_resize lets go of it.
+// Allocated by the first mpt_display.
 struct DisplayState {
     DevMem<uint32_t> out;          // W * H words: r | g << 8 | b << 16 | 255 << 24
     DevMem<uint32_t> hist;         // MPT_DP_BINS counts
@@ -218,7 +231,7 @@ struct DisplayState {
 };
 
 // Ambient occlusion (mpt_ao.h): the result of the last mpt_ambient_occlusion and the two totals of its info.  Allocated by the first
-// pass; valid while `epoch` is the context's guide_epoch, as TemporalState; mpt_resize and the scene calls let go of it.
+// pass; the scene calls let go of it too.
 struct AoState {
     DevMem<float> out;             // AoPass::out: W * H floats of ao, W * H counts, the two totals
     uint32_t W = 0, H = 0;
@@ -299,19 +312,9 @@ struct mpt_ctx : SceneState {
     int wgs_per_cu = 0;  // 0 = as many as the occupancy query admits
     size_t lds_budget = 78 * 1024;  // per workgroup; two workgroups per CU share the 160 KiB
     mpt_stats stats = {};
-    // denoiser (mpt_denoise.h): the first-hit guide buffers, traced again when stale, and the filter's own buffers (W x H each,
-    // allocated by the first mpt_read_aovs / mpt_denoise after a resize)
-    DevMem<float4> d_aov_ad;        // (albedo rgb, t)
-    DevMem<float4> d_aov_nc;        // (normal rgb, class)
-    DevMem<int> d_aov_prim;         // caller's primitive id, -1 = miss
-    DevMem<float4> d_dn_guide;      // packed per-tap guide (normal, t or MPT_DN_SKIP)
-    DevMem<float4> d_dn_x[2];       // ping-pong (x rgb, luminance) of the levels
-    DevMem<float4> d_denoised;
-    uint32_t dn_W = 0, dn_H = 0;    // size of those buffers
     uint64_t guide_epoch = 1;       // bumped by every scene upload / build and every mpt_resize
-    uint64_t guide_built = 0;       // the epoch the guide buffers were traced in (0 = never)
-    float guide_cam[14] = {};       // camera fields of the uniforms they were traced with
-    bool denoised_valid = false;    // d_denoised holds the result of an mpt_denoise at the current size
+    GuideState gd;
+    DenoiseState dn;
     // adaptive sampling (mpt_adaptive.h): the moments buffer (W x H, allocated by the first render with MPT_FLAG_MOMENTS) and the
     // tile buffers of mpt_render_adaptive; mpt_resize drops both
     DevMem<float4> d_m2;
@@ -964,7 +967,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->H = height;
     ctx->cur_target = 0;
     ctx->guide_epoch++;
-    ctx->denoised_valid = false;
+    ctx->dn.valid = false;
     return MPT_OK;
 }
 
@@ -2252,183 +2255,6 @@ extern "C" int mpt_accel_info(mpt_ctx* ctx, uint64_t out[8]) {
 
 extern "C" int mpt_gpu_leaf_max(uint64_t n_prims) { return gpu_leaf_max(n_prims); }
 
-// Position-sensitive 64-bit digest of a device array of 32-bit words: sum over i of splitmix64(i << 32 | word[i]) (a commutative sum, so
-// the order in which the waves add is free).  What the tests compare two builds of a scene by, array by array (mpt_scene_digest).
-// ---- denoiser (mpt_denoise.h; the specification is in include/mpt.h) ---------------------------------------------------------
-struct DnSigmas {
-    int iterations;
-    float sl, sn, sz;
-};
-static int dn_resolve(mpt_ctx* ctx, const mpt_denoise_params* p, DnSigmas& r) {
-    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null denoise params");
-    if (p->iterations > MPT_DENOISE_MAX_ITERATIONS) return fail(ctx, MPT_ERR_INVALID_ARG, "denoise iterations > 8");
-    r.iterations = p->iterations < 0 ? MPT_DENOISE_DEFAULT_ITERATIONS : p->iterations;
-    r.sl = p->sigma_luminance > 0.0f ? p->sigma_luminance : MPT_DENOISE_DEFAULT_SIGMA_LUMINANCE;
-    r.sn = p->sigma_normal > 0.0f ? p->sigma_normal : MPT_DENOISE_DEFAULT_SIGMA_NORMAL;
-    r.sz = p->sigma_depth > 0.0f ? p->sigma_depth : MPT_DENOISE_DEFAULT_SIGMA_DEPTH;
-    return MPT_OK;
-}
-// N levels on `stream`: level 0 demodulates `color` / samples, level N-1 remodulates into `out`; x[2] are the ping-pong buffers.
-static int dn_filter(mpt_ctx* ctx, hipStream_t stream, uint32_t W, uint32_t H, const float4* color, float samples, const float4* ad,
-                     const float4* guide, float4* const x[2], const DnSigmas& sg, float4* out) {
-    const uint32_t n = W * H;
-    if (sg.iterations == 0) {
-        hipLaunchKernelGGL(k_dn_copy, dim3((n + 255) / 256), dim3(256), 0, stream, color, samples, n, out);
-        HIPCHK(hipGetLastError());
-        return MPT_OK;
-    }
-    const dim3 grid((W + MPT_DN_TILE - 1) / MPT_DN_TILE, (H + MPT_DN_TILE - 1) / MPT_DN_TILE);
-    for (int i = 0; i < sg.iterations; ++i) {
-        const bool first = i == 0, last = i == sg.iterations - 1;
-        DnLevel L;
-        L.color = color;
-        L.ad = ad;
-        L.guide = guide;
-        L.xin = first ? nullptr : x[(i - 1) & 1];
-        L.xout = last ? out : x[i & 1];
-        L.W = W;
-        L.H = H;
-        L.step = 1u << i;
-        L.samples = samples;
-        L.sigma_n = sg.sn;
-        L.sigma_z = sg.sz;
-        L.sigma_l = sg.sl * ldexpf(1.0f, -i);
-        const bool lds = L.step <= MPT_DN_LDS_MAX_STEP;
-        const uint32_t T = MPT_DN_TILE + 4u * L.step;
-        const void* k = lds ? dn_level_kernel<true>(first, last) : dn_level_kernel<false>(first, last);
-        void* args[] = {&L};
-        HIPCHK(hipLaunchKernel(k, grid, dim3(256), args, lds ? (size_t)T * T * 32u : 0u, stream));
-    }
-    return MPT_OK;
-}
-static int ensure_dn_buffers(mpt_ctx* ctx) {
-    if (ctx->d_denoised && ctx->dn_W == ctx->W && ctx->dn_H == ctx->H) return MPT_OK;
-    ctx->dn_W = ctx->dn_H = 0;
-    ctx->guide_built = 0;
-    ctx->denoised_valid = false;
-    const size_t n = (size_t)ctx->W * ctx->H;
-    for (DevMem<float4>* b : {&ctx->d_aov_ad, &ctx->d_aov_nc, &ctx->d_dn_guide, &ctx->d_dn_x[0], &ctx->d_dn_x[1], &ctx->d_denoised})
-        HIPCHK(b->alloc(n * 16));
-    HIPCHK(ctx->d_aov_prim.alloc(n * 4));
-    ctx->dn_W = ctx->W;
-    ctx->dn_H = ctx->H;
-    return MPT_OK;
-}
-static void guide_key(const mpt_uniforms& u, float k[14]) {
-    memcpy(k, u.cameraPosition, 12);
-    memcpy(k + 3, u.viewportU, 12);
-    memcpy(k + 6, u.viewportV, 12);
-    memcpy(k + 9, u.firstPixelPosition, 12);
-    memcpy(k + 12, u.screenSize, 8);
-}
-// The guide pass, when the guides are stale: one thread per pixel, 16 x 16 pixels per workgroup of four 8 x 8 tiles, the top of the
-// tree staged in LDS as k_trace_rays does (the reference-order walk: it returns what the closest-first walk returns).
-static int refresh_guides(mpt_ctx* ctx) {
-    if (!ctx->have_scene || !ctx->have_uniforms || !ctx->W) return fail(ctx, MPT_ERR_NOT_READY, "scene, uniforms or size not set");
-    if ((uint32_t)ctx->u.screenSize[0] != ctx->W || (uint32_t)ctx->u.screenSize[1] != ctx->H)
-        return fail(ctx, MPT_ERR_INVALID_ARG, "uniforms.screenSize does not match mpt_resize");
-    int rc = ensure_dn_buffers(ctx);
-    if (rc) return rc;
-    float key[14];
-    guide_key(ctx->u, key);
-    if (ctx->guide_built == ctx->guide_epoch && memcmp(key, ctx->guide_cam, sizeof key) == 0) return MPT_OK;
-    const mpt_uniforms& u = ctx->u;
-    const SceneDev sc = scene_dev(ctx);
-    const dim3 grid((ctx->W + MPT_DN_TILE - 1) / MPT_DN_TILE, (ctx->H + MPT_DN_TILE - 1) / MPT_DN_TILE);
-    hipLaunchKernelGGL(k_dn_guide, grid, dim3(256), (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA,
-                       ctx->stream, sc, F3{u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2]},
-                       F3{u.firstPixelPosition[0], u.firstPixelPosition[1], u.firstPixelPosition[2]},
-                       F3{u.viewportU[0], u.viewportU[1], u.viewportU[2]}, F3{u.viewportV[0], u.viewportV[1], u.viewportV[2]},
-                       u.screenSize[0], u.screenSize[1], ctx->W, ctx->H, ctx->d_aov_ad.get(), ctx->d_aov_nc.get(), ctx->d_aov_prim.get(),
-                       ctx->d_dn_guide.get());
-    HIPCHK(hipGetLastError());
-    ctx->guide_built = ctx->guide_epoch;
-    memcpy(ctx->guide_cam, key, sizeof key);
-    return MPT_OK;
-}
-static int read_aovs_impl(mpt_ctx* ctx, float* ad, float* nc, int32_t* prim) {
-    if (!ctx || !ad || !nc) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-    int rc = wait_impl(ctx);
-    if (rc) return rc;
-    if ((rc = refresh_guides(ctx))) return rc;
-    const size_t n = (size_t)ctx->W * ctx->H;
-    HIPCHK(hipMemcpyAsync(ad, ctx->d_aov_ad.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(nc, ctx->d_aov_nc.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (prim) HIPCHK(hipMemcpyAsync(prim, ctx->d_aov_prim.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MPT_OK;
-}
-static int denoise_impl(mpt_ctx* ctx, const mpt_denoise_params* p) {
-    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-    DnSigmas sg;
-    int rc = dn_resolve(ctx, p, sg);
-    if (rc) return rc;
-    if (p->source != MPT_DENOISE_SUM && p->source != MPT_DENOISE_FRAME) return fail(ctx, MPT_ERR_INVALID_ARG, "bad denoise source");
-    if (p->source == MPT_DENOISE_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "denoise of the sum with samples = 0");
-    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
-    if ((rc = refresh_guides(ctx))) return rc;
-    const bool sum = p->source == MPT_DENOISE_SUM;
-    float4* x[2] = {ctx->d_dn_x[0].get(), ctx->d_dn_x[1].get()};
-    ctx->denoised_valid = false;
-    if ((rc = dn_filter(ctx, ctx->stream, ctx->W, ctx->H, sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target].get(), sum ? (float)p->samples : 1.0f,
-                        ctx->d_aov_ad.get(), ctx->d_dn_guide.get(), x, sg, ctx->d_denoised.get())))
-        return rc;
-    ctx->denoised_valid = true;
-    return MPT_OK;
-}
-static int read_denoised_impl(mpt_ctx* ctx, float* out) {
-    if (!ctx || !out) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-    if (!ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
-    HIPCHK(hipMemcpyAsync(out, ctx->d_denoised.get(), (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MPT_OK;
-}
-static int denoise_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const float* ad, const float* nc,
-                              const mpt_denoise_params* p, float* out) {
-    if (!ctx || !color || !ad || !nc || !p || !out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31))
-        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
-    DnSigmas sg;
-    int rc = dn_resolve(ctx, p, sg);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H;
-    DevMem<> d_c, d_ad, d_nc, d_g, d_x0, d_x1, d_o;
-    for (DevMem<>* b : {&d_c, &d_ad, &d_nc, &d_g, &d_x0, &d_x1, &d_o}) HIPCHK(b->alloc(n * 16));
-    HIPCHK(hipMemcpyAsync(d_c.get(), color, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_dn_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)d_ad.get(), (const float4*)d_nc.get(),
-                       (uint32_t)n, (float4*)d_g.get());
-    HIPCHK(hipGetLastError());
-    float4* x[2] = {(float4*)d_x0.get(), (float4*)d_x1.get()};
-    if ((rc = dn_filter(ctx, ctx->stream, W, H, (const float4*)d_c.get(), 1.0f, (const float4*)d_ad.get(), (const float4*)d_g.get(), x, sg,
-                        (float4*)d_o.get())))
-        return rc;
-    HIPCHK(hipMemcpyAsync(out, d_o.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MPT_OK;
-}
-extern "C" int mpt_read_aovs(mpt_ctx* ctx, float* albedo_depth, float* normal_class, int32_t* prim) {
-    return guarded(ctx, [&] { return read_aovs_impl(ctx, albedo_depth, normal_class, prim); });
-}
-extern "C" int mpt_denoise(mpt_ctx* ctx, const mpt_denoise_params* p) {
-    return guarded(ctx, [&] { return denoise_impl(ctx, p); });
-}
-extern "C" int mpt_read_denoised(mpt_ctx* ctx, float* rgba) {
-    return guarded(ctx, [&] { return read_denoised_impl(ctx, rgba); });
-}
-extern "C" int mpt_denoised_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
-    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
-    if (!ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
-    *p = ctx->d_denoised.get();
-    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 16;
-    return MPT_OK;
-}
-extern "C" int mpt_denoise_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth, const float* normal_class,
-                                 const mpt_denoise_params* p, float* out) {
-    return guarded(ctx, [&] { return denoise_image_impl(ctx, w, h, color, albedo_depth, normal_class, p, out); });
-}
-
 // ---- shadow rays (mpt_anyhit.h, mpt_ao.h; the specification is in include/mpt.h) ----------------------------------------------------
 // MPT_WALK_* -> does the own tree answer?  (-1: a bad value)
 static int resolve_walk(const mpt_ctx* ctx, int32_t walk) {
@@ -2544,125 +2370,6 @@ static int time_trace_impl(mpt_ctx* ctx, const float* o, const float* d, const f
     return MPT_OK;
 }
 
-static int ao_check(mpt_ctx* ctx, const mpt_ao_params* p) {
-    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null ambient-occlusion params");
-    if (p->sample_count == 0 || p->sample_count > MPT_AO_MAX_SAMPLES) return fail(ctx, MPT_ERR_INVALID_ARG, "ambient occlusion: sample_count outside 1..1024");
-    if (p->radius != p->radius) return fail(ctx, MPT_ERR_INVALID_ARG, "ambient occlusion: the radius is NaN");
-    if (!walk_valid(p->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "ambient occlusion: bad walk");
-    return MPT_OK;
-}
-// One pass on ctx->stream over guides on the device; `key`: cam, vu, vv, first as guide_key lays them out; out: ao_out_bytes(W * H).
-static int ao_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad, const float4* nc, const float key[12], const mpt_ao_params* p, float* out) {
-    AoPass P = {};
-    P.ad = ad;
-    P.nc = nc;
-    P.out = out;
-    P.n_pixels = W * H;
-    HIPCHK(hipMemsetAsync(P.totals(), 0, 16, ctx->stream));
-    P.cam = F3{key[0], key[1], key[2]};
-    P.vu = F3{key[3], key[4], key[5]};
-    P.vv = F3{key[6], key[7], key[8]};
-    P.first = F3{key[9], key[10], key[11]};
-    P.fW = (float)W;
-    P.fH = (float)H;
-    P.W = W;
-    P.H = H;
-    P.sample_begin = p->sample_begin;
-    P.sample_count = p->sample_count;
-    uint32_t gl = 0;
-    while (gl < 6u && (2u << gl) <= p->sample_count) ++gl;   // min(N, 64) rounded down to a power of two
-    P.group_log2 = gl;
-    P.tmax = p->radius > 0.0f ? p->radius : INFINITY;
-    P.seed_lo = p->seed_lo;
-    P.seed_hi = p->seed_hi;
-    const dim3 grid((W + MPT_DN_TILE - 1) / MPT_DN_TILE, (H + MPT_DN_TILE - 1) / MPT_DN_TILE);
-    SceneDev sc = scene_dev(ctx);
-    AccelDev ac = {};
-    if (resolve_walk(ctx, p->walk) == 1) {
-        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);
-        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        hipLaunchKernelGGL(k_ao<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
-    } else if (ctx->n_lds_nodes == ctx->n_nodes) {
-        hipLaunchKernelGGL(k_ao<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    } else {
-        hipLaunchKernelGGL(k_ao<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    }
-    HIPCHK(hipGetLastError());
-    return MPT_OK;
-}
-static size_t ao_out_bytes(size_t n_pixels) { return n_pixels * 8 + 16; }
-static bool ao_have(const mpt_ctx* ctx) {
-    return ctx->ao.epoch != 0 && ctx->ao.epoch == ctx->guide_epoch && ctx->ao.W == ctx->W && ctx->ao.H == ctx->H && ctx->ao.out;
-}
-static int ambient_occlusion_impl(mpt_ctx* ctx, const mpt_ao_params* p, mpt_ao_info* out) {
-    if (!ctx) return MPT_ERR_INVALID_ARG;
-    int rc = ao_check(ctx, p);
-    if (rc) return rc;
-    if ((rc = wait_impl(ctx))) return rc;
-    if ((rc = refresh_guides(ctx))) return rc;
-    AoState& a = ctx->ao;
-    const size_t n = (size_t)ctx->W * ctx->H;
-    if (!a.out || a.W != ctx->W || a.H != ctx->H) {
-        a = AoState{};
-        HIPCHK(a.out.alloc(ao_out_bytes(n)));
-        a.W = ctx->W;
-        a.H = ctx->H;
-    }
-    a.epoch = 0;
-    float key[14];
-    guide_key(ctx->u, key);
-    Event e0, e1;
-    HIPCHK(e0.create(hipEventCreate));
-    HIPCHK(e1.create(hipEventCreate));
-    HIPCHK(hipEventRecord(e0.get(), ctx->stream));
-    if ((rc = ao_launch(ctx, ctx->W, ctx->H, ctx->d_aov_ad.get(), ctx->d_aov_nc.get(), key, p, a.out.get()))) return rc;
-    HIPCHK(hipEventRecord(e1.get(), ctx->stream));
-    unsigned long long totals[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(totals, a.out.get() + 2 * n, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    a.epoch = ctx->guide_epoch;
-    if (out) {
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
-        out->pixels_surface = totals[0];
-        out->rays = totals[0] * p->sample_count;
-        out->rays_occluded = totals[1];
-        out->device_ms = (double)ms;
-    }
-    return MPT_OK;
-}
-static int read_ao_impl(mpt_ctx* ctx, float* ao, uint32_t* occluded) {
-    if (!ctx || !ao) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-    if (!ao_have(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_ambient_occlusion result for this scene and size");
-    const size_t n = (size_t)ctx->W * ctx->H;
-    HIPCHK(hipMemcpyAsync(ao, ctx->ao.out.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (occluded) HIPCHK(hipMemcpyAsync(occluded, ctx->ao.out.get() + n, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MPT_OK;
-}
-static int ao_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* ad, const float* nc, const mpt_uniforms* cam, const mpt_ao_params* p,
-                         float* ao_out, uint32_t* occ_out) {
-    if (!ctx || !ad || !nc || !cam || !ao_out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
-    int rc = ao_check(ctx, p);
-    if (rc) return rc;
-    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H;
-    DevMem<> d_ad, d_nc;
-    DevMem<float> d_out;
-    HIPCHK(d_ad.alloc(n * 16));
-    HIPCHK(d_nc.alloc(n * 16));
-    HIPCHK(d_out.alloc(ao_out_bytes(n)));
-    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    float key[14];
-    guide_key(*cam, key);
-    if ((rc = ao_launch(ctx, W, H, (const float4*)d_ad.get(), (const float4*)d_nc.get(), key, p, d_out.get()))) return rc;
-    HIPCHK(hipMemcpyAsync(ao_out, d_out.get(), n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (occ_out) HIPCHK(hipMemcpyAsync(occ_out, d_out.get() + n, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MPT_OK;
-}
 extern "C" int mpt_trace_occluded(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, int32_t walk, uint8_t* occluded_out,
                                   uint32_t* flags_out) {
     return guarded(ctx, [&] { return trace_occluded_impl(ctx, o, d, tmax, n, walk, occluded_out, flags_out); });
@@ -2670,692 +2377,12 @@ extern "C" int mpt_trace_occluded(mpt_ctx* ctx, const float* o, const float* d, 
 extern "C" int mpt_time_trace(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, uint32_t warmup, uint32_t reps, double* ms_out) {
     return guarded(ctx, [&] { return time_trace_impl(ctx, o, d, tmax, n, warmup, reps, ms_out); });
 }
-extern "C" int mpt_ambient_occlusion(mpt_ctx* ctx, const mpt_ao_params* p, mpt_ao_info* out) {
-    return guarded(ctx, [&] { return ambient_occlusion_impl(ctx, p, out); });
-}
-extern "C" int mpt_read_ao(mpt_ctx* ctx, float* ao, uint32_t* occluded) {
-    return guarded(ctx, [&] { return read_ao_impl(ctx, ao, occluded); });
-}
-extern "C" int mpt_ao_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
-    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
-    if (!ao_have(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_ambient_occlusion result for this scene and size");
-    *p = ctx->ao.out.get();
-    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 4;
-    return MPT_OK;
-}
-extern "C" int mpt_ao_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* albedo_depth, const float* normal_class, const mpt_uniforms* cam,
-                            const mpt_ao_params* p, float* ao_out, uint32_t* occluded_out) {
-    return guarded(ctx, [&] { return ao_image_impl(ctx, w, h, albedo_depth, normal_class, cam, p, ao_out, occluded_out); });
-}
 
-// ---- temporal accumulation (mpt_temporal.h; the specification is in include/mpt.h) ---------------------------------------------
-struct TpResolved {
-    float max_history, depth_tol, normal_thr, min_weight;
-};
-static int tp_resolve(mpt_ctx* ctx, const mpt_temporal_params* p, bool use_source, TpResolved& r) {
-    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null temporal params");
-    if (use_source) {
-        if (p->source != MPT_DENOISE_SUM && p->source != MPT_DENOISE_FRAME) return fail(ctx, MPT_ERR_INVALID_ARG, "bad temporal source");
-        if (p->source == MPT_DENOISE_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "temporal accumulation of the sum with samples = 0");
-    }
-    if (p->depth_tolerance != p->depth_tolerance || p->normal_threshold != p->normal_threshold || p->min_weight != p->min_weight)
-        return fail(ctx, MPT_ERR_INVALID_ARG, "a temporal tolerance is NaN");
-    r.max_history = (float)(p->max_history ? p->max_history : MPT_TEMPORAL_DEFAULT_MAX_HISTORY);
-    r.depth_tol = p->depth_tolerance > 0.0f ? p->depth_tolerance : MPT_TEMPORAL_DEFAULT_DEPTH_TOLERANCE;
-    r.normal_thr = p->normal_threshold > 0.0f ? p->normal_threshold : MPT_TEMPORAL_DEFAULT_NORMAL_THRESHOLD;
-    r.min_weight = p->min_weight > 0.0f ? p->min_weight : MPT_TEMPORAL_DEFAULT_MIN_WEIGHT;
-    return MPT_OK;
-}
-// The per-frame constants of k_tp_reproject from the two cameras' guide_key (cam, vu, vv, first, screen size), by the expressions of
-// include/mpt.h in float32, and the launch.  key_h = nullptr: no history.  Returns the number of pixels reset in *n_reset_out.
-template <class Frame>
-static int tp_frame_constants(Frame& T, const float key[14], const float* key_h, const TpResolved& r) {
-    T.fW = (float)T.W;
-    T.fH = (float)T.H;
-    T.cam = F3{key[0], key[1], key[2]};
-    T.vu = F3{key[3], key[4], key[5]};
-    T.vv = F3{key[6], key[7], key[8]};
-    T.first = F3{key[9], key[10], key[11]};
-    T.depth_tol = r.depth_tol;
-    T.normal_thr = r.normal_thr;
-    T.min_weight = r.min_weight;
-    T.max_history = r.max_history;
-    int mode = MPT_TP_NONE;
-    if (key_h) {
-        mode = memcmp(key, key_h, 14 * sizeof(float)) == 0 ? MPT_TP_SAME : MPT_TP_MOVED;
-        T.cam_h = F3{key_h[0], key_h[1], key_h[2]};
-        T.vu_h = F3{key_h[3], key_h[4], key_h[5]};
-        T.vv_h = F3{key_h[6], key_h[7], key_h[8]};
-        const F3 a = T.vu_h, b = T.vv_h;
-        T.nn = F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-        T.fc = F3{key_h[9] - key_h[0], key_h[10] - key_h[1], key_h[11] - key_h[2]};
-        T.fcnn = tp_dot(T.fc, T.nn);
-        T.uu = tp_dot(T.vu_h, T.vu_h);
-        T.vvl = tp_dot(T.vv_h, T.vv_h);
-    }
-    return mode;
-}
-static int tp_launch(mpt_ctx* ctx, TpFrame T, const float key[14], const float* key_h, const TpResolved& r, uint64_t* n_reset_out) {
-    const int mode = tp_frame_constants(T, key, key_h, r);
-    HIPCHK(hipMemsetAsync(T.n_reset, 0, 8, ctx->stream));
-    const dim3 grid((T.W + MPT_DN_TILE - 1) / MPT_DN_TILE, (T.H + MPT_DN_TILE - 1) / MPT_DN_TILE);
-    void* args[] = {&T};
-    HIPCHK(hipLaunchKernel(tp_kernel(mode), grid, dim3(256), args, 0, ctx->stream));
-    unsigned long long n = 0;
-    HIPCHK(hipMemcpyAsync(&n, T.n_reset, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    *n_reset_out = n;
-    return MPT_OK;
-}
-static bool tp_have_history(const mpt_ctx* ctx) {
-    return ctx->tp.epoch != 0 && ctx->tp.epoch == ctx->guide_epoch && ctx->tp.W == ctx->W && ctx->tp.H == ctx->H && ctx->tp.hist[ctx->tp.cur];
-}
-static int temporal_accumulate_impl(mpt_ctx* ctx, const mpt_temporal_params* p, mpt_temporal_info* out) {
-    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-    TpResolved r;
-    int rc = tp_resolve(ctx, p, true, r);
-    if (rc) return rc;
-    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
-    if ((rc = refresh_guides(ctx))) return rc;
-    TemporalState& tp = ctx->tp;
-    const size_t n = (size_t)ctx->W * ctx->H;
-    const bool have = tp_have_history(ctx);
-    if (!tp.hist[0] || tp.W != ctx->W || tp.H != ctx->H) {
-        tp.W = tp.H = 0;
-        tp.epoch = 0;
-        for (DevMem<float4>* b : {&tp.hist[0], &tp.hist[1], &tp.guide[0], &tp.guide[1]}) HIPCHK(b->alloc(n * 16));
-        HIPCHK(tp.n_reset.alloc(8));
-        tp.W = ctx->W;
-        tp.H = ctx->H;
-        tp.cur = 0;
-    }
-    const bool sum = p->source == MPT_DENOISE_SUM;
-    const int nxt = tp.cur ^ 1;
-    TpFrame T = {};
-    T.color = sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target].get();
-    T.samples = sum ? (float)p->samples : 1.0f;
-    T.ad = ctx->d_aov_ad.get();
-    T.nc = ctx->d_aov_nc.get();
-    T.hist_in = tp.hist[tp.cur].get();
-    T.guide_in = tp.guide[tp.cur].get();
-    T.hist_out = tp.hist[nxt].get();
-    T.guide_out = tp.guide[nxt].get();
-    T.n_reset = tp.n_reset.get();
-    T.W = ctx->W;
-    T.H = ctx->H;
-    float key[14];
-    guide_key(ctx->u, key);
-    uint64_t n_reset = 0;
-    tp.epoch = 0;   // (no history if the launch fails)
-    if ((rc = tp_launch(ctx, T, key, have ? tp.cam : nullptr, r, &n_reset))) return rc;
-    tp.cur = nxt;
-    tp.epoch = ctx->guide_epoch;
-    memcpy(tp.cam, key, sizeof key);
-    if (out) {
-        out->pixels_reset = n_reset;
-        out->pixels_reprojected = (uint64_t)n - n_reset;
-    }
-    return MPT_OK;
-}
-static int temporal_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const float* ad, const float* nc, const mpt_uniforms* cam,
-                               const float* hist_h, const float* ad_h, const float* nc_h, const mpt_uniforms* cam_h,
-                               const mpt_temporal_params* p, float* hist_out, mpt_temporal_info* out) {
-    if (!ctx || !color || !ad || !nc || !cam || !p || !hist_out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31))
-        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
-    if (hist_h && (!ad_h || !nc_h || !cam_h)) return fail(ctx, MPT_ERR_INVALID_ARG, "a history without its guides or camera");
-    TpResolved r;
-    int rc = tp_resolve(ctx, p, false, r);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H;
-    DevMem<> d_c, d_ad, d_nc, d_h, d_adh, d_nch, d_gh, d_o, d_go;
-    DevMem<unsigned long long> d_cnt;
-    for (DevMem<>* b : {&d_c, &d_ad, &d_nc, &d_o, &d_go}) HIPCHK(b->alloc(n * 16));
-    HIPCHK(d_cnt.alloc(8));
-    HIPCHK(hipMemcpyAsync(d_c.get(), color, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    float key[14], key_h[14];
-    guide_key(*cam, key);
-    if (hist_h) {
-        for (DevMem<>* b : {&d_h, &d_adh, &d_nch, &d_gh}) HIPCHK(b->alloc(n * 16));
-        HIPCHK(hipMemcpyAsync(d_h.get(), hist_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(d_adh.get(), ad_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(d_nch.get(), nc_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_tp_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float4*)d_adh.get(),
-                           (const float4*)d_nch.get(), (uint32_t)n, (float4*)d_gh.get());
-        HIPCHK(hipGetLastError());
-        guide_key(*cam_h, key_h);
-    }
-    TpFrame T = {};
-    T.color = (const float4*)d_c.get();
-    T.samples = 1.0f;
-    T.ad = (const float4*)d_ad.get();
-    T.nc = (const float4*)d_nc.get();
-    T.hist_in = (const float4*)d_h.get();
-    T.guide_in = (const float4*)d_gh.get();
-    T.hist_out = (float4*)d_o.get();
-    T.guide_out = (float4*)d_go.get();
-    T.n_reset = d_cnt.get();
-    T.W = W;
-    T.H = H;
-    uint64_t n_reset = 0;
-    if ((rc = tp_launch(ctx, T, key, hist_h ? key_h : nullptr, r, &n_reset))) return rc;
-    HIPCHK(hipMemcpyAsync(hist_out, d_o.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (out) {
-        out->pixels_reset = n_reset;
-        out->pixels_reprojected = (uint64_t)n - n_reset;
-    }
-    return MPT_OK;
-}
-static int denoise_temporal_impl(mpt_ctx* ctx, const mpt_denoise_params* p) {
-    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-    DnSigmas sg;
-    int rc = dn_resolve(ctx, p, sg);
-    if (rc) return rc;
-    if (!tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
-    if ((rc = wait_impl(ctx))) return rc;
-    if ((rc = refresh_guides(ctx))) return rc;
-    float4* x[2] = {ctx->d_dn_x[0].get(), ctx->d_dn_x[1].get()};
-    ctx->denoised_valid = false;
-    if ((rc = dn_filter(ctx, ctx->stream, ctx->W, ctx->H, ctx->tp.hist[ctx->tp.cur].get(), 1.0f, ctx->d_aov_ad.get(), ctx->d_dn_guide.get(), x, sg,
-                        ctx->d_denoised.get())))
-        return rc;
-    ctx->denoised_valid = true;
-    return MPT_OK;
-}
-extern "C" int mpt_temporal_accumulate(mpt_ctx* ctx, const mpt_temporal_params* p, mpt_temporal_info* out) {
-    return guarded(ctx, [&] { return temporal_accumulate_impl(ctx, p, out); });
-}
-extern "C" int mpt_read_temporal(mpt_ctx* ctx, float* rgba) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx || !rgba) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-        if (!tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
-        HIPCHK(hipMemcpyAsync(rgba, ctx->tp.hist[ctx->tp.cur].get(), (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_temporal_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
-    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
-    if (!tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
-    *p = ctx->tp.hist[ctx->tp.cur].get();
-    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 16;
-    return MPT_OK;
-}
-extern "C" int mpt_temporal_reset(mpt_ctx* ctx) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx) return MPT_ERR_INVALID_ARG;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        ctx->tp = TemporalState{};
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_denoise_temporal(mpt_ctx* ctx, const mpt_denoise_params* p) {
-    return guarded(ctx, [&] { return denoise_temporal_impl(ctx, p); });
-}
-extern "C" int mpt_temporal_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth_cur, const float* normal_class_cur,
-                                  const mpt_uniforms* cam_cur, const float* history_prev, const float* albedo_depth_prev, const float* normal_class_prev,
-                                  const mpt_uniforms* cam_prev, const mpt_temporal_params* p, float* history_out, mpt_temporal_info* out) {
-    return guarded(ctx, [&] {
-        return temporal_image_impl(ctx, w, h, color, albedo_depth_cur, normal_class_cur, cam_cur, history_prev, albedo_depth_prev, normal_class_prev,
-                                   cam_prev, p, history_out, out);
-    });
-}
+// ---- the post-processing stages: guide pass and denoiser, ambient occlusion, temporal accumulation, SVGF, display ----------------------
+#include "mpt_post.h"
 
-// ---- SVGF (mpt_svgf.h; the specification is in include/mpt.h) -------------------------------------------------------------------
-struct SvResolved {
-    TpResolved tp;
-    int iterations, feedback;
-    float sl, sn, sz;
-};
-static int sv_resolve(mpt_ctx* ctx, const mpt_svgf_params* p, bool use_source, SvResolved& r) {
-    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null svgf params");
-    if (use_source) {
-        if (p->source != MPT_DENOISE_SUM && p->source != MPT_DENOISE_FRAME) return fail(ctx, MPT_ERR_INVALID_ARG, "bad svgf source");
-        if (p->source == MPT_DENOISE_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "svgf accumulation of the sum with samples = 0");
-    }
-    if (p->depth_tolerance != p->depth_tolerance || p->normal_threshold != p->normal_threshold || p->min_weight != p->min_weight)
-        return fail(ctx, MPT_ERR_INVALID_ARG, "an svgf tolerance is NaN");
-    const mpt_temporal_params t = {p->source, p->samples, p->max_history, p->depth_tolerance, p->normal_threshold, p->min_weight};
-    const int rc = tp_resolve(ctx, &t, false, r.tp);   // (checked above: only the defaults of step A are taken from it)
-    if (rc) return rc;
-    if (p->sigma_luminance != p->sigma_luminance || p->sigma_normal != p->sigma_normal || p->sigma_depth != p->sigma_depth)
-        return fail(ctx, MPT_ERR_INVALID_ARG, "an svgf sigma is NaN");
-    if (p->iterations > MPT_DENOISE_MAX_ITERATIONS) return fail(ctx, MPT_ERR_INVALID_ARG, "svgf iterations > 8");
-    r.iterations = p->iterations < 0 ? MPT_SVGF_DEFAULT_ITERATIONS : p->iterations;
-    r.sl = p->sigma_luminance > 0.0f ? p->sigma_luminance : MPT_SVGF_DEFAULT_SIGMA_LUMINANCE;
-    r.sn = p->sigma_normal > 0.0f ? p->sigma_normal : MPT_SVGF_DEFAULT_SIGMA_NORMAL;
-    r.sz = p->sigma_depth > 0.0f ? p->sigma_depth : MPT_SVGF_DEFAULT_SIGMA_DEPTH;
-    r.feedback = p->feedback < 0 ? MPT_SVGF_DEFAULT_FEEDBACK : p->feedback != 0;
-    return MPT_OK;
-}
-// Steps A, B, C on the stream, then one wait for the reset count.  T: the buffers of step A (its hist_out / mom_out are what B and C
-// read); dn_guide: the denoiser's packed guide of the current frame; xv[0] = (X, V_0), xv[1], xv[2] the ping-pong; out: the frame.
-static int sv_run(mpt_ctx* ctx, SvFrame T, const float4* dn_guide, float4* const xv[3], float4* out, const float key[14], const float* key_h,
-                  const SvResolved& r, uint64_t* n_reset_out) {
-    const int mode = tp_frame_constants(T, key, key_h, r.tp);
-    const uint32_t W = T.W, H = T.H, n = W * H;
-    HIPCHK(hipMemsetAsync(T.n_reset, 0, 8, ctx->stream));
-    const dim3 grid((W + MPT_DN_TILE - 1) / MPT_DN_TILE, (H + MPT_DN_TILE - 1) / MPT_DN_TILE);
-    {
-        void* args[] = {&T};
-        HIPCHK(hipLaunchKernel(sv_reproject_kernel(mode), grid, dim3(256), args, 0, ctx->stream));
-    }
-    SvVariance S = {T.hist_out, T.mom_out, dn_guide, xv[0], W, H, r.sn, r.sz};
-    hipLaunchKernelGGL(k_sv_variance, grid, dim3(256), 0, ctx->stream, S);
-    HIPCHK(hipGetLastError());
-    if (r.iterations == 0) {
-        hipLaunchKernelGGL(k_sv_modulate, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const float4*)T.hist_out, T.ad, dn_guide, n, out);
-        HIPCHK(hipGetLastError());
-    }
-    for (int i = 0; i < r.iterations; ++i) {
-        const bool last = i == r.iterations - 1;
-        SvLevel L;
-        L.xin = i == 0 ? xv[0] : xv[1 + ((i - 1) & 1)];
-        L.guide = dn_guide;
-        L.ad = T.ad;
-        L.hist = T.hist_out;
-        L.xout = last ? out : xv[1 + (i & 1)];
-        L.feedback = i == 0 && r.feedback ? T.hist_out : nullptr;
-        L.W = W;
-        L.H = H;
-        L.step = 1u << i;
-        L.sigma_n = r.sn;
-        L.sigma_z = r.sz;
-        L.sigma_l = r.sl;
-        const bool lds = L.step <= MPT_DN_LDS_MAX_STEP;
-        const uint32_t Tl = MPT_DN_TILE + 4u * L.step;
-        const void* k = lds ? sv_level_kernel<true>(last) : sv_level_kernel<false>(last);
-        void* args[] = {&L};
-        HIPCHK(hipLaunchKernel(k, grid, dim3(256), args, lds ? (size_t)Tl * Tl * 32u : 0u, ctx->stream));
-    }
-    unsigned long long cnt = 0;
-    HIPCHK(hipMemcpyAsync(&cnt, T.n_reset, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    *n_reset_out = cnt;
-    return MPT_OK;
-}
-static bool sv_have_state(const mpt_ctx* ctx) {
-    return ctx->sv.epoch != 0 && ctx->sv.epoch == ctx->guide_epoch && ctx->sv.W == ctx->W && ctx->sv.H == ctx->H && ctx->sv.hist[ctx->sv.cur];
-}
-static int svgf_accumulate_impl(mpt_ctx* ctx, const mpt_svgf_params* p, mpt_svgf_info* out) {
-    if (!ctx || !p) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-    SvResolved r;
-    int rc = sv_resolve(ctx, p, true, r);
-    if (rc) return rc;
-    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
-    if ((rc = refresh_guides(ctx))) return rc;
-    SvgfState& sv = ctx->sv;
-    const size_t n = (size_t)ctx->W * ctx->H;
-    const bool have = sv_have_state(ctx);
-    if (!sv.hist[0] || sv.W != ctx->W || sv.H != ctx->H) {
-        sv.W = sv.H = 0;
-        sv.epoch = 0;
-        for (DevMem<float4>* b : {&sv.hist[0], &sv.hist[1], &sv.guide[0], &sv.guide[1], &sv.xv[0], &sv.xv[1], &sv.xv[2], &sv.out}) HIPCHK(b->alloc(n * 16));
-        for (DevMem<float2>* b : {&sv.mom[0], &sv.mom[1]}) HIPCHK(b->alloc(n * 8));
-        HIPCHK(sv.n_reset.alloc(8));
-        sv.W = ctx->W;
-        sv.H = ctx->H;
-        sv.cur = 0;
-    }
-    const bool sum = p->source == MPT_DENOISE_SUM;
-    const int nxt = sv.cur ^ 1;
-    SvFrame T = {};
-    T.color = sum ? ctx->d_sum : ctx->d_accum[ctx->cur_target].get();
-    T.samples = sum ? (float)p->samples : 1.0f;
-    T.ad = ctx->d_aov_ad.get();
-    T.nc = ctx->d_aov_nc.get();
-    T.hist_in = sv.hist[sv.cur].get();
-    T.mom_in = sv.mom[sv.cur].get();
-    T.guide_in = sv.guide[sv.cur].get();
-    T.hist_out = sv.hist[nxt].get();
-    T.mom_out = sv.mom[nxt].get();
-    T.guide_out = sv.guide[nxt].get();
-    T.n_reset = sv.n_reset.get();
-    T.W = ctx->W;
-    T.H = ctx->H;
-    float key[14];
-    guide_key(ctx->u, key);
-    float4* xv[3] = {sv.xv[0].get(), sv.xv[1].get(), sv.xv[2].get()};
-    uint64_t n_reset = 0;
-    sv.epoch = 0;   // (no state if a launch fails)
-    if ((rc = sv_run(ctx, T, ctx->d_dn_guide.get(), xv, sv.out.get(), key, have ? sv.cam : nullptr, r, &n_reset))) return rc;
-    sv.cur = nxt;
-    sv.epoch = ctx->guide_epoch;
-    memcpy(sv.cam, key, sizeof key);
-    if (out) {
-        out->pixels_reset = n_reset;
-        out->pixels_reprojected = (uint64_t)n - n_reset;
-    }
-    return MPT_OK;
-}
-// (M1, M2) and (X, V_0) of the device -> the (M1, M2, V_0, 0) the readers return
-static void sv_moments_variance(const std::vector<float>& mom, const std::vector<float>& xv, size_t n, float* out) {
-    for (size_t i = 0; i < n; ++i) {
-        out[4 * i + 0] = mom[2 * i];
-        out[4 * i + 1] = mom[2 * i + 1];
-        out[4 * i + 2] = xv[4 * i + 3];
-        out[4 * i + 3] = 0.0f;
-    }
-}
-static int svgf_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const float* ad, const float* nc, const mpt_uniforms* cam,
-                           const float* hist_h, const float* mom_h, const float* ad_h, const float* nc_h, const mpt_uniforms* cam_h,
-                           const mpt_svgf_params* p, float* hist_out, float* mv_out, float* filtered_out, mpt_svgf_info* out) {
-    if (!ctx || !color || !ad || !nc || !cam || !p || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31))
-        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
-    if (hist_h && (!mom_h || !ad_h || !nc_h || !cam_h)) return fail(ctx, MPT_ERR_INVALID_ARG, "a history without its moments, guides or camera");
-    SvResolved r;
-    int rc = sv_resolve(ctx, p, false, r);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    const size_t n = (size_t)W * H;
-    DevMem<> d_c, d_ad, d_nc, d_g, d_h, d_m, d_adh, d_nch, d_gh, d_ho, d_mo, d_go, d_x0, d_x1, d_x2, d_o;
-    DevMem<unsigned long long> d_cnt;
-    for (DevMem<>* b : {&d_c, &d_ad, &d_nc, &d_g, &d_ho, &d_go, &d_x0, &d_x1, &d_x2, &d_o}) HIPCHK(b->alloc(n * 16));
-    HIPCHK(d_mo.alloc(n * 8));
-    HIPCHK(d_cnt.alloc(8));
-    HIPCHK(hipMemcpyAsync(d_c.get(), color, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_ad.get(), ad, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_nc.get(), nc, n * 16, hipMemcpyHostToDevice, ctx->stream));
-    const dim3 lin((uint32_t)((n + 255) / 256));
-    hipLaunchKernelGGL(k_dn_pack, lin, dim3(256), 0, ctx->stream, (const float4*)d_ad.get(), (const float4*)d_nc.get(), (uint32_t)n, (float4*)d_g.get());
-    HIPCHK(hipGetLastError());
-    float key[14], key_h[14];
-    guide_key(*cam, key);
-    if (hist_h) {
-        for (DevMem<>* b : {&d_h, &d_adh, &d_nch, &d_gh}) HIPCHK(b->alloc(n * 16));
-        HIPCHK(d_m.alloc(n * 8));
-        HIPCHK(hipMemcpyAsync(d_h.get(), hist_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(d_m.get(), mom_h, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(d_adh.get(), ad_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipMemcpyAsync(d_nch.get(), nc_h, n * 16, hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_sv_pack, lin, dim3(256), 0, ctx->stream, (const float4*)d_adh.get(), (const float4*)d_nch.get(), (uint32_t)n,
-                           (float4*)d_gh.get());
-        HIPCHK(hipGetLastError());
-        guide_key(*cam_h, key_h);
-    }
-    SvFrame T = {};
-    T.color = (const float4*)d_c.get();
-    T.samples = 1.0f;
-    T.ad = (const float4*)d_ad.get();
-    T.nc = (const float4*)d_nc.get();
-    T.hist_in = (const float4*)d_h.get();
-    T.mom_in = (const float2*)d_m.get();
-    T.guide_in = (const float4*)d_gh.get();
-    T.hist_out = (float4*)d_ho.get();
-    T.mom_out = (float2*)d_mo.get();
-    T.guide_out = (float4*)d_go.get();
-    T.n_reset = d_cnt.get();
-    T.W = W;
-    T.H = H;
-    float4* xv[3] = {(float4*)d_x0.get(), (float4*)d_x1.get(), (float4*)d_x2.get()};
-    uint64_t n_reset = 0;
-    if ((rc = sv_run(ctx, T, (const float4*)d_g.get(), xv, (float4*)d_o.get(), key, hist_h ? key_h : nullptr, r, &n_reset))) return rc;
-    if (hist_out) HIPCHK(hipMemcpyAsync(hist_out, d_ho.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (filtered_out) HIPCHK(hipMemcpyAsync(filtered_out, d_o.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<float> mom, x0;
-    if (mv_out) {
-        mom.resize(n * 2);
-        x0.resize(n * 4);
-        HIPCHK(hipMemcpyAsync(mom.data(), d_mo.get(), n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(x0.data(), d_x0.get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (mv_out) sv_moments_variance(mom, x0, n, mv_out);
-    if (out) {
-        out->pixels_reset = n_reset;
-        out->pixels_reprojected = (uint64_t)n - n_reset;
-    }
-    return MPT_OK;
-}
-extern "C" int mpt_svgf_accumulate(mpt_ctx* ctx, const mpt_svgf_params* p, mpt_svgf_info* out) {
-    return guarded(ctx, [&] { return svgf_accumulate_impl(ctx, p, out); });
-}
-extern "C" int mpt_read_svgf(mpt_ctx* ctx, float* rgba) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx || !rgba) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-        if (!sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
-        HIPCHK(hipMemcpyAsync(rgba, ctx->sv.out.get(), (size_t)ctx->W * ctx->H * 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_svgf_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
-    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
-    if (!sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
-    *p = ctx->sv.out.get();
-    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 16;
-    return MPT_OK;
-}
-extern "C" int mpt_read_svgf_state(mpt_ctx* ctx, float* history, float* moments_variance) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx || !history || !moments_variance) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-        if (!sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
-        const size_t n = (size_t)ctx->W * ctx->H;
-        std::vector<float> mom(n * 2), x0(n * 4);
-        HIPCHK(hipMemcpyAsync(history, ctx->sv.hist[ctx->sv.cur].get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(mom.data(), ctx->sv.mom[ctx->sv.cur].get(), n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipMemcpyAsync(x0.data(), ctx->sv.xv[0].get(), n * 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        sv_moments_variance(mom, x0, n, moments_variance);
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_svgf_reset(mpt_ctx* ctx) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx) return MPT_ERR_INVALID_ARG;
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        ctx->sv = SvgfState{};
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_svgf_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* color, const float* albedo_depth_cur, const float* normal_class_cur,
-                              const mpt_uniforms* cam_cur, const float* history_prev, const float* moments_prev, const float* albedo_depth_prev,
-                              const float* normal_class_prev, const mpt_uniforms* cam_prev, const mpt_svgf_params* p, float* history_out,
-                              float* moments_variance_out, float* filtered_out, mpt_svgf_info* out) {
-    return guarded(ctx, [&] {
-        return svgf_image_impl(ctx, w, h, color, albedo_depth_cur, normal_class_cur, cam_cur, history_prev, moments_prev, albedo_depth_prev,
-                               normal_class_prev, cam_prev, p, history_out, moments_variance_out, filtered_out, out);
-    });
-}
-
-// ---- display (mpt_display.h; the specification is in include/mpt.h) --------------------------------------------------------------
-static_assert(sizeof(mpt_display_info) == 32 && offsetof(DpState, kept) == 32, "DpState begins with mpt_display_info");
-struct DpResolved {
-    DpExposure E;
-    float ww;   // REINHARD's white * white
-};
-static int dp_resolve(mpt_ctx* ctx, const mpt_display_params* p, bool use_source, DpResolved& r) {
-    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null display params");
-    if (use_source) {
-        if (p->source < MPT_DISPLAY_SUM || p->source > MPT_DISPLAY_ADAPTIVE) return fail(ctx, MPT_ERR_INVALID_ARG, "bad display source");
-        if (p->source == MPT_DISPLAY_SUM && p->samples == 0) return fail(ctx, MPT_ERR_INVALID_ARG, "display of the sum with samples = 0");
-    }
-    if (p->tone < MPT_TONE_CLAMP || p->tone > MPT_TONE_ACES) return fail(ctx, MPT_ERR_INVALID_ARG, "bad tone curve");
-    if (p->transfer < MPT_TRANSFER_SRGB || p->transfer > MPT_TRANSFER_LINEAR) return fail(ctx, MPT_ERR_INVALID_ARG, "bad transfer function");
-    if (p->percentile > 100u) return fail(ctx, MPT_ERR_INVALID_ARG, "display percentile above 100");
-    if (p->exposure != p->exposure || p->white != p->white || p->key != p->key || p->adaptation != p->adaptation)
-        return fail(ctx, MPT_ERR_INVALID_ARG, "a display parameter is NaN");
-    const float white = p->white > 0.0f ? p->white : 4.0f;
-    r.ww = white * white;
-    r.E.exposure = p->exposure > 0.0f ? p->exposure : 1.0f;
-    r.E.key = p->key > 0.0f ? p->key : 0.18f;
-    r.E.adaptation = p->adaptation > 0.0f && p->adaptation < 1.0f ? p->adaptation : 0.0f;
-    r.E.percentile = p->percentile ? p->percentile : 50u;
-    r.E.auto_exposure = p->auto_exposure != 0;
-    return MPT_OK;
-}
-// histogram (auto-exposure only) -> exposure -> present, back to back on the context's stream; the host reads the 32-byte result once
-static int dp_run(mpt_ctx* ctx, DpSource S, int src_kind, const mpt_display_params* p, const DpResolved& r, uint32_t* hist, DpState* st,
-                  const float* tables, uint32_t* out_words, mpt_display_info* info) {
-    if (r.E.auto_exposure) {
-        HIPCHK(hipMemsetAsync(hist, 0, MPT_DP_BINS * 4, ctx->stream));
-        const uint32_t blocks = std::min<uint32_t>((S.n + 255u) / 256u, (uint32_t)std::max(1, ctx->prop.multiProcessorCount) * 8u);
-        void* args[] = {&S, &hist};
-        HIPCHK(hipLaunchKernel(dp_histogram_kernel(src_kind, ctx->dp_hist_agg), dim3(blocks), dim3(256), args, 0, ctx->stream));
-    }
-    DpExposure E = r.E;
-    hipLaunchKernelGGL(k_dp_exposure, dim3(1), dim3(64), 0, ctx->stream, (const uint32_t*)hist, E, st);
-    HIPCHK(hipGetLastError());
-    DpTone P = {tables + (size_t)p->transfer * 255, r.ww};
-    const uint32_t per_block = 256u * (uint32_t)ctx->dp_px;
-    void* args[] = {&S, &P, &st, &out_words};
-    HIPCHK(hipLaunchKernel(dp_present_kernel(src_kind, p->tone, ctx->dp_px), dim3((S.n + per_block - 1u) / per_block), dim3(256), args, 0, ctx->stream));
-    mpt_display_info got = {};
-    HIPCHK(hipMemcpyAsync(&got, st, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (info) *info = got;
-    return MPT_OK;
-}
-static bool dp_have_state(const mpt_ctx* ctx) {
-    return ctx->dp.epoch != 0 && ctx->dp.epoch == ctx->guide_epoch && ctx->dp.W == ctx->W && ctx->dp.H == ctx->H && ctx->dp.out;
-}
-static int dp_upload_tables(mpt_ctx* ctx, DevMem<float>& tables) {
-    HIPCHK(tables.alloc(sizeof MPT_DISPLAY_TABLE));
-    HIPCHK(hipMemcpy(tables.get(), MPT_DISPLAY_TABLE, sizeof MPT_DISPLAY_TABLE, hipMemcpyHostToDevice));
-    return MPT_OK;
-}
-static int display_impl(mpt_ctx* ctx, const mpt_display_params* p, mpt_display_info* out) {
-    if (!ctx) return MPT_ERR_INVALID_ARG;
-    DpResolved r;
-    int rc = dp_resolve(ctx, p, true, r);
-    if (rc) return rc;
-    if (!ctx->d_sum) return fail(ctx, MPT_ERR_NOT_READY, "mpt_resize not called");
-    if (p->source == MPT_DISPLAY_DENOISED && !ctx->denoised_valid) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_denoise result at this size");
-    if (p->source == MPT_DISPLAY_TEMPORAL && !tp_have_history(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no temporal history");
-    if (p->source == MPT_DISPLAY_SVGF && !sv_have_state(ctx)) return fail(ctx, MPT_ERR_NOT_READY, "no svgf state");
-    if (p->source == MPT_DISPLAY_ADAPTIVE && !ctx->ad.tile_count) return fail(ctx, MPT_ERR_NOT_READY, "no adaptive render at this size");
-    if ((rc = wait_impl(ctx))) return rc;   // (reports a failed mpt_render_async; the sum is complete afterwards)
-    HIPCHK(hipSetDevice(ctx->device));
-    const uint32_t n = ctx->W * ctx->H;
-    if (!dp_have_state(ctx)) {   // the first call, or the first after a scene call: the buffers are made whole before they replace the old ones
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        DisplayState d;
-        HIPCHK(d.out.alloc(((size_t)n * 4 + 15) & ~(size_t)15));
-        HIPCHK(d.hist.alloc(MPT_DP_BINS * 4));
-        HIPCHK(d.st.alloc(sizeof(DpState)));
-        HIPCHK(hipMemset(d.hist.get(), 0, MPT_DP_BINS * 4));
-        HIPCHK(hipMemset(d.st.get(), 0, sizeof(DpState)));
-        if ((rc = dp_upload_tables(ctx, d.tables))) return rc;
-        d.W = ctx->W;
-        d.H = ctx->H;
-        d.epoch = ctx->guide_epoch;
-        ctx->dp = std::move(d);
-    }
-    DisplayState& dp = ctx->dp;
-    DpSource S = {};
-    S.n = n;
-    S.W = ctx->W;
-    S.tiles_x = (ctx->W + 7) / 8;
-    S.samples = 1.0f;
-    int kind = MPT_DP_SRC_RAW;
-    switch (p->source) {
-    case MPT_DISPLAY_SUM:
-        S.color = ctx->d_sum;
-        S.samples = (float)p->samples;
-        kind = MPT_DP_SRC_DIV;
-        break;
-    case MPT_DISPLAY_FRAME: S.color = ctx->d_accum[ctx->cur_target].get(); break;
-    case MPT_DISPLAY_DENOISED: S.color = ctx->d_denoised.get(); break;
-    case MPT_DISPLAY_TEMPORAL: S.color = ctx->tp.hist[ctx->tp.cur].get(); break;
-    case MPT_DISPLAY_SVGF: S.color = ctx->sv.out.get(); break;
-    default:
-        S.color = ctx->d_sum;
-        S.tile_count = ctx->ad.tile_count.get();
-        kind = MPT_DP_SRC_TILE;
-        break;
-    }
-    dp.shown = false;
-    if ((rc = dp_run(ctx, S, kind, p, r, dp.hist.get(), dp.st.get(), dp.tables.get(), dp.out.get(), out))) return rc;
-    dp.shown = true;
-    return MPT_OK;
-}
-static int display_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* color, const mpt_display_params* p, const float* prev_auto_scale,
-                              uint8_t* rgba8_out, uint32_t* histogram_out, mpt_display_info* out) {
-    if (!ctx || !color || !rgba8_out || W == 0 || H == 0 || (uint64_t)W * H >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
-    DpResolved r;
-    int rc = dp_resolve(ctx, p, false, r);
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(ctx->device));
-    const uint32_t n = W * H;
-    DevMem<float4> d_c;
-    DevMem<uint32_t> d_o, d_h;
-    DevMem<DpState> d_st;
-    DevMem<float> d_t;
-    HIPCHK(d_c.alloc((size_t)n * 16));
-    HIPCHK(d_o.alloc(((size_t)n * 4 + 15) & ~(size_t)15));
-    HIPCHK(d_h.alloc(MPT_DP_BINS * 4));
-    HIPCHK(d_st.alloc(sizeof(DpState)));
-    if ((rc = dp_upload_tables(ctx, d_t))) return rc;
-    DpState st0 = {};
-    if (prev_auto_scale) {
-        st0.kept = *prev_auto_scale;
-        st0.have_kept = 1;
-    }
-    HIPCHK(hipMemcpyAsync(d_c.get(), color, (size_t)n * 16, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_st.get(), &st0, sizeof st0, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemsetAsync(d_h.get(), 0, MPT_DP_BINS * 4, ctx->stream));
-    DpSource S = {};
-    S.color = d_c.get();
-    S.n = n;
-    S.W = W;
-    S.tiles_x = (W + 7) / 8;
-    S.samples = 1.0f;
-    if ((rc = dp_run(ctx, S, MPT_DP_SRC_RAW, p, r, d_h.get(), d_st.get(), d_t.get(), d_o.get(), out))) return rc;
-    HIPCHK(hipMemcpyAsync(rgba8_out, d_o.get(), (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (histogram_out) HIPCHK(hipMemcpyAsync(histogram_out, d_h.get(), MPT_DP_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return MPT_OK;
-}
-extern "C" int mpt_display(mpt_ctx* ctx, const mpt_display_params* p, mpt_display_info* out) {
-    return guarded(ctx, [&] { return display_impl(ctx, p, out); });
-}
-extern "C" int mpt_read_display(mpt_ctx* ctx, uint8_t* rgba8) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx || !rgba8) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-        if (!dp_have_state(ctx) || !ctx->dp.shown) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_display result");
-        HIPCHK(hipMemcpyAsync(rgba8, ctx->dp.out.get(), (size_t)ctx->W * ctx->H * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_display_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) {
-    if (!ctx || !p) return MPT_ERR_INVALID_ARG;
-    if (!dp_have_state(ctx) || !ctx->dp.shown) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_display result");
-    *p = ctx->dp.out.get();
-    if (bytes) *bytes = (uint64_t)ctx->W * ctx->H * 4;
-    return MPT_OK;
-}
-extern "C" int mpt_read_display_histogram(mpt_ctx* ctx, uint32_t out[256]) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx || !out) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
-        if (!dp_have_state(ctx) || !ctx->dp.shown) return fail(ctx, MPT_ERR_NOT_READY, "no mpt_display result");
-        HIPCHK(hipMemcpyAsync(out, ctx->dp.hist.get(), MPT_DP_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_display_reset(mpt_ctx* ctx) {
-    return guarded(ctx, [&]() -> int {
-        if (!ctx) return MPT_ERR_INVALID_ARG;
-        if (!dp_have_state(ctx)) return MPT_OK;   // (nothing kept)
-        HIPCHK(hipMemsetAsync((char*)ctx->dp.st.get() + offsetof(DpState, kept), 0, sizeof(DpState) - offsetof(DpState, kept), ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        return MPT_OK;
-    });
-}
-extern "C" int mpt_display_table(int transfer, float out[255]) {
-    if (!out || transfer < MPT_TRANSFER_SRGB || transfer > MPT_TRANSFER_LINEAR) return MPT_ERR_INVALID_ARG;
-    memcpy(out, MPT_DISPLAY_TABLE[transfer], sizeof MPT_DISPLAY_TABLE[transfer]);
-    return MPT_OK;
-}
-extern "C" int mpt_display_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* color, const mpt_display_params* p,
-                                 const float* prev_auto_scale, uint8_t* rgba8_out, uint32_t* histogram_out, mpt_display_info* out) {
-    return guarded(ctx, [&] { return display_image_impl(ctx, width, height, color, p, prev_auto_scale, rgba8_out, histogram_out, out); });
-}
-
+// Position-sensitive 64-bit digest of a device array of 32-bit words: sum over i of splitmix64(i << 32 | word[i]) (a commutative sum, so
+// the order in which the waves add is free).  What the tests compare two builds of a scene by, array by array (mpt_scene_digest).
 __global__ void k_digest(const uint32_t* w, uint64_t n_words, unsigned long long* out) {
     unsigned long long acc = 0ull;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += (uint64_t)gridDim.x * blockDim.x) {
