@@ -672,6 +672,74 @@ int mpt_ao_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);    /* the W
 int mpt_ao_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* albedo_depth, const float* normal_class,
                  const mpt_uniforms* cam_uniforms, const mpt_ao_params* params, float* ao_out, uint32_t* occluded_out);
 
+/* ---- direct lighting: the light table and one shadow ray per sample -------------------------------------------------------------------
+ * No reference counterpart (the reference finds its lights by bounces alone).  tests/direct_ref.py restates both parts in numpy.
+ *
+ * The light table.  A primitive is a LIGHT iff its material has emissionPower > 0 (the guide pass's class 1).  Its radiance is
+ * Le = emission.rgb * power (one float32 multiply per channel).  A triangle emits from both sides, as the path tracer adds emission
+ * whichever side is hit; a sphere emits OUTWARD only for this pass — a shading point inside an emissive sphere gets nothing from it (a
+ * departure from the path tracer, which adds emission for a hit from inside too).  Geometry as the device holds it: triangle v0,
+ * e1 = v1 - v0, e2 = v2 - v0 (float32); sphere centre c and radius r.  Weights in float64 from those float32 values:
+ *   A = 0.5 * |cross(e1, e2)| (cross as below, |v| = sqrt((v.x v.x + v.y v.y) + v.z v.z)),  or ((4 pi) r) r
+ *   l = (0.2126 Le.r + 0.7152 Le.g) + 0.0722 Le.b,   W = A * l
+ * A light whose W is zero or not finite is left out (a degenerate triangle, black emission).  The others stand in ascending caller
+ * primitive id (the id mpt_trace_rays and mpt_read_aovs report); C_k is the running sum of W in that order and C the last one:
+ *   cdf[k] = (float)(C_k / C), cdf[last] = 1.0f exactly;   inv_pdf[k] = (float)(C / l_k)   (= A_k / p_k, the reciprocal of the area
+ *   pdf when a light is drawn in proportion to its power)
+ * The table is built by the first call that needs it after mpt_upload_scene / mpt_build_and_upload, from the arrays on the device, and
+ * is the same for the same scene through either call and any tree.  More than MPT_LIGHTS_MAX emissive primitives: MPT_ERR_BAD_SCENE
+ * from the call that needed the table, nothing kept.  A scene without lights is not an error (n = 0).
+ * mpt_light_info: out = {lights, emissive primitives seen, triangle lights, sphere lights}.  mpt_read_lights: the first
+ * min(n, capacity) lights — prim_id, 16 floats each (v0 | c, type: 1 triangle, 0 sphere) (e1 | r 0 0, 0) (e2 | 0, 0) (Le, inv_pdf), cdf —
+ * and n itself in n_out; any of the three arrays may be NULL.  Both: MPT_ERR_NOT_READY without a scene.                               */
+#define MPT_LIGHTS_MAX 65536u
+int mpt_light_info(mpt_ctx* ctx, uint64_t out[4]);
+int mpt_read_lights(mpt_ctx* ctx, uint32_t capacity, int32_t* prim_id, float* records, float* cdf, uint32_t* n_out);
+
+/* Direct lighting over the first-hit guide buffers (float32, one IEEE operation at a time in the order given; dot and normalize as the
+ * AO pass, cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), u01 and sincos_2pi as mpt_kat_philox / mpt_kat_sincos
+ * pin them).  EVERY surface pixel is shaded as a Lambert surface (MPT_BSDF_LAMBERT: the guides carry no material type).
+ * Class 1 and 2: rgba = (0, 0, 0, 1), traced = unoccluded = 0, no ray — EMITTERS SHOW BLACK in this pass.  Class 0:
+ *   o = (cam + t * dc) + 0.0001f * n          (dc: the pixel-centre direction, as in the AO pass)
+ *   for sample s in [sample_begin, sample_begin + N), ascending:
+ *     r = philox4x32_10(counter = (py * W + px, s, 0xFFFFFFFD, 0), key = (seed_lo, seed_hi))   — word 2 = 0xFFFFFFFD is taken by no
+ *         bounce, not by the pixel jitter (0xFFFFFFFF) and not by AO (0xFFFFFFFE)
+ *     u = u01(r.x); the light k = the smallest index with u < cdf[k]
+ *     triangle: a = u01(r.y), b = u01(r.z); if (a + b > 1) { a = 1 - a; b = 1 - b; }   P = (v0 + a * e1) + b * e2,
+ *               nl = normalize(cross(e1, e2))
+ *     sphere:   z = 2 * u01(r.y) - 1, (sn, cs) = sincos_2pi(u01(r.z)), rr = sqrt(1 - z * z), nl = (rr * cs, rr * sn, z), P = c + r * nl
+ *     v = P - o, d2 = dot(v, v), dist = sqrt(d2), wi = v * (1 / dist)
+ *     cos_s = dot(n, wi);  cos_l = |dot(nl, wi)| (triangle), -dot(nl, wi) (sphere)
+ *     the sample is SKIPPED unless d2 > 0 && cos_s > 0 && cos_l > 0 (a NaN skips): no ray, counted neither as traced nor as unoccluded
+ *     traced += 1; the shadow ray is any-hit(o, wi, tmax = dist * 0.9990234375f) (1 - 2^-10: the sampled light itself is outside)
+ *     not occluded: unoccluded += 1, g = (cos_s * cos_l) / d2, w = g * inv_pdf[k], S += (Le.r * w, Le.g * w, Le.b * w)
+ *   rgba = ((albedo.r * 0.31830987f) * (S.r / (float)N), likewise g and b, 1)
+ * With no light in the table every class 0 pixel is (0, 0, 0, 1) with zero counts.  One lane per pixel: S runs in sample order.
+ * The pass waits for queued renders, refreshes the guides if stale, builds the light table if stale and writes none of: the HDR sum,
+ * the frame targets, the moments, the denoised buffer, the temporal, SVGF, display and AO state, mpt_stats.  Its result is dropped by
+ * mpt_resize, mpt_upload_scene and mpt_build_and_upload.
+ * MPT_ERR_INVALID_ARG, with nothing changed: null params, sample_count 0 or > MPT_DIRECT_MAX_SAMPLES, a bad walk.
+ * MPT_ERR_NOT_READY before scene, uniforms and size, and from mpt_read_direct / mpt_direct_buffer before the first pass.              */
+#define MPT_DIRECT_MAX_SAMPLES 1024u
+typedef struct mpt_direct_params {
+    uint32_t sample_begin, sample_count;   /* sample_count: 1..MPT_DIRECT_MAX_SAMPLES                                                  */
+    uint32_t seed_lo, seed_hi;
+    int32_t walk;                          /* MPT_WALK_*                                                                               */
+} mpt_direct_params;
+typedef struct mpt_direct_info {
+    uint64_t pixels_surface, rays /* traced */, rays_occluded, lights;
+    double device_ms;                      /* HIP-event time of the pass (guide refresh and table build not included)                  */
+} mpt_direct_info;
+int mpt_direct_lighting(mpt_ctx* ctx, const mpt_direct_params* params, mpt_direct_info* out /* may be NULL */);
+int mpt_read_direct(mpt_ctx* ctx, float* rgba /* W*H*4 */, uint32_t* traced /* W*H, may be NULL */, uint32_t* unoccluded /* may be NULL */);
+int mpt_direct_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);   /* the RGBA32F image, laid out as the HDR sum                */
+/* The same kernel on caller guides (host arrays as mpt_read_aovs returns them; the unit-test hook: it needs a scene but no size and
+ * touches no state of the context except a stale light table).  Of cam_uniforms only cameraPosition, viewportU, viewportV and
+ * firstPixelPosition are read.  traced_out and unoccluded_out may be NULL.                                                            */
+int mpt_direct_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* albedo_depth, const float* normal_class,
+                     const mpt_uniforms* cam_uniforms, const mpt_direct_params* params, float* rgba_out, uint32_t* traced_out,
+                     uint32_t* unoccluded_out);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

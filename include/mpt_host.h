@@ -100,6 +100,9 @@ int mpt_renderer_display(mpt_renderer* r, const mpt_display_params* params, uint
 /* mpt_ambient_occlusion + mpt_read_ao (include/mpt.h) for the renderer's camera: `samples` shadow rays per surface pixel numbered from
  * 0, keyed by the render parameters' seed, radius <= 0 = no limit, MPT_WALK_AUTO.  ao: W*H floats (1 = open).  out may be NULL.     */
 int mpt_renderer_ambient_occlusion(mpt_renderer* r, uint32_t samples, float radius, float* ao, mpt_ao_info* out);
+/* mpt_direct_lighting + mpt_read_direct (include/mpt.h) for the renderer's camera: `samples` light samples per surface pixel numbered
+ * from 0, keyed by the render parameters' seed, `walk` one of MPT_WALK_*.  rgba: W*H*4 floats.  out may be NULL.                     */
+int mpt_renderer_direct_lighting(mpt_renderer* r, uint32_t samples, int32_t walk, float* rgba, mpt_direct_info* out);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 

@@ -37,6 +37,7 @@ SYMBOLS = (
     "mpt_display", "mpt_read_display", "mpt_display_buffer", "mpt_read_display_histogram", "mpt_display_reset", "mpt_display_table",
     "mpt_display_image",
     "mpt_trace_occluded", "mpt_time_trace", "mpt_ambient_occlusion", "mpt_read_ao", "mpt_ao_buffer", "mpt_ao_image",
+    "mpt_light_info", "mpt_read_lights", "mpt_direct_lighting", "mpt_read_direct", "mpt_direct_buffer", "mpt_direct_image",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
@@ -58,6 +59,8 @@ DISPLAY_DEFAULTS = dict(white=4.0, percentile=50, key=0.18)
 DISPLAY_NO_BIN = 0xFFFFFFFF
 WALK_REFERENCE, WALK_OWN, WALK_AUTO = 0, 1, 2
 AO_MAX_SAMPLES = 1024
+DIRECT_MAX_SAMPLES = 1024
+LIGHTS_MAX = 65536
 
 
 class MptError(RuntimeError):
@@ -215,6 +218,24 @@ def ao_params(samples=16, radius=0.0, sample_begin=0, seed=(0, 0), walk=WALK_AUT
     return AoParams(int(sample_begin), int(samples), float(radius), int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF, int(walk))
 
 
+class DirectParams(C.Structure):
+    _fields_ = [("sample_begin", C.c_uint32), ("sample_count", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
+                ("walk", C.c_int32)]
+
+
+class DirectInfo(C.Structure):
+    _fields_ = [("pixels_surface", C.c_uint64), ("rays", C.c_uint64), ("rays_occluded", C.c_uint64), ("lights", C.c_uint64),
+                ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def direct_params(samples=16, sample_begin=0, seed=(0, 0), walk=WALK_AUTO):
+    """mpt_direct_params: `samples` light samples per surface pixel, numbered from sample_begin."""
+    return DirectParams(int(sample_begin), int(samples), int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF, int(walk))
+
+
 def display_table(transfer):
     """mpt_display_table: the 255 float32 thresholds T[1..255] of a transfer function (index k - 1); needs no context."""
     out = np.empty(255, np.float32)
@@ -348,6 +369,12 @@ def load():
     L.mpt_read_ao.argtypes = [vp, fp, up]
     L.mpt_ao_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.mpt_ao_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(AoParams), fp, up]
+    L.mpt_light_info.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.mpt_read_lights.argtypes = [vp, C.c_uint32, ip, fp, fp, up]
+    L.mpt_direct_lighting.argtypes = [vp, C.POINTER(DirectParams), C.POINTER(DirectInfo)]
+    L.mpt_read_direct.argtypes = [vp, fp, up, up]
+    L.mpt_direct_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_direct_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(DirectParams), fp, up, up]
     _lib = L
     return L
 
@@ -613,6 +640,59 @@ class Context:
         p = ao_params(**kw)
         self._chk(self.L.mpt_ao_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), C.byref(p), _fp(ao), _up(occ)), "mpt_ao_image")
         return ao, occ
+
+    def light_info(self):
+        """mpt_light_info: the light table of the scene in place (built if stale) as a dict of counts."""
+        out = (C.c_uint64 * 4)()
+        self._chk(self.L.mpt_light_info(self.h, out), "mpt_light_info")
+        return dict(lights=out[0], emissive_prims=out[1], triangle_lights=out[2], sphere_lights=out[3])
+
+    def read_lights(self):
+        """mpt_read_lights: (prim_id [n] int32, records [n, 4, 4] float32, cdf [n] float32) of the light table."""
+        n = C.c_uint32()
+        self._chk(self.L.mpt_read_lights(self.h, 0, None, None, None, C.byref(n)), "mpt_read_lights")
+        ids = np.empty(n.value, np.int32)
+        rec = np.empty((n.value, 4, 4), np.float32)
+        cdf = np.empty(n.value, np.float32)
+        if n.value:
+            self._chk(self.L.mpt_read_lights(self.h, n.value, _ip(ids), _fp(rec), _fp(cdf), C.byref(n)), "mpt_read_lights")
+        return ids, rec, cdf
+
+    def direct_lighting(self, **kw):
+        """mpt_direct_lighting over the context's guide buffers (direct_params' keywords); returns the info dict."""
+        p = direct_params(**kw)
+        info = DirectInfo()
+        self._chk(self.L.mpt_direct_lighting(self.h, C.byref(p), C.byref(info)), "mpt_direct_lighting")
+        return info.as_dict()
+
+    def read_direct(self):
+        """(rgba [H,W,4] float32, traced [H,W] uint32, unoccluded [H,W] uint32) of the last direct_lighting."""
+        rgba = np.empty((self.height, self.width, 4), np.float32)
+        traced = np.empty((self.height, self.width), np.uint32)
+        unocc = np.empty((self.height, self.width), np.uint32)
+        self._chk(self.L.mpt_read_direct(self.h, _fp(rgba), _up(traced), _up(unocc)), "mpt_read_direct")
+        return rgba, traced, unocc
+
+    def direct_buffer(self):
+        """(device pointer, bytes) of the last direct_lighting's RGBA32F image."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_direct_buffer(self.h, C.byref(p), C.byref(n)), "mpt_direct_buffer")
+        return p.value, n.value
+
+    def direct_image(self, albedo_depth, normal_class, cam, **kw):
+        """The direct-lighting kernel on caller guides [H,W,4] with the camera of `cam` (Uniforms); needs a scene."""
+        ad = np.ascontiguousarray(albedo_depth, np.float32)
+        nc = np.ascontiguousarray(normal_class, np.float32)
+        if ad.ndim != 3 or ad.shape[2] != 4 or nc.shape != ad.shape:
+            raise ValueError("direct_image: albedo_depth and normal_class must be [H, W, 4] arrays of one shape")
+        H, W = ad.shape[:2]
+        rgba = np.empty((H, W, 4), np.float32)
+        traced = np.empty((H, W), np.uint32)
+        unocc = np.empty((H, W), np.uint32)
+        p = direct_params(**kw)
+        self._chk(self.L.mpt_direct_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), C.byref(p), _fp(rgba), _up(traced), _up(unocc)),
+                  "mpt_direct_image")
+        return rgba, traced, unocc
 
     def build_bvh(self, prims):
         """GPU LBVH over the packed primitive array (12 floats each) -> (bvh [N, 8] f32, prim_idx [P] i32, device ms)."""

@@ -369,6 +369,19 @@ void Renderer::readAmbientOcclusion(std::vector<float>& ao) {
     ao.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y));
     check(mpt_read_ao(ctx_, ao.data(), nullptr), "mpt_read_ao");
 }
+mpt_direct_info Renderer::renderDirectLighting(uint32_t samples, int32_t walk) {
+    uniforms_.primitiveCount = scene_->getPrimitiveCount();
+    uniforms_.triangleCount = scene_->getTriangleCount();
+    check(mpt_set_uniforms(ctx_, &uniforms_), "mpt_set_uniforms");
+    const mpt_direct_params p = {0u, samples, params_.seed_lo, params_.seed_hi, walk};
+    mpt_direct_info info;
+    check(mpt_direct_lighting(ctx_, &p, &info), "mpt_direct_lighting");
+    return info;
+}
+void Renderer::readDirectLighting(std::vector<float>& rgba) {
+    rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_direct(ctx_, rgba.data(), nullptr, nullptr), "mpt_read_direct");
+}
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     if (rgba.size() != n) throw std::runtime_error("writeSum: the array does not have the size of the frame");

@@ -83,6 +83,10 @@ public:
     // the W*H floats of ao (1 = open)
     mpt_ao_info renderAmbientOcclusion(uint32_t samples, float radius);
     void readAmbientOcclusion(std::vector<float>& ao);
+    // mpt_direct_lighting over the same guides: `samples` light samples per surface pixel, numbered from 0, keyed by the render
+    // parameters' seed, one shadow ray each through `walk` (MPT_WALK_*); readDirectLighting = the W*H*4 floats of the pass's rgba
+    mpt_direct_info renderDirectLighting(uint32_t samples, int32_t walk = MPT_WALK_AUTO);
+    void readDirectLighting(std::vector<float>& rgba);
 
 private:
     void check(int status, const char* where);

@@ -333,6 +333,16 @@ int mpt_renderer_ambient_occlusion(mpt_renderer* r, uint32_t samples, float radi
         if (out) *out = info;
     });
 }
+int mpt_renderer_direct_lighting(mpt_renderer* r, uint32_t samples, int32_t walk, float* rgba, mpt_direct_info* out) {
+    if (!r || !rgba) return MPT_ERR_INVALID_ARG;
+    std::vector<float> img;
+    GUARD({
+        const mpt_direct_info info = r->r->renderDirectLighting(samples, walk);
+        r->r->readDirectLighting(img);
+        std::memcpy(rgba, img.data(), img.size() * sizeof(float));
+        if (out) *out = info;
+    });
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

@@ -43,6 +43,7 @@ static void usage() {
         "           [--camera-pos x,y,z] [--camera-dir x,y,z] [--camera-up x,y,z] [--vfov degrees]\n"
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]] [--ao N [--ao-radius R]]\n"
+        "           [--direct N [--direct-walk reference|own|auto]]\n"
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
         "           [--svgf [--svgf-iterations N] [--temporal-history N] [--temporal-spp K]]\n"
@@ -78,6 +79,12 @@ static void usage() {
         "                    first hits (mpt_ambient_occlusion, include/mpt.h), no farther than --ao-radius R (default: no limit); grey,\n"
         "                    1 = open, through the same .ppm writer; the JSON line gains an \"ao\" object.  Nothing is path traced.\n"
         "                    Only with a plain run: not with --frames, --camera-path, --gpus > 1, --adaptive, --denoise, the display\n"
+        "                    flags, --checkpoint or --resume\n"
+        "  --direct N        write direct lighting instead of the radiance to --out (a .ppm): N points on the scene's lights per surface\n"
+        "                    pixel of the first hits, drawn by power, one shadow ray each (mpt_direct_lighting, include/mpt.h) through\n"
+        "                    the --direct-walk tree (default auto); every surface shaded as Lambert, emitters black, through the same\n"
+        "                    .ppm writer; the JSON line gains a \"direct\" object.  Nothing is path traced.  Only with a plain run: not\n"
+        "                    with --ao, --frames, --camera-path, --gpus > 1, --adaptive, --denoise, --temporal, --svgf, the display\n"
         "                    flags, --checkpoint or --resume\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
@@ -358,6 +365,9 @@ int main(int argc, char** argv) {
     bool haveAo = false;    // --ao was given (with whatever count: 0 is refused, not ignored)
     float aoRadius = 0.0f;
     bool haveAoRadius = false;
+    int direct = 0;         // --direct N: light samples per surface pixel (0 = none)
+    bool haveDirect = false, haveDirectWalk = false;
+    int32_t directWalk = MPT_WALK_AUTO;
     bool display = false;   // a display flag was given: .ppm files come from mpt_display
     DisplayOut shown;
     std::memset(&shown.params, 0, sizeof shown.params);   // (clamp, srgb, and 0 = the defaults of include/mpt.h)
@@ -405,6 +415,15 @@ int main(int argc, char** argv) {
         else if (a == "--ao-radius") {
             aoRadius = static_cast<float>(std::atof(next()));
             haveAoRadius = true;
+        }
+        else if (a == "--direct") {
+            direct = std::atoi(next());
+            haveDirect = true;
+        }
+        else if (a == "--direct-walk") {
+            const char* v = next();
+            directWalk = std::strcmp(v, "reference") == 0 ? MPT_WALK_REFERENCE : std::strcmp(v, "own") == 0 ? MPT_WALK_OWN : MPT_WALK_AUTO;
+            haveDirectWalk = true;
         }
         else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
         else if (a == "--adaptive") {
@@ -501,6 +520,16 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "mpt_render: --key, --percentile and --adaptation go with --auto-exposure\n");
         return 2;
     }
+    if (haveDirect || haveDirectWalk) {
+        const char* why = direct < 1 || direct > static_cast<int>(MPT_DIRECT_MAX_SAMPLES) ? "a sample count outside 1..1024" : !outPpm ? "an --out that is no .ppm"
+                          : haveAo || haveAoRadius ? "--ao" : frames > 0 ? "--frames" : !cameraPath.empty() ? "--camera-path" : gpus > 1 ? "--gpus > 1"
+                          : adaptive ? "--adaptive" : denoise ? "--denoise" : display ? "the display flags" : temporal ? "--temporal" : svgf ? "--svgf"
+                          : !checkpoint.empty() ? "--checkpoint" : !resume.empty() ? "--resume" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: --direct cannot be combined with %s\n", why);
+            return 2;
+        }
+    }
     if (haveAo || haveAoRadius) {
         const char* why = ao < 1 || ao > static_cast<int>(MPT_AO_MAX_SAMPLES) ? "a sample count outside 1..1024" : !outPpm ? "an --out that is no .ppm"
                           : frames > 0 ? "--frames" : !cameraPath.empty() ? "--camera-path" : gpus > 1 ? "--gpus > 1" : adaptive ? "--adaptive"
@@ -577,6 +606,14 @@ int main(int argc, char** argv) {
             std::snprintf(buf, sizeof buf, ", \"ao\": {\"samples\": %d, \"radius\": %.9g, \"pixels_surface\": %llu, \"rays\": %llu, \"rays_occluded\": %llu, \"device_ms\": %.3f}",
                           ao, static_cast<double>(aoRadius), (unsigned long long)info.pixels_surface, (unsigned long long)info.rays,
                           (unsigned long long)info.rays_occluded, info.device_ms);
+            adaptiveJson = buf;
+        } else if (direct > 0) {   // the pass's rgba through the writer the radiance goes through
+            const mpt_direct_info info = r.renderDirectLighting(static_cast<uint32_t>(direct), directWalk);
+            r.readDirectLighting(img);
+            char buf[320];
+            std::snprintf(buf, sizeof buf, ", \"direct\": {\"samples\": %d, \"pixels_surface\": %llu, \"rays\": %llu, \"rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f}",
+                          direct, (unsigned long long)info.pixels_surface, (unsigned long long)info.rays, (unsigned long long)info.rays_occluded,
+                          (unsigned long long)info.lights, info.device_ms);
             adaptiveJson = buf;
         } else if (adaptive) {
             const mpt_adaptive_info info = r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);

@@ -1,0 +1,179 @@
+// mpt_direct.h — direct lighting over the first-hit guide buffers (included by mpt_hip.hip after mpt_anyhit.h):
+//   k_light_collect   one thread per device primitive: the emissive ones are appended to a list (the host sorts it into the light table)
+//   k_direct<WALK>    per surface pixel, N points on the lights drawn by power, one shadow ray each through an any-hit walk
+// The pass is specified exactly in include/mpt.h (mpt_direct_params) and restated in numpy in tests/direct_ref.py; DESIGN.md §16 has the
+// table, the lane mapping and the registers.
+#pragma once
+#include "mpt_anyhit.h"
+#include "mpt_ao.h"
+
+#define MPT_LIGHT_F4 4u   // float4 per light: (v0 | c, type) (e1 | r 0 0, 0) (e2 | 0, 0) (Le, inv_pdf); type 1 triangle, 0 sphere
+
+// A primitive is a light iff its material has emissionPower > 0 (the guide pass's class 1).  Appends (geometry, Le = emission * power)
+// in the table's record layout, with the caller's primitive id in the unused last word of the second float4 (the host takes it out).
+// `counter` counts every emissive primitive; entries beyond `cap` are not written.
+__global__ __launch_bounds__(256) void k_light_collect(const float4* prims, const float4* mats, uint32_t n_prims, uint32_t cap, uint32_t* counter,
+                                                       float4* list) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_prims) return;
+    const float4 p0 = prims[3 * (size_t)i], p1 = prims[3 * (size_t)i + 1], p2 = prims[3 * (size_t)i + 2];
+    const float4 m1 = mats[2 * (size_t)__float_as_int(p1.w) + 1];
+    if (!(m1.w > 0.0f)) return;
+    const uint32_t k = atomicAdd(counter, 1u);
+    if (k >= cap) return;
+    const bool tri = prim_type(p0) == 1;
+    float4* r = list + (size_t)MPT_LIGHT_F4 * k;
+    r[0] = make_float4(p0.x, p0.y, p0.z, tri ? 1.0f : 0.0f);
+    r[1] = make_float4(p1.x, tri ? p1.y : 0.0f, tri ? p1.z : 0.0f, p2.w);
+    r[2] = make_float4(p2.x, p2.y, p2.z, 0.0f);
+    r[3] = make_float4(m1.x * m1.w, m1.y * m1.w, m1.z * m1.w, 0.0f);
+}
+
+struct DirectPass {
+    const float4* ad;            // (albedo, t)
+    const float4* nc;            // (normal facing the ray, class)
+    float4* out;                 // ONE block: [0, n) rgba, then n uint32 traced, n uint32 unoccluded, then three 64-bit totals:
+    uint32_t n_pixels;           //   += surface pixels, += rays traced, += rays not occluded (one atomic each per wave that has any)
+    __host__ __device__ uint32_t* traced() const { return (uint32_t*)(out + n_pixels); }
+    __host__ __device__ uint32_t* unoccluded() const { return traced() + n_pixels; }
+    __host__ __device__ unsigned long long* totals() const { return (unsigned long long*)(unoccluded() + n_pixels); }
+    const float4* lights;        // MPT_LIGHT_F4 float4 per light, ascending caller id
+    const float* cdf;            // cdf[n_lights - 1] = 1
+    uint32_t n_lights;
+    F3 cam, first, vu, vv;
+    float fW, fH;
+    uint32_t W, H;
+    uint32_t sample_begin, sample_count;
+    uint32_t seed_lo, seed_hi;
+};
+
+// Lane mapping.  A workgroup of four waves takes a 16 x 16 pixel block, each wave one 8 x 8 tile of it (as k_ao), ONE LANE PER PIXEL, and
+// a round per sample: all 64 lanes trace sample s of their own pixels together.  The shadow rays of neighbouring pixels towards a handful
+// of lights start next to each other and point the same way, so a round's walk is coherent as it is, and a pixel's sum runs in sample
+// order in its one lane: no cross-lane work.  A round in which no lane has a ray skips the walk; a tile without a surface pixel
+// returns after writing its constants.  The table is fetched per lane from global memory (it is small and stays in L2).
+template <int WALK>
+__global__ __launch_bounds__(256) void k_direct(SceneDev sc, AccelDev ac, DirectPass P) {
+    extern __shared__ float4 lds_raw[];
+    if (WALK == MPT_AO_OWN) ot_stage(sc, ac, lds_raw);
+    else stage_nodes(sc, lds_raw);
+    const LdsNodes lds = (LdsNodes)lds_raw;
+    OtStack st = {};
+    if (WALK == MPT_AO_OWN) st = ot_stack(ac, lds_raw, 0u);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t tx0 = blockIdx.x * MPT_DN_TILE + (wave & 1u) * 8u, ty0 = blockIdx.y * MPT_DN_TILE + (wave >> 1) * 8u;
+    if (tx0 >= P.W || ty0 >= P.H) return;   // (wave-uniform: the tile lies outside the image)
+    F3 o = f3(1.0f, 1.0f, 1.0f), n = f3(0.0f, 0.0f, 0.0f), albedo = f3(0.0f, 0.0f, 0.0f);
+    uint32_t pixel = 0u;
+    bool surface = false;
+    {
+        const uint32_t px = tx0 + (lane & 7u), py = ty0 + (lane >> 3);
+        if (px < P.W && py < P.H) {
+            pixel = py * P.W + px;
+            const float4 g = P.nc[pixel];
+            const float4 a = P.ad[pixel];
+            surface = g.w == 0.0f;
+            if (surface) {
+                const float uvx = ((float)px + 0.5f) / P.fW, uvy = ((float)py + 0.5f) / P.fH;
+                const F3 dv = (P.first + uvx * P.vu + uvy * P.vv) - P.cam;
+                const F3 dc = dv * (1.0f / sqrtf(dot3(dv, dv)));   // normalize3, with the division written out (the lanes diverge here)
+                n = f3(g.x, g.y, g.z);
+                o = (P.cam + a.w * dc) + 0.0001f * n;   // the origin of the bounce ray, exactly as k_ao forms it
+                albedo = f3(a.x, a.y, a.z);
+            } else {
+                P.out[pixel] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+                P.traced()[pixel] = 0u;
+                P.unoccluded()[pixel] = 0u;
+            }
+        }
+    }
+    const uint32_t n_surface = (uint32_t)__popcll(__ballot(surface));
+    if (n_surface == 0u) return;   // (wave-uniform: nothing to shade in this tile)
+    // What a round or the end needs from the pass goes into VECTOR registers (an empty asm makes the value opaque, as in k_ao): the walks
+    // hold the scalar file.
+    float4* out = P.out;
+    const float4* lights = P.lights;
+    const float* cdf = P.cdf;
+    uint32_t n_pixels = P.n_pixels, N = P.sample_count, sample_begin = P.sample_begin, last = P.n_lights - 1u;
+    asm volatile("" : "+v"(out), "+v"(lights), "+v"(cdf), "+v"(n_pixels), "+v"(N), "+v"(sample_begin), "+v"(last));
+    uint32_t n_traced = 0u, n_unoccluded = 0u;
+    F3 S = f3(0.0f, 0.0f, 0.0f);
+    const uint32_t search_steps = P.n_lights > 1u ? 32u - (uint32_t)__builtin_clz(P.n_lights - 1u) : 0u;   // ceil(log2(n_lights))
+    const uint32_t rounds = P.n_lights != 0u ? P.sample_count : 0u;   // (no lights: nothing to sample, every surface pixel is black)
+    for (uint32_t s = 0; s < rounds; ++s) {
+        const U4 r = philox4x32_10<true>(pixel, sample_begin + s, 0xFFFFFFFDu, 0u, P.seed_lo, P.seed_hi);
+        // the smallest k with u < cdf[k] (u < 1 = cdf[last]): a binary search of the same length in every lane
+        const float u = u01(r.x);
+        uint32_t lo = 0u, hi = last;
+        for (uint32_t step = 0; step < search_steps; ++step) {
+            const uint32_t mid = (lo + hi) >> 1;
+            const bool below = u < cdf[mid];
+            const bool open = lo < hi;
+            hi = open && below ? mid : hi;
+            lo = open && !below ? mid + 1u : lo;
+        }
+        const float4 L0 = lights[MPT_LIGHT_F4 * lo], L1 = lights[MPT_LIGHT_F4 * lo + 1u], L2 = lights[MPT_LIGHT_F4 * lo + 2u],
+                     L3 = lights[MPT_LIGHT_F4 * lo + 3u];
+        const bool tri = L0.w != 0.0f;
+        const float ua = u01(r.y), ub = u01(r.z);
+        // a point of the triangle ...
+        float a = ua, b = ub;
+        if (a + b > 1.0f) {
+            a = 1.0f - a;
+            b = 1.0f - b;
+        }
+        const F3 e1 = f3(L1.x, L1.y, L1.z), e2 = f3(L2.x, L2.y, L2.z), c = f3(L0.x, L0.y, L0.z);
+        const F3 pt = (c + a * e1) + b * e2;
+        const F3 ng = normalize3(cross3(e1, e2));
+        // ... or of the sphere
+        const float z = 2.0f * ua - 1.0f;
+        float sn, cs;
+        sincos_2pi(ub, sn, cs);
+        const float rr = sqrtf(1.0f - z * z);
+        const F3 ns = f3(rr * cs, rr * sn, z);
+        const F3 ps = c + L1.x * ns;
+        const F3 nl = tri ? ng : ns;
+        const F3 p = tri ? pt : ps;
+        const F3 v = p - o;
+        const float d2 = dot3(v, v);
+        const float dist = sqrtf(d2);
+        const F3 wi = v * mpt_rcp(dist);
+        const float cos_s = dot3(n, wi);
+        const float dl = dot3(nl, wi);
+        const float cos_l = tri ? fabsf(dl) : -dl;
+        const bool live = surface && d2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;   // (a NaN skips)
+        if (__ballot(live) == 0ull) continue;   // (wave-uniform)
+        const float tmax = dist * 0.9990234375f;
+        bool hit;
+        if (WALK == MPT_AO_OWN) {
+            uint32_t flags;
+            hit = any_hit_own(ac, sc, lds, st, o, wi, tmax, live, flags);
+        } else {
+            hit = any_hit_ref<WALK == MPT_AO_REF_ALL_LDS>(sc, lds, o, wi, tmax, live);
+        }
+        if (live) {
+            n_traced += 1u;
+            if (!hit) {
+                n_unoccluded += 1u;
+                const float g = (cos_s * cos_l) / d2;
+                const float w = g * L3.w;
+                S = S + f3(L3.x * w, L3.y * w, L3.z * w);
+            }
+        }
+    }
+    if (surface) {
+        const float fN = (float)N;
+        out[pixel] = make_float4((albedo.x * 0.31830987f) * (S.x / fN), (albedo.y * 0.31830987f) * (S.y / fN), (albedo.z * 0.31830987f) * (S.z / fN), 1.0f);
+        ((uint32_t*)(out + n_pixels))[pixel] = n_traced;                // (DirectPass::traced, unoccluded)
+        ((uint32_t*)(out + n_pixels))[n_pixels + pixel] = n_unoccluded;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        n_traced += (uint32_t)__shfl_down((int)n_traced, off);
+        n_unoccluded += (uint32_t)__shfl_down((int)n_unoccluded, off);
+    }
+    if (lane == 0u) {
+        atomicAdd(P.totals(), (unsigned long long)n_surface);
+        if (n_traced != 0u) atomicAdd(P.totals() + 1, (unsigned long long)n_traced);
+        if (n_unoccluded != 0u) atomicAdd(P.totals() + 2, (unsigned long long)n_unoccluded);
+    }
+}

@@ -41,6 +41,7 @@
 #include "mpt_display.h"
 #include "mpt_anyhit.h"
 #include "mpt_ao.h"
+#include "mpt_direct.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -238,6 +239,26 @@ struct AoState {
     uint64_t epoch = 0;            // the guide_epoch the result was written in (0 = none)
 };
 
+// The light table (mpt_direct.h): every primitive whose material has emissionPower > 0 and a usable weight, in ascending caller id.
+// Built by the first call that needs it after a scene call (ensure_lights, mpt_post.h) from the arrays already on the device; the
+// scene calls only let go of it.
+struct LightState {
+    DevMem<float4> rec;            // MPT_LIGHT_F4 float4 per light
+    DevMem<float> cdf;
+    std::vector<int32_t> ids;      // host copies for mpt_read_lights
+    std::vector<float> h_rec, h_cdf;
+    uint64_t seen = 0, n_tri = 0, n_sph = 0;   // emissive primitives of the scene; lights of either type
+    bool built = false;
+    uint32_t n() const { return (uint32_t)ids.size(); }
+};
+// Direct lighting (mpt_direct.h): the result of the last mpt_direct_lighting.  Allocated by the first pass; mpt_resize and the scene
+// calls let go of it.
+struct DirectState {
+    DevMem<float4> out;            // DirectPass::out: W * H rgba, W * H traced, W * H unoccluded, the three totals
+    uint32_t W = 0, H = 0;
+    uint64_t epoch = 0;            // the guide_epoch the result was written in (0 = none)
+};
+
 struct mpt_ctx : SceneState {
     int device = 0;
     std::unique_ptr<Submitter> sub;      // mpt_render_async's submit thread (none until the first asynchronous render)
@@ -323,6 +344,8 @@ struct mpt_ctx : SceneState {
     SvgfState sv;
     DisplayState dp;
     AoState ao;
+    LightState lights;
+    DirectState di;
     int dp_px = 4;                  // MPT_DISPLAY_PX: pixels per thread of k_dp_present, 1 or 4 (the same bytes)
     bool dp_hist_agg = true;        // MPT_DISPLAY_HIST=plain: k_dp_histogram without the aggregation within the wave
 };
@@ -501,7 +524,8 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     hipFuncSetAttribute((const void*)k_trace_rays, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_dn_guide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // (the image of k_trace_rays)
     for (const void* k : {(const void*)k_occluded_ref<false>, (const void*)k_occluded_ref<true>, (const void*)k_occluded_own, (const void*)k_ao<MPT_AO_REF>,
-                          (const void*)k_ao<MPT_AO_REF_ALL_LDS>, (const void*)k_ao<MPT_AO_OWN>})
+                          (const void*)k_ao<MPT_AO_REF_ALL_LDS>, (const void*)k_ao<MPT_AO_OWN>, (const void*)k_direct<MPT_AO_REF>,
+                          (const void*)k_direct<MPT_AO_REF_ALL_LDS>, (const void*)k_direct<MPT_AO_OWN>})
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = ctx.release();
     return MPT_OK;
@@ -590,6 +614,8 @@ static void install_scene(mpt_ctx* ctx, SceneState&& s) {
     ctx->have_scene = true;
     ctx->guide_epoch++;
     ctx->ao = AoState{};   // (an AO result belongs to the scene it was traced in)
+    ctx->di = DirectState{};
+    ctx->lights = LightState{};   // (built again by the first call that needs it)
 }
 
 // the per-primitive reference-leaf boxes of an uploaded scene (k_prim_refbox, mpt_devbuild.h)
@@ -963,6 +989,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->sv = SvgfState{};
     ctx->dp = DisplayState{};
     ctx->ao = AoState{};
+    ctx->di = DirectState{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;

@@ -448,6 +448,236 @@ extern "C" int mpt_ao_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* a
     return guarded(ctx, [&] { return ao_image_impl(ctx, w, h, albedo_depth, normal_class, cam, p, ao_out, occluded_out); });
 }
 
+// ---- direct lighting (mpt_direct.h; the specification is in include/mpt.h) -----------------------------------------------------------
+// The light table of the scene in place, built when stale: k_light_collect appends the emissive primitives of the device arrays, the host
+// sorts them by caller id, weighs them in float64 and uploads the table.  Nothing is kept of a build that fails.
+static int ensure_lights(mpt_ctx* ctx) {
+    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
+    if (ctx->lights.built) return MPT_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    DevMem<uint32_t> d_count;
+    HIPCHK(d_count.alloc(4));
+    HIPCHK(hipMemsetAsync(d_count.get(), 0, 4, ctx->stream));
+    const uint32_t cap = (uint32_t)std::min<uint64_t>(ctx->n_prims, MPT_LIGHTS_MAX);
+    DevMem<float4> d_list;
+    HIPCHK(d_list.alloc((size_t)std::max(cap, 1u) * MPT_LIGHT_F4 * 16));
+    hipLaunchKernelGGL(k_light_collect, dim3((ctx->n_prims + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)ctx->d_prims, (const float4*)ctx->d_mats,
+                       ctx->n_prims, cap, d_count.get(), d_list.get());
+    HIPCHK(hipGetLastError());
+    uint32_t seen = 0;
+    HIPCHK(hipMemcpyAsync(&seen, d_count.get(), 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (seen > MPT_LIGHTS_MAX) return fail(ctx, MPT_ERR_BAD_SCENE, "more than MPT_LIGHTS_MAX (65536) emissive primitives: " + std::to_string(seen));
+    std::vector<float> list((size_t)seen * 16);
+    if (seen) HIPCHK(hipMemcpy(list.data(), d_list.get(), list.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> order(seen);
+    for (uint32_t i = 0; i < seen; ++i) order[i] = i;
+    auto id_of = [&](uint32_t i) {
+        int32_t id;
+        memcpy(&id, &list[(size_t)i * 16 + 7], 4);
+        return id;
+    };
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return id_of(a) < id_of(b); });
+    LightState t;
+    std::vector<double> lum, csum;
+    double C = 0.0;
+    for (uint32_t i : order) {
+        const float* r = &list[(size_t)i * 16];
+        const bool tri = r[3] != 0.0f;
+        double A;
+        if (tri) {
+            const double ax = r[4], ay = r[5], az = r[6], bx = r[8], by = r[9], bz = r[10];
+            const double cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+            A = 0.5 * sqrt((cx * cx + cy * cy) + cz * cz);
+        } else {
+            const double rad = r[4];
+            A = ((4.0 * 3.14159265358979323846) * rad) * rad;
+        }
+        const double l = (0.2126 * (double)r[12] + 0.7152 * (double)r[13]) + 0.0722 * (double)r[14];
+        const double Wk = A * l;
+        if (!(std::isfinite(Wk) && Wk != 0.0)) continue;
+        C += Wk;
+        csum.push_back(C);
+        lum.push_back(l);
+        t.ids.push_back(id_of(i));
+        t.h_rec.insert(t.h_rec.end(), r, r + 16);
+        t.h_rec[t.h_rec.size() - 16 + 7] = 0.0f;   // (the id travelled here)
+        (tri ? t.n_tri : t.n_sph)++;
+    }
+    const uint32_t n = t.n();
+    t.h_cdf.resize(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        t.h_cdf[k] = k + 1 == n ? 1.0f : (float)(csum[k] / C);
+        t.h_rec[(size_t)k * 16 + 15] = (float)(C / lum[k]);
+    }
+    if (n) {
+        HIPCHK(t.rec.alloc((size_t)n * 64));
+        HIPCHK(t.cdf.alloc((size_t)n * 4));
+        HIPCHK(hipMemcpy(t.rec.get(), t.h_rec.data(), (size_t)n * 64, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(t.cdf.get(), t.h_cdf.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    t.seen = seen;
+    t.built = true;
+    ctx->lights = std::move(t);
+    return MPT_OK;
+}
+static int light_info_impl(mpt_ctx* ctx, uint64_t out[4]) {
+    if (!ctx || !out) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    int rc = wait_impl(ctx);
+    if (rc || (rc = ensure_lights(ctx))) return rc;
+    const LightState& t = ctx->lights;
+    out[0] = t.n();
+    out[1] = t.seen;
+    out[2] = t.n_tri;
+    out[3] = t.n_sph;
+    return MPT_OK;
+}
+static int read_lights_impl(mpt_ctx* ctx, uint32_t capacity, int32_t* prim_id, float* records, float* cdf, uint32_t* n_out) {
+    if (!ctx || !n_out) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    int rc = wait_impl(ctx);
+    if (rc || (rc = ensure_lights(ctx))) return rc;
+    const LightState& t = ctx->lights;
+    const size_t m = std::min(capacity, t.n());
+    if (prim_id && m) memcpy(prim_id, t.ids.data(), m * 4);
+    if (records && m) memcpy(records, t.h_rec.data(), m * 64);
+    if (cdf && m) memcpy(cdf, t.h_cdf.data(), m * 4);
+    *n_out = t.n();
+    return MPT_OK;
+}
+static int direct_check(mpt_ctx* ctx, const mpt_direct_params* p) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null direct-lighting params");
+    if (p->sample_count == 0 || p->sample_count > MPT_DIRECT_MAX_SAMPLES) return fail(ctx, MPT_ERR_INVALID_ARG, "direct lighting: sample_count outside 1..1024");
+    if (!walk_valid(p->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "direct lighting: bad walk");
+    return MPT_OK;
+}
+static size_t direct_out_bytes(size_t n_pixels) { return n_pixels * 24 + 24; }
+// One pass on ctx->stream over guides on the device, at the camera `key`, with the (built) light table; out: direct_out_bytes(W * H).
+static int direct_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad, const float4* nc, const float key[14], const mpt_direct_params* p, float4* out) {
+    DirectPass P = {};
+    P.ad = ad;
+    P.nc = nc;
+    P.out = out;
+    P.n_pixels = W * H;
+    HIPCHK(hipMemsetAsync(P.totals(), 0, 24, ctx->stream));
+    P.lights = ctx->lights.rec.get();
+    P.cdf = ctx->lights.cdf.get();
+    P.n_lights = ctx->lights.n();
+    P.cam = key_f3(key, KEY_CAM);
+    P.vu = key_f3(key, KEY_VU);
+    P.vv = key_f3(key, KEY_VV);
+    P.first = key_f3(key, KEY_FIRST);
+    P.fW = (float)W;
+    P.fH = (float)H;
+    P.W = W;
+    P.H = H;
+    P.sample_begin = p->sample_begin;
+    P.sample_count = p->sample_count;
+    P.seed_lo = p->seed_lo;
+    P.seed_hi = p->seed_hi;
+    const dim3 grid = tile_grid(W, H);
+    SceneDev sc = scene_dev(ctx);
+    AccelDev ac = {};
+    if (resolve_walk(ctx, p->walk) == 1) {
+        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);
+        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+        hipLaunchKernelGGL(k_direct<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
+    } else if (ctx->n_lds_nodes == ctx->n_nodes) {
+        hipLaunchKernelGGL(k_direct<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+    } else {
+        hipLaunchKernelGGL(k_direct<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+    }
+    HIPCHK(hipGetLastError());
+    return MPT_OK;
+}
+static StageResult di_result(const mpt_ctx* c) {
+    return stage_result(c, stage_valid(c, c->di), c->di.out.get(), 16, "no mpt_direct_lighting result for this scene and size");
+}
+static int direct_lighting_impl(mpt_ctx* ctx, const mpt_direct_params* p, mpt_direct_info* out) {
+    if (!ctx) return MPT_ERR_INVALID_ARG;
+    int rc = direct_check(ctx, p);
+    if (rc || (rc = settle_and_guide(ctx)) || (rc = ensure_lights(ctx))) return rc;
+    DirectState& d = ctx->di;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    if (!d.out || d.W != ctx->W || d.H != ctx->H) {
+        d = DirectState{};
+        HIPCHK(d.out.alloc(direct_out_bytes(n)));
+        d.W = ctx->W;
+        d.H = ctx->H;
+    }
+    d.epoch = 0;
+    float key[14];
+    guide_key(ctx->u, key);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventCreate));
+    HIPCHK(e1.create(hipEventCreate));
+    HIPCHK(hipEventRecord(e0.get(), ctx->stream));
+    if ((rc = direct_launch(ctx, ctx->W, ctx->H, ctx->gd.ad.get(), ctx->gd.nc.get(), key, p, d.out.get()))) return rc;
+    HIPCHK(hipEventRecord(e1.get(), ctx->stream));
+    unsigned long long totals[3] = {0, 0, 0};
+    HIPCHK(hipMemcpyAsync(totals, (const char*)d.out.get() + n * 24, 24, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    d.epoch = ctx->guide_epoch;
+    if (out) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
+        out->pixels_surface = totals[0];
+        out->rays = totals[1];
+        out->rays_occluded = totals[1] - totals[2];
+        out->lights = ctx->lights.n();
+        out->device_ms = (double)ms;
+    }
+    return MPT_OK;
+}
+// (rgba, then the optional counts behind it: up to three copies and one wait, so not read_result)
+static int read_direct_impl(mpt_ctx* ctx, float* rgba, uint32_t* traced, uint32_t* unoccluded) {
+    if (!ctx || !rgba) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    const StageResult r = di_result(ctx);
+    int rc = need(ctx, r);
+    const size_t n = (size_t)ctx->W * ctx->H;
+    if (rc || (rc = copy_out(ctx, rgba, r.p, r.bytes)) || (rc = copy_out(ctx, traced, (const char*)r.p + n * 16, n * 4)) ||
+        (rc = copy_out(ctx, unoccluded, (const char*)r.p + n * 20, n * 4)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+static int direct_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* ad, const float* nc, const mpt_uniforms* cam, const mpt_direct_params* p,
+                             float* rgba_out, uint32_t* traced_out, uint32_t* unocc_out) {
+    if (!ctx || !ad || !nc || !cam || !rgba_out || bad_image_size(W, H)) return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    int rc = direct_check(ctx, p);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = ensure_lights(ctx))) return rc;
+    const size_t n = (size_t)W * H;
+    DevMem<float4> d_ad, d_nc, d_out;
+    HIPCHK(d_out.alloc(direct_out_bytes(n)));
+    if ((rc = stage_in(ctx, d_ad, ad, n * 16)) || (rc = stage_in(ctx, d_nc, nc, n * 16))) return rc;
+    float key[14];
+    guide_key(*cam, key);
+    const char* o = (const char*)d_out.get();
+    if ((rc = direct_launch(ctx, W, H, d_ad.get(), d_nc.get(), key, p, d_out.get())) || (rc = copy_out(ctx, rgba_out, o, n * 16)) ||
+        (rc = copy_out(ctx, traced_out, o + n * 16, n * 4)) || (rc = copy_out(ctx, unocc_out, o + n * 20, n * 4)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+extern "C" int mpt_light_info(mpt_ctx* ctx, uint64_t out[4]) {
+    return guarded(ctx, [&] { return light_info_impl(ctx, out); });
+}
+extern "C" int mpt_read_lights(mpt_ctx* ctx, uint32_t capacity, int32_t* prim_id, float* records, float* cdf, uint32_t* n_out) {
+    return guarded(ctx, [&] { return read_lights_impl(ctx, capacity, prim_id, records, cdf, n_out); });
+}
+extern "C" int mpt_direct_lighting(mpt_ctx* ctx, const mpt_direct_params* p, mpt_direct_info* out) {
+    return guarded(ctx, [&] { return direct_lighting_impl(ctx, p, out); });
+}
+extern "C" int mpt_read_direct(mpt_ctx* ctx, float* rgba, uint32_t* traced, uint32_t* unoccluded) {
+    return guarded(ctx, [&] { return read_direct_impl(ctx, rgba, traced, unoccluded); });
+}
+extern "C" int mpt_direct_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) { return result_buffer(ctx, di_result, p, bytes); }
+extern "C" int mpt_direct_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* albedo_depth, const float* normal_class, const mpt_uniforms* cam,
+                                const mpt_direct_params* p, float* rgba_out, uint32_t* traced_out, uint32_t* unoccluded_out) {
+    return guarded(ctx, [&] { return direct_image_impl(ctx, w, h, albedo_depth, normal_class, cam, p, rgba_out, traced_out, unoccluded_out); });
+}
+
 // ---- temporal accumulation (mpt_temporal.h; the specification is in include/mpt.h) ---------------------------------------------
 struct TpResolved {
     float max_history, depth_tol, normal_thr, min_weight;

@@ -26,7 +26,7 @@ SYMBOLS = (
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
-    "mpt_renderer_ambient_occlusion",
+    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting",
 )
 
 _lib = None
@@ -84,6 +84,7 @@ def load():
     L.mpt_renderer_display.argtypes = [vp, C.POINTER(capi.DisplayParams), C.POINTER(C.c_uint8), C.POINTER(capi.DisplayInfo)]
     L.mpt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
     L.mpt_renderer_ambient_occlusion.argtypes = [vp, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(capi.AoInfo)]
+    L.mpt_renderer_direct_lighting.argtypes = [vp, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.POINTER(capi.DirectInfo)]
     _lib = L
     return L
 
@@ -394,6 +395,15 @@ class Renderer:
         out = np.empty((int(u.screenSize[1]), int(u.screenSize[0])), np.float32)
         info = capi.AoInfo()
         self._chk(self.L.mpt_renderer_ambient_occlusion(self.h, int(samples), float(radius), _fp(out), C.byref(info)), "renderAmbientOcclusion")
+        return out, info.as_dict()
+
+    def renderDirectLighting(self, samples, walk=capi.WALK_AUTO):
+        """mpt_renderer_direct_lighting: `samples` light samples per surface pixel of the current camera's first hits, one shadow ray
+        each.  Returns (rgba [H, W, 4] float32: the direct lighting of a Lambert surface, emitters black; the mpt_direct_info as a dict)."""
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
+        info = capi.DirectInfo()
+        self._chk(self.L.mpt_renderer_direct_lighting(self.h, int(samples), int(walk), _fp(out), C.byref(info)), "renderDirectLighting")
         return out, info.as_dict()
 
     def scene(self):
