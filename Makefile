@@ -26,7 +26,7 @@ oracle:
 	$(MAKE) --no-print-directory -C oracle
 
 # test infrastructure: the librccl test double that lets the N > 1 collective path run on one GPU (tests/test_gpu_stub_rccl.py)
-teststub: tests/stub_rccl/_build/librccl.so.1 tests/holder/_build/libholdchip.so
+teststub: tests/stub_rccl/_build/librccl.so.1 tests/holder/_build/libholdchip.so tests/radix/_build/libradixharness.so
 # ... and the foreign persistent kernel of the residency-gate test (tests/test_gpu_parity.py)
 tests/holder/_build/libholdchip.so: tests/holder/hold_chip.hip
 	@mkdir -p tests/holder/_build
@@ -35,7 +35,13 @@ tests/stub_rccl/_build/librccl.so.1: tests/stub_rccl/stub_rccl.hip
 	@mkdir -p tests/stub_rccl/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -fPIC -shared -o $@ $<
 
+# ... and the builders' radix sort and material hash behind C entry points (tests/test_gpu_radix.py, tests/test_gpu_materials.py): the product's
+# headers, included — so its -ffp-contract=off and include paths
+tests/radix/_build/libradixharness.so: tests/radix/radix_harness.hip $(wildcard $(PKG)/csrc/*.h) include/mpt.h
+	@mkdir -p tests/radix/_build
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -fPIC -ffp-contract=off -Iinclude -I$(PKG)/csrc -Wno-unused-function -Wno-unused-value -Wno-unused-result -Wno-pass-failed -shared -o $@ $<
+
 clean:
-	rm -rf $(LIBDIR) oracle/_build oracle/_ref tests/stub_rccl/_build tests/holder/_build
+	rm -rf $(LIBDIR) oracle/_build oracle/_ref tests/stub_rccl/_build tests/holder/_build tests/radix/_build
 
 .PHONY: all host oracle teststub clean

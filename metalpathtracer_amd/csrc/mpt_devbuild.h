@@ -704,7 +704,8 @@ static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_m
     // behind every buffer intact, input untouched; 5 items: right).  That is what round 4's experiment hit: material ids from garbage keys
     // — images off in 1.5 % of the pixels, and once ids far outside the table, a memory fault inside this build (gpurun_out/r04/
     // s46_tests.log).  The same program finds every range the product uses right: [0, 64), [0, 63) (mpt_lbvh.h), [0, 13), [0, 8) on
-    // 32-bit keys (docs/HISTORY.md); full-width 32-bit keys are checked by the recorded digests, tests/golden/devbuild_digests.json.]
+    // 32-bit keys (docs/HISTORY.md).  The sort used here has a test of its own, tests/test_gpu_radix.py: full-width 32-bit keys of every
+    // kind against numpy's stable sort; tests/test_gpu_materials.py runs this chain with up to 40,000 materials and with a real collision.]
     uint32_t *mk32 = nullptr, *mk32s = nullptr;
     if (!wide_mat_sort) {
         MPT_LB(sc.alloc(&mk32, n));
