@@ -59,7 +59,14 @@ enum { MPT_BSDF_LAMBERT = 0, /* what rayColor executes (PathTracing.h:251-255)  
                                   dead code in the reference; diffuse surfaces (materialType == 0) keep rayColor's own
                                   bounce (PathTracing.h:251-255).  Own choices, DESIGN.md "RNG / math specification":
                                   pow(x, 5) is a multiply chain and a transmitted ray starts at p - 1e-4 n (the
-                                  reference's + n would re-hit the surface).                                        */
+                                  reference's + n would re-hit the surface).  Two behaviours that follow from the
+                                  reference's text and that tests/test_optics_cpu.py pins: (1) the sphere test takes the
+                                  near root alone (PathTracing.h:120-142), so a ray that starts inside a sphere does
+                                  not see it: a glass sphere refracts on entry only.  (2) a refraction whose
+                                  discriminant 1 - ri^2 (1 - cos^2) rounds below zero while ri * sin > 1 is false (a
+                                  few 1e-6 rad around the critical angle) returns the zero vector, whose normalize is
+                                  a NaN direction; that ray hits nothing, the sample ends as a miss and contributes
+                                  (0, 0, 0) with alpha 1 (clamp of a NaN colour is 0).                              */
        MPT_BSDF_SCATTER_ALL = 2 }; /* scatter() for every material: as MPT_BSDF_SCATTER, and diffuse surfaces take
                                   Scatter.h's own Lambert branch too (Scatter.h:24-27,42: normalize(normal +
                                   normalize(randomFloat3(seed))), a point of the cube [-1,1]^3 per Random.h:18-30 —

@@ -50,6 +50,10 @@ class RenderParams(C.Structure):
     ]
 
 
+# RayHook of mpt_oracle.cpp: (origin[3], direction[3], t, primitiveId, user) per closest-hit query of a render
+RAY_HOOK = C.CFUNCTYPE(None, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_void_p)
+
+
 def build(force=False):
     """Compile the oracle (and oracle/_ref when /root/reference is present)."""
     if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(
@@ -102,6 +106,8 @@ def lib():
         L.orc_first_hit.argtypes = [fp, fp, fp, fp, ip, fp, ip, fp, ip]
         L.orc_fnv1a64.restype = C.c_uint64
         L.orc_fnv1a64.argtypes = [C.c_void_p, C.c_uint64]
+        L.orc_set_ray_hook.restype = None
+        L.orc_set_ray_hook.argtypes = [RAY_HOOK, C.c_void_p]
         _lib = L
     return _lib
 
@@ -212,6 +218,28 @@ def render(u, buffers, rng_mode=RNG_PHILOX, bsdf_mode=BSDF_LAMBERT, max_depth=32
     else:
         lib().orc_render(*args)
     return out, dict(zip(COUNTER_NAMES, [int(x) for x in ctr]))
+
+
+def ray_log(u, buffers, **render_kwargs):
+    """render() with every closest-hit query recorded.  Returns (image, counters, rays): rays [n, 8] float64 = origin, direction,
+    t (+inf for a miss), primitive id (-1 for a miss), in path order — pixels row by row, a pixel's samples in turn, a path's rays
+    in bounce order.  The hook is process-wide and called from the render threads, so the render is single-threaded; the hook is
+    cleared before this returns."""
+    if render_kwargs.pop("threads", 1) != 1:
+        raise ValueError("ray_log: the ray hook is process-wide, the render must be single-threaded")
+    rows = []
+
+    def record(o, d, t, prim, _user):
+        rows.append((o[0], o[1], o[2], d[0], d[1], d[2], t, prim))
+
+    hook = RAY_HOOK(record)                     # (kept alive by this frame until the hook is cleared)
+    L = lib()
+    L.orc_set_ray_hook(hook, None)
+    try:
+        image, counters = render(u, buffers, threads=1, **render_kwargs)
+    finally:
+        L.orc_set_ray_hook(RAY_HOOK(), None)
+    return image, counters, np.array(rows, np.float64).reshape(-1, 8)
 
 
 def first_hit(o, d, buffers):
