@@ -747,6 +747,64 @@ int mpt_direct_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float*
                      const mpt_uniforms* cam_uniforms, const mpt_direct_params* params, float* rgba_out, uint32_t* traced_out,
                      uint32_t* unoccluded_out);
 
+/* ---- next-event estimation: a light sample with MIS at every Lambert vertex of a path render -------------------------------------------
+ * No reference counterpart.  mpt_render_nee renders what mpt_render renders — same primary rays, same bounces, same HDR sum — with one
+ * more estimate of the direct light at every diffuse vertex: a point on a light of the table above, one shadow ray, combined with the
+ * light the bounce finds by the power heuristic.  tests/nee_ref.py restates the estimator in numpy.
+ *
+ * The call is synchronous, like mpt_render: it waits for the renders queued and in flight (reporting a failed mpt_render_async), builds
+ * the light table if stale and, for every pixel, adds the per-sample values v_s of samples [sample_begin, sample_begin + sample_count)
+ * to the HDR sum IN SAMPLE ORDER, sum = ((sum + v_b) + v_{b+1}) + ..., all four channels — the caller's storage of mpt_set_sum_buffer
+ * included.  Denoiser, temporal, SVGF, display, checkpoint and mpt_read_sum work on the result unchanged.  From p it reads rng_mode
+ * (must be MPT_RNG_PHILOX), bsdf_mode (MPT_BSDF_LAMBERT or MPT_BSDF_SCATTER), max_depth, sample_begin, sample_count, seed_lo, seed_hi;
+ * pipeline and slots_per_iter are ignored.  It writes none of: the frame targets, the moments, the denoised buffer, the temporal, SVGF,
+ * display, AO and direct state.  mpt_get_stats: paths and rays grow by the info's, trace_kernel_ms and total_ms are set as after an
+ * mpt_render, trace_launches = 1.
+ * OUT OF SCOPE: moments (MPT_FLAG_MOMENTS), shards, the asynchronous lane and adaptive rendering over this estimator.
+ * MPT_ERR_INVALID_ARG, with nothing rendered: a null p or n, MPT_RNG_LITERAL, MPT_BSDF_SCATTER_ALL (its direction pdf is not the cosine
+ * pdf), shard_count != 1 or shard_rank != 0, flags != 0, sample_count == 0, max_depth < 1, a bad walk, a NaN clamp, and mpt_render's
+ * upper limits: max_depth > 32, sample_begin + sample_count > 2^27.  MPT_ERR_NOT_READY before scene, uniforms and size.  MPT_ERR_BAD_SCENE from the light table, as mpt_direct_lighting.
+ *
+ * The estimator.  float32, one IEEE operation at a time in the order written; dot, cross and normalize as in the direct-lighting section;
+ * philox(a, b, c, e) = philox4x32_10(counter = (a, b, c, e), key = (seed_lo, seed_hi)).  Sample s of pixel p = py * W + px:
+ *   primary ray: mpt_render's for philox (jitter block (p, s, 0xFFFFFFFF, 0)).  thr = (1, 1, 1), L = (0, 0, 0), La = 0, b = 0,
+ *   sampled = false, pb = 0.  Loop: (t, prim) = closest hit of (o, d).
+ *   miss: L += thr * sky(d), La += 1, exactly as mpt_render; the path ends.  The sky is never sampled as a light and counts in full.
+ *   hit: point P_h = o + t * d, n = the geometric normal facing the ray, front = whether the ray met the outside.  A primitive whose
+ *     caller id is >= uniforms.primitiveCount ends the path (the material guard of PathTracing.h:234-236).
+ *   emission, if power > 0 || materialType == 2 (mpt_render's condition):
+ *     w = 1, unless all of: sampled; the primitive is light k of the table (a binary search of the ascending ids); for a sphere, front.
+ *     Then cos_l = -dot(n, d), pl = (t * t) / (cos_l * inv_pdf[k]), q = pl / pb, w = 1 / (1 + q * q)  (the power heuristic, written so
+ *     that no inf / inf arises).   L.c += ((thr.c * emission.c) * power) * w  (with w = 1: mpt_render's bits);  La += power.
+ *   Lambert vertex (MPT_BSDF_LAMBERT, or materialType == 0):
+ *     nd = normalize(n + ruv), ruv from block (p, s, b, 0) as mpt_render draws it;  o' = P_h + 0.0001f * n.
+ *     light sample, only if the table has a light and b + 1 < max_depth (the ray that could find the light by a bounce is traced):
+ *       r = philox(p, s, b, 1) — word 3 = 1 is used by nothing else: every other block has word 3 = 0.
+ *       light k, the point P, nl, v, d2, dist, wi, cos_s, cos_l, the skip rule and the shadow ray any-hit(o', wi, dist * 0.9990234375f)
+ *       are EXACTLY the direct-lighting pass's, with its n = n and its o = o'.  Not skipped and not occluded:
+ *         g = (cos_s * cos_l) / d2,  pl = d2 / (cos_l * inv_pdf[k]),  pbs = cos_s * 0.31830987f,  q = pbs / pl,  wl = 1 / (1 + q * q),
+ *         m = (g * inv_pdf[k]) * wl,   L.c += ((thr.c * albedo.c) * 0.31830987f) * (Le_k.c * m)
+ *     sampled = whether a light sample was attempted at this vertex (skipped samples included);  pb = dot(n, nd) * 0.31830987f.
+ *   specular vertex (MPT_BSDF_SCATTER and materialType != 0): mpt_render's mirror / dielectric bounce unchanged, no light sample,
+ *     sampled = false.
+ *   thr *= albedo;  (o, d) = (o' or the transmitted origin, nd);  b += 1;  the path continues iff b < max_depth.
+ *   per-sample value: v.c = L.c > 0 ? min(L.c, clamp) : 0 (a NaN gives 0);  v.a = min(max(La, 0), 1).
+ * Hence: with an empty light table, or with max_depth = 1, and with clamp = 1, the call adds bit for bit what mpt_render adds; with
+ * clamp = +inf its expectation is that of the unclamped path tracer at the same max_depth.  Sphere lights are sampled uniformly over
+ * their whole surface, as in the direct pass (sampling the visible cap is a follow-up).
+ * walk: the tree BOTH the closest hits and the shadow rays walk; MPT_WALK_OWN / MPT_WALK_AUTO fall back as in mpt_direct_lighting.  With
+ * the own tree the closest hits are those of MPT_PIPE_ORDERED (its exactness note above applies) and the shadow rays those of
+ * mpt_trace_occluded(MPT_WALK_OWN).                                                                                                   */
+typedef struct mpt_nee_params {
+    int32_t walk;        /* MPT_WALK_*                                                                                                   */
+    float clamp;         /* per-sample, per-channel upper clamp; <= 0 selects +inf (none); a NaN is MPT_ERR_INVALID_ARG                  */
+} mpt_nee_params;
+typedef struct mpt_nee_info {
+    uint64_t paths, rays /* closest-hit queries */, shadow_rays, shadow_rays_occluded, lights;
+    double device_ms;    /* HIP-event time of the trace kernel (table build not included)                                               */
+} mpt_nee_info;
+int mpt_render_nee(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out /* may be NULL */);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

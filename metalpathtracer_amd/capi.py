@@ -38,6 +38,7 @@ SYMBOLS = (
     "mpt_display_image",
     "mpt_trace_occluded", "mpt_time_trace", "mpt_ambient_occlusion", "mpt_read_ao", "mpt_ao_buffer", "mpt_ao_image",
     "mpt_light_info", "mpt_read_lights", "mpt_direct_lighting", "mpt_read_direct", "mpt_direct_buffer", "mpt_direct_image",
+    "mpt_render_nee",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
@@ -236,6 +237,18 @@ def direct_params(samples=16, sample_begin=0, seed=(0, 0), walk=WALK_AUTO):
     return DirectParams(int(sample_begin), int(samples), int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF, int(walk))
 
 
+class NeeParams(C.Structure):
+    _fields_ = [("walk", C.c_int32), ("clamp", C.c_float)]
+
+
+class NeeInfo(C.Structure):
+    _fields_ = [("paths", C.c_uint64), ("rays", C.c_uint64), ("shadow_rays", C.c_uint64), ("shadow_rays_occluded", C.c_uint64),
+                ("lights", C.c_uint64), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 def display_table(transfer):
     """mpt_display_table: the 255 float32 thresholds T[1..255] of a transfer function (index k - 1); needs no context."""
     out = np.empty(255, np.float32)
@@ -375,6 +388,7 @@ def load():
     L.mpt_read_direct.argtypes = [vp, fp, up, up]
     L.mpt_direct_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.mpt_direct_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(DirectParams), fp, up, up]
+    L.mpt_render_nee.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(NeeInfo)]
     _lib = L
     return L
 
@@ -693,6 +707,15 @@ class Context:
         self._chk(self.L.mpt_direct_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), C.byref(p), _fp(rgba), _up(traced), _up(unocc)),
                   "mpt_direct_image")
         return rgba, traced, unocc
+
+    def render_nee(self, walk=WALK_AUTO, clamp=0.0, **params):
+        """mpt_render_nee: the samples of `params` (the keywords of render) with a light sample and MIS at every Lambert vertex, added
+        to the HDR sum; clamp <= 0 = no per-sample clamp, 1 = mpt_render's.  Returns the mpt_nee_info as a dict."""
+        p = self.params(**params)
+        n = NeeParams(int(walk), float(clamp))
+        info = NeeInfo()
+        self._chk(self.L.mpt_render_nee(self.h, C.byref(p), C.byref(n), C.byref(info)), "mpt_render_nee")
+        return info.as_dict()
 
     def build_bvh(self, prims):
         """GPU LBVH over the packed primitive array (12 floats each) -> (bvh [N, 8] f32, prim_idx [P] i32, device ms)."""

@@ -382,6 +382,21 @@ void Renderer::readDirectLighting(std::vector<float>& rgba) {
     rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
     check(mpt_read_direct(ctx_, rgba.data(), nullptr, nullptr), "mpt_read_direct");
 }
+mpt_nee_info Renderer::renderNee(uint32_t spp, int32_t depth, int32_t walk, float clamp, uint32_t sampleBegin) {
+    uniforms_.primitiveCount = scene_->getPrimitiveCount();
+    uniforms_.triangleCount = scene_->getTriangleCount();
+    check(mpt_set_uniforms(ctx_, &uniforms_), "mpt_set_uniforms");
+    mpt_render_params p = params_;
+    p.max_depth = depth;
+    p.sample_begin = sampleBegin;
+    p.sample_count = spp;
+    const mpt_nee_params n = {walk, clamp};
+    mpt_nee_info info;
+    check(mpt_render_nee(ctx_, &p, &n, &info), "mpt_render_nee");
+    lastSource_ = MPT_DENOISE_SUM;
+    sumSamples_ += spp;
+    return info;
+}
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     if (rgba.size() != n) throw std::runtime_error("writeSum: the array does not have the size of the frame");

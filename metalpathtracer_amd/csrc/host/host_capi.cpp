@@ -343,6 +343,13 @@ int mpt_renderer_direct_lighting(mpt_renderer* r, uint32_t samples, int32_t walk
         if (out) *out = info;
     });
 }
+int mpt_renderer_render_nee(mpt_renderer* r, uint32_t spp, int32_t depth, int32_t walk, float clamp, mpt_nee_info* out) {
+    if (!r) return MPT_ERR_INVALID_ARG;
+    GUARD({
+        const mpt_nee_info info = r->r->renderNee(spp, depth, walk, clamp);
+        if (out) *out = info;
+    });
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

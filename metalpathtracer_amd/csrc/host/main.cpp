@@ -44,6 +44,7 @@ static void usage() {
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]] [--ao N [--ao-radius R]]\n"
         "           [--direct N [--direct-walk reference|own|auto]]\n"
+        "           [--nee [--nee-walk reference|own|auto] [--nee-clamp C]]\n"
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
         "           [--svgf [--svgf-iterations N] [--temporal-history N] [--temporal-spp K]]\n"
@@ -86,6 +87,14 @@ static void usage() {
         "                    .ppm writer; the JSON line gains a \"direct\" object.  Nothing is path traced.  Only with a plain run: not\n"
         "                    with --ao, --frames, --camera-path, --gpus > 1, --adaptive, --denoise, --temporal, --svgf, the display\n"
         "                    flags, --checkpoint or --resume\n"
+        "  --nee             render the still image (--out, --spp, --depth) with next-event estimation (mpt_render_nee, include/mpt.h): a\n"
+        "                    point on the scene's lights and a shadow ray at every diffuse vertex, weighted against the light the bounce\n"
+        "                    finds; both kinds of ray through the --nee-walk tree (default auto); --nee-clamp C clamps every sample's\n"
+        "                    channels at C (default: no clamp; 1 is the plain render's).  The JSON line gains a \"nee\" object.  --denoise,\n"
+        "                    --checkpoint / --resume and the display flags work on the sum; a checkpoint of an --nee render records the\n"
+        "                    estimator and its clamp (header MPTNEE1) and is resumed only by an --nee run with the same clamp, a plain one\n"
+        "                    only by a plain run.  Not with --adaptive, --gpus > 1, --camera-path (hence --temporal, --svgf), --frames,\n"
+        "                    --ao, --direct, --rng literal or --bsdf scatter-all\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
@@ -368,6 +377,9 @@ int main(int argc, char** argv) {
     int direct = 0;         // --direct N: light samples per surface pixel (0 = none)
     bool haveDirect = false, haveDirectWalk = false;
     int32_t directWalk = MPT_WALK_AUTO;
+    bool nee = false, haveNeeOpt = false;   // --nee; --nee-walk / --nee-clamp were given
+    int32_t neeWalk = MPT_WALK_AUTO;
+    float neeClamp = 0.0f;
     bool display = false;   // a display flag was given: .ppm files come from mpt_display
     DisplayOut shown;
     std::memset(&shown.params, 0, sizeof shown.params);   // (clamp, srgb, and 0 = the defaults of include/mpt.h)
@@ -424,6 +436,16 @@ int main(int argc, char** argv) {
             const char* v = next();
             directWalk = std::strcmp(v, "reference") == 0 ? MPT_WALK_REFERENCE : std::strcmp(v, "own") == 0 ? MPT_WALK_OWN : MPT_WALK_AUTO;
             haveDirectWalk = true;
+        }
+        else if (a == "--nee") nee = true;
+        else if (a == "--nee-walk") {
+            const char* v = next();
+            neeWalk = std::strcmp(v, "reference") == 0 ? MPT_WALK_REFERENCE : std::strcmp(v, "own") == 0 ? MPT_WALK_OWN : MPT_WALK_AUTO;
+            haveNeeOpt = true;
+        }
+        else if (a == "--nee-clamp") {
+            neeClamp = static_cast<float>(std::atof(next()));
+            haveNeeOpt = true;
         }
         else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
         else if (a == "--adaptive") {
@@ -520,6 +542,16 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "mpt_render: --key, --percentile and --adaptation go with --auto-exposure\n");
         return 2;
     }
+    if (nee || haveNeeOpt) {
+        const char* why = !nee ? "a run without --nee" : neeClamp != neeClamp ? "a --nee-clamp that is no number" : adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1"
+                          : !cameraPath.empty() ? "--camera-path" : frames > 0 ? "--frames" : haveAo || haveAoRadius ? "--ao"
+                          : haveDirect || haveDirectWalk ? "--direct"
+                          : prm.rng_mode == MPT_RNG_LITERAL ? "--rng literal" : prm.bsdf_mode == MPT_BSDF_SCATTER_ALL ? "--bsdf scatter-all" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: --nee cannot be combined with %s\n", why);
+            return 2;
+        }
+    }
     if (haveDirect || haveDirectWalk) {
         const char* why = direct < 1 || direct > static_cast<int>(MPT_DIRECT_MAX_SAMPLES) ? "a sample count outside 1..1024" : !outPpm ? "an --out that is no .ppm"
                           : haveAo || haveAoRadius ? "--ao" : frames > 0 ? "--frames" : !cameraPath.empty() ? "--camera-path" : gpus > 1 ? "--gpus > 1"
@@ -591,7 +623,7 @@ int main(int argc, char** argv) {
         r.drawableSizeWillChange(&view, DrawableSize{(double)width, (double)height});
         std::vector<float> img;
         float scale = 1.0f;
-        std::string adaptiveJson;
+        std::string extraJson;
         auto t0 = std::chrono::steady_clock::now();
         if (ao > 0) {   // grey (ao, ao, ao, 1) through the writer the radiance goes through
             const mpt_ao_info info = r.renderAmbientOcclusion(static_cast<uint32_t>(ao), aoRadius);
@@ -606,7 +638,7 @@ int main(int argc, char** argv) {
             std::snprintf(buf, sizeof buf, ", \"ao\": {\"samples\": %d, \"radius\": %.9g, \"pixels_surface\": %llu, \"rays\": %llu, \"rays_occluded\": %llu, \"device_ms\": %.3f}",
                           ao, static_cast<double>(aoRadius), (unsigned long long)info.pixels_surface, (unsigned long long)info.rays,
                           (unsigned long long)info.rays_occluded, info.device_ms);
-            adaptiveJson = buf;
+            extraJson = buf;
         } else if (direct > 0) {   // the pass's rgba through the writer the radiance goes through
             const mpt_direct_info info = r.renderDirectLighting(static_cast<uint32_t>(direct), directWalk);
             r.readDirectLighting(img);
@@ -614,7 +646,7 @@ int main(int argc, char** argv) {
             std::snprintf(buf, sizeof buf, ", \"direct\": {\"samples\": %d, \"pixels_surface\": %llu, \"rays\": %llu, \"rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f}",
                           direct, (unsigned long long)info.pixels_surface, (unsigned long long)info.rays, (unsigned long long)info.rays_occluded,
                           (unsigned long long)info.lights, info.device_ms);
-            adaptiveJson = buf;
+            extraJson = buf;
         } else if (adaptive) {
             const mpt_adaptive_info info = r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);
             if (!display || denoise) r.readAdaptiveMean(img);
@@ -638,7 +670,7 @@ int main(int argc, char** argv) {
                           ", \"adaptive\": {\"passes\": %u, \"samples\": %llu, \"tiles_converged\": %u, \"tiles_at_max\": %u, \"mean_spp\": %.4f}",
                           info.passes, (unsigned long long)info.samples, info.tiles_converged, info.tiles_at_max,
                           pixels > 0 ? static_cast<double>(info.samples) / pixels : 0.0);
-            adaptiveJson = buf;
+            extraJson = buf;
         } else if (!cameraPath.empty()) {
             if (temporal) r.setTemporalParams(tpp);
             if (svgf) {
@@ -680,6 +712,8 @@ int main(int argc, char** argv) {
             // another scene or material model is refused instead of mixing sums.  Written to a temporary file and renamed over the target,
             // so that a crash mid-write never destroys the checkpoint that --resume just read.
             uint32_t have = 0;
+            unsigned neeClampBits = 0;   // the bits of the clamp in force (0: none)
+            if (nee && neeClamp > 0.0f) std::memcpy(&neeClampBits, &neeClamp, sizeof neeClampBits);
             r.clearSum();
             const unsigned long long sceneHash = sceneFingerprint(*r.scene());
             if (!resume.empty()) {
@@ -687,9 +721,18 @@ int main(int argc, char** argv) {
                 int w = 0, h = 0, rngm = 0, dep = 0, bs = 0;
                 unsigned sd = 0;
                 unsigned long long sh = 0;
-                if (!f || std::fscanf(f, "MPTSUM2 %d %d %u %u %d %d %d %llx", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh) != 8 || std::fgetc(f) != '\n') {
+                // (an --nee sum is another estimator's: its header is "MPTNEE1 ... scene-hash clamp-bits\n", which the plain format does not
+                //  parse and the other way round, so neither run continues the other's sum, nor an --nee run one of another clamp)
+                unsigned cb = 0;
+                const bool parsed = f && (nee ? std::fscanf(f, "MPTNEE1 %d %d %u %u %d %d %d %llx %x", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb) == 9
+                                              : std::fscanf(f, "MPTSUM2 %d %d %u %u %d %d %d %llx", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh) == 8);
+                if (!parsed || std::fgetc(f) != '\n') {
                     if (f) std::fclose(f);
-                    throw std::runtime_error("cannot read the checkpoint " + resume);
+                    throw std::runtime_error("cannot read the checkpoint " + resume + (nee ? " as one of an --nee render" : " as one of a plain render"));
+                }
+                if (nee && cb != neeClampBits) {
+                    std::fclose(f);
+                    throw std::runtime_error("the checkpoint " + resume + " was written with another --nee-clamp");
                 }
                 if (w != width || h != height || sd != seed || rngm != prm.rng_mode || dep != depth || bs != prm.bsdf_mode || sh != sceneHash) {
                     std::fclose(f);
@@ -701,14 +744,27 @@ int main(int argc, char** argv) {
                 if (got != sum.size()) throw std::runtime_error("the checkpoint " + resume + " is truncated");
                 r.writeSum(sum);
             }
-            r.renderBatch(have, static_cast<uint32_t>(spp));
+            if (nee) {
+                const mpt_nee_info info = r.renderNee(static_cast<uint32_t>(spp), depth, neeWalk, neeClamp, have);
+                char buf[320];
+                std::snprintf(buf, sizeof buf, ", \"nee\": {\"paths\": %llu, \"rays\": %llu, \"shadow_rays\": %llu, \"shadow_rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f}",
+                              (unsigned long long)info.paths, (unsigned long long)info.rays, (unsigned long long)info.shadow_rays,
+                              (unsigned long long)info.shadow_rays_occluded, (unsigned long long)info.lights, info.device_ms);
+                extraJson = buf;
+            } else {
+                r.renderBatch(have, static_cast<uint32_t>(spp));
+            }
             if (!display || !checkpoint.empty()) r.readSum(img);
             if (!checkpoint.empty()) {
                 const std::string tmp = checkpoint + ".tmp";
                 FILE* f = std::fopen(tmp.c_str(), "wb");
                 if (!f) throw std::runtime_error("cannot write " + tmp);
-                std::fprintf(f, "MPTSUM2 %d %d %u %u %d %d %d %llx\n", width, height, have + static_cast<uint32_t>(spp), seed, prm.rng_mode, depth, prm.bsdf_mode,
-                             sceneHash);
+                if (nee)
+                    std::fprintf(f, "MPTNEE1 %d %d %u %u %d %d %d %llx %x\n", width, height, have + static_cast<uint32_t>(spp), seed, prm.rng_mode, depth,
+                                 prm.bsdf_mode, sceneHash, neeClampBits);
+                else
+                    std::fprintf(f, "MPTSUM2 %d %d %u %u %d %d %d %llx\n", width, height, have + static_cast<uint32_t>(spp), seed, prm.rng_mode, depth, prm.bsdf_mode,
+                                 sceneHash);
                 const bool ok = std::fwrite(img.data(), sizeof(float), img.size(), f) == img.size();
                 if (std::fclose(f) != 0 || !ok || std::rename(tmp.c_str(), checkpoint.c_str()) != 0) {
                     std::remove(tmp.c_str());
@@ -730,7 +786,7 @@ int main(int argc, char** argv) {
         mpt_stats st = r.stats();
         std::printf("{\"paths\": %llu, \"rays\": %llu, \"seconds\": %.6f, \"device_ms\": %.3f, \"mrays_per_s\": %.1f%s}\n",
                     (unsigned long long)st.paths, (unsigned long long)st.rays, sec, st.total_ms,
-                    st.total_ms > 0 ? st.rays / st.total_ms / 1e3 : 0.0, adaptiveJson.c_str());
+                    st.total_ms > 0 ? st.rays / st.total_ms / 1e3 : 0.0, extraJson.c_str());
         if (!out.empty()) {
             int rc = display && shown.rgba8.empty() ? MPT_ERR_NOT_READY   // (a camera path without a frame)
                      : display ? mpt_write_ppm8(out.c_str(), shown.rgba8.data(), width, height)

@@ -42,6 +42,7 @@
 #include "mpt_anyhit.h"
 #include "mpt_ao.h"
 #include "mpt_direct.h"
+#include "mpt_nee.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -245,6 +246,7 @@ struct AoState {
 struct LightState {
     DevMem<float4> rec;            // MPT_LIGHT_F4 float4 per light
     DevMem<float> cdf;
+    DevMem<int32_t> d_ids;         // the lights' caller ids on the device (k_nee looks an emitter up in them)
     std::vector<int32_t> ids;      // host copies for mpt_read_lights
     std::vector<float> h_rec, h_cdf;
     uint64_t seen = 0, n_tri = 0, n_sph = 0;   // emissive primitives of the scene; lights of either type
@@ -257,6 +259,14 @@ struct DirectState {
     DevMem<float4> out;            // DirectPass::out: W * H rgba, W * H traced, W * H unoccluded, the three totals
     uint32_t W = 0, H = 0;
     uint64_t epoch = 0;            // the guide_epoch the result was written in (0 = none)
+};
+
+// Next-event estimation (mpt_nee.h): what every mpt_render_nee call needs besides the sum — the four totals of mpt_nee_info on the device
+// and the pair of timing events.  Made by the first call, kept for the context's life (an allocation per call would cost a device
+// synchronisation each time).
+struct NeeState {
+    DevMem<unsigned long long> totals;
+    Event e0, e1;
 };
 
 struct mpt_ctx : SceneState {
@@ -346,6 +356,7 @@ struct mpt_ctx : SceneState {
     AoState ao;
     LightState lights;
     DirectState di;
+    NeeState nee;
     int dp_px = 4;                  // MPT_DISPLAY_PX: pixels per thread of k_dp_present, 1 or 4 (the same bytes)
     bool dp_hist_agg = true;        // MPT_DISPLAY_HIST=plain: k_dp_histogram without the aggregation within the wave
 };
@@ -525,7 +536,8 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     hipFuncSetAttribute((const void*)k_dn_guide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // (the image of k_trace_rays)
     for (const void* k : {(const void*)k_occluded_ref<false>, (const void*)k_occluded_ref<true>, (const void*)k_occluded_own, (const void*)k_ao<MPT_AO_REF>,
                           (const void*)k_ao<MPT_AO_REF_ALL_LDS>, (const void*)k_ao<MPT_AO_OWN>, (const void*)k_direct<MPT_AO_REF>,
-                          (const void*)k_direct<MPT_AO_REF_ALL_LDS>, (const void*)k_direct<MPT_AO_OWN>})
+                          (const void*)k_direct<MPT_AO_REF_ALL_LDS>, (const void*)k_direct<MPT_AO_OWN>, (const void*)k_nee<MPT_AO_REF>,
+                          (const void*)k_nee<MPT_AO_REF_ALL_LDS>, (const void*)k_nee<MPT_AO_OWN>})
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = ctx.release();
     return MPT_OK;
@@ -2407,6 +2419,99 @@ extern "C" int mpt_time_trace(mpt_ctx* ctx, const float* o, const float* d, cons
 
 // ---- the post-processing stages: guide pass and denoiser, ambient occlusion, temporal accumulation, SVGF, display ----------------------
 #include "mpt_post.h"
+
+// ---- next-event estimation (mpt_nee.h; the estimator is specified in include/mpt.h) -------------------------------------------------
+// One launch of k_nee<WALK> over the whole image on ctx->stream, synchronous like mpt_render: the renders in flight are collected first,
+// the light table is built if stale, the kernel adds its samples onto the HDR sum in place.
+static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
+    if (!ctx) return MPT_ERR_INVALID_ARG;
+    if (!p || !n) return fail(ctx, MPT_ERR_INVALID_ARG, "null render or NEE params");
+    if (p->rng_mode != MPT_RNG_PHILOX) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: rng_mode must be MPT_RNG_PHILOX");
+    if (p->bsdf_mode != MPT_BSDF_LAMBERT && p->bsdf_mode != MPT_BSDF_SCATTER)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: bsdf_mode must be MPT_BSDF_LAMBERT or MPT_BSDF_SCATTER");
+    if (p->shard_count != 1 || p->shard_rank != 0) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: no shards");
+    if (p->flags != 0u) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: flags must be 0");
+    if (p->sample_count == 0u || (uint64_t)p->sample_begin + p->sample_count > (1ull << 27))
+        return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: sample_count 0 or samples beyond 2^27");
+    if (p->max_depth < 1 || p->max_depth > 32) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: max_depth outside 1..32");
+    if (!walk_valid(n->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: bad walk");
+    if (n->clamp != n->clamp) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: NaN clamp");
+    int rc = wait_impl(ctx);
+    if (rc) return rc;
+    if (!ctx->have_scene || !ctx->have_uniforms || !ctx->W) return fail(ctx, MPT_ERR_NOT_READY, "scene, uniforms or size not set");
+    if ((uint32_t)ctx->u.screenSize[0] != ctx->W || (uint32_t)ctx->u.screenSize[1] != ctx->H)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "uniforms.screenSize does not match mpt_resize");
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = ensure_lights(ctx))) return rc;
+    NeeState& ns = ctx->nee;
+    if (!ns.totals) {
+        HIPCHK(ns.totals.alloc(32));
+        HIPCHK(ns.e0.create(hipEventCreate));
+        HIPCHK(ns.e1.create(hipEventCreate));
+    }
+    HIPCHK(hipMemsetAsync(ns.totals.get(), 0, 32, ctx->stream));
+    const mpt_uniforms& u = ctx->u;
+    NeePass P = {};
+    P.sum = ctx->d_sum;
+    P.totals = ns.totals.get();
+    P.lights = ctx->lights.rec.get();
+    P.cdf = ctx->lights.cdf.get();
+    P.ids = ctx->lights.d_ids.get();
+    P.n_lights = ctx->lights.n();
+    P.cam = F3{u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2]};
+    P.first = F3{u.firstPixelPosition[0], u.firstPixelPosition[1], u.firstPixelPosition[2]};
+    P.vu = F3{u.viewportU[0], u.viewportU[1], u.viewportU[2]};
+    P.vv = F3{u.viewportV[0], u.viewportV[1], u.viewportV[2]};
+    P.fW = u.screenSize[0];
+    P.fH = u.screenSize[1];
+    P.W = ctx->W;
+    P.H = ctx->H;
+    P.sample_begin = p->sample_begin;
+    P.sample_count = p->sample_count;
+    P.seed_lo = p->seed_lo;
+    P.seed_hi = p->seed_hi;
+    P.bsdf_mode = p->bsdf_mode;
+    P.max_depth = p->max_depth;
+    P.primitive_count = (uint32_t)std::min<uint64_t>(u.primitiveCount, 0xFFFFFFFFull);
+    P.clamp = n->clamp > 0.0f ? n->clamp : INFINITY;
+    const dim3 grid = tile_grid(ctx->W, ctx->H);
+    SceneDev sc = scene_dev(ctx);
+    AccelDev ac = {};
+    HIPCHK(hipEventRecord(ns.e0.get(), ctx->stream));
+    if (resolve_walk(ctx, n->walk) == 1) {
+        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the image of k_trace_rays_ordered: workgroups of 256)
+        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+        hipLaunchKernelGGL(k_nee<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
+    } else if (ctx->n_lds_nodes == ctx->n_nodes) {
+        hipLaunchKernelGGL(k_nee<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+    } else {
+        hipLaunchKernelGGL(k_nee<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ns.e1.get(), ctx->stream));
+    unsigned long long totals[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(totals, ns.totals.get(), 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, ns.e0.get(), ns.e1.get()));
+    ctx->stats.paths += totals[0];
+    ctx->stats.rays += totals[1];
+    ctx->stats.trace_kernel_ms = (double)ms;
+    ctx->stats.total_ms = (double)ms;
+    ctx->stats.trace_launches = 1;
+    if (out) {
+        out->paths = totals[0];
+        out->rays = totals[1];
+        out->shadow_rays = totals[2];
+        out->shadow_rays_occluded = totals[3];
+        out->lights = ctx->lights.n();
+        out->device_ms = (double)ms;
+    }
+    return MPT_OK;
+}
+extern "C" int mpt_render_nee(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
+    return guarded(ctx, [&] { return render_nee_impl(ctx, p, n, out); });
+}
 
 // Position-sensitive 64-bit digest of a device array of 32-bit words: sum over i of splitmix64(i << 32 | word[i]) (a commutative sum, so
 // the order in which the waves add is free).  What the tests compare two builds of a scene by, array by array (mpt_scene_digest).

@@ -515,6 +515,8 @@ static int ensure_lights(mpt_ctx* ctx) {
         HIPCHK(t.cdf.alloc((size_t)n * 4));
         HIPCHK(hipMemcpy(t.rec.get(), t.h_rec.data(), (size_t)n * 64, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(t.cdf.get(), t.h_cdf.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIPCHK(t.d_ids.alloc((size_t)n * 4));
+        HIPCHK(hipMemcpy(t.d_ids.get(), t.ids.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     }
     t.seen = seen;
     t.built = true;

@@ -26,7 +26,7 @@ SYMBOLS = (
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
-    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting",
+    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_render_nee",
 )
 
 _lib = None
@@ -85,6 +85,7 @@ def load():
     L.mpt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
     L.mpt_renderer_ambient_occlusion.argtypes = [vp, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(capi.AoInfo)]
     L.mpt_renderer_direct_lighting.argtypes = [vp, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.POINTER(capi.DirectInfo)]
+    L.mpt_renderer_render_nee.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.NeeInfo)]
     _lib = L
     return L
 
@@ -405,6 +406,13 @@ class Renderer:
         info = capi.DirectInfo()
         self._chk(self.L.mpt_renderer_direct_lighting(self.h, int(samples), int(walk), _fp(out), C.byref(info)), "renderDirectLighting")
         return out, info.as_dict()
+
+    def renderNee(self, spp, depth, walk=capi.WALK_AUTO, clamp=0.0):
+        """mpt_renderer_render_nee: samples [0, spp) onto the HDR sum (readSum) with a light sample and MIS at every Lambert vertex, at
+        max_depth `depth`; clamp <= 0 = no per-sample clamp.  Returns the mpt_nee_info as a dict."""
+        info = capi.NeeInfo()
+        self._chk(self.L.mpt_renderer_render_nee(self.h, int(spp), int(depth), int(walk), float(clamp), C.byref(info)), "renderNee")
+        return info.as_dict()
 
     def scene(self):
         return Scene(_borrowed=self.L.mpt_renderer_scene(self.h))
