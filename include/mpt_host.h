@@ -106,6 +106,9 @@ int mpt_renderer_direct_lighting(mpt_renderer* r, uint32_t samples, int32_t walk
 /* mpt_render_nee (include/mpt.h) for the renderer's camera and render parameters: samples [0, spp) onto the HDR sum (read it with
  * mpt_renderer_read_sum) at max_depth `depth`, `walk` one of MPT_WALK_*, clamp <= 0 = no per-sample clamp.  out may be NULL.          */
 int mpt_renderer_render_nee(mpt_renderer* r, uint32_t spp, int32_t depth, int32_t walk, float clamp, mpt_nee_info* out);
+/* mpt_set_light_sampling (include/mpt.h) on the renderer's context: MPT_LIGHT_SAMPLING_AREA (the default) or MPT_LIGHT_SAMPLING_CONE for
+ * the two calls above.  A bad mode: MPT_ERR_INVALID_ARG, nothing changed.                                                             */
+int mpt_renderer_set_light_sampling(mpt_renderer* r, int32_t mode);
 mpt_ctx* mpt_renderer_context(mpt_renderer* r);
 mpt_scene* mpt_renderer_scene(mpt_renderer* r);               /* borrowed                                */
 

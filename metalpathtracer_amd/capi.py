@@ -38,7 +38,7 @@ SYMBOLS = (
     "mpt_display_image",
     "mpt_trace_occluded", "mpt_time_trace", "mpt_ambient_occlusion", "mpt_read_ao", "mpt_ao_buffer", "mpt_ao_image",
     "mpt_light_info", "mpt_read_lights", "mpt_direct_lighting", "mpt_read_direct", "mpt_direct_buffer", "mpt_direct_image",
-    "mpt_render_nee",
+    "mpt_render_nee", "mpt_set_light_sampling", "mpt_get_light_sampling",
 )
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
@@ -62,6 +62,7 @@ WALK_REFERENCE, WALK_OWN, WALK_AUTO = 0, 1, 2
 AO_MAX_SAMPLES = 1024
 DIRECT_MAX_SAMPLES = 1024
 LIGHTS_MAX = 65536
+LIGHT_SAMPLING_AREA, LIGHT_SAMPLING_CONE = 0, 1
 
 
 class MptError(RuntimeError):
@@ -389,6 +390,8 @@ def load():
     L.mpt_direct_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.mpt_direct_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(DirectParams), fp, up, up]
     L.mpt_render_nee.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(NeeInfo)]
+    L.mpt_set_light_sampling.argtypes = [vp, C.c_int32]
+    L.mpt_get_light_sampling.argtypes = [vp, C.POINTER(C.c_int32)]
     _lib = L
     return L
 
@@ -716,6 +719,17 @@ class Context:
         info = NeeInfo()
         self._chk(self.L.mpt_render_nee(self.h, C.byref(p), C.byref(n), C.byref(info)), "mpt_render_nee")
         return info.as_dict()
+
+    def set_light_sampling(self, mode):
+        """mpt_set_light_sampling: LIGHT_SAMPLING_AREA (the default) or LIGHT_SAMPLING_CONE — how direct_lighting, direct_image and
+        render_nee sample a sphere light."""
+        self._chk(self.L.mpt_set_light_sampling(self.h, int(mode)), "mpt_set_light_sampling")
+
+    @property
+    def light_sampling(self):
+        mode = C.c_int32(-1)
+        self._chk(self.L.mpt_get_light_sampling(self.h, C.byref(mode)), "mpt_get_light_sampling")
+        return mode.value
 
     def build_bvh(self, prims):
         """GPU LBVH over the packed primitive array (12 floats each) -> (bvh [N, 8] f32, prim_idx [P] i32, device ms)."""

@@ -397,6 +397,7 @@ mpt_nee_info Renderer::renderNee(uint32_t spp, int32_t depth, int32_t walk, floa
     sumSamples_ += spp;
     return info;
 }
+void Renderer::setLightSampling(int mode) { check(mpt_set_light_sampling(ctx_, static_cast<int32_t>(mode)), "mpt_set_light_sampling"); }
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     if (rgba.size() != n) throw std::runtime_error("writeSum: the array does not have the size of the frame");

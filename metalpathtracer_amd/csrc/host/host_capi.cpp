@@ -350,6 +350,10 @@ int mpt_renderer_render_nee(mpt_renderer* r, uint32_t spp, int32_t depth, int32_
         if (out) *out = info;
     });
 }
+int mpt_renderer_set_light_sampling(mpt_renderer* r, int32_t mode) {
+    if (!r) return MPT_ERR_INVALID_ARG;
+    return mpt_set_light_sampling(r->r->context(), mode);   // (the status itself: a bad mode is MPT_ERR_INVALID_ARG)
+}
 mpt_ctx* mpt_renderer_context(mpt_renderer* r) { return r ? r->r->context() : nullptr; }
 mpt_scene* mpt_renderer_scene(mpt_renderer* r) {
     if (!r) return nullptr;

@@ -45,6 +45,7 @@ static void usage() {
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]] [--ao N [--ao-radius R]]\n"
         "           [--direct N [--direct-walk reference|own|auto]]\n"
         "           [--nee [--nee-walk reference|own|auto] [--nee-clamp C]]\n"
+        "           [--light-sampling area|cone]\n"
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
         "           [--svgf [--svgf-iterations N] [--temporal-history N] [--temporal-spp K]]\n"
@@ -95,6 +96,11 @@ static void usage() {
         "                    estimator and its clamp (header MPTNEE1) and is resumed only by an --nee run with the same clamp, a plain one\n"
         "                    only by a plain run.  Not with --adaptive, --gpus > 1, --camera-path (hence --temporal, --svgf), --frames,\n"
         "                    --ao, --direct, --rng literal or --bsdf scatter-all\n"
+        "  --light-sampling  with --direct or --nee: how a sphere light is sampled (mpt_set_light_sampling, include/mpt.h) — area: uniformly\n"
+        "                    over its whole surface (the default); cone: uniformly in the cone of directions it subtends from the\n"
+        "                    shading point, so that every sample meets the light.  Triangle lights are sampled the same either way.  The\n"
+        "                    \"direct\" / \"nee\" JSON object gains \"light_sampling\"; a checkpoint of an --nee render with cone sampling\n"
+        "                    has the header MPTNEE2 and is resumed only by such a run, one with area sampling (MPTNEE1) only by such a run\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
@@ -380,6 +386,8 @@ int main(int argc, char** argv) {
     bool nee = false, haveNeeOpt = false;   // --nee; --nee-walk / --nee-clamp were given
     int32_t neeWalk = MPT_WALK_AUTO;
     float neeClamp = 0.0f;
+    bool haveLightSampling = false;   // --light-sampling was given
+    int lightSampling = MPT_LIGHT_SAMPLING_AREA;
     bool display = false;   // a display flag was given: .ppm files come from mpt_display
     DisplayOut shown;
     std::memset(&shown.params, 0, sizeof shown.params);   // (clamp, srgb, and 0 = the defaults of include/mpt.h)
@@ -446,6 +454,15 @@ int main(int argc, char** argv) {
         else if (a == "--nee-clamp") {
             neeClamp = static_cast<float>(std::atof(next()));
             haveNeeOpt = true;
+        }
+        else if (a == "--light-sampling") {
+            const char* v = next();
+            if (std::strcmp(v, "area") != 0 && std::strcmp(v, "cone") != 0) {
+                std::fprintf(stderr, "mpt_render: --light-sampling takes area or cone\n");
+                return 2;
+            }
+            lightSampling = std::strcmp(v, "cone") == 0 ? MPT_LIGHT_SAMPLING_CONE : MPT_LIGHT_SAMPLING_AREA;
+            haveLightSampling = true;
         }
         else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
         else if (a == "--adaptive") {
@@ -542,6 +559,10 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "mpt_render: --key, --percentile and --adaptation go with --auto-exposure\n");
         return 2;
     }
+    if (haveLightSampling && !nee && !haveDirect) {
+        std::fprintf(stderr, "mpt_render: --light-sampling goes with --direct or --nee\n");
+        return 2;
+    }
     if (nee || haveNeeOpt) {
         const char* why = !nee ? "a run without --nee" : neeClamp != neeClamp ? "a --nee-clamp that is no number" : adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1"
                           : !cameraPath.empty() ? "--camera-path" : frames > 0 ? "--frames" : haveAo || haveAoRadius ? "--ao"
@@ -614,6 +635,7 @@ int main(int argc, char** argv) {
     try {
         Renderer r(device, scene, assetRoot, bvh);
         r.setRenderParams(prm);
+        if (haveLightSampling) r.setLightSampling(lightSampling);
         // the reference hard-codes Camera::reset(); the flags overwrite the same globals before the viewport is built
         if (havePos) Camera::position = mpt::float3(camPos[0], camPos[1], camPos[2]);
         if (haveDir) Camera::forward = mpt::normalize(mpt::float3(camDir[0], camDir[1], camDir[2]));
@@ -624,6 +646,9 @@ int main(int argc, char** argv) {
         std::vector<float> img;
         float scale = 1.0f;
         std::string extraJson;
+        // (the "direct" / "nee" object names the sampling only when the flag was given: without it the line is what it was)
+        const std::string samplingJson = !haveLightSampling ? "" : lightSampling == MPT_LIGHT_SAMPLING_CONE ? ", \"light_sampling\": \"cone\"" : ", \"light_sampling\": \"area\"";
+        const bool neeCone = nee && lightSampling == MPT_LIGHT_SAMPLING_CONE;
         auto t0 = std::chrono::steady_clock::now();
         if (ao > 0) {   // grey (ao, ao, ao, 1) through the writer the radiance goes through
             const mpt_ao_info info = r.renderAmbientOcclusion(static_cast<uint32_t>(ao), aoRadius);
@@ -643,10 +668,10 @@ int main(int argc, char** argv) {
             const mpt_direct_info info = r.renderDirectLighting(static_cast<uint32_t>(direct), directWalk);
             r.readDirectLighting(img);
             char buf[320];
-            std::snprintf(buf, sizeof buf, ", \"direct\": {\"samples\": %d, \"pixels_surface\": %llu, \"rays\": %llu, \"rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f}",
+            std::snprintf(buf, sizeof buf, ", \"direct\": {\"samples\": %d, \"pixels_surface\": %llu, \"rays\": %llu, \"rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f",
                           direct, (unsigned long long)info.pixels_surface, (unsigned long long)info.rays, (unsigned long long)info.rays_occluded,
                           (unsigned long long)info.lights, info.device_ms);
-            extraJson = buf;
+            extraJson = buf + samplingJson + "}";
         } else if (adaptive) {
             const mpt_adaptive_info info = r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);
             if (!display || denoise) r.readAdaptiveMean(img);
@@ -722,13 +747,18 @@ int main(int argc, char** argv) {
                 unsigned sd = 0;
                 unsigned long long sh = 0;
                 // (an --nee sum is another estimator's: its header is "MPTNEE1 ... scene-hash clamp-bits\n", which the plain format does not
-                //  parse and the other way round, so neither run continues the other's sum, nor an --nee run one of another clamp)
+                //  parse and the other way round, so neither run continues the other's sum, nor an --nee run one of another clamp; with
+                //  cone sampling of the sphere lights it is "MPTNEE2 ... clamp-bits sampling\n": the two samplings do not mix either)
                 unsigned cb = 0;
-                const bool parsed = f && (nee ? std::fscanf(f, "MPTNEE1 %d %d %u %u %d %d %d %llx %x", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb) == 9
+                int ls = 0;
+                const bool parsed = f && (neeCone ? std::fscanf(f, "MPTNEE2 %d %d %u %u %d %d %d %llx %x %d", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb, &ls) == 10 &&
+                                                        ls == lightSampling
+                                          : nee ? std::fscanf(f, "MPTNEE1 %d %d %u %u %d %d %d %llx %x", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb) == 9
                                               : std::fscanf(f, "MPTSUM2 %d %d %u %u %d %d %d %llx", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh) == 8);
                 if (!parsed || std::fgetc(f) != '\n') {
                     if (f) std::fclose(f);
-                    throw std::runtime_error("cannot read the checkpoint " + resume + (nee ? " as one of an --nee render" : " as one of a plain render"));
+                    throw std::runtime_error("cannot read the checkpoint " + resume + (neeCone ? " as one of an --nee render with cone light sampling"
+                                                                                     : nee   ? " as one of an --nee render with area light sampling" : " as one of a plain render"));
                 }
                 if (nee && cb != neeClampBits) {
                     std::fclose(f);
@@ -747,10 +777,10 @@ int main(int argc, char** argv) {
             if (nee) {
                 const mpt_nee_info info = r.renderNee(static_cast<uint32_t>(spp), depth, neeWalk, neeClamp, have);
                 char buf[320];
-                std::snprintf(buf, sizeof buf, ", \"nee\": {\"paths\": %llu, \"rays\": %llu, \"shadow_rays\": %llu, \"shadow_rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f}",
+                std::snprintf(buf, sizeof buf, ", \"nee\": {\"paths\": %llu, \"rays\": %llu, \"shadow_rays\": %llu, \"shadow_rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f",
                               (unsigned long long)info.paths, (unsigned long long)info.rays, (unsigned long long)info.shadow_rays,
                               (unsigned long long)info.shadow_rays_occluded, (unsigned long long)info.lights, info.device_ms);
-                extraJson = buf;
+                extraJson = buf + samplingJson + "}";
             } else {
                 r.renderBatch(have, static_cast<uint32_t>(spp));
             }
@@ -759,7 +789,10 @@ int main(int argc, char** argv) {
                 const std::string tmp = checkpoint + ".tmp";
                 FILE* f = std::fopen(tmp.c_str(), "wb");
                 if (!f) throw std::runtime_error("cannot write " + tmp);
-                if (nee)
+                if (neeCone)
+                    std::fprintf(f, "MPTNEE2 %d %d %u %u %d %d %d %llx %x %d\n", width, height, have + static_cast<uint32_t>(spp), seed, prm.rng_mode, depth,
+                                 prm.bsdf_mode, sceneHash, neeClampBits, lightSampling);
+                else if (nee)
                     std::fprintf(f, "MPTNEE1 %d %d %u %u %d %d %d %llx %x\n", width, height, have + static_cast<uint32_t>(spp), seed, prm.rng_mode, depth,
                                  prm.bsdf_mode, sceneHash, neeClampBits);
                 else

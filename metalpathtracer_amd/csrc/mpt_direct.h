@@ -1,6 +1,8 @@
 // mpt_direct.h — direct lighting over the first-hit guide buffers (included by mpt_hip.hip after mpt_anyhit.h):
 //   k_light_collect   one thread per device primitive: the emissive ones are appended to a list (the host sorts it into the light table)
 //   k_direct<WALK>    per surface pixel, N points on the lights drawn by power, one shadow ray each through an any-hit walk
+//   k_direct_cone<WALK>  the same pass with a sphere light sampled in the cone it subtends (MPT_LIGHT_SAMPLING_CONE); both kernels are
+//                     direct_pass<WALK, CONE>, which differ in the sphere sample alone
 // The pass is specified exactly in include/mpt.h (mpt_direct_params) and restated in numpy in tests/direct_ref.py; DESIGN.md §16 has the
 // table, the lane mapping and the registers.
 #pragma once
@@ -29,6 +31,37 @@ __global__ __launch_bounds__(256) void k_light_collect(const float4* prims, cons
     r[3] = make_float4(m1.x * m1.w, m1.y * m1.w, m1.z * m1.w, 0.0f);
 }
 
+// ---- a sphere light sampled by solid angle (MPT_LIGHT_SAMPLING_CONE; include/mpt.h has the rule, tests/cone_ref.py restates it) ----------
+// The cap a point sees of the sphere (c, r), from w = c - o: false unless the point lies outside (a NaN: false).  omc = 1 - cos(theta_max)
+// without cancellation; J = the reciprocal of the solid-angle pdf, the selection of the light included (inv_pdf = 4 pi r^2 / p_k).
+__device__ __forceinline__ bool cone_cap(F3 w, float r, float inv_pdf, float& dc2, float& omc, float& J) {
+    dc2 = dot3(w, w);
+    const float r2 = r * r;
+    const float s2 = r2 / dc2;
+    const float cm = sqrtf(1.0f - s2);
+    omc = s2 / (1.0f + cm);
+    J = omc * (inv_pdf / ((2.0f * r) * r));
+    return dc2 > r2;
+}
+// The direction drawn uniformly in that cone from (u1, u2), in the frame of Duff et al. 2017 around wc = w / |w|, and the distance to the
+// near intersection with the sphere: r^2 - dc^2 sin^2(theta) as a product of factors that do not cancel at the cone's edge.
+__device__ __forceinline__ void cone_sample(F3 w, float dc2, float omc, float u1, float u2, F3& wi, float& dist) {
+    const float k = u1 * omc;
+    const float ct = 1.0f - k;
+    const float st = sqrtf(k * (2.0f - k));
+    float sn, cs;
+    sincos_2pi(u2, sn, cs);
+    const float dc = sqrtf(dc2);
+    const F3 wc = w * mpt_rcp(dc);
+    const float sg = wc.z >= 0.0f ? 1.0f : -1.0f;
+    const float a = -1.0f / (sg + wc.z);
+    const float b = (wc.x * wc.y) * a;
+    const F3 t1 = f3(1.0f + ((sg * wc.x) * wc.x) * a, sg * b, -(sg * wc.x));
+    const F3 t2 = f3(b, sg + (wc.y * wc.y) * a, -wc.y);
+    wi = normalize3(((st * cs) * t1 + (st * sn) * t2) + ct * wc);
+    dist = dc * ct - sqrtf(dc2 * ((omc * (1.0f - u1)) * ((2.0f - omc) - k)));
+}
+
 struct DirectPass {
     const float4* ad;            // (albedo, t)
     const float4* nc;            // (normal facing the ray, class)
@@ -52,8 +85,9 @@ struct DirectPass {
 // of lights start next to each other and point the same way, so a round's walk is coherent as it is, and a pixel's sum runs in sample
 // order in its one lane: no cross-lane work.  A round in which no lane has a ray skips the walk; a tile without a surface pixel
 // returns after writing its constants.  The table is fetched per lane from global memory (it is small and stays in L2).
-template <int WALK>
-__global__ __launch_bounds__(256) void k_direct(SceneDev sc, AccelDev ac, DirectPass P) {
+// CONE: a sphere light is sampled by cone_cap / cone_sample; a triangle light, the selection and everything else are the same.
+template <int WALK, bool CONE>
+__device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass P) {
     extern __shared__ float4 lds_raw[];
     if (WALK == MPT_AO_OWN) ot_stage(sc, ac, lds_raw);
     else stage_nodes(sc, lds_raw);
@@ -125,23 +159,48 @@ __global__ __launch_bounds__(256) void k_direct(SceneDev sc, AccelDev ac, Direct
         const F3 e1 = f3(L1.x, L1.y, L1.z), e2 = f3(L2.x, L2.y, L2.z), c = f3(L0.x, L0.y, L0.z);
         const F3 pt = (c + a * e1) + b * e2;
         const F3 ng = normalize3(cross3(e1, e2));
-        // ... or of the sphere
-        const float z = 2.0f * ua - 1.0f;
-        float sn, cs;
-        sincos_2pi(ub, sn, cs);
-        const float rr = sqrtf(1.0f - z * z);
-        const F3 ns = f3(rr * cs, rr * sn, z);
-        const F3 ps = c + L1.x * ns;
-        const F3 nl = tri ? ng : ns;
-        const F3 p = tri ? pt : ps;
-        const F3 v = p - o;
-        const float d2 = dot3(v, v);
-        const float dist = sqrtf(d2);
-        const F3 wi = v * mpt_rcp(dist);
-        const float cos_s = dot3(n, wi);
-        const float dl = dot3(nl, wi);
-        const float cos_l = tri ? fabsf(dl) : -dl;
-        const bool live = surface && d2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;   // (a NaN skips)
+        F3 wi;
+        float d2, dist, cos_s, cos_l, fac = 0.0f;
+        bool live;
+        if (!CONE) {
+            // ... or of the sphere
+            const float z = 2.0f * ua - 1.0f;
+            float sn, cs;
+            sincos_2pi(ub, sn, cs);
+            const float rr = sqrtf(1.0f - z * z);
+            const F3 ns = f3(rr * cs, rr * sn, z);
+            const F3 ps = c + L1.x * ns;
+            const F3 nl = tri ? ng : ns;
+            const F3 p = tri ? pt : ps;
+            const F3 v = p - o;
+            d2 = dot3(v, v);
+            dist = sqrtf(d2);
+            wi = v * mpt_rcp(dist);
+            cos_s = dot3(n, wi);
+            const float dl = dot3(nl, wi);
+            cos_l = tri ? fabsf(dl) : -dl;
+            live = surface && d2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;   // (a NaN skips)
+        } else {
+            // ... or a direction of the cone the sphere subtends; the sample's factor is formed here, so one value crosses the walk
+            const F3 vt = pt - o;
+            d2 = dot3(vt, vt);
+            const float dist_t = sqrtf(d2);
+            const F3 wi_t = vt * mpt_rcp(dist_t);
+            const float cos_t = dot3(n, wi_t);
+            cos_l = fabsf(dot3(ng, wi_t));
+            const float g = (cos_t * cos_l) / d2;
+            const F3 w = c - o;
+            float dc2, omc, J, dist_c;
+            const bool outside = cone_cap(w, L1.x, L3.w, dc2, omc, J);
+            F3 wi_c;
+            cone_sample(w, dc2, omc, ua, ub, wi_c, dist_c);
+            const float cos_c = dot3(n, wi_c);
+            wi = tri ? wi_t : wi_c;
+            dist = tri ? dist_t : dist_c;
+            cos_s = tri ? cos_t : cos_c;
+            fac = tri ? g * L3.w : cos_c * J;
+            live = surface && cos_s > 0.0f && (tri ? d2 > 0.0f && cos_l > 0.0f : outside && dist_c > 0.0f);   // (a NaN skips)
+        }
         if (__ballot(live) == 0ull) continue;   // (wave-uniform)
         const float tmax = dist * 0.9990234375f;
         bool hit;
@@ -155,8 +214,11 @@ __global__ __launch_bounds__(256) void k_direct(SceneDev sc, AccelDev ac, Direct
             n_traced += 1u;
             if (!hit) {
                 n_unoccluded += 1u;
-                const float g = (cos_s * cos_l) / d2;
-                const float w = g * L3.w;
+                float w = fac;
+                if (!CONE) {
+                    const float g = (cos_s * cos_l) / d2;
+                    w = g * L3.w;
+                }
                 S = S + f3(L3.x * w, L3.y * w, L3.z * w);
             }
         }
@@ -176,4 +238,12 @@ __global__ __launch_bounds__(256) void k_direct(SceneDev sc, AccelDev ac, Direct
         if (n_traced != 0u) atomicAdd(P.totals() + 1, (unsigned long long)n_traced);
         if (n_unoccluded != 0u) atomicAdd(P.totals() + 2, (unsigned long long)n_unoccluded);
     }
+}
+template <int WALK>
+__global__ __launch_bounds__(256) void k_direct(SceneDev sc, AccelDev ac, DirectPass P) {
+    direct_pass<WALK, false>(sc, ac, P);
+}
+template <int WALK>
+__global__ __launch_bounds__(256) void k_direct_cone(SceneDev sc, AccelDev ac, DirectPass P) {
+    direct_pass<WALK, true>(sc, ac, P);
 }

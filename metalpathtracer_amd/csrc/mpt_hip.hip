@@ -357,6 +357,7 @@ struct mpt_ctx : SceneState {
     LightState lights;
     DirectState di;
     NeeState nee;
+    int32_t light_sampling = MPT_LIGHT_SAMPLING_AREA;   // mpt_set_light_sampling: host state, read at the start of the three calls that sample lights
     int dp_px = 4;                  // MPT_DISPLAY_PX: pixels per thread of k_dp_present, 1 or 4 (the same bytes)
     bool dp_hist_agg = true;        // MPT_DISPLAY_HIST=plain: k_dp_histogram without the aggregation within the wave
 };
@@ -537,7 +538,9 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     for (const void* k : {(const void*)k_occluded_ref<false>, (const void*)k_occluded_ref<true>, (const void*)k_occluded_own, (const void*)k_ao<MPT_AO_REF>,
                           (const void*)k_ao<MPT_AO_REF_ALL_LDS>, (const void*)k_ao<MPT_AO_OWN>, (const void*)k_direct<MPT_AO_REF>,
                           (const void*)k_direct<MPT_AO_REF_ALL_LDS>, (const void*)k_direct<MPT_AO_OWN>, (const void*)k_nee<MPT_AO_REF>,
-                          (const void*)k_nee<MPT_AO_REF_ALL_LDS>, (const void*)k_nee<MPT_AO_OWN>})
+                          (const void*)k_nee<MPT_AO_REF_ALL_LDS>, (const void*)k_nee<MPT_AO_OWN>, (const void*)k_direct_cone<MPT_AO_REF>,
+                          (const void*)k_direct_cone<MPT_AO_REF_ALL_LDS>, (const void*)k_direct_cone<MPT_AO_OWN>, (const void*)k_nee_cone<MPT_AO_REF>,
+                          (const void*)k_nee_cone<MPT_AO_REF_ALL_LDS>, (const void*)k_nee_cone<MPT_AO_OWN>})
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = ctx.release();
     return MPT_OK;
@@ -2477,15 +2480,16 @@ static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_n
     const dim3 grid = tile_grid(ctx->W, ctx->H);
     SceneDev sc = scene_dev(ctx);
     AccelDev ac = {};
+    const bool cone = ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE;
     HIPCHK(hipEventRecord(ns.e0.get(), ctx->stream));
     if (resolve_walk(ctx, n->walk) == 1) {
         const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the image of k_trace_rays_ordered: workgroups of 256)
         if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        hipLaunchKernelGGL(k_nee<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
+        hipLaunchKernelGGL(cone ? k_nee_cone<MPT_AO_OWN> : k_nee<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
     } else if (ctx->n_lds_nodes == ctx->n_nodes) {
-        hipLaunchKernelGGL(k_nee<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+        hipLaunchKernelGGL(cone ? k_nee_cone<MPT_AO_REF_ALL_LDS> : k_nee<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
     } else {
-        hipLaunchKernelGGL(k_nee<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+        hipLaunchKernelGGL(cone ? k_nee_cone<MPT_AO_REF> : k_nee<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ns.e1.get(), ctx->stream));
@@ -2511,6 +2515,24 @@ static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_n
 }
 extern "C" int mpt_render_nee(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
     return guarded(ctx, [&] { return render_nee_impl(ctx, p, n, out); });
+}
+// How mpt_direct_lighting, mpt_direct_image and mpt_render_nee sample a sphere light: host state of the context alone — no scene call,
+// mpt_resize or mpt_clear_sum touches it, and the light table does not depend on it.
+extern "C" int mpt_set_light_sampling(mpt_ctx* ctx, int32_t mode) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx) return MPT_ERR_INVALID_ARG;
+        if (mode != MPT_LIGHT_SAMPLING_AREA && mode != MPT_LIGHT_SAMPLING_CONE)
+            return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_set_light_sampling: mode must be MPT_LIGHT_SAMPLING_AREA or MPT_LIGHT_SAMPLING_CONE");
+        ctx->light_sampling = mode;
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_get_light_sampling(mpt_ctx* ctx, int32_t* mode) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx || !mode) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+        *mode = ctx->light_sampling;
+        return MPT_OK;
+    });
 }
 
 // Position-sensitive 64-bit digest of a device array of 32-bit words: sum over i of splitmix64(i << 32 | word[i]) (a commutative sum, so

@@ -1,6 +1,8 @@
 // mpt_nee.h — next-event estimation inside the path loop (included by mpt_hip.hip after mpt_direct.h):
 //   k_nee<WALK>   one lane per pixel: the pixel's samples in turn, a light sample with a shadow ray at every Lambert vertex, the light a
 //                 bounce finds weighted against it (power heuristic), the HDR sum updated in registers in sample order
+//   k_nee_cone<WALK>  the same render with a sphere light sampled in the cone it subtends (MPT_LIGHT_SAMPLING_CONE): its light sample and
+//                 the weight of a sphere light a bounce finds change, nothing else; both kernels are nee_render<WALK, CONE>
 // The estimator is specified exactly in include/mpt.h (mpt_nee_params) and restated in numpy in tests/nee_ref.py; DESIGN.md §17 has the
 // lane mapping, the registers and the measured times.  Nothing here edits a kernel or a device function of the plain render: the walks
 // (closest_hit_resume, closest_hit_ordered, any_hit_ref, any_hit_own), finish_hit, the Philox block and the light table are the tested ones.
@@ -30,8 +32,8 @@ struct NeePass {
 // ray.  A round is one closest-hit walk for the lanes that hold a ray, the shading of what they found, and one any-hit walk for the
 // lanes whose vertex drew a light sample (skipped when there is none).  The pixel's running sum lives in the lane's registers from
 // the first round to the last: no result slots, no resolve, no atomics on the image, and no value depends on which lane has which pixel.
-template <int WALK>
-__global__ __launch_bounds__(256) void k_nee(SceneDev sc, AccelDev ac, NeePass P) {
+template <int WALK, bool CONE>
+__device__ __forceinline__ void nee_render(SceneDev sc, AccelDev ac, NeePass P) {
     extern __shared__ float4 lds_raw[];
     if (WALK == MPT_AO_OWN) ot_stage(sc, ac, lds_raw);
     else stage_nodes(sc, lds_raw);
@@ -151,10 +153,19 @@ __global__ __launch_bounds__(256) void k_nee(SceneDev sc, AccelDev ac, NeePass P
                             if (ids[lo] == h.orig_id) {
                                 const float4 L0 = lights[MPT_LIGHT_F4 * lo], L3 = lights[MPT_LIGHT_F4 * lo + 3u];
                                 if (L0.w != 0.0f || h.front) {   // (a sphere emits outward only where it is sampled)
-                                    const float cos_l = -dot3(h.normal, d);
-                                    const float pl = (t * t) / (cos_l * L3.w);
-                                    const float q = pl / pb;
-                                    w = 1.0f / (1.0f + q * q);
+                                    if (!CONE || L0.w != 0.0f) {
+                                        const float cos_l = -dot3(h.normal, d);
+                                        const float pl = (t * t) / (cos_l * L3.w);
+                                        const float q = pl / pb;
+                                        w = 1.0f / (1.0f + q * q);
+                                    } else {   // the solid-angle pdf of the cone from this ray's origin: neither t nor cos_l enters
+                                        const float4 L1 = lights[MPT_LIGHT_F4 * lo + 1u];
+                                        float dc2, omc, J;
+                                        if (cone_cap(f3(L0.x, L0.y, L0.z) - o, L1.x, L3.w, dc2, omc, J)) {
+                                            const float q = 1.0f / (J * pb);
+                                            w = 1.0f / (1.0f + q * q);
+                                        }
+                                    }
                                 }
                             }
                         }
@@ -196,29 +207,55 @@ __global__ __launch_bounds__(256) void k_nee(SceneDev sc, AccelDev ac, NeePass P
                             const F3 e1 = f3(L1.x, L1.y, L1.z), e2 = f3(L2.x, L2.y, L2.z), c = f3(L0.x, L0.y, L0.z);
                             const F3 pt = (c + a * e1) + bb * e2;
                             const F3 ng = normalize3(cross3(e1, e2));
-                            const float zl = 2.0f * ua - 1.0f;
-                            float snl, csl;
-                            sincos_2pi(ub, snl, csl);
-                            const float rl = sqrtf(1.0f - zl * zl);
-                            const F3 ns = f3(rl * csl, rl * snl, zl);
-                            const F3 ps = c + L1.x * ns;
-                            const F3 nl = tri ? ng : ns;
-                            const F3 p = tri ? pt : ps;
-                            const F3 v = p - on;
-                            const float d2 = dot3(v, v);
-                            const float dist = sqrtf(d2);
-                            wi = v * mpt_rcp(dist);
-                            const float cos_s = dot3(h.normal, wi);
-                            const float dl = dot3(nl, wi);
-                            const float cos_l = tri ? fabsf(dl) : -dl;
-                            shadow = d2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;   // (a NaN skips)
-                            tmax = dist * 0.9990234375f;
-                            const float g = (cos_s * cos_l) / d2;
-                            const float pl = d2 / (cos_l * L3.w);
-                            const float pbs = cos_s * 0.31830987f;
-                            const float q = pbs / pl;
-                            const float wl = 1.0f / (1.0f + q * q);
-                            const float m = (g * L3.w) * wl;
+                            float m;
+                            if (!CONE) {
+                                const float zl = 2.0f * ua - 1.0f;
+                                float snl, csl;
+                                sincos_2pi(ub, snl, csl);
+                                const float rl = sqrtf(1.0f - zl * zl);
+                                const F3 ns = f3(rl * csl, rl * snl, zl);
+                                const F3 ps = c + L1.x * ns;
+                                const F3 nl = tri ? ng : ns;
+                                const F3 p = tri ? pt : ps;
+                                const F3 v = p - on;
+                                const float d2 = dot3(v, v);
+                                const float dist = sqrtf(d2);
+                                wi = v * mpt_rcp(dist);
+                                const float cos_s = dot3(h.normal, wi);
+                                const float dl = dot3(nl, wi);
+                                const float cos_l = tri ? fabsf(dl) : -dl;
+                                shadow = d2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;   // (a NaN skips)
+                                tmax = dist * 0.9990234375f;
+                                const float g = (cos_s * cos_l) / d2;
+                                const float pl = d2 / (cos_l * L3.w);
+                                const float pbs = cos_s * 0.31830987f;
+                                const float q = pbs / pl;
+                                const float wl = 1.0f / (1.0f + q * q);
+                                m = (g * L3.w) * wl;
+                            } else {
+                                const F3 vt = pt - on;
+                                const float d2 = dot3(vt, vt);
+                                const float dist_t = sqrtf(d2);
+                                const F3 wi_t = vt * mpt_rcp(dist_t);
+                                const float cos_t = dot3(h.normal, wi_t);
+                                const float cos_l = fabsf(dot3(ng, wi_t));
+                                const float g = (cos_t * cos_l) / d2;
+                                const float pl = d2 / (cos_l * L3.w);
+                                const float q_t = (cos_t * 0.31830987f) / pl;
+                                const float m_t = (g * L3.w) * (1.0f / (1.0f + q_t * q_t));
+                                const F3 w = c - on;
+                                float dc2, omc, J, dist_c;
+                                const bool outside = cone_cap(w, L1.x, L3.w, dc2, omc, J);
+                                F3 wi_c;
+                                cone_sample(w, dc2, omc, ua, ub, wi_c, dist_c);
+                                const float cos_c = dot3(h.normal, wi_c);
+                                const float q_c = (cos_c * 0.31830987f) * J;
+                                const float m_c = (cos_c * J) * (1.0f / (1.0f + q_c * q_c));
+                                wi = tri ? wi_t : wi_c;
+                                shadow = (tri ? cos_t > 0.0f && d2 > 0.0f && cos_l > 0.0f : cos_c > 0.0f && outside && dist_c > 0.0f);   // (a NaN skips)
+                                tmax = (tri ? dist_t : dist_c) * 0.9990234375f;
+                                m = tri ? m_t : m_c;
+                            }
                             C = f3(((thr.x * m0.x) * 0.31830987f) * (L3.x * m), ((thr.y * m0.y) * 0.31830987f) * (L3.y * m),
                                    ((thr.z * m0.z) * 0.31830987f) * (L3.z * m));
                         }
@@ -287,4 +324,12 @@ __global__ __launch_bounds__(256) void k_nee(SceneDev sc, AccelDev ac, NeePass P
         if (n_shadow != 0ull) atomicAdd(P.totals + 2, n_shadow);
         if (n_occluded != 0ull) atomicAdd(P.totals + 3, n_occluded);
     }
+}
+template <int WALK>
+__global__ __launch_bounds__(256) void k_nee(SceneDev sc, AccelDev ac, NeePass P) {
+    nee_render<WALK, false>(sc, ac, P);
+}
+template <int WALK>
+__global__ __launch_bounds__(256) void k_nee_cone(SceneDev sc, AccelDev ac, NeePass P) {
+    nee_render<WALK, true>(sc, ac, P);
 }

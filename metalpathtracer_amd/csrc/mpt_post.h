@@ -579,14 +579,15 @@ static int direct_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad,
     const dim3 grid = tile_grid(W, H);
     SceneDev sc = scene_dev(ctx);
     AccelDev ac = {};
+    const bool cone = ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE;
     if (resolve_walk(ctx, p->walk) == 1) {
         const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);
         if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        hipLaunchKernelGGL(k_direct<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
+        hipLaunchKernelGGL(cone ? k_direct_cone<MPT_AO_OWN> : k_direct<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
     } else if (ctx->n_lds_nodes == ctx->n_nodes) {
-        hipLaunchKernelGGL(k_direct<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+        hipLaunchKernelGGL(cone ? k_direct_cone<MPT_AO_REF_ALL_LDS> : k_direct<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
     } else {
-        hipLaunchKernelGGL(k_direct<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
+        hipLaunchKernelGGL(cone ? k_direct_cone<MPT_AO_REF> : k_direct<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
     }
     HIPCHK(hipGetLastError());
     return MPT_OK;

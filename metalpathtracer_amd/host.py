@@ -26,7 +26,7 @@ SYMBOLS = (
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
-    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_render_nee",
+    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_render_nee", "mpt_renderer_set_light_sampling",
 )
 
 _lib = None
@@ -86,6 +86,7 @@ def load():
     L.mpt_renderer_ambient_occlusion.argtypes = [vp, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(capi.AoInfo)]
     L.mpt_renderer_direct_lighting.argtypes = [vp, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.POINTER(capi.DirectInfo)]
     L.mpt_renderer_render_nee.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.NeeInfo)]
+    L.mpt_renderer_set_light_sampling.argtypes = [vp, C.c_int32]
     _lib = L
     return L
 
@@ -413,6 +414,11 @@ class Renderer:
         info = capi.NeeInfo()
         self._chk(self.L.mpt_renderer_render_nee(self.h, int(spp), int(depth), int(walk), float(clamp), C.byref(info)), "renderNee")
         return info.as_dict()
+
+    def setLightSampling(self, mode):
+        """mpt_renderer_set_light_sampling: capi.LIGHT_SAMPLING_AREA (the default) or capi.LIGHT_SAMPLING_CONE for renderDirectLighting
+        and renderNee."""
+        self._chk(self.L.mpt_renderer_set_light_sampling(self.h, int(mode)), "setLightSampling")
 
     def scene(self):
         return Scene(_borrowed=self.L.mpt_renderer_scene(self.h))
