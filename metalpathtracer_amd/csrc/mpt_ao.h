@@ -1,11 +1,54 @@
 // mpt_ao.h — ambient occlusion over the first-hit guide buffers (included by mpt_hip.hip after mpt_anyhit.h):
 //   k_ao<WALK>   per surface pixel, N Lambert-distributed shadow rays from the bounce ray's origin through an any-hit walk
+// and what the per-tile shadow-ray kernels (k_ao, k_direct, k_nee and the cone variants) start from, written once:
+//   tile_walk<WALK>      the scene image staged in LDS, the own tree's stack, the wave's 8 x 8 tile
+//   any_hit<WALK>        the one dispatch to any_hit_own / any_hit_ref<ALL_LDS>
+//   guide_origin         the bounce ray's origin at a surface pixel of the guide buffers
 // The pass is specified exactly in include/mpt.h (mpt_ao_params) and restated in numpy in tests/ao_ref.py; DESIGN.md §15 has the layout,
 // the lane mapping and the measured times.
 #pragma once
 #include "mpt_anyhit.h"
 
 enum { MPT_AO_REF = 0, MPT_AO_REF_ALL_LDS = 1, MPT_AO_OWN = 2 };   // WALK: which tree, and whether all of it is in LDS
+
+// A workgroup of four waves takes a 16 x 16 pixel block, each wave one 8 x 8 tile of it (as k_dn_guide): (tx0, ty0) is the tile's first
+// pixel.  Every wave stages, also one whose tile lies outside the image (the callers return after this, wave-uniformly).
+struct TileWalk {
+    LdsNodes lds;
+    OtStack st;
+    uint32_t lane, tx0, ty0;
+};
+template <int WALK>
+__device__ __forceinline__ TileWalk tile_walk(const SceneDev& sc, const AccelDev& ac) {
+    extern __shared__ float4 lds_raw[];
+    if (WALK == MPT_AO_OWN) ot_stage(sc, ac, lds_raw);
+    else stage_nodes(sc, lds_raw);
+    TileWalk T = {};
+    T.lds = (LdsNodes)lds_raw;
+    if (WALK == MPT_AO_OWN) T.st = ot_stack(ac, lds_raw, 0u);
+    const uint32_t wave = threadIdx.x >> 6;
+    T.lane = threadIdx.x & 63u;
+    T.tx0 = blockIdx.x * MPT_DN_TILE + (wave & 1u) * 8u;
+    T.ty0 = blockIdx.y * MPT_DN_TILE + (wave >> 1) * 8u;
+    return T;
+}
+template <int WALK>
+__device__ __forceinline__ bool any_hit(const SceneDev& sc, const AccelDev& ac, const TileWalk& T, F3 o, F3 d, float tmax, bool live) {
+    if (WALK == MPT_AO_OWN) {
+        uint32_t flags;
+        return any_hit_own(ac, sc, T.lds, T.st, o, d, tmax, live, flags);
+    }
+    return any_hit_ref<WALK == MPT_AO_REF_ALL_LDS>(sc, T.lds, o, d, tmax, live);
+}
+// The origin of the bounce ray (shade_bounce) at pixel (px, py) of the guide buffers: t = ad.w, n = the normal of nc; P: any pass with a camera.
+template <class Pass>
+__device__ __forceinline__ F3 guide_origin(const Pass& P, uint32_t px, uint32_t py, float t, F3 n) {
+    const float uvx = ((float)px + 0.5f) / P.fW, uvy = ((float)py + 0.5f) / P.fH;
+    const F3 dv = (P.first + uvx * P.vu + uvy * P.vv) - P.cam;
+    const F3 dc = dv * (1.0f / sqrtf(dot3(dv, dv)));   // normalize3, with the division written out (the lanes diverge here)
+    const F3 hitp = P.cam + t * dc;
+    return hitp + 0.0001f * n;
+}
 
 struct AoPass {
     const float4* ad;            // (albedo, t)
@@ -34,14 +77,8 @@ struct AoPass {
 // no surface gets ao = 1, occluded = 0 from the lane that prepared it.
 template <int WALK>
 __global__ __launch_bounds__(256) void k_ao(SceneDev sc, AccelDev ac, AoPass P) {
-    extern __shared__ float4 lds_raw[];
-    if (WALK == MPT_AO_OWN) ot_stage(sc, ac, lds_raw);
-    else stage_nodes(sc, lds_raw);
-    const LdsNodes lds = (LdsNodes)lds_raw;
-    OtStack st = {};
-    if (WALK == MPT_AO_OWN) st = ot_stack(ac, lds_raw, 0u);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t tx0 = blockIdx.x * MPT_DN_TILE + (wave & 1u) * 8u, ty0 = blockIdx.y * MPT_DN_TILE + (wave >> 1) * 8u;
+    const TileWalk T = tile_walk<WALK>(sc, ac);
+    const uint32_t lane = T.lane, tx0 = T.tx0, ty0 = T.ty0;
     if (tx0 >= P.W || ty0 >= P.H) return;   // (wave-uniform: the tile lies outside the image)
     // every lane first prepares ONE pixel of the tile — its class, its normal and the origin of its rays — and the chunks below fetch
     // a pixel's values from the lane that holds them (ds_bpermute): the camera is not needed beyond this point
@@ -57,12 +94,8 @@ __global__ __launch_bounds__(256) void k_ao(SceneDev sc, AccelDev ac, AoPass P) 
             const float t = P.ad[i].w;
             my_surface = g.w == 0.0f;
             if (my_surface) {
-                const float uvx = ((float)px + 0.5f) / P.fW, uvy = ((float)py + 0.5f) / P.fH;
-                const F3 dv = (P.first + uvx * P.vu + uvy * P.vv) - P.cam;
-                const F3 dc = dv * (1.0f / sqrtf(dot3(dv, dv)));   // normalize3, with the division written out (the lanes diverge here)
                 const F3 n = f3(g.x, g.y, g.z);
-                const F3 hitp = P.cam + t * dc;
-                const F3 o = hitp + 0.0001f * n;   // the origin of the bounce ray (shade_bounce)
+                const F3 o = guide_origin(P, px, py, t, n);
                 ox = o.x, oy = o.y, oz = o.z;
                 nx = n.x, ny = n.y, nz = n.z;
             } else {
@@ -101,13 +134,7 @@ __global__ __launch_bounds__(256) void k_ao(SceneDev sc, AccelDev ac, AoPass P) 
             sincos_2pi(uphi, sn, cs);
             const float rr = sqrtf(1.0f - z * z);
             const F3 dir = normalize3(n + f3(rr * cs, rr * sn, z));   // the Lambert direction (PathTracing.h:252-254)
-            bool hit;
-            if (WALK == MPT_AO_OWN) {
-                uint32_t flags;
-                hit = any_hit_own(ac, sc, lds, st, o, dir, P.tmax, live, flags);
-            } else {
-                hit = any_hit_ref<WALK == MPT_AO_REF_ALL_LDS>(sc, lds, o, dir, P.tmax, live);
-            }
+            const bool hit = any_hit<WALK>(sc, ac, T, o, dir, P.tmax, live);
             // the group's G bits of the ballot: shifted down to bit 0, then up until the bits of the groups above fall off
             const unsigned long long mine = (__ballot(hit && live) >> (slot << gl)) << (64u - G);
             count += (uint32_t)__popcll(mine);

@@ -3,6 +3,8 @@
 //   k_direct<WALK>    per surface pixel, N points on the lights drawn by power, one shadow ray each through an any-hit walk
 //   k_direct_cone<WALK>  the same pass with a sphere light sampled in the cone it subtends (MPT_LIGHT_SAMPLING_CONE); both kernels are
 //                     direct_pass<WALK, CONE>, which differ in the sphere sample alone
+//   table_search, light_sample<CONE>   one sample of the light table — the selection, the point or direction on the light, the skip
+//                     predicate — for direct_pass and for nee_render (mpt_nee.h): the only copy
 // The pass is specified exactly in include/mpt.h (mpt_direct_params) and restated in numpy in tests/direct_ref.py; DESIGN.md §16 has the
 // table, the lane mapping and the registers.
 #pragma once
@@ -62,6 +64,91 @@ __device__ __forceinline__ void cone_sample(F3 w, float dc2, float omc, float u1
     dist = dc * ct - sqrtf(dc2 * ((omc * (1.0f - u1)) * ((2.0f - omc) - k)));
 }
 
+// ---- one sample of the light table: what k_direct and k_nee (and their cone variants) draw at a vertex, written once -----------------
+// The smallest k in [0, last] with below(k), for a predicate that is false up to some k and true from it on (true at `last`): a binary
+// search of the same length, table_search_steps(last + 1), in every lane.  Serves u < cdf[k] and id <= ids[k].
+__device__ __forceinline__ uint32_t table_search_steps(uint32_t n) { return n > 1u ? 32u - (uint32_t)__builtin_clz(n - 1u) : 0u; }   // ceil(log2(n))
+template <class Below>
+__device__ __forceinline__ uint32_t table_search(uint32_t last, uint32_t steps, Below below) {
+    uint32_t lo = 0u, hi = last;
+    for (uint32_t step = 0; step < steps; ++step) {
+        const uint32_t mid = (lo + hi) >> 1;
+        const bool b = below(mid);
+        const bool open = lo < hi;
+        hi = open && b ? mid : hi;
+        lo = open && !b ? mid + 1u : lo;
+    }
+    return lo;
+}
+// Light k sampled from the point o with the normal n by (ua, ub).  A triangle, and a sphere unless CONE: a point p of its area —
+// d2 = |p - o|^2, cos_l at the light; the estimator's factor is (cos_s cos_l / d2) inv_pdf.  CONE, a sphere: a direction of the cone it
+// subtends — the factor is cos_s J (d2 and cos_l are the triangle branch's and mean nothing).  ok: the sample can carry light (a NaN: false).
+struct LightSample {
+    F3 wi;                       // unit direction towards the light
+    float dist;                  // ... and the distance to it along wi
+    float cos_s, cos_l, d2, J;   // cos_s = n . wi
+    float inv_pdf;               // the record's: area / p_k
+    F3 Le;
+    bool tri, ok;
+};
+template <bool CONE>
+__device__ __forceinline__ LightSample light_sample(const float4* lights, uint32_t k, F3 o, F3 n, float ua, float ub) {
+    const float4 L0 = lights[MPT_LIGHT_F4 * k], L1 = lights[MPT_LIGHT_F4 * k + 1u], L2 = lights[MPT_LIGHT_F4 * k + 2u],
+                 L3 = lights[MPT_LIGHT_F4 * k + 3u];
+    LightSample s;
+    s.tri = L0.w != 0.0f;
+    s.Le = f3(L3.x, L3.y, L3.z);
+    s.inv_pdf = L3.w;
+    s.J = 0.0f;
+    // a point of the triangle ...
+    float a = ua, b = ub;
+    if (a + b > 1.0f) {
+        a = 1.0f - a;
+        b = 1.0f - b;
+    }
+    const F3 e1 = f3(L1.x, L1.y, L1.z), e2 = f3(L2.x, L2.y, L2.z), c = f3(L0.x, L0.y, L0.z);
+    const F3 pt = (c + a * e1) + b * e2;
+    const F3 ng = normalize3(cross3(e1, e2));
+    if (!CONE) {
+        // ... or of the sphere
+        const float z = 2.0f * ua - 1.0f;
+        float sn, cs;
+        sincos_2pi(ub, sn, cs);
+        const float rr = sqrtf(1.0f - z * z);
+        const F3 ns = f3(rr * cs, rr * sn, z);
+        const F3 ps = c + L1.x * ns;
+        const F3 nl = s.tri ? ng : ns;
+        const F3 p = s.tri ? pt : ps;
+        const F3 v = p - o;
+        s.d2 = dot3(v, v);
+        s.dist = sqrtf(s.d2);
+        s.wi = v * mpt_rcp(s.dist);
+        s.cos_s = dot3(n, s.wi);
+        const float dl = dot3(nl, s.wi);
+        s.cos_l = s.tri ? fabsf(dl) : -dl;
+        s.ok = s.d2 > 0.0f && s.cos_s > 0.0f && s.cos_l > 0.0f;
+    } else {
+        // ... or a direction of the cone the sphere subtends
+        const F3 vt = pt - o;
+        s.d2 = dot3(vt, vt);
+        const float dist_t = sqrtf(s.d2);
+        const F3 wi_t = vt * mpt_rcp(dist_t);
+        const float cos_t = dot3(n, wi_t);
+        s.cos_l = fabsf(dot3(ng, wi_t));
+        const F3 w = c - o;
+        float dc2, omc, dist_c;
+        const bool outside = cone_cap(w, L1.x, L3.w, dc2, omc, s.J);
+        F3 wi_c;
+        cone_sample(w, dc2, omc, ua, ub, wi_c, dist_c);
+        const float cos_c = dot3(n, wi_c);
+        s.wi = s.tri ? wi_t : wi_c;
+        s.dist = s.tri ? dist_t : dist_c;
+        s.cos_s = s.tri ? cos_t : cos_c;
+        s.ok = s.cos_s > 0.0f && (s.tri ? s.d2 > 0.0f && s.cos_l > 0.0f : outside && dist_c > 0.0f);
+    }
+    return s;
+}
+
 struct DirectPass {
     const float4* ad;            // (albedo, t)
     const float4* nc;            // (normal facing the ray, class)
@@ -85,17 +172,11 @@ struct DirectPass {
 // of lights start next to each other and point the same way, so a round's walk is coherent as it is, and a pixel's sum runs in sample
 // order in its one lane: no cross-lane work.  A round in which no lane has a ray skips the walk; a tile without a surface pixel
 // returns after writing its constants.  The table is fetched per lane from global memory (it is small and stays in L2).
-// CONE: a sphere light is sampled by cone_cap / cone_sample; a triangle light, the selection and everything else are the same.
+// CONE: a sphere light is sampled by cone_cap / cone_sample (light_sample<true>); a triangle light, the selection and everything else are the same.
 template <int WALK, bool CONE>
 __device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass P) {
-    extern __shared__ float4 lds_raw[];
-    if (WALK == MPT_AO_OWN) ot_stage(sc, ac, lds_raw);
-    else stage_nodes(sc, lds_raw);
-    const LdsNodes lds = (LdsNodes)lds_raw;
-    OtStack st = {};
-    if (WALK == MPT_AO_OWN) st = ot_stack(ac, lds_raw, 0u);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t tx0 = blockIdx.x * MPT_DN_TILE + (wave & 1u) * 8u, ty0 = blockIdx.y * MPT_DN_TILE + (wave >> 1) * 8u;
+    const TileWalk T = tile_walk<WALK>(sc, ac);
+    const uint32_t lane = T.lane, tx0 = T.tx0, ty0 = T.ty0;
     if (tx0 >= P.W || ty0 >= P.H) return;   // (wave-uniform: the tile lies outside the image)
     F3 o = f3(1.0f, 1.0f, 1.0f), n = f3(0.0f, 0.0f, 0.0f), albedo = f3(0.0f, 0.0f, 0.0f);
     uint32_t pixel = 0u;
@@ -108,11 +189,8 @@ __device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass
             const float4 a = P.ad[pixel];
             surface = g.w == 0.0f;
             if (surface) {
-                const float uvx = ((float)px + 0.5f) / P.fW, uvy = ((float)py + 0.5f) / P.fH;
-                const F3 dv = (P.first + uvx * P.vu + uvy * P.vv) - P.cam;
-                const F3 dc = dv * (1.0f / sqrtf(dot3(dv, dv)));   // normalize3, with the division written out (the lanes diverge here)
                 n = f3(g.x, g.y, g.z);
-                o = (P.cam + a.w * dc) + 0.0001f * n;   // the origin of the bounce ray, exactly as k_ao forms it
+                o = guide_origin(P, px, py, a.w, n);
                 albedo = f3(a.x, a.y, a.z);
             } else {
                 P.out[pixel] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
@@ -132,94 +210,27 @@ __device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass
     asm volatile("" : "+v"(out), "+v"(lights), "+v"(cdf), "+v"(n_pixels), "+v"(N), "+v"(sample_begin), "+v"(last));
     uint32_t n_traced = 0u, n_unoccluded = 0u;
     F3 S = f3(0.0f, 0.0f, 0.0f);
-    const uint32_t search_steps = P.n_lights > 1u ? 32u - (uint32_t)__builtin_clz(P.n_lights - 1u) : 0u;   // ceil(log2(n_lights))
+    // (the count is wave-uniform and stays in the scalar file: formed from n_lights - 1, which `last` above has put in a vector register,
+    // it would follow it there and take a vector register across the walk)
+    const uint32_t search_steps = __builtin_amdgcn_readfirstlane(table_search_steps(P.n_lights));
     const uint32_t rounds = P.n_lights != 0u ? P.sample_count : 0u;   // (no lights: nothing to sample, every surface pixel is black)
     for (uint32_t s = 0; s < rounds; ++s) {
         const U4 r = philox4x32_10<true>(pixel, sample_begin + s, 0xFFFFFFFDu, 0u, P.seed_lo, P.seed_hi);
-        // the smallest k with u < cdf[k] (u < 1 = cdf[last]): a binary search of the same length in every lane
-        const float u = u01(r.x);
-        uint32_t lo = 0u, hi = last;
-        for (uint32_t step = 0; step < search_steps; ++step) {
-            const uint32_t mid = (lo + hi) >> 1;
-            const bool below = u < cdf[mid];
-            const bool open = lo < hi;
-            hi = open && below ? mid : hi;
-            lo = open && !below ? mid + 1u : lo;
-        }
-        const float4 L0 = lights[MPT_LIGHT_F4 * lo], L1 = lights[MPT_LIGHT_F4 * lo + 1u], L2 = lights[MPT_LIGHT_F4 * lo + 2u],
-                     L3 = lights[MPT_LIGHT_F4 * lo + 3u];
-        const bool tri = L0.w != 0.0f;
-        const float ua = u01(r.y), ub = u01(r.z);
-        // a point of the triangle ...
-        float a = ua, b = ub;
-        if (a + b > 1.0f) {
-            a = 1.0f - a;
-            b = 1.0f - b;
-        }
-        const F3 e1 = f3(L1.x, L1.y, L1.z), e2 = f3(L2.x, L2.y, L2.z), c = f3(L0.x, L0.y, L0.z);
-        const F3 pt = (c + a * e1) + b * e2;
-        const F3 ng = normalize3(cross3(e1, e2));
-        F3 wi;
-        float d2, dist, cos_s, cos_l, fac = 0.0f;
-        bool live;
-        if (!CONE) {
-            // ... or of the sphere
-            const float z = 2.0f * ua - 1.0f;
-            float sn, cs;
-            sincos_2pi(ub, sn, cs);
-            const float rr = sqrtf(1.0f - z * z);
-            const F3 ns = f3(rr * cs, rr * sn, z);
-            const F3 ps = c + L1.x * ns;
-            const F3 nl = tri ? ng : ns;
-            const F3 p = tri ? pt : ps;
-            const F3 v = p - o;
-            d2 = dot3(v, v);
-            dist = sqrtf(d2);
-            wi = v * mpt_rcp(dist);
-            cos_s = dot3(n, wi);
-            const float dl = dot3(nl, wi);
-            cos_l = tri ? fabsf(dl) : -dl;
-            live = surface && d2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;   // (a NaN skips)
-        } else {
-            // ... or a direction of the cone the sphere subtends; the sample's factor is formed here, so one value crosses the walk
-            const F3 vt = pt - o;
-            d2 = dot3(vt, vt);
-            const float dist_t = sqrtf(d2);
-            const F3 wi_t = vt * mpt_rcp(dist_t);
-            const float cos_t = dot3(n, wi_t);
-            cos_l = fabsf(dot3(ng, wi_t));
-            const float g = (cos_t * cos_l) / d2;
-            const F3 w = c - o;
-            float dc2, omc, J, dist_c;
-            const bool outside = cone_cap(w, L1.x, L3.w, dc2, omc, J);
-            F3 wi_c;
-            cone_sample(w, dc2, omc, ua, ub, wi_c, dist_c);
-            const float cos_c = dot3(n, wi_c);
-            wi = tri ? wi_t : wi_c;
-            dist = tri ? dist_t : dist_c;
-            cos_s = tri ? cos_t : cos_c;
-            fac = tri ? g * L3.w : cos_c * J;
-            live = surface && cos_s > 0.0f && (tri ? d2 > 0.0f && cos_l > 0.0f : outside && dist_c > 0.0f);   // (a NaN skips)
-        }
+        const float u = u01(r.x);   // the smallest k with u < cdf[k] (u < 1 = cdf[last])
+        const uint32_t k = table_search(last, search_steps, [&](uint32_t mid) { return u < cdf[mid]; });
+        const LightSample ls = light_sample<CONE>(lights, k, o, n, u01(r.y), u01(r.z));
+        // the sample's factor: CONE forms it here, so one value crosses the walk; AREA forms it behind the walk, for the rays that arrive
+        float fac = 0.0f;
+        if (CONE) fac = ls.tri ? ((ls.cos_s * ls.cos_l) / ls.d2) * ls.inv_pdf : ls.cos_s * ls.J;
+        const bool live = surface && ls.ok;
         if (__ballot(live) == 0ull) continue;   // (wave-uniform)
-        const float tmax = dist * 0.9990234375f;
-        bool hit;
-        if (WALK == MPT_AO_OWN) {
-            uint32_t flags;
-            hit = any_hit_own(ac, sc, lds, st, o, wi, tmax, live, flags);
-        } else {
-            hit = any_hit_ref<WALK == MPT_AO_REF_ALL_LDS>(sc, lds, o, wi, tmax, live);
-        }
+        const bool hit = any_hit<WALK>(sc, ac, T, o, ls.wi, ls.dist * 0.9990234375f, live);
         if (live) {
             n_traced += 1u;
             if (!hit) {
                 n_unoccluded += 1u;
-                float w = fac;
-                if (!CONE) {
-                    const float g = (cos_s * cos_l) / d2;
-                    w = g * L3.w;
-                }
-                S = S + f3(L3.x * w, L3.y * w, L3.z * w);
+                if (!CONE) fac = ((ls.cos_s * ls.cos_l) / ls.d2) * ls.inv_pdf;
+                S = S + f3(ls.Le.x * fac, ls.Le.y * fac, ls.Le.z * fac);
             }
         }
     }

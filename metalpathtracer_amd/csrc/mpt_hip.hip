@@ -2453,7 +2453,6 @@ static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_n
         HIPCHK(ns.e1.create(hipEventCreate));
     }
     HIPCHK(hipMemsetAsync(ns.totals.get(), 0, 32, ctx->stream));
-    const mpt_uniforms& u = ctx->u;
     NeePass P = {};
     P.sum = ctx->d_sum;
     P.totals = ns.totals.get();
@@ -2461,37 +2460,19 @@ static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_n
     P.cdf = ctx->lights.cdf.get();
     P.ids = ctx->lights.d_ids.get();
     P.n_lights = ctx->lights.n();
-    P.cam = F3{u.cameraPosition[0], u.cameraPosition[1], u.cameraPosition[2]};
-    P.first = F3{u.firstPixelPosition[0], u.firstPixelPosition[1], u.firstPixelPosition[2]};
-    P.vu = F3{u.viewportU[0], u.viewportU[1], u.viewportU[2]};
-    P.vv = F3{u.viewportV[0], u.viewportV[1], u.viewportV[2]};
-    P.fW = u.screenSize[0];
-    P.fH = u.screenSize[1];
-    P.W = ctx->W;
-    P.H = ctx->H;
-    P.sample_begin = p->sample_begin;
-    P.sample_count = p->sample_count;
-    P.seed_lo = p->seed_lo;
-    P.seed_hi = p->seed_hi;
+    float key[14];
+    guide_key(ctx->u, key);
+    pass_frame(P, key, ctx->W, ctx->H, *p);
+    P.fW = key[12];   // uniforms.screenSize itself, as gen_primary divides by it (the check above compares it with (W, H) as integers)
+    P.fH = key[13];
     P.bsdf_mode = p->bsdf_mode;
     P.max_depth = p->max_depth;
-    P.primitive_count = (uint32_t)std::min<uint64_t>(u.primitiveCount, 0xFFFFFFFFull);
+    P.primitive_count = (uint32_t)std::min<uint64_t>(ctx->u.primitiveCount, 0xFFFFFFFFull);
     P.clamp = n->clamp > 0.0f ? n->clamp : INFINITY;
-    const dim3 grid = tile_grid(ctx->W, ctx->H);
-    SceneDev sc = scene_dev(ctx);
-    AccelDev ac = {};
-    const bool cone = ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE;
+    static const WalkKernel<NeePass> area[3] = {k_nee<MPT_AO_REF>, k_nee<MPT_AO_REF_ALL_LDS>, k_nee<MPT_AO_OWN>},
+                                     cone[3] = {k_nee_cone<MPT_AO_REF>, k_nee_cone<MPT_AO_REF_ALL_LDS>, k_nee_cone<MPT_AO_OWN>};
     HIPCHK(hipEventRecord(ns.e0.get(), ctx->stream));
-    if (resolve_walk(ctx, n->walk) == 1) {
-        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the image of k_trace_rays_ordered: workgroups of 256)
-        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        hipLaunchKernelGGL(cone ? k_nee_cone<MPT_AO_OWN> : k_nee<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
-    } else if (ctx->n_lds_nodes == ctx->n_nodes) {
-        hipLaunchKernelGGL(cone ? k_nee_cone<MPT_AO_REF_ALL_LDS> : k_nee<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    } else {
-        hipLaunchKernelGGL(cone ? k_nee_cone<MPT_AO_REF> : k_nee<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    }
-    HIPCHK(hipGetLastError());
+    if ((rc = tile_walk_launch(ctx, ctx->W, ctx->H, n->walk, ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE ? cone : area, P))) return rc;
     HIPCHK(hipEventRecord(ns.e1.get(), ctx->stream));
     unsigned long long totals[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(totals, ns.totals.get(), 32, hipMemcpyDeviceToHost, ctx->stream));

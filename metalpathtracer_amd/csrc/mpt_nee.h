@@ -6,6 +6,8 @@
 // The estimator is specified exactly in include/mpt.h (mpt_nee_params) and restated in numpy in tests/nee_ref.py; DESIGN.md §17 has the
 // lane mapping, the registers and the measured times.  Nothing here edits a kernel or a device function of the plain render: the walks
 // (closest_hit_resume, closest_hit_ordered, any_hit_ref, any_hit_own), finish_hit, the Philox block and the light table are the tested ones.
+// The tile prologue and the shadow walk's dispatch are mpt_ao.h's (tile_walk, any_hit), the light sample is mpt_direct.h's (table_search,
+// light_sample): what is written here is the path loop, the MIS weights and the weight of an emitter a bounce finds.
 #pragma once
 #include "mpt_direct.h"
 
@@ -34,14 +36,9 @@ struct NeePass {
 // the first round to the last: no result slots, no resolve, no atomics on the image, and no value depends on which lane has which pixel.
 template <int WALK, bool CONE>
 __device__ __forceinline__ void nee_render(SceneDev sc, AccelDev ac, NeePass P) {
-    extern __shared__ float4 lds_raw[];
-    if (WALK == MPT_AO_OWN) ot_stage(sc, ac, lds_raw);
-    else stage_nodes(sc, lds_raw);
-    const LdsNodes lds = (LdsNodes)lds_raw;
-    OtStack st = {};
-    if (WALK == MPT_AO_OWN) st = ot_stack(ac, lds_raw, 0u);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t tx0 = blockIdx.x * MPT_DN_TILE + (wave & 1u) * 8u, ty0 = blockIdx.y * MPT_DN_TILE + (wave >> 1) * 8u;
+    const TileWalk T = tile_walk<WALK>(sc, ac);
+    const LdsNodes lds = T.lds;
+    const uint32_t lane = T.lane, tx0 = T.tx0, ty0 = T.ty0;
     if (tx0 >= P.W || ty0 >= P.H) return;   // (wave-uniform: the tile lies outside the image)
     const uint32_t px = tx0 + (lane & 7u), py = ty0 + (lane >> 3);
     const bool inside = px < P.W && py < P.H;
@@ -53,7 +50,7 @@ __device__ __forceinline__ void nee_render(SceneDev sc, AccelDev ac, NeePass P) 
     const float* cdf = P.cdf;
     const int32_t* ids = P.ids;
     uint32_t last = P.n_lights - 1u, sample_begin = P.sample_begin, prim_count = P.primitive_count;
-    uint32_t search_steps = P.n_lights > 1u ? 32u - (uint32_t)__builtin_clz(P.n_lights - 1u) : 0u;   // ceil(log2(n_lights))
+    uint32_t search_steps = table_search_steps(P.n_lights);
     int32_t bsdf_mode = P.bsdf_mode, max_depth = P.max_depth;
     float clamp_hi = P.clamp, fW = P.fW, fH = P.fH;
     F3 cam = P.cam, first = P.first, vu = P.vu, vv = P.vv;
@@ -99,7 +96,7 @@ __device__ __forceinline__ void nee_render(SceneDev sc, AccelDev ac, NeePass P) 
         int prim;
         if (WALK == MPT_AO_OWN) {
             uint32_t flags;
-            closest_hit_ordered<false>(ac, sc, lds, st, o, d, has_ray, t, prim, flags, wc);
+            closest_hit_ordered<false>(ac, sc, lds, T.st, o, d, has_ray, t, prim, flags, wc);
         } else {   // closest_hit, with the lanes that hold no ray done before the first node
             uint32_t node = has_ray ? 0u : sc.n_nodes;
             t = INFINITY;
@@ -141,15 +138,8 @@ __device__ __forceinline__ void nee_render(SceneDev sc, AccelDev ac, NeePass P) 
                         // the light a bounce found: in full, unless the vertex before drew a light sample that could have found it too
                         float w = 1.0f;
                         if (sampled) {
-                            // the smallest k with id <= ids[k]: a binary search of the same length in every lane
-                            uint32_t lo = 0u, hi = last;
-                            for (uint32_t step = 0; step < search_steps; ++step) {
-                                const uint32_t mid = (lo + hi) >> 1;
-                                const bool below = h.orig_id <= ids[mid];
-                                const bool open = lo < hi;
-                                hi = open && below ? mid : hi;
-                                lo = open && !below ? mid + 1u : lo;
-                            }
+                            // the smallest k with id <= ids[k]
+                            const uint32_t lo = table_search(last, search_steps, [&](uint32_t mid) { return h.orig_id <= ids[mid]; });
                             if (ids[lo] == h.orig_id) {
                                 const float4 L0 = lights[MPT_LIGHT_F4 * lo], L3 = lights[MPT_LIGHT_F4 * lo + 3u];
                                 if (L0.w != 0.0f || h.front) {   // (a sphere emits outward only where it is sampled)
@@ -187,77 +177,24 @@ __device__ __forceinline__ void nee_render(SceneDev sc, AccelDev ac, NeePass P) 
                         if (attempt) {   // the sample of k_direct, with n = h.normal and o = on, from the block with word 3 = 1
                             const U4 r = philox4x32_10<true>(pixel, sample, b, 1u, P.seed_lo, P.seed_hi);
                             const float u = u01(r.x);
-                            uint32_t lo = 0u, hi = last;
-                            for (uint32_t step = 0; step < search_steps; ++step) {
-                                const uint32_t mid = (lo + hi) >> 1;
-                                const bool below = u < cdf[mid];
-                                const bool open = lo < hi;
-                                hi = open && below ? mid : hi;
-                                lo = open && !below ? mid + 1u : lo;
-                            }
-                            const float4 L0 = lights[MPT_LIGHT_F4 * lo], L1 = lights[MPT_LIGHT_F4 * lo + 1u], L2 = lights[MPT_LIGHT_F4 * lo + 2u],
-                                         L3 = lights[MPT_LIGHT_F4 * lo + 3u];
-                            const bool tri = L0.w != 0.0f;
-                            const float ua = u01(r.y), ub = u01(r.z);
-                            float a = ua, bb = ub;
-                            if (a + bb > 1.0f) {
-                                a = 1.0f - a;
-                                bb = 1.0f - bb;
-                            }
-                            const F3 e1 = f3(L1.x, L1.y, L1.z), e2 = f3(L2.x, L2.y, L2.z), c = f3(L0.x, L0.y, L0.z);
-                            const F3 pt = (c + a * e1) + bb * e2;
-                            const F3 ng = normalize3(cross3(e1, e2));
+                            const uint32_t k = table_search(last, search_steps, [&](uint32_t mid) { return u < cdf[mid]; });
+                            const LightSample ls = light_sample<CONE>(lights, k, on, h.normal, u01(r.y), u01(r.z));
+                            wi = ls.wi;
+                            shadow = ls.ok;
+                            tmax = ls.dist * 0.9990234375f;
+                            // the sample's factor times its weight against the bounce's pdf (power heuristic), both per solid angle
                             float m;
-                            if (!CONE) {
-                                const float zl = 2.0f * ua - 1.0f;
-                                float snl, csl;
-                                sincos_2pi(ub, snl, csl);
-                                const float rl = sqrtf(1.0f - zl * zl);
-                                const F3 ns = f3(rl * csl, rl * snl, zl);
-                                const F3 ps = c + L1.x * ns;
-                                const F3 nl = tri ? ng : ns;
-                                const F3 p = tri ? pt : ps;
-                                const F3 v = p - on;
-                                const float d2 = dot3(v, v);
-                                const float dist = sqrtf(d2);
-                                wi = v * mpt_rcp(dist);
-                                const float cos_s = dot3(h.normal, wi);
-                                const float dl = dot3(nl, wi);
-                                const float cos_l = tri ? fabsf(dl) : -dl;
-                                shadow = d2 > 0.0f && cos_s > 0.0f && cos_l > 0.0f;   // (a NaN skips)
-                                tmax = dist * 0.9990234375f;
-                                const float g = (cos_s * cos_l) / d2;
-                                const float pl = d2 / (cos_l * L3.w);
-                                const float pbs = cos_s * 0.31830987f;
-                                const float q = pbs / pl;
-                                const float wl = 1.0f / (1.0f + q * q);
-                                m = (g * L3.w) * wl;
+                            if (!CONE || ls.tri) {
+                                const float g = (ls.cos_s * ls.cos_l) / ls.d2;
+                                const float pl = ls.d2 / (ls.cos_l * ls.inv_pdf);
+                                const float q = (ls.cos_s * 0.31830987f) / pl;
+                                m = (g * ls.inv_pdf) * (1.0f / (1.0f + q * q));
                             } else {
-                                const F3 vt = pt - on;
-                                const float d2 = dot3(vt, vt);
-                                const float dist_t = sqrtf(d2);
-                                const F3 wi_t = vt * mpt_rcp(dist_t);
-                                const float cos_t = dot3(h.normal, wi_t);
-                                const float cos_l = fabsf(dot3(ng, wi_t));
-                                const float g = (cos_t * cos_l) / d2;
-                                const float pl = d2 / (cos_l * L3.w);
-                                const float q_t = (cos_t * 0.31830987f) / pl;
-                                const float m_t = (g * L3.w) * (1.0f / (1.0f + q_t * q_t));
-                                const F3 w = c - on;
-                                float dc2, omc, J, dist_c;
-                                const bool outside = cone_cap(w, L1.x, L3.w, dc2, omc, J);
-                                F3 wi_c;
-                                cone_sample(w, dc2, omc, ua, ub, wi_c, dist_c);
-                                const float cos_c = dot3(h.normal, wi_c);
-                                const float q_c = (cos_c * 0.31830987f) * J;
-                                const float m_c = (cos_c * J) * (1.0f / (1.0f + q_c * q_c));
-                                wi = tri ? wi_t : wi_c;
-                                shadow = (tri ? cos_t > 0.0f && d2 > 0.0f && cos_l > 0.0f : cos_c > 0.0f && outside && dist_c > 0.0f);   // (a NaN skips)
-                                tmax = (tri ? dist_t : dist_c) * 0.9990234375f;
-                                m = tri ? m_t : m_c;
+                                const float q = (ls.cos_s * 0.31830987f) * ls.J;
+                                m = (ls.cos_s * ls.J) * (1.0f / (1.0f + q * q));
                             }
-                            C = f3(((thr.x * m0.x) * 0.31830987f) * (L3.x * m), ((thr.y * m0.y) * 0.31830987f) * (L3.y * m),
-                                   ((thr.z * m0.z) * 0.31830987f) * (L3.z * m));
+                            C = f3(((thr.x * m0.x) * 0.31830987f) * (ls.Le.x * m), ((thr.y * m0.y) * 0.31830987f) * (ls.Le.y * m),
+                                   ((thr.z * m0.z) * 0.31830987f) * (ls.Le.z * m));
                         }
                         sampled = attempt;
                         pb = dot3(h.normal, nd) * 0.31830987f;
@@ -282,13 +219,7 @@ __device__ __forceinline__ void nee_render(SceneDev sc, AccelDev ac, NeePass P) 
             }
         }
         if (__ballot(shadow) != 0ull) {   // (wave-uniform) the shadow rays of this round's vertices, from the bounce rays' origins
-            bool hit;
-            if (WALK == MPT_AO_OWN) {
-                uint32_t flags;
-                hit = any_hit_own(ac, sc, lds, st, o, wi, tmax, shadow, flags);
-            } else {
-                hit = any_hit_ref<WALK == MPT_AO_REF_ALL_LDS>(sc, lds, o, wi, tmax, shadow);
-            }
+            const bool hit = any_hit<WALK>(sc, ac, T, o, wi, tmax, shadow);
             if (shadow) {
                 n_shadow += 1ull;
                 if (hit) {

@@ -25,6 +25,42 @@ static void guide_key(const mpt_uniforms& u, float k[14]) {
 enum { KEY_CAM = 0, KEY_VU = 1, KEY_VV = 2, KEY_FIRST = 3 };
 static F3 key_f3(const float key[14], int which) { return F3{key[3 * which], key[3 * which + 1], key[3 * which + 2]}; }
 
+// A pass's camera, size, sample range and seeds from a camera key and any params struct that names them (AoPass, DirectPass, NeePass)
+template <class Pass, class Params>
+static void pass_frame(Pass& P, const float key[14], uint32_t W, uint32_t H, const Params& p) {
+    P.cam = key_f3(key, KEY_CAM);
+    P.vu = key_f3(key, KEY_VU);
+    P.vv = key_f3(key, KEY_VV);
+    P.first = key_f3(key, KEY_FIRST);
+    P.fW = (float)W;
+    P.fH = (float)H;
+    P.W = W;
+    P.H = H;
+    P.sample_begin = p.sample_begin;
+    P.sample_count = p.sample_count;
+    P.seed_lo = p.seed_lo;
+    P.seed_hi = p.seed_hi;
+}
+// The launch of a per-tile shadow-ray kernel (mpt_ao.h: tile_walk) on ctx->stream: k = its three instantiations in the order of MPT_AO_*,
+// of which `walk` (MPT_WALK_*) and the scene pick one — the own tree, or the reference-order tree wholly or partly in LDS.
+template <class Pass>
+using WalkKernel = void (*)(SceneDev, AccelDev, Pass);
+template <class Pass>
+static int tile_walk_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, int32_t walk, const WalkKernel<Pass> k[3], const Pass& P) {
+    SceneDev sc = scene_dev(ctx);
+    AccelDev ac = {};
+    size_t lds = ref_lds_bytes(ctx);
+    int which = ctx->n_lds_nodes == ctx->n_nodes ? MPT_AO_REF_ALL_LDS : MPT_AO_REF;
+    if (resolve_walk(ctx, walk) == 1) {
+        lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the image of k_trace_rays_ordered: workgroups of 256)
+        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+        which = MPT_AO_OWN;
+    }
+    hipLaunchKernelGGL(k[which], tile_grid(W, H), dim3(256), lds, ctx->stream, sc, ac, P);
+    HIPCHK(hipGetLastError());
+    return MPT_OK;
+}
+
 // ---- shared: the device side of an image hook ---------------------------------------------------------------------------------------
 // The mpt_*_image hooks run a stage on host arrays of any size and touch no state of the context: their device buffers are locals
 // that free themselves, filled and read back on ctx->stream.
@@ -167,6 +203,33 @@ static int history_accumulate(mpt_ctx* ctx, History& h, Pass&& pass) {
     h.cur ^= 1;
     h.epoch = ctx->guide_epoch;
     memcpy(h.cam, key, sizeof key);
+    return MPT_OK;
+}
+
+// One call of a stage that keeps a per-pixel result with 64-bit totals behind it (AoState, DirectState): the buffer at the context's
+// size, launch(key, out) at the current camera's key between a pair of events, then the totals — the one host wait — and the epoch.
+template <class State, class Launch>
+static int stage_run(mpt_ctx* ctx, State& s, size_t out_bytes, unsigned long long* totals, size_t n_totals, float* ms, Launch&& launch) {
+    if (!s.out || s.W != ctx->W || s.H != ctx->H) {
+        s = State{};
+        HIPCHK(s.out.alloc(out_bytes));
+        s.W = ctx->W;
+        s.H = ctx->H;
+    }
+    s.epoch = 0;
+    float key[14];
+    guide_key(ctx->u, key);
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventCreate));
+    HIPCHK(e1.create(hipEventCreate));
+    HIPCHK(hipEventRecord(e0.get(), ctx->stream));
+    const int rc = launch(key, s.out.get());
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(e1.get(), ctx->stream));
+    HIPCHK(hipMemcpyAsync(totals, (const char*)s.out.get() + out_bytes - n_totals * 8, n_totals * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    s.epoch = ctx->guide_epoch;
+    if (ms) HIPCHK(hipEventElapsedTime(ms, e0.get(), e1.get()));
     return MPT_OK;
 }
 
@@ -340,66 +403,26 @@ static int ao_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad, con
     P.out = out;
     P.n_pixels = W * H;
     HIPCHK(hipMemsetAsync(P.totals(), 0, 16, ctx->stream));
-    P.cam = key_f3(key, KEY_CAM);
-    P.vu = key_f3(key, KEY_VU);
-    P.vv = key_f3(key, KEY_VV);
-    P.first = key_f3(key, KEY_FIRST);
-    P.fW = (float)W;
-    P.fH = (float)H;
-    P.W = W;
-    P.H = H;
-    P.sample_begin = p->sample_begin;
-    P.sample_count = p->sample_count;
+    pass_frame(P, key, W, H, *p);
     uint32_t gl = 0;
     while (gl < 6u && (2u << gl) <= p->sample_count) ++gl;   // min(N, 64) rounded down to a power of two
     P.group_log2 = gl;
     P.tmax = p->radius > 0.0f ? p->radius : INFINITY;
-    P.seed_lo = p->seed_lo;
-    P.seed_hi = p->seed_hi;
-    const dim3 grid = tile_grid(W, H);
-    SceneDev sc = scene_dev(ctx);
-    AccelDev ac = {};
-    if (resolve_walk(ctx, p->walk) == 1) {
-        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);
-        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        hipLaunchKernelGGL(k_ao<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
-    } else if (ctx->n_lds_nodes == ctx->n_nodes) {
-        hipLaunchKernelGGL(k_ao<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    } else {
-        hipLaunchKernelGGL(k_ao<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    }
-    HIPCHK(hipGetLastError());
-    return MPT_OK;
+    static const WalkKernel<AoPass> k[3] = {k_ao<MPT_AO_REF>, k_ao<MPT_AO_REF_ALL_LDS>, k_ao<MPT_AO_OWN>};
+    return tile_walk_launch(ctx, W, H, p->walk, k, P);
 }
 static size_t ao_out_bytes(size_t n_pixels) { return n_pixels * 8 + 16; }
 static int ambient_occlusion_impl(mpt_ctx* ctx, const mpt_ao_params* p, mpt_ao_info* out) {
     if (!ctx) return MPT_ERR_INVALID_ARG;
     int rc = ao_check(ctx, p);
     if (rc || (rc = settle_and_guide(ctx))) return rc;
-    AoState& a = ctx->ao;
-    const size_t n = (size_t)ctx->W * ctx->H;
-    if (!a.out || a.W != ctx->W || a.H != ctx->H) {
-        a = AoState{};
-        HIPCHK(a.out.alloc(ao_out_bytes(n)));
-        a.W = ctx->W;
-        a.H = ctx->H;
-    }
-    a.epoch = 0;
-    float key[14];
-    guide_key(ctx->u, key);
-    Event e0, e1;
-    HIPCHK(e0.create(hipEventCreate));
-    HIPCHK(e1.create(hipEventCreate));
-    HIPCHK(hipEventRecord(e0.get(), ctx->stream));
-    if ((rc = ao_launch(ctx, ctx->W, ctx->H, ctx->gd.ad.get(), ctx->gd.nc.get(), key, p, a.out.get()))) return rc;
-    HIPCHK(hipEventRecord(e1.get(), ctx->stream));
     unsigned long long totals[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(totals, a.out.get() + 2 * n, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    a.epoch = ctx->guide_epoch;
+    float ms = 0.0f;
+    rc = stage_run(ctx, ctx->ao, ao_out_bytes((size_t)ctx->W * ctx->H), totals, 2, out ? &ms : nullptr, [&](const float* key, float* o) {
+        return ao_launch(ctx, ctx->W, ctx->H, ctx->gd.ad.get(), ctx->gd.nc.get(), key, p, o);
+    });
+    if (rc) return rc;
     if (out) {
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
         out->pixels_surface = totals[0];
         out->rays = totals[0] * p->sample_count;
         out->rays_occluded = totals[1];
@@ -564,33 +587,10 @@ static int direct_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad,
     P.lights = ctx->lights.rec.get();
     P.cdf = ctx->lights.cdf.get();
     P.n_lights = ctx->lights.n();
-    P.cam = key_f3(key, KEY_CAM);
-    P.vu = key_f3(key, KEY_VU);
-    P.vv = key_f3(key, KEY_VV);
-    P.first = key_f3(key, KEY_FIRST);
-    P.fW = (float)W;
-    P.fH = (float)H;
-    P.W = W;
-    P.H = H;
-    P.sample_begin = p->sample_begin;
-    P.sample_count = p->sample_count;
-    P.seed_lo = p->seed_lo;
-    P.seed_hi = p->seed_hi;
-    const dim3 grid = tile_grid(W, H);
-    SceneDev sc = scene_dev(ctx);
-    AccelDev ac = {};
-    const bool cone = ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE;
-    if (resolve_walk(ctx, p->walk) == 1) {
-        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);
-        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        hipLaunchKernelGGL(cone ? k_direct_cone<MPT_AO_OWN> : k_direct<MPT_AO_OWN>, grid, dim3(256), lds, ctx->stream, sc, ac, P);
-    } else if (ctx->n_lds_nodes == ctx->n_nodes) {
-        hipLaunchKernelGGL(cone ? k_direct_cone<MPT_AO_REF_ALL_LDS> : k_direct<MPT_AO_REF_ALL_LDS>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    } else {
-        hipLaunchKernelGGL(cone ? k_direct_cone<MPT_AO_REF> : k_direct<MPT_AO_REF>, grid, dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, ac, P);
-    }
-    HIPCHK(hipGetLastError());
-    return MPT_OK;
+    pass_frame(P, key, W, H, *p);
+    static const WalkKernel<DirectPass> area[3] = {k_direct<MPT_AO_REF>, k_direct<MPT_AO_REF_ALL_LDS>, k_direct<MPT_AO_OWN>},
+                                        cone[3] = {k_direct_cone<MPT_AO_REF>, k_direct_cone<MPT_AO_REF_ALL_LDS>, k_direct_cone<MPT_AO_OWN>};
+    return tile_walk_launch(ctx, W, H, p->walk, ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE ? cone : area, P);
 }
 static StageResult di_result(const mpt_ctx* c) {
     return stage_result(c, stage_valid(c, c->di), c->di.out.get(), 16, "no mpt_direct_lighting result for this scene and size");
@@ -599,30 +599,13 @@ static int direct_lighting_impl(mpt_ctx* ctx, const mpt_direct_params* p, mpt_di
     if (!ctx) return MPT_ERR_INVALID_ARG;
     int rc = direct_check(ctx, p);
     if (rc || (rc = settle_and_guide(ctx)) || (rc = ensure_lights(ctx))) return rc;
-    DirectState& d = ctx->di;
-    const size_t n = (size_t)ctx->W * ctx->H;
-    if (!d.out || d.W != ctx->W || d.H != ctx->H) {
-        d = DirectState{};
-        HIPCHK(d.out.alloc(direct_out_bytes(n)));
-        d.W = ctx->W;
-        d.H = ctx->H;
-    }
-    d.epoch = 0;
-    float key[14];
-    guide_key(ctx->u, key);
-    Event e0, e1;
-    HIPCHK(e0.create(hipEventCreate));
-    HIPCHK(e1.create(hipEventCreate));
-    HIPCHK(hipEventRecord(e0.get(), ctx->stream));
-    if ((rc = direct_launch(ctx, ctx->W, ctx->H, ctx->gd.ad.get(), ctx->gd.nc.get(), key, p, d.out.get()))) return rc;
-    HIPCHK(hipEventRecord(e1.get(), ctx->stream));
     unsigned long long totals[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(totals, (const char*)d.out.get() + n * 24, 24, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    d.epoch = ctx->guide_epoch;
+    float ms = 0.0f;
+    rc = stage_run(ctx, ctx->di, direct_out_bytes((size_t)ctx->W * ctx->H), totals, 3, out ? &ms : nullptr, [&](const float* key, float4* o) {
+        return direct_launch(ctx, ctx->W, ctx->H, ctx->gd.ad.get(), ctx->gd.nc.get(), key, p, o);
+    });
+    if (rc) return rc;
     if (out) {
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
         out->pixels_surface = totals[0];
         out->rays = totals[1];
         out->rays_occluded = totals[1] - totals[2];
