@@ -260,8 +260,35 @@ struct WorkCount {
 struct Prim3 {
     float4 p0, p1, p2;
 };
+// LEAN (the lean wave-local kernels, mpt_kernels.h): the record's address is a 32-bit BYTE offset, i * 48 as one full-rate 24-bit
+// multiply, added to the scalar base (global: base in scalar registers + 32-bit vector offset; LDS: a 32-bit address anyway) — the
+// generic form multiplies in 64 bits (v_mad_u64_u32, quarter rate).  The host admits a scene only when i < 2^24 for every record
+// (wl_lean_ok, mpt_wl_lean.h), so i * 48 < 2^32: the same address, the same record.
+// (MPT_LEAN_INT24=0: pricing build of the lean kernels without the 24-bit index arithmetic — profiles/r15_fast_kernel.txt)
+#ifndef MPT_LEAN_INT24
+#define MPT_LEAN_INT24 1
+#endif
+typedef const __attribute__((address_space(3))) char* LdsBytes;
+__device__ __forceinline__ uint32_t mul_u24(uint32_t a, uint32_t b) { return (uint32_t)__umul24(a, b); }   // v_mul_u32_u24: low 32 bits of the product of the low 24 bits (__umul24 returns int: a product >= 2^31 must not meet a signed shift)
+template <bool LEAN = false>
 __device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uint32_t i) {
     Prim3 r;
+    if (LEAN && MPT_LEAN_INT24) {
+        const uint32_t off = mul_u24(i, 48u);
+        if (i < sc.n_lds_prims) {
+            const LdsNodes q = (LdsNodes)((LdsBytes)lds + (sc.lds_prim_off * 16u + off));
+            const v4f a = q[0], b = q[1], c = q[2];
+            r.p0 = make_float4(a.x, a.y, a.z, a.w);
+            r.p1 = make_float4(b.x, b.y, b.z, b.w);
+            r.p2 = make_float4(c.x, c.y, c.z, c.w);
+        } else {
+            const float4* q = (const float4*)((const char*)sc.prims + off);
+            r.p0 = q[0];
+            r.p1 = q[1];
+            r.p2 = q[2];
+        }
+        return r;
+    }
     if (i < sc.n_lds_prims) {
         const LdsNodes q = lds + sc.lds_prim_off + 3u * i;
         const v4f a = q[0], b = q[1], c = q[2];
@@ -277,13 +304,13 @@ __device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uin
 }
 
 // Primitives of one leaf, in index order — PathTracing.h:106-186.
-template <bool COUNT>
+template <bool COUNT, bool LEAN = false>
 __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint32_t first, uint32_t count, F3 o, F3 d,
                                           float& best_t, int& best_prim, WorkCount& wc) {
     for (uint32_t k = 0; k < count; ++k) {
         // the three 16-byte loads of a primitive are issued together (the third is used by triangles only, but a
         // load that waits for the type check costs a second L2 round trip per primitive)
-        const Prim3 pr = load_prim(sc, lds, first + k);
+        const Prim3 pr = load_prim<LEAN>(sc, lds, first + k);
         const float4 p0 = pr.p0, p1 = pr.p1, p2 = pr.p2;
         if (COUNT) {
             wc.prim_tests++;
@@ -349,7 +376,11 @@ __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint
 #define MPT_LEAF_EARLY 8u
 #endif
 #define MPT_NODE_HOLD 0x80000000u   // hit link of a leaf record: HOLD | first << 4 | (count - 1)
-template <bool COUNT, bool ALL_LDS, bool BUDGETED>
+// LEAN: 32-bit primitive addressing (load_prim).  (The box loop's fminf(best_t, ..) canonicalises best_t on every trip — v_max_f32 t, t, t —
+// although best_t does not change inside the loop.  Making it canonical once per round, best_t = fminf(best_t, INFINITY) in front of
+// the loop, does not remove that instruction: the compiler decides "known canonical" per basic block, and the loop body is a block of
+// its own.  Tried and left out, profiles/r15_fast_kernel.txt.)
+template <bool COUNT, bool ALL_LDS, bool BUDGETED, bool LEAN = false>
 __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes lds_nodes, F3 o, F3 d, uint32_t& node,
                                                    float& best_t, int& best_prim, uint32_t budget, WorkCount& wc,
                                                    uint32_t min_active = 0u) {
@@ -445,7 +476,7 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         if ((i & MPT_NODE_HOLD) != 0u) {
             const uint32_t enc = i & ~MPT_NODE_HOLD;
             if (COUNT && first_active_lane()) wc.outer_iters++;
-            leaf_test<COUNT>(sc, lds_nodes, enc >> 4, (enc & 15u) + 1u, o, d, best_t, best_prim, wc);
+            leaf_test<COUNT, LEAN>(sc, lds_nodes, enc >> 4, (enc & 15u) + 1u, o, d, best_t, best_prim, wc);
             i = skip;
         }
         MPT_TOC(wc.t_leaf, tic_);
@@ -478,9 +509,10 @@ struct HitInfo {
 };
 // Surface point / geometric normal of the winning primitive — the values PathTracing.h:138-139,
 // 168-169 compute when the hit is accepted, and the front-face flip of :196-201.
+template <bool LEAN = false>
 __device__ __forceinline__ HitInfo finish_hit(const SceneDev& sc, LdsNodes lds, F3 o, F3 d, float t, int prim) {
     HitInfo h;
-    const Prim3 pr = load_prim(sc, lds, (uint32_t)prim);
+    const Prim3 pr = load_prim<LEAN>(sc, lds, (uint32_t)prim);
     const float4 p0 = pr.p0, p1 = pr.p1, p2 = pr.p2;
     h.point = o + t * d;
     if (prim_type(p0) == 1) {
@@ -523,9 +555,10 @@ struct PathRngDev {
 struct BounceRandoms {
     float uz, uphi, u_extra;   // z = 2 uz - 1, phi = 2 pi uphi, Fresnel test
 };
+template <bool LEAN = false>   // LEAN: Philox, decided when the kernel is compiled
 __device__ __forceinline__ BounceRandoms draw_bounce_randoms(const ShadeParams& sp, const PathRngDev& g, uint32_t bounce) {
     BounceRandoms b;
-    if (sp.rng_mode == 0) {
+    if (!LEAN && sp.rng_mode == 0) {
         b.uz = b.uphi = b.u_extra = pcg_float(g.lit_seed);
     } else {
         const U4 r = philox4x32_10<true>(g.pixel, g.sample, bounce, 0u, sp.seed_lo, sp.seed_hi);
@@ -535,9 +568,10 @@ __device__ __forceinline__ BounceRandoms draw_bounce_randoms(const ShadeParams& 
     }
     return b;
 }
+template <bool LEAN = false>
 __device__ __forceinline__ F3 random_unit_vector(const ShadeParams& sp, const BounceRandoms& b) {
     float z = 2.0f * b.uz - 1.0f, s, c;
-    if (sp.rng_mode == 0) {
+    if (!LEAN && sp.rng_mode == 0) {
         const float t = 2.0f * 3.14159274101257324f * b.uphi;
         s = sinf(t);
         c = cosf(t);
@@ -570,6 +604,8 @@ __device__ __forceinline__ bool mirror_angle(float ri, F3 normal, F3 rayDir, flo
 // One iteration of the bounce loop of rayColor (PathTracing.h:221-256) for a ray whose closest hit is
 // (t, prim).  Returns true if the path continues (ps holds the next ray), false if it ended (ps.L/La
 // hold the final light, to be clamped by the caller: PathTracing.h:258).
+// LEAN: the Philox RNG and the Lambert bounce (bsdf_mode 0) are decided when the kernel is compiled; g.lit_seed is not read.
+template <bool LEAN = false>
 __device__ __forceinline__ bool shade_bounce(const SceneDev& sc, LdsNodes lds, const ShadeParams& sp, const PathRngDev& g,
                                              PathState& ps, float t, int prim) {
     if (prim < 0) {  // PathTracing.h:225-232 sky
@@ -582,8 +618,8 @@ __device__ __forceinline__ bool shade_bounce(const SceneDev& sc, LdsNodes lds, c
         ps.La += 1.0f;
         return false;
     }
-    const BounceRandoms rnd = draw_bounce_randoms(sp, g, ps.bounce);
-    HitInfo h = finish_hit(sc, lds, ps.o, ps.d, t, prim);
+    const BounceRandoms rnd = draw_bounce_randoms<LEAN>(sp, g, ps.bounce);
+    HitInfo h = finish_hit<LEAN>(sc, lds, ps.o, ps.d, t, prim);
     if ((uint32_t)h.orig_id >= sp.primitive_count) return false;  // PathTracing.h:234-236
     float4 m0, m1;
     if ((uint32_t)h.mat < sc.n_lds_mats) {  // the de-duplicated material table is tiny: served from LDS
@@ -603,10 +639,12 @@ __device__ __forceinline__ bool shade_bounce(const SceneDev& sc, LdsNodes lds, c
         ps.La += power;
     }
     const float u_extra = rnd.u_extra;
-    F3 ruv = random_unit_vector(sp, rnd);
+    F3 ruv = random_unit_vector<LEAN>(sp, rnd);
     F3 nd;
     bool through = false;
-    if (sp.bsdf_mode == 2 && mtype == 0.0f) {  // Scatter.h:24-27,42 with randomFloat3 of Random.h:18-30 (dead in the reference)
+    if (LEAN) {
+        nd = normalize3(h.normal + ruv);  // PathTracing.h:252-254
+    } else if (sp.bsdf_mode == 2 && mtype == 0.0f) {  // Scatter.h:24-27,42 with randomFloat3 of Random.h:18-30 (dead in the reference)
         F3 c;
         if (sp.rng_mode == 0) {
             uint32_t s = g.lit_seed;

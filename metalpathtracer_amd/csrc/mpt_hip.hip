@@ -339,6 +339,7 @@ struct mpt_ctx : SceneState {
     // small (a 1/8 shard: 11 k paths per wave) and up to 256 when it is large (a full 1080p x 256 spp pass: 86 k): scene.xml with 64 /
     // 128 / 256 / 512 / 1024 -> 16.79-16.86 / 16.70 / 16.62-16.65 / 16.65 / 17.87 ms, the 1/8 shard's serial step 2.54 / - / 2.71 / 3.36
     uint32_t wl_min = 0, wl_div = 32;
+    bool wl_lean = true;               // MPT_WL_LEAN=0: every wave-local pass runs the generic kernels (development knob)
     uint32_t wl_block = MPT_WL_BLOCK;  // path ids a wave claims per atomic (multiple of 64)
     int wgs_per_cu = 0;  // 0 = as many as the occupancy query admits
     size_t lds_budget = 78 * 1024;  // per workgroup; two workgroups per CU share the 160 KiB
@@ -378,7 +379,12 @@ static const void* ordered_kernel(bool count, bool all_lds, bool six = false) {
     return all_lds ? (const void*)k_ordered<false, true> : (const void*)k_ordered<false, false>;
 }
 
-static const void* wavelocal_kernel(bool count, bool all_lds, bool corun) {
+// lean: the pass is one the lean kernels may run (wl_lean_ok, mpt_wl_lean.h: Philox, Lambert, no counters, every index range checked)
+static const void* wavelocal_kernel(bool count, bool all_lds, bool corun, bool lean = false) {
+    if (lean && !count) {
+        if (corun) return all_lds ? (const void*)k_wavelocal_lean_corun<true> : (const void*)k_wavelocal_lean_corun<false>;
+        return all_lds ? (const void*)k_wavelocal_lean<true> : (const void*)k_wavelocal_lean<false>;
+    }
     if (corun && !count) return all_lds ? (const void*)k_wavelocal_corun<true> : (const void*)k_wavelocal_corun<false>;
     if (count) return all_lds ? (const void*)k_wavelocal<true, true> : (const void*)k_wavelocal<true, false>;
     return all_lds ? (const void*)k_wavelocal<false, true> : (const void*)k_wavelocal<false, false>;
@@ -501,6 +507,7 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     }
     if ((e = getenv("MPT_OT_OCC")) && (atoi(e) == 5 || atoi(e) == 6)) ctx->ot_occ = atoi(e);
     if ((e = getenv("MPT_WL_DIV")) && atoi(e) >= 1) ctx->wl_div = (uint32_t)atoi(e);
+    if ((e = getenv("MPT_WL_LEAN"))) ctx->wl_lean = atoi(e) != 0;
     if ((e = getenv("MPT_OT_STACK")) && atoi(e) >= 2 && atoi(e) <= (int)MPT_OT_PARK) ctx->ot_stack_depth = (uint32_t)atoi(e);
     for (int which = 0; which < 2; ++which)
         if ((e = getenv(which ? "MPT_OT_MIN_ACTIVE" : "MPT_OT_BUDGETS"))) {  // "a,b,c": one number per tree-walk ring
@@ -526,6 +533,8 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
             hipFuncSetAttribute(mega_kernel(c, a), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             hipFuncSetAttribute(wavelocal_kernel(c, a, false), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (!c) hipFuncSetAttribute(wavelocal_kernel(false, a, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (!c) hipFuncSetAttribute(wavelocal_kernel(false, a, false, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (!c) hipFuncSetAttribute(wavelocal_kernel(false, a, true, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         }
     for (int c = 0; c < 2; ++c)
         for (int a = 0; a < 2; ++a) {
@@ -1371,8 +1380,12 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     // resolve of the render before it (k_wavelocal_corun); only then may the end of one pass overlap the start of the next (below)
     const bool corun = (ctx->lane_order & 4) && !ctx->sync_render && pipeline == MPT_PIPE_WAVELOCAL && !count_flag(p);
     const int ot_point = pipeline == MPT_PIPE_ORDERED ? ordered_point(ctx, count_flag(p)) : 0;
+    // Philox + Lambert without counters, inside the ranges of the lean kernels' 24-bit index arithmetic: the lean variant of the same kernel
+    WlLean lean_args = {0u, 0u, 0u};
+    const bool lean = pipeline == MPT_PIPE_WAVELOCAL && ctx->wl_lean &&
+                      wl_lean_ok(ctx->n_prims, n_local_tiles, tiles_x, ctx->W, ctx->H, nr, S, pp.tile_magic, p->rng_mode, p->bsdf_mode, count_flag(p), &lean_args);
     const void* kfun = pipeline == MPT_PIPE_MEGAKERNEL ? mega_kernel(count_flag(p), all_lds)
-                       : pipeline == MPT_PIPE_WAVELOCAL ? wavelocal_kernel(count_flag(p), all_lds, corun)
+                       : pipeline == MPT_PIPE_WAVELOCAL ? wavelocal_kernel(count_flag(p), all_lds, corun, lean)
                        : pipeline == MPT_PIPE_ORDERED  ? ordered_kernel(count_flag(p), ctx->ot_pt[ot_point].lds_nodes == ctx->n_acc_nodes, ot_point == 1)
                                                         : step_kernel(count_flag(p), all_lds);
     // workgroup size = the kernel's launch bound (mpt_kernels.h: 768 for the wave-local kernel; mpt_ordered.h: 256 or 768 by operating point)
@@ -1392,7 +1405,11 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         ctx->occ_per_cu = per_cu;
     }
     if (per_cu < 1) return fail(ctx, MPT_ERR_HIP, "kernel does not fit on a CU");
-    if (getenv("MPT_DEBUG_LAUNCH")) fprintf(stderr, "[mpt] pipeline %d: %d workgroups of %d per CU, %zu B of LDS each\n", pipeline, per_cu, wg, lds);
+    if (getenv("MPT_DEBUG_LAUNCH")) {
+        const char* kname = pipeline == MPT_PIPE_MEGAKERNEL ? "k_megakernel" : pipeline == MPT_PIPE_ORDERED ? "k_ordered" : pipeline != MPT_PIPE_WAVELOCAL ? "k_step"
+                            : lean ? (corun ? "k_wavelocal_lean_corun" : "k_wavelocal_lean") : (corun ? "k_wavelocal_corun" : "k_wavelocal");
+        fprintf(stderr, "[mpt] pipeline %d: %d workgroups of %d per CU, %zu B of LDS each, kernel %s\n", pipeline, per_cu, wg, lds, kname);
+    }
     if (ctx->wgs_per_cu > 0 && per_cu > ctx->wgs_per_cu) per_cu = ctx->wgs_per_cu;
     const int grid = ctx->prop.multiProcessorCount * per_cu;
     hipStream_t st = L.stream.get();
@@ -1471,7 +1488,7 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
                 void* args[] = {(void*)&pp, (void*)&accel, (void*)&L.ot_ring, (void*)&ctx->ot_budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div};
                 HIPCHK(hipLaunchKernel(kfun, dim3(grid), dim3(wg), args, lds, st));
             } else {
-                void* args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div};
+                void* args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div, (void*)&lean_args};   // (the last: lean kernels only)
                 HIPCHK(hipLaunchKernel(kfun, dim3(grid), dim3(wg), args, lds, st));
             }
         } else {

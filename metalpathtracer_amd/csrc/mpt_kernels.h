@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "mpt_device.h"
+#include "mpt_wl_lean.h"
 
 // Minimum waves per SIMD the two secondary trace kernels (k_step, k_megakernel) are compiled for (2nd __launch_bounds__
 // argument): 8 waves/SIMD (<= 64 VGPRs, 2 x 1024-thread workgroups per CU next to 2 x 57 KB of LDS).  k_wavelocal has
@@ -126,10 +127,32 @@ __device__ __forceinline__ void flush_stats(PassDesc* desc, uint32_t n_rays, uin
 // tile_xy[tile_local] = tile x | tile y << 16 of this rank's tile_local-th tile: the host lays the rank's tiles out
 // in a strided (low-discrepancy) order so that any window of consecutive path ids mixes cheap (sky) and expensive
 // (mesh) tiles — with row-major order the expensive tiles cluster and the end of a pass is all slow work.
+// LEAN (the lean wave-local kernels below): the same values from full-rate 24-bit multiplies and multiply-shift divisions whose
+// ranges the host has checked for the pass (wl_lean_ok, mpt_wl_lean.h, where each bound is derived); no tile table.  `cfg`: the
+// kernel's configuration words in LDS (words 20, 21 = WlLean::s_mul, s_shift, read only when S is not a power of two).
+typedef const __attribute__((address_space(3))) uint32_t* LdsWords;
+__device__ __forceinline__ uint32_t mul24_shift(uint32_t x, uint32_t m, uint32_t sh) {   // (x * m) >> sh, x and m < 2^24, sh <= 47, result < 2^32
+    return (uint32_t)(((uint64_t)(x & 0xFFFFFFu) * (uint64_t)(m & 0xFFFFFFu)) >> sh);
+}
+template <bool LEAN = false>
 __device__ __forceinline__ bool path_to_pixel(const PassParams& pp, uint32_t path, uint32_t& px, uint32_t& py,
-                                              uint32_t& s) {
+                                              uint32_t& s, uint32_t tile_mul = 0u, LdsWords cfg = nullptr) {
     const uint32_t lane = path & 63u, chunk = path >> 6;
     uint32_t tl;
+    if (LEAN && MPT_LEAN_INT24) {
+        if (pp.s_shift != 0xFFu) {
+            tl = chunk >> pp.s_shift;
+            s = chunk & (pp.S - 1u);
+        } else {
+            const uint32_t s_mul = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg[20]), s_sh = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg[21]);
+            tl = mul24_shift(chunk, s_mul, s_sh);
+            s = chunk - mul_u24(tl, pp.S);
+        }
+        const uint32_t T = mul_u24(tl, pp.nranks) + pp.rank, ty = mul_u24(T, tile_mul) >> MPT_WL_LEAN_TILE_SHIFT, tx = T - mul_u24(ty, pp.tiles_x);
+        px = tx * 8u + (lane & 7u);
+        py = ty * 8u + (lane >> 3);
+        return px < pp.width && py < pp.height;
+    }
     if (pp.s_shift != 0xFFu) {  // samples per pass is a power of two (the usual case): no division
         tl = chunk >> pp.s_shift;
         s = chunk & (pp.S - 1u);
@@ -164,12 +187,13 @@ __device__ __forceinline__ void pixel_uv(const CamView& cv, uint32_t px, uint32_
     uvy = ((float)py + 0.5f) / cv.H;
 }
 __device__ __forceinline__ void pixel_uv(const PassParams& pp, uint32_t px, uint32_t py, float& uvx, float& uvy) { pixel_uv(cam_of(pp), px, py, uvx, uvy); }
+template <bool LEAN = false>   // LEAN: Philox decided at compile time, the pixel index by a 24-bit multiply-add
 __device__ __forceinline__ void gen_primary(const PassParams& pp, const CamView& cv, uint32_t px, uint32_t py, float uvx, float uvy, uint32_t sample,
                                             PathState& ps, PathRngDev& g) {
     float xOff, yOff;
-    g.pixel = py * pp.width + px;
+    g.pixel = LEAN && MPT_LEAN_INT24 ? mul_u24(py, pp.width) + px : py * pp.width + px;
     g.sample = sample;
-    if (pp.sp.rng_mode == 0) {
+    if (!LEAN && pp.sp.rng_mode == 0) {
         uint32_t seed = pp.pixel_seed[g.pixel];
         xOff = (pcg_float(seed) - 0.5f) / cv.W;
         seed = pcg_hash(seed);
@@ -649,9 +673,9 @@ struct WaveBudgets {
 #endif
 #define MPT_WL_THREADS(ALL_LDS) MPT_WL_THREADS_N
 #define MPT_WL_WAVES(ALL_LDS) MPT_WL_WAVES_N
-template <bool COUNT, bool ALL_LDS>
+template <bool COUNT, bool ALL_LDS, bool LEAN = false>
 __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveRings& ring, const WaveBudgets& budgets, uint32_t wl_block, uint32_t wl_min,
-                                               uint32_t wl_div);
+                                               uint32_t wl_div, const WlLean& lean = WlLean{0u, 0u, 0u});
 template <bool COUNT, bool ALL_LDS>
 __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) void k_wavelocal(PassParams pp, WaveRings ring, WaveBudgets budgets,
                                                                                              uint32_t wl_block, uint32_t wl_min, uint32_t wl_div) {
@@ -671,9 +695,27 @@ __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) __a
 void k_wavelocal_corun(PassParams pp, WaveRings ring, WaveBudgets budgets, uint32_t wl_block, uint32_t wl_min, uint32_t wl_div) {
     wavelocal_body<false, ALL_LDS>(pp, ring, budgets, wl_block, wl_min, wl_div);
 }
-template <bool COUNT, bool ALL_LDS>
+// The lean kernels: the same step loop for the one mode the headline render uses — Philox, Lambert, no work counters — decided when
+// the kernel is compiled (wavelocal_body<.., LEAN = true>).  The generic kernels above carry both RNGs and the three BSDF modes behind
+// wave-uniform branches: sinf / cosf with their argument reduction, the pixel-seed pointer, the Scatter.h bounces — code the headline
+// render never runs, and scalar values it keeps alive (or spilled to VGPR lanes) across the step loop.  The lean body also computes its
+// indices with full-rate 24-bit instructions (load_prim, path_to_pixel, gen_primary), for which the host checks the ranges of every
+// pass (wl_lean_ok, mpt_wl_lean.h; anything else runs the kernels above).  Step schedule, rings, records, carry and claim rules and
+// every floating-point operation a ray sees are the generic kernels'.  Measured: DESIGN.md 5, profiles/r15_fast_kernel.txt.  The names carry "k_wavelocal" (bench.py finds its counter profile by that) and none of the generic kernels' names.
+template <bool ALL_LDS>
+__global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) void k_wavelocal_lean(PassParams pp, WaveRings ring, WaveBudgets budgets,
+                                                                                                  uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean) {
+    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean);
+}
+template <bool ALL_LDS>
+__global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) __attribute__((amdgpu_num_sgpr(MPT_WL_CORUN_SGPRS)))
+void k_wavelocal_lean_corun(PassParams pp, WaveRings ring, WaveBudgets budgets, uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean) {
+    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean);
+}
+template <bool COUNT, bool ALL_LDS, bool LEAN>
 __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveRings& ring, const WaveBudgets& budgets, uint32_t wl_block, uint32_t wl_min,
-                                               uint32_t wl_div) {
+                                               uint32_t wl_div, const WlLean& lean) {
+    static_assert(!(LEAN && COUNT), "the lean body does not count");
     extern __shared__ float4 lds_nodes_raw[];
     // what only some steps need goes to LDS, behind the scene image (the 256-byte descriptor area of MPT_LDS_EXTRA), instead of
     // living in scalar registers across the whole step loop: the camera (14 words, primary steps) and the ring budgets (10 words,
@@ -691,11 +733,15 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             w[8u + k] = budgets.min_active[k];
         }
         // ... and what only a CLAIM of path ids needs (words 16..19 of the block's 32: static_assert below)
-        static_assert(4u * (MPT_LDS_CFG_F4 - 4u) >= 20u, "configuration block too small");
+        static_assert(4u * (MPT_LDS_CFG_F4 - 4u) >= 22u, "configuration block too small");
         w[16] = wl_block;
         w[17] = wl_min;
         w[18] = wl_div * (((uint32_t)(gridDim.x * (blockDim.x >> 6)) + MPT_NGROUP - 1u) / MPT_NGROUP);   // wl_div * waves per claim range
         w[19] = pp.desc->total_paths / (pp.S * 64u);                                                   // this rank's tiles
+        if (LEAN) {   // the division by a sample count that is no power of two (path_to_pixel<true>)
+            w[20] = lean.s_mul;
+            w[21] = lean.s_shift;
+        }
     }
     stage_nodes(pp.scene, lds_nodes_raw);
     MPT_CLOCK_BEGIN();
@@ -864,7 +910,12 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             const bool new_tile = tl != tile_cached;
             if (new_tile) {
                 tile_cached = tl;
-                tile_xy_cached = (uint32_t)__builtin_amdgcn_readfirstlane((int)pp.tile_xy[tl]);
+                if (LEAN) {   // the table's entry by (scalar) arithmetic, as path_to_pixel<true>: no load, no table pointer in the loop
+                    const uint32_t T = tl * pp.nranks + pp.rank, ty = (T * lean.tile_mul) >> MPT_WL_LEAN_TILE_SHIFT;
+                    tile_xy_cached = (T - ty * pp.tiles_x) | (ty << 16);
+                } else {
+                    tile_xy_cached = (uint32_t)__builtin_amdgcn_readfirstlane((int)pp.tile_xy[tl]);
+                }
             }
             PathState np;   // (every lane's ray is replaced, also in the lanes outside the image, which hold none: nothing of the step before stays live)
             np.path = pchunk * 64u + lane;
@@ -881,7 +932,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             }
             if (new_tile) pixel_uv(cv, px, py, uvx_cached, uvy_cached);
             if (px < pp.width && py < pp.height) {
-                gen_primary(pp, cv, px, py, uvx_cached, uvy_cached, pp.sample_begin + sidx, np, g);
+                gen_primary<LEAN>(pp, cv, px, py, uvx_cached, uvy_cached, pp.sample_begin + sidx, np, g);
                 valid = true;
             }
             n_paths += (uint32_t)__popcll(__ballot(valid));
@@ -956,12 +1007,12 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         // ---- the hits popped from ring 0 are shaded first — all 64 lanes of a ring-0 step — and leave their bounce rays in `ps` ------
         if (need_shade) {
             uint32_t px, py, sidx;
-            path_to_pixel(pp, ps.path, px, py, sidx);
-            g.pixel = py * pp.width + px;
+            path_to_pixel<LEAN>(pp, ps.path, px, py, sidx, lean.tile_mul, (LdsWords)lds_cfg_u32);
+            g.pixel = LEAN && MPT_LEAN_INT24 ? mul_u24(py, pp.width) + px : py * pp.width + px;
             g.sample = pp.sample_begin + sidx;
             g.lit_seed = 0;
-            if (pp.sp.rng_mode == 0) g.lit_seed = pcg_hash(pcg_hash(pp.pixel_seed[g.pixel]));
-            if (!shade_bounce(pp.scene, lds_nodes, pp.sp, g, ps, hit_t, hit_prim)) {   // the path ends here (depth limit, material guard)
+            if (!LEAN && pp.sp.rng_mode == 0) g.lit_seed = pcg_hash(pcg_hash(pp.pixel_seed[g.pixel]));
+            if (!shade_bounce<LEAN>(pp.scene, lds_nodes, pp.sp, g, ps, hit_t, hit_prim)) {   // the path ends here (depth limit, material guard)
                 store_slot(pp.slots, ps.path, clamp01(ps.L.x), clamp01(ps.L.y), clamp01(ps.L.z), clamp01(ps.La));
                 valid = false;
             }
@@ -980,11 +1031,11 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         if (valid) {
             bool done;
             if (budgeted)
-                done = closest_hit_resume<COUNT, ALL_LDS, true>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                               budget, wc, min_active);
+                done = closest_hit_resume<COUNT, ALL_LDS, true, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
+                                                                     budget, wc, min_active);
             else
-                done = closest_hit_resume<COUNT, ALL_LDS, false>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                0xFFFFFFFFu, wc);
+                done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
+                                                                      0xFFFFFFFFu, wc);
             MPT_TOC(reg_trace, tic_);
 #ifdef MPT_DEBUG_WAVE_TIMES
             if (COUNT) {  // per-level divergence diagnostics: [level + 1][steps, box trips, box lane work, prim trips, prim lane work]
@@ -1004,7 +1055,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             if (done) {
                 alive = best_prim >= 0;   // a hit: to ring 0 as it is, shaded by the step that pops it
                 if (!alive) {             // the sky ends the path (PathTracing.h:225-232)
-                    shade_bounce(pp.scene, lds_nodes, pp.sp, g, ps, best_t, -1);
+                    shade_bounce<LEAN>(pp.scene, lds_nodes, pp.sp, g, ps, best_t, -1);
                     store_slot(pp.slots, ps.path, clamp01(ps.L.x), clamp01(ps.L.y), clamp01(ps.L.z), clamp01(ps.La));
                 }
             } else {
