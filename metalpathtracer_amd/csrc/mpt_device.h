@@ -99,6 +99,62 @@ __device__ __forceinline__ F3 normalize3(F3 a) {
     float inv = mpt_rcp(sqrtf(dot3(a, a)));
     return a * inv;
 }
+// ---- sqrtf(x), and the inverse length, in the lean kernels ------------------------------------------------------------------------
+// The compiler expands a correctly rounded FP32 square root into 16 vector instructions, 7 of them range handling: the 2^32 pre-scale
+// of operands below 2^-96 with its 2^-16 post-scale, and the pass-through of +-0 and +inf.  What is left — sqrt_core() — is v_sqrt_f32,
+// its two neighbours in the last place, one fma residual for each and two selects: the SAME operations in the same order, so for
+// 2^-96 <= x < inf (sqrt_core_exact) the bits are sqrtf's.  Measured over all 2^32 operands, not argued (tests/test_gpu_lean_math.py).
+// normalize3<true> needs ONE wave-uniform guard (one ballot, as mpt_rcp) for both the root and the reciprocal: 2^-96 <= l2 <= 2^126 puts
+// the root into [2^-48, 2^63], well inside the range of rcp_chain; a wave with a lane outside takes today's expression.  That is 7 vector
+// instructions and the reciprocal's own guard less per normalize.  MPT_LEAN_SQRT=0: pricing build of the lean kernels with the parent's
+// normalize.  (The two bare square roots — leaf_test's sphere, random_unit_vector — need a guard of their own for the same core; priced,
+// it did not pay and is not here: profiles/r16_lean_math.txt.)
+#ifndef MPT_LEAN_SQRT
+#define MPT_LEAN_SQRT 1
+#endif
+#define MPT_SQRT_LO 0x1p-96f
+#define MPT_NORM_HI 0x1p126f
+__device__ __forceinline__ float sqrt_core(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float lo = __uint_as_float(__float_as_uint(s) - 1u), hi = __uint_as_float(__float_as_uint(s) + 1u);
+    const float vlo = fmaf(-lo, s, x), vhi = fmaf(-hi, s, x);
+    float r = vlo <= 0.0f ? lo : s;
+    r = vhi > 0.0f ? hi : r;
+    return r;
+}
+__device__ __forceinline__ bool sqrt_core_exact(float x) { return x >= MPT_SQRT_LO && x < INFINITY; }
+__device__ __forceinline__ bool norm_core_exact(float l2) { return l2 >= MPT_SQRT_LO && l2 <= MPT_NORM_HI; }
+__device__ __forceinline__ float inv_len_core(float l2) { return rcp_chain(sqrt_core(l2)); }   // 1.0f / sqrtf(l2) where norm_core_exact(l2)
+template <bool LEAN>
+__device__ __forceinline__ F3 normalize3(F3 a) {
+    if (LEAN && MPT_LEAN_SQRT) {
+        const float l2 = dot3(a, a);
+        if (__builtin_expect(__ballot(!norm_core_exact(l2)) == 0ull, 1)) return a * inv_len_core(l2);
+        return a * mpt_rcp(sqrtf(l2));
+    }
+    return normalize3(a);
+}
+// ---- x / W for a wave-uniform W that stays the same through a render (gen_primary<true>: the jitter over the image's width and height) ----
+// The compiler's division computes v_rcp_f32 of the denominator and one Newton step — cdiv_recip(), W alone — and then the division
+// proper: one multiply and four fused multiply-adds, cdiv_chain().  v_div_scale and v_div_fixup around them do nothing for the operands
+// gen_primary has (1 <= W < 2^24, x = k 2^-24 - 0.5): MEASURED per (W, H) by k_lean_cdiv_check over all 2^24 numerators before a context
+// takes the lean kernels at that size (mpt_lean_cdiv.h), and for a list of sizes by tests/test_gpu_lean_math.py.
+// MPT_LEAN_CDIV=0: pricing build, the parent's two divisions.
+#ifndef MPT_LEAN_CDIV
+#define MPT_LEAN_CDIV 1
+#endif
+__device__ __forceinline__ float cdiv_recip(float W) {
+    const float r0 = __builtin_amdgcn_rcpf(W);
+    const float e = fmaf(-W, r0, 1.0f);
+    return fmaf(e, r0, r0);
+}
+__device__ __forceinline__ float cdiv_chain(float x, float W, float r) {
+    float q = x * r;
+    const float e1 = fmaf(-W, q, x);
+    q = fmaf(e1, r, q);
+    const float e2 = fmaf(-W, q, x);
+    return fmaf(e2, r, q);
+}
 __device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
 // ---- RNG ------------------------------------------------------------------------------------------
@@ -516,9 +572,9 @@ __device__ __forceinline__ HitInfo finish_hit(const SceneDev& sc, LdsNodes lds, 
     const float4 p0 = pr.p0, p1 = pr.p1, p2 = pr.p2;
     h.point = o + t * d;
     if (prim_type(p0) == 1) {
-        h.normal = normalize3(cross3(f3(p1.x, p1.y, p1.z), f3(p2.x, p2.y, p2.z)));
+        h.normal = normalize3<LEAN>(cross3(f3(p1.x, p1.y, p1.z), f3(p2.x, p2.y, p2.z)));
     } else {
-        h.normal = normalize3(h.point - f3(p0.x, p0.y, p0.z));
+        h.normal = normalize3<LEAN>(h.point - f3(p0.x, p0.y, p0.z));
     }
     h.mat = __float_as_int(p1.w);
     h.orig_id = __float_as_int(p2.w);
@@ -609,7 +665,7 @@ template <bool LEAN = false>
 __device__ __forceinline__ bool shade_bounce(const SceneDev& sc, LdsNodes lds, const ShadeParams& sp, const PathRngDev& g,
                                              PathState& ps, float t, int prim) {
     if (prim < 0) {  // PathTracing.h:225-232 sky
-        F3 ud = normalize3(ps.d);
+        F3 ud = normalize3<LEAN>(ps.d);
         float tt = 0.5f * (ud.y + 1.0f);
         F3 sky = f3(1.0f + (0.6f - 1.0f) * tt, 1.0f + (0.7f - 1.0f) * tt, 1.0f + (1.0f - 1.0f) * tt);
         ps.L.x += ps.thr.x * sky.x;
@@ -643,7 +699,7 @@ __device__ __forceinline__ bool shade_bounce(const SceneDev& sc, LdsNodes lds, c
     F3 nd;
     bool through = false;
     if (LEAN) {
-        nd = normalize3(h.normal + ruv);  // PathTracing.h:252-254
+        nd = normalize3<LEAN>(h.normal + ruv);  // PathTracing.h:252-254
     } else if (sp.bsdf_mode == 2 && mtype == 0.0f) {  // Scatter.h:24-27,42 with randomFloat3 of Random.h:18-30 (dead in the reference)
         F3 c;
         if (sp.rng_mode == 0) {

@@ -31,6 +31,7 @@
 #include "mpt_own.h"
 
 #include "mpt_kernels.h"
+#include "mpt_lean_cdiv.h"
 #include "mpt_lbvh.h"
 #include "mpt_devbuild.h"
 #include "mpt_ordered.h"
@@ -340,6 +341,8 @@ struct mpt_ctx : SceneState {
     // 128 / 256 / 512 / 1024 -> 16.79-16.86 / 16.70 / 16.62-16.65 / 16.65 / 17.87 ms, the 1/8 shard's serial step 2.54 / - / 2.71 / 3.36
     uint32_t wl_min = 0, wl_div = 32;
     bool wl_lean = true;               // MPT_WL_LEAN=0: every wave-local pass runs the generic kernels (development knob)
+    LeanCdivCache lean_cdiv;           // is the lean kernels' division by W and H exact at this context's size (mpt_lean_cdiv.h)
+    DevMem<uint32_t> d_cdiv_bad;       // the mismatch count of k_lean_cdiv_check
     uint32_t wl_block = MPT_WL_BLOCK;  // path ids a wave claims per atomic (multiple of 64)
     int wgs_per_cu = 0;  // 0 = as many as the occupancy query admits
     size_t lds_budget = 78 * 1024;  // per workgroup; two workgroups per CU share the 160 KiB
@@ -377,6 +380,23 @@ static const void* ordered_kernel(bool count, bool all_lds, bool six = false) {
     if (six && !count) return all_lds ? (const void*)k_ordered<false, true, MPT_OT6_WAVES> : (const void*)k_ordered<false, false, MPT_OT6_WAVES>;
     if (count) return all_lds ? (const void*)k_ordered<true, true> : (const void*)k_ordered<true, false>;
     return all_lds ? (const void*)k_ordered<false, true> : (const void*)k_ordered<false, false>;
+}
+
+// The device check behind lean_cdiv_ok (mpt_lean_cdiv.h): all 2^24 numerators of gen_primary<true> over W and over H, on `st`, waited for.
+// Runs when a context's size has changed since its last lean pass, never inside a render.
+static bool lean_cdiv_device_check(mpt_ctx* ctx, hipStream_t st, float W, float H, uint32_t* mismatches) {
+#if MPT_LEAN_CDIV
+    if (!ctx->d_cdiv_bad && ctx->d_cdiv_bad.alloc(sizeof(uint32_t)) != hipSuccess) return false;
+    if (hipMemsetAsync(ctx->d_cdiv_bad.get(), 0, sizeof(uint32_t), st) != hipSuccess) return false;
+    hipLaunchKernelGGL(k_lean_cdiv_check, dim3(256), dim3(256), 0, st, W, H, ctx->d_cdiv_bad.get());
+    if (hipGetLastError() != hipSuccess) return false;
+    if (hipMemcpyAsync(mismatches, ctx->d_cdiv_bad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+    return hipStreamSynchronize(st) == hipSuccess;
+#else
+    (void)ctx, (void)st, (void)W, (void)H;
+    *mismatches = 0u;   // (the pricing build without the constant division has nothing to check)
+    return true;
+#endif
 }
 
 // lean: the pass is one the lean kernels may run (wl_lean_ok, mpt_wl_lean.h: Philox, Lambert, no counters, every index range checked)
@@ -1383,7 +1403,8 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     // Philox + Lambert without counters, inside the ranges of the lean kernels' 24-bit index arithmetic: the lean variant of the same kernel
     WlLean lean_args = {0u, 0u, 0u};
     const bool lean = pipeline == MPT_PIPE_WAVELOCAL && ctx->wl_lean &&
-                      wl_lean_ok(ctx->n_prims, n_local_tiles, tiles_x, ctx->W, ctx->H, nr, S, pp.tile_magic, p->rng_mode, p->bsdf_mode, count_flag(p), &lean_args);
+                      wl_lean_ok(ctx->n_prims, n_local_tiles, tiles_x, ctx->W, ctx->H, nr, S, pp.tile_magic, p->rng_mode, p->bsdf_mode, count_flag(p), &lean_args) &&
+                      lean_cdiv_ok(ctx->lean_cdiv, pp.W, pp.H, [&](float W, float H, uint32_t* bad) { return lean_cdiv_device_check(ctx, L.stream.get(), W, H, bad); });
     const void* kfun = pipeline == MPT_PIPE_MEGAKERNEL ? mega_kernel(count_flag(p), all_lds)
                        : pipeline == MPT_PIPE_WAVELOCAL ? wavelocal_kernel(count_flag(p), all_lds, corun, lean)
                        : pipeline == MPT_PIPE_ORDERED  ? ordered_kernel(count_flag(p), ctx->ot_pt[ot_point].lds_nodes == ctx->n_acc_nodes, ot_point == 1)

@@ -180,6 +180,7 @@ __device__ __forceinline__ bool path_to_pixel(const PassParams& pp, uint32_t pat
 struct CamView {
     F3 cam, first, vu, vv;
     float W, H;
+    float rW, rH;   // cdiv_recip(W), cdiv_recip(H): the lean wave-local kernels only (the .w words of vu and vv in their LDS copy)
 };
 __device__ __forceinline__ CamView cam_of(const PassParams& pp) { return CamView{pp.cam, pp.first, pp.vu, pp.vv, pp.W, pp.H}; }
 __device__ __forceinline__ void pixel_uv(const CamView& cv, uint32_t px, uint32_t py, float& uvx, float& uvy) {
@@ -202,13 +203,18 @@ __device__ __forceinline__ void gen_primary(const PassParams& pp, const CamView&
         g.lit_seed = seed;
     } else {
         U4 r = philox4x32_10<true>(g.pixel, sample, 0xFFFFFFFFu, 0u, pp.sp.seed_lo, pp.sp.seed_hi);
-        xOff = (u01(r.x) - 0.5f) / cv.W;
-        yOff = (u01(r.y) - 0.5f) / cv.H;
+        if (LEAN && MPT_LEAN_CDIV) {   // the division proper, its reciprocal step done once per workgroup (cdiv_chain, mpt_device.h)
+            xOff = cdiv_chain(u01(r.x) - 0.5f, cv.W, cv.rW);
+            yOff = cdiv_chain(u01(r.y) - 0.5f, cv.H, cv.rH);
+        } else {
+            xOff = (u01(r.x) - 0.5f) / cv.W;
+            yOff = (u01(r.y) - 0.5f) / cv.H;
+        }
         g.lit_seed = 0;
     }
     F3 dir = (cv.first + (uvx + xOff) * cv.vu + (uvy + yOff) * cv.vv) - cv.cam;
     ps.o = cv.cam;
-    ps.d = normalize3(dir);
+    ps.d = normalize3<LEAN>(dir);
     ps.thr = f3(1, 1, 1);
     ps.L = f3(0, 0, 0);
     ps.La = 0.0f;
@@ -725,8 +731,8 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         announce_resident(pp);
         lds_nodes_raw[cfg_off + 0] = make_float4(pp.cam.x, pp.cam.y, pp.cam.z, pp.W);
         lds_nodes_raw[cfg_off + 1] = make_float4(pp.first.x, pp.first.y, pp.first.z, pp.H);
-        lds_nodes_raw[cfg_off + 2] = make_float4(pp.vu.x, pp.vu.y, pp.vu.z, 0.0f);
-        lds_nodes_raw[cfg_off + 3] = make_float4(pp.vv.x, pp.vv.y, pp.vv.z, 0.0f);
+        lds_nodes_raw[cfg_off + 2] = make_float4(pp.vu.x, pp.vu.y, pp.vu.z, LEAN && MPT_LEAN_CDIV ? cdiv_recip(pp.W) : 0.0f);
+        lds_nodes_raw[cfg_off + 3] = make_float4(pp.vv.x, pp.vv.y, pp.vv.z, LEAN && MPT_LEAN_CDIV ? cdiv_recip(pp.H) : 0.0f);
         uint32_t* w = (uint32_t*)(lds_nodes_raw + cfg_off + 4);
         for (uint32_t k = 0; k < MPT_WL_LEVELS; ++k) {
             w[k] = budgets.b[k];
@@ -929,6 +935,8 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 cv.vv = f3(c3.x, c3.y, c3.z);
                 cv.W = c0.w;
                 cv.H = c1.w;
+                cv.rW = c2.w;
+                cv.rH = c3.w;
             }
             if (new_tile) pixel_uv(cv, px, py, uvx_cached, uvy_cached);
             if (px < pp.width && py < pp.height) {
@@ -1312,6 +1320,25 @@ __global__ void k_kat_rcp(unsigned long long* out) {
         if (bad_out) atomicAdd(out + 2, bad_out);
         atomicAdd(out + 3, n_out);
     }
+}
+// The lean kernels' division by the image's width or height (cdiv_chain, mpt_device.h) against the compiler's x / W, bit for bit, for
+// all 2^24 numerators gen_primary<true> can have: x = k 2^-24 - 0.5.  *bad += the numerators whose two quotients differ (two NaNs are
+// the same answer).  Launched with 256 x 256 threads; run per (W, H) of a context (mpt_lean_cdiv.h) and by tests/lean_math.
+__device__ __forceinline__ uint32_t cdiv_mismatches(float W, uint32_t first, uint32_t stride) {
+    const float r = cdiv_recip(W);
+    uint32_t bad = 0;
+    for (uint32_t k = first; k < (1u << 24); k += stride) {
+        const float x = u01(k << 8) - 0.5f;
+        const uint32_t a = __float_as_uint(cdiv_chain(x, W, r)), b = __float_as_uint(x / W);
+        bad += (a == b || ((a & 0x7FFFFFFFu) > 0x7F800000u && (b & 0x7FFFFFFFu) > 0x7F800000u)) ? 0u : 1u;
+    }
+    return bad;
+}
+__global__ void k_lean_cdiv_check(float W, float H, uint32_t* bad) {
+    const uint32_t first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    uint32_t n = cdiv_mismatches(W, first, stride) + cdiv_mismatches(H, first, stride);
+    for (int off = 32; off > 0; off >>= 1) n += __shfl_down(n, off);
+    if ((threadIdx.x & 63u) == 0 && n) atomicAdd(bad, n);
 }
 __global__ void k_kat_sincos(const float* u, uint32_t n, float* s, float* c) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
