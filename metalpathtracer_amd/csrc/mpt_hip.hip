@@ -1,7 +1,8 @@
 // mpt_hip.hip — host side of the C ABI (include/mpt.h) of the MI355X path-tracing hot path: context and resource
-// management, conversion of the reference's flat scene arrays into the device layout (threaded breadth-first BVH,
-// leaf-ordered primitives, de-duplicated materials), pass scheduling and kernel launches.  The kernels themselves are
-// in mpt_kernels.h, their building blocks in mpt_device.h.
+// management, upload of a scene (its conversion into the device layout — threaded breadth-first BVH, leaf-ordered
+// primitives, de-duplicated materials — is pure host code in mpt_scene_layout.h), pass scheduling and kernel launches.
+// The kernels themselves are in mpt_kernels.h, their building blocks in mpt_device.h; the host side of the
+// post-processing stages is mpt_post.h, the RCCL reduce mpt_comm.h, both included below.
 //
 // One mpt_render = one pass per <= 2^30 paths: k_begin_pass, ONE k_wavelocal launch (default pipeline; the global
 // wavefront launches k_step + k_advance per bounce generation instead), k_resolve_sum, one host synchronisation.
@@ -27,6 +28,8 @@
 
 #include "mpt.h"
 #include "mpt_accel.h"
+#include "mpt_scene_layout.h"
+#include "mpt_env.h"
 #include "mpt_device.h"
 #include "mpt_own.h"
 
@@ -366,20 +369,54 @@ struct mpt_ctx : SceneState {
     bool dp_hist_agg = true;        // MPT_DISPLAY_HIST=plain: k_dp_histogram without the aggregation within the wave
 };
 
-// kernel variants: COUNT (work counters) x ALL_LDS (the whole BVH fits the LDS budget)
-static const void* step_kernel(bool count, bool all_lds) {
-    if (count) return all_lds ? (const void*)k_step<true, true> : (const void*)k_step<true, false>;
-    return all_lds ? (const void*)k_step<false, true> : (const void*)k_step<false, false>;
-}
-static const void* mega_kernel(bool count, bool all_lds) {
-    if (count) return all_lds ? (const void*)k_megakernel<true, true> : (const void*)k_megakernel<true, false>;
-    return all_lds ? (const void*)k_megakernel<false, true> : (const void*)k_megakernel<false, false>;
-}
-
-static const void* ordered_kernel(bool count, bool all_lds, bool six = false) {
-    if (six && !count) return all_lds ? (const void*)k_ordered<false, true, MPT_OT6_WAVES> : (const void*)k_ordered<false, false, MPT_OT6_WAVES>;
-    if (count) return all_lds ? (const void*)k_ordered<true, true> : (const void*)k_ordered<true, false>;
-    return all_lds ? (const void*)k_ordered<false, true> : (const void*)k_ordered<false, false>;
+// The trace kernels: every instantiation the four pipelines launch, ONCE.  trace_kernel picks a pass's row, create_impl raises the
+// dynamic-LDS limit of every row, MPT_DEBUG_LAUNCH prints the row's name: a new variant is one more row and its term in trace_kernel.
+struct TraceKernel {
+    const void* fn;
+    const char* name;   // as MPT_DEBUG_LAUNCH prints it
+    int wg_max;         // the kernel's launch bound = its workgroup size (mpt_kernels.h: 768 for the wave-local kernels; mpt_ordered.h: 256 or 768 by operating point)
+};
+// variant of a row: plain, or (wave-local, never counted) the kernel that leaves room for a resolve beside it and / or the lean one
+// (wl_lean_ok, mpt_wl_lean.h), or (closest-first, never counted) the six-wave operating point
+enum { TK_PLAIN = 0, TK_CORUN = 1, TK_LEAN = 2, TK_SIX = 4 };
+static const struct TraceKernelRow {
+    int pipeline;
+    bool count, all_lds;   // COUNT (work counters) x ALL_LDS (the whole tree fits the LDS budget)
+    int variant;
+    TraceKernel k;
+} g_trace_kernels[] = {
+    {MPT_PIPE_WAVEFRONT, true, true, TK_PLAIN, {(const void*)k_step<true, true>, "k_step", 1024}},
+    {MPT_PIPE_WAVEFRONT, true, false, TK_PLAIN, {(const void*)k_step<true, false>, "k_step", 1024}},
+    {MPT_PIPE_WAVEFRONT, false, true, TK_PLAIN, {(const void*)k_step<false, true>, "k_step", 1024}},
+    {MPT_PIPE_WAVEFRONT, false, false, TK_PLAIN, {(const void*)k_step<false, false>, "k_step", 1024}},
+    {MPT_PIPE_MEGAKERNEL, true, true, TK_PLAIN, {(const void*)k_megakernel<true, true>, "k_megakernel", 1024}},
+    {MPT_PIPE_MEGAKERNEL, true, false, TK_PLAIN, {(const void*)k_megakernel<true, false>, "k_megakernel", 1024}},
+    {MPT_PIPE_MEGAKERNEL, false, true, TK_PLAIN, {(const void*)k_megakernel<false, true>, "k_megakernel", 1024}},
+    {MPT_PIPE_MEGAKERNEL, false, false, TK_PLAIN, {(const void*)k_megakernel<false, false>, "k_megakernel", 1024}},
+    {MPT_PIPE_ORDERED, false, true, TK_SIX, {(const void*)k_ordered<false, true, MPT_OT6_WAVES>, "k_ordered", MPT_OT6_THREADS}},
+    {MPT_PIPE_ORDERED, false, false, TK_SIX, {(const void*)k_ordered<false, false, MPT_OT6_WAVES>, "k_ordered", MPT_OT6_THREADS}},
+    {MPT_PIPE_ORDERED, true, true, TK_PLAIN, {(const void*)k_ordered<true, true>, "k_ordered", MPT_OT_THREADS}},
+    {MPT_PIPE_ORDERED, true, false, TK_PLAIN, {(const void*)k_ordered<true, false>, "k_ordered", MPT_OT_THREADS}},
+    {MPT_PIPE_ORDERED, false, true, TK_PLAIN, {(const void*)k_ordered<false, true>, "k_ordered", MPT_OT_THREADS}},
+    {MPT_PIPE_ORDERED, false, false, TK_PLAIN, {(const void*)k_ordered<false, false>, "k_ordered", MPT_OT_THREADS}},
+    {MPT_PIPE_WAVELOCAL, false, true, TK_LEAN | TK_CORUN, {(const void*)k_wavelocal_lean_corun<true>, "k_wavelocal_lean_corun", MPT_WL_THREADS(true)}},
+    {MPT_PIPE_WAVELOCAL, false, false, TK_LEAN | TK_CORUN, {(const void*)k_wavelocal_lean_corun<false>, "k_wavelocal_lean_corun", MPT_WL_THREADS(false)}},
+    {MPT_PIPE_WAVELOCAL, false, true, TK_LEAN, {(const void*)k_wavelocal_lean<true>, "k_wavelocal_lean", MPT_WL_THREADS(true)}},
+    {MPT_PIPE_WAVELOCAL, false, false, TK_LEAN, {(const void*)k_wavelocal_lean<false>, "k_wavelocal_lean", MPT_WL_THREADS(false)}},
+    {MPT_PIPE_WAVELOCAL, false, true, TK_CORUN, {(const void*)k_wavelocal_corun<true>, "k_wavelocal_corun", MPT_WL_THREADS(true)}},
+    {MPT_PIPE_WAVELOCAL, false, false, TK_CORUN, {(const void*)k_wavelocal_corun<false>, "k_wavelocal_corun", MPT_WL_THREADS(false)}},
+    {MPT_PIPE_WAVELOCAL, true, true, TK_PLAIN, {(const void*)k_wavelocal<true, true>, "k_wavelocal", MPT_WL_THREADS(true)}},
+    {MPT_PIPE_WAVELOCAL, true, false, TK_PLAIN, {(const void*)k_wavelocal<true, false>, "k_wavelocal", MPT_WL_THREADS(false)}},
+    {MPT_PIPE_WAVELOCAL, false, true, TK_PLAIN, {(const void*)k_wavelocal<false, true>, "k_wavelocal", MPT_WL_THREADS(true)}},
+    {MPT_PIPE_WAVELOCAL, false, false, TK_PLAIN, {(const void*)k_wavelocal<false, false>, "k_wavelocal", MPT_WL_THREADS(false)}},
+};
+// The row of a pass (pipeline: resolved).  A counted pass runs the plain kernel of its pipeline; a combination without a row is a null
+// pointer, which run_pass reports: there is no other kernel to fall back to.
+static const TraceKernel* trace_kernel(int pipeline, bool count, bool all_lds, int variant) {
+    if (count) variant = TK_PLAIN;
+    for (const TraceKernelRow& r : g_trace_kernels)
+        if (r.pipeline == pipeline && r.count == count && r.all_lds == all_lds && r.variant == variant) return &r.k;
+    return nullptr;
 }
 
 // The device check behind lean_cdiv_ok (mpt_lean_cdiv.h): all 2^24 numerators of gen_primary<true> over W and over H, on `st`, waited for.
@@ -397,17 +434,6 @@ static bool lean_cdiv_device_check(mpt_ctx* ctx, hipStream_t st, float W, float 
     *mismatches = 0u;   // (the pricing build without the constant division has nothing to check)
     return true;
 #endif
-}
-
-// lean: the pass is one the lean kernels may run (wl_lean_ok, mpt_wl_lean.h: Philox, Lambert, no counters, every index range checked)
-static const void* wavelocal_kernel(bool count, bool all_lds, bool corun, bool lean = false) {
-    if (lean && !count) {
-        if (corun) return all_lds ? (const void*)k_wavelocal_lean_corun<true> : (const void*)k_wavelocal_lean_corun<false>;
-        return all_lds ? (const void*)k_wavelocal_lean<true> : (const void*)k_wavelocal_lean<false>;
-    }
-    if (corun && !count) return all_lds ? (const void*)k_wavelocal_corun<true> : (const void*)k_wavelocal_corun<false>;
-    if (count) return all_lds ? (const void*)k_wavelocal<true, true> : (const void*)k_wavelocal<true, false>;
-    return all_lds ? (const void*)k_wavelocal<false, true> : (const void*)k_wavelocal<false, false>;
 }
 
 #define MPT_LDS_MATS MPT_LDS_MATS_N               // materials staged in LDS (32 B each; mpt_kernels.h)
@@ -485,37 +511,8 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     if ((e = getenv("MPT_WL_BLOCK")) && atoi(e) >= 64) ctx->wl_block = (uint32_t)atoi(e) & ~63u;
     if ((e = getenv("MPT_DISPLAY_PX")) && (atoi(e) == 1 || atoi(e) == 4)) ctx->dp_px = atoi(e);
     if ((e = getenv("MPT_DISPLAY_HIST"))) ctx->dp_hist_agg = strcmp(e, "plain") != 0;
-    if ((e = getenv("MPT_BUDGETS"))) {  // e.g. "8,20,50,125": box-test trips per step of ring 0, 1, ... (the last ring has none)
-        unsigned prev = 4;
-        const char* q = e;
-        for (uint32_t k = 0; k + 1 < MPT_WL_LEVELS; ++k) {
-            unsigned v = 0;
-            int used = 0;
-            if (q && sscanf(q, "%u%n", &v, &used) == 1) {
-                q += used;
-                if (*q == ',') ++q;
-            } else {
-                v = prev * 2;
-                q = nullptr;
-            }
-            ctx->budgets.b[k] = v < 1 ? 1 : v;
-            prev = ctx->budgets.b[k];
-        }
-    }
-    if ((e = getenv("MPT_MIN_ACTIVE"))) {  // "a,b,c,d,e": lanes that must still be traversing for a step of ring k to go on
-        const char* q = e;
-        unsigned v = 0;
-        for (uint32_t k = 0; k < MPT_WL_LEVELS; ++k) {
-            int used = 0;
-            if (q && sscanf(q, "%u%n", &v, &used) == 1) {
-                q += used;
-                if (*q == ',') ++q;
-            } else {
-                q = nullptr;
-            }
-            ctx->budgets.min_active[k] = v > 64 ? 64 : v;
-        }
-    }
+    if ((e = getenv("MPT_BUDGETS"))) fill_budgets(e, ctx->budgets.b, MPT_WL_LEVELS - 1u);   // (the last ring has none)
+    if ((e = getenv("MPT_MIN_ACTIVE"))) fill_min_active(e, ctx->budgets.min_active, MPT_WL_LEVELS);
     if ((e = getenv("MPT_LIGHT_BUDGET")) && atoi(e) >= 1) {  // one number: geometric ladder b, 2b, 4b, 8b
         uint32_t b = (uint32_t)atoi(e);
         for (uint32_t k = 0; k + 1 < MPT_WL_LEVELS; ++k) ctx->budgets.b[k] = b > (1u << 28) ? b : std::min<uint64_t>((uint64_t)b << k, MPT_WL_NO_BUDGET);
@@ -529,38 +526,17 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     if ((e = getenv("MPT_WL_DIV")) && atoi(e) >= 1) ctx->wl_div = (uint32_t)atoi(e);
     if ((e = getenv("MPT_WL_LEAN"))) ctx->wl_lean = atoi(e) != 0;
     if ((e = getenv("MPT_OT_STACK")) && atoi(e) >= 2 && atoi(e) <= (int)MPT_OT_PARK) ctx->ot_stack_depth = (uint32_t)atoi(e);
-    for (int which = 0; which < 2; ++which)
-        if ((e = getenv(which ? "MPT_OT_MIN_ACTIVE" : "MPT_OT_BUDGETS"))) {  // "a,b,c": one number per tree-walk ring
-            const char* q = e;
-            for (uint32_t k = 0; k < MPT_OT_MLEVELS && q; ++k) {
-                unsigned v = 0;
-                int used = 0;
-                if (sscanf(q, "%u%n", &v, &used) != 1) break;
-                q += used;
-                if (*q == ',') ++q;
-                if (which) ctx->ot_budgets.min_active[k] = v > 64 ? 64 : v;
-                else if (k + 1 < MPT_OT_MLEVELS) ctx->ot_budgets.trips[k] = v < 1 ? 1 : v;
-            }
-        }
+    unsigned ot[MPT_OT_MLEVELS];   // "a,b,c": one number per tree-walk ring; the rings a list leaves out keep their defaults
+    if ((e = getenv("MPT_OT_BUDGETS")))
+        for (unsigned k = 0, n = parse_uint_list(e, ot, MPT_OT_MLEVELS); k < n && k + 1 < MPT_OT_MLEVELS; ++k) ctx->ot_budgets.trips[k] = ot[k] < 1 ? 1 : ot[k];
+    if ((e = getenv("MPT_OT_MIN_ACTIVE")))
+        for (unsigned k = 0, n = parse_uint_list(e, ot, MPT_OT_MLEVELS); k < n; ++k) ctx->ot_budgets.min_active[k] = ot[k] > 64 ? 64 : ot[k];
     if ((e = getenv("MPT_OT_INPLACE")) && atoi(e) >= 1) ctx->ot_budgets.inplace_min = (uint32_t)atoi(e);
     if ((e = getenv("MPT_OT_CULL_REL")) && atof(e) > 0.0) ctx->acc_cull_rel = (float)atof(e);
     if (ctx->wg_size < 64 || ctx->wg_size > 1024 || (ctx->wg_size & 63)) ctx->wg_size = 0;
     if (ctx->lds_budget > 160 * 1024) ctx->lds_budget = 160 * 1024;
     // allow the full 160 KiB of dynamic LDS
-    for (int c = 0; c < 2; ++c)
-        for (int a = 0; a < 2; ++a) {
-            hipFuncSetAttribute(step_kernel(c, a), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipFuncSetAttribute(mega_kernel(c, a), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipFuncSetAttribute(wavelocal_kernel(c, a, false), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (!c) hipFuncSetAttribute(wavelocal_kernel(false, a, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (!c) hipFuncSetAttribute(wavelocal_kernel(false, a, false, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (!c) hipFuncSetAttribute(wavelocal_kernel(false, a, true, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        }
-    for (int c = 0; c < 2; ++c)
-        for (int a = 0; a < 2; ++a) {
-            hipFuncSetAttribute(ordered_kernel(c, a), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (!c) hipFuncSetAttribute(ordered_kernel(false, a, true), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        }
+    for (const TraceKernelRow& r : g_trace_kernels) hipFuncSetAttribute(r.k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_trace_rays_ordered, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_trace_rays, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     hipFuncSetAttribute((const void*)k_dn_guide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);   // (the image of k_trace_rays)
@@ -586,23 +562,6 @@ extern "C" int mpt_destroy(mpt_ctx* ctx) {
 }
 
 // ---- scene upload: reference arrays -> threaded, breadth-first, leaf-ordered device layout ----------------
-namespace {
-struct HostNode {
-    float bmin[3], bmax[3];
-    int leftFirst, count;
-};
-static inline int bits_to_int(float f) {
-    int i;
-    memcpy(&i, &f, 4);
-    return i;
-}
-static inline float int_to_bits(int i) {
-    float f;
-    memcpy(&f, &i, 4);
-    return f;
-}
-}  // namespace
-
 // What each kernel stages in LDS, from the sizes of the uploaded scene.
 static void size_lds_images(mpt_ctx* ctx) {
     // LDS image of the reference-order kernels = top of the tree + primitives of the shallowest leaves.  When the whole
@@ -683,320 +642,37 @@ static int upload_scene_impl(mpt_ctx* ctx, const float* bvh, uint64_t n_nodes, c
         int wrc = wait_impl(ctx);  // renders in flight still read the old scene
         if (wrc) return wrc;
     }
-    const uint32_t N = (uint32_t)n_nodes, P = (uint32_t)n_prims;
-
-    // 1. walk the reference tree in ITS visit order (root; right subtree; left subtree —
-    //    PathTracing.h:188-193 pushes left then right, so right pops first) and record the order.
-    std::vector<uint32_t> order;   // visit position -> reference node
-    std::vector<uint32_t> sub_end; // visit position -> visit position just past its subtree
-    order.reserve(N);
-    std::vector<uint8_t> seen(N, 0);
+    mpt_layout::SceneLayout lay;
     {
-        // iterative DFS with explicit post-processing for subtree ends
-        struct Fr {
-            uint32_t node, pos;
-            int stage;
-        };
-        std::vector<Fr> st;
-        st.push_back({0u, 0u, 0});
-        sub_end.assign(N, 0);
-        while (!st.empty()) {
-            Fr& f = st.back();
-            if (f.stage == 0) {
-                if (f.node >= N || seen[f.node]) return fail(ctx, MPT_ERR_BAD_SCENE, "BVH is not a tree (cycle or index out of range)");
-                seen[f.node] = 1;
-                f.pos = (uint32_t)order.size();
-                order.push_back(f.node);
-                int count = bits_to_int(bvh[8 * (size_t)f.node + 7]);
-                if (count > 0) {
-                    int first = bits_to_int(bvh[8 * (size_t)f.node + 3]);
-                    if (first < 0 || (uint64_t)first + (uint64_t)count > n_prims)
-                        return fail(ctx, MPT_ERR_BAD_SCENE, "leaf primitive range out of bounds");
-                    sub_end[f.pos] = f.pos + 1;
-                    st.pop_back();
-                } else {
-                    f.stage = 1;
-                    uint32_t right = (uint32_t)(-(long long)count);
-                    if (count == 0) return fail(ctx, MPT_ERR_BAD_SCENE, "internal node with right child 0");
-                    st.push_back({right, 0u, 0});
-                }
-            } else if (f.stage == 1) {
-                f.stage = 2;
-                int left = bits_to_int(bvh[8 * (size_t)f.node + 3]);
-                if (left < 0) return fail(ctx, MPT_ERR_BAD_SCENE, "negative left child");
-                st.push_back({(uint32_t)left, 0u, 0});
-            } else {
-                sub_end[f.pos] = (uint32_t)order.size();
-                st.pop_back();
-            }
-        }
+        std::string why;
+        const int lrc = mpt_layout::layout_scene(bvh, n_nodes, prims, mats, prim_idx, n_prims, lay, why);
+        if (lrc) return fail(ctx, lrc, why);
     }
-    const uint32_t NV = (uint32_t)order.size();  // reachable nodes
-
-    // 1b. every child box must lie inside its parent's box: then the reference's walk equals a scan over the leaves in
-    //     visit order (mpt_ordered.h) and the closest-first pipeline may be used; otherwise only the reference-order ones.
-    bool nested = true;
-    for (uint32_t pos = 0; pos < NV && nested; ++pos) {
-        const float* n = bvh + 8 * (size_t)order[pos];
-        if (bits_to_int(n[7]) > 0) continue;
-        const uint32_t kids[2] = {pos + 1, pos + 1 < NV ? sub_end[pos + 1] : NV};
-        for (uint32_t k : kids) {
-            if (k >= NV) continue;
-            const float* c = bvh + 8 * (size_t)order[k];
-            for (int a = 0; a < 3; ++a)
-                if (!(c[a] >= n[a] && c[4 + a] <= n[4 + a])) nested = false;
-        }
-    }
-
-    // 2. leaves: gather primitives into leaf order; split leaves of more than 16 primitives into a chain.
-    //    Device node list in VISIT order first (dn), then permuted breadth-first.
-    struct DNode {
-        float bmin[3], bmax[3];
-        bool leaf;
-        uint32_t first, count;   // leaf
-        uint32_t hit, miss;      // links as indices into dn (visit order); N_total = end
-        uint32_t ref_leaf;       // leaf: number of the reference leaf it came from (visit order)
-    };
-    std::vector<DNode> dn;
-    dn.reserve(NV + 16);
-    std::vector<uint32_t> pos_to_dn(NV + 1, 0);  // visit position -> dn index of its (first) node
-    std::vector<float> dprims;
-    dprims.reserve((size_t)P * 12);
-    std::vector<float> mat_table;
-    std::vector<float> refleaf;  // 8 floats per reference leaf: (bmin, 0) (bmax, 0)
-    std::map<std::vector<uint32_t>, uint32_t> mat_lookup;
-    auto mat_index = [&](uint32_t pid) -> uint32_t {
-        std::vector<uint32_t> key(8);
-        memcpy(key.data(), mats + 8 * (size_t)pid, 32);
-        auto it = mat_lookup.find(key);
-        if (it != mat_lookup.end()) return it->second;
-        uint32_t id = (uint32_t)(mat_table.size() / 8);
-        mat_table.insert(mat_table.end(), mats + 8 * (size_t)pid, mats + 8 * (size_t)pid + 8);
-        mat_lookup.emplace(std::move(key), id);
-        return id;
-    };
-    uint32_t n_spheres = 0;
-    float tri_extent = 0.0f;  // largest |coordinate| of a triangle vertex
-    // first pass: create dn entries; a long leaf becomes ceil(count/16) chained nodes
-    for (uint32_t pos = 0; pos < NV; ++pos) {
-        const float* n = bvh + 8 * (size_t)order[pos];
-        int count = bits_to_int(n[7]);
-        pos_to_dn[pos] = (uint32_t)dn.size();
-        DNode d;
-        memcpy(d.bmin, n, 12);
-        memcpy(d.bmax, n + 4, 12);
-        d.hit = d.miss = 0;
-        d.ref_leaf = 0;
-        if (count > 0) {
-            int first = bits_to_int(n[3]);
-            d.leaf = true;
-            d.ref_leaf = (uint32_t)(refleaf.size() / 8);
-            const float rl[8] = {n[0], n[1], n[2], 0.0f, n[4], n[5], n[6], 0.0f};
-            refleaf.insert(refleaf.end(), rl, rl + 8);
-            for (int k0 = 0; k0 < count; k0 += 16) {
-                d.first = (uint32_t)(dprims.size() / 12);
-                d.count = (uint32_t)std::min(16, count - k0);
-                for (uint32_t k = 0; k < d.count; ++k) {
-                    int32_t pid = prim_idx[first + k0 + (int)k];
-                    if (pid < 0 || (uint64_t)pid >= n_prims) return fail(ctx, MPT_ERR_BAD_SCENE, "primitive index out of range");
-                    const float* p = prims + 12 * (size_t)pid;
-                    float rec[12];
-                    int type = (int)p[3];
-                    uint32_t m = mat_index((uint32_t)pid);
-                    if (type == 1) {  // triangle: v0, e1 = v1 - v0, e2 = v2 - v0 (PathTracing.h:149-150)
-                        rec[0] = p[0]; rec[1] = p[1]; rec[2] = p[2];
-                        rec[4] = p[4] - p[0]; rec[5] = p[5] - p[1]; rec[6] = p[6] - p[2];
-                        rec[8] = p[8] - p[0]; rec[9] = p[9] - p[1]; rec[10] = p[10] - p[2];
-                        for (int q = 0; q < 11; ++q)
-                            if ((q & 3) != 3 && std::isfinite(p[q])) tri_extent = std::max(tri_extent, fabsf(p[q]));
-                    } else {  // sphere; anything that is neither is never hit (PathTracing.h:120,143) — kept as a sphere of radius NaN
-                        rec[0] = p[0]; rec[1] = p[1]; rec[2] = p[2];
-                        rec[4] = type == 0 ? p[4] : NAN; rec[5] = 0; rec[6] = 0;
-                        rec[8] = 0; rec[9] = 0; rec[10] = 0;
-                        n_spheres++;
-                    }
-                    rec[3] = int_to_bits((int)((d.ref_leaf << 1) | (type == 1 ? 1u : 0u)));
-                    rec[7] = int_to_bits((int)m);
-                    rec[11] = int_to_bits(pid);
-                    dprims.insert(dprims.end(), rec, rec + 12);
-                }
-                dn.push_back(d);
-            }
-        } else {
-            d.leaf = false;
-            d.first = d.count = 0;
-            dn.push_back(d);
-        }
-    }
-    pos_to_dn[NV] = (uint32_t)dn.size();
-    const uint32_t ND = (uint32_t)dn.size();
-    // second pass: links.  In visit order the node after position pos is pos+1; a missed internal node
-    // skips to sub_end[pos].
-    for (uint32_t pos = 0; pos < NV; ++pos) {
-        uint32_t a = pos_to_dn[pos], b = pos_to_dn[pos + 1];
-        if (dn[a].leaf) {
-            for (uint32_t k = a; k < b; ++k) dn[k].hit = dn[k].miss = k + 1;  // chain, then the next position
-        } else {
-            dn[a].hit = a + 1;
-            dn[a].miss = pos_to_dn[sub_end[pos]];
-        }
-    }
-
-    // 3. the product's own tree over the leaves (mpt_accel.h): spheres go to the always list (their t has no usable
-    //    error bound: the r = 10^4 ground sphere), every leaf that holds triangles becomes an item whose box contains
-    //    the reference leaf box — or, for the triangles that share a leaf with a sphere, a tight box of their own.
-    const bool use_always = n_spheres <= MPT_ACCEL_MAX_ALWAYS;
-    const float pad = std::max(tri_extent, 1e-6f) * 6.103515625e-05f;  // 2^-14: covers the rcp / fma slab arithmetic
-    std::vector<mpt_accel::Item> items;
-    std::vector<uint32_t> item_dn;  // item -> dn index
-    std::vector<uint32_t> sphere_only_dn;
-    std::vector<float> always;
-    for (uint32_t i = 0; i < ND; ++i) {
-        const DNode& d = dn[i];
-        if (!d.leaf) continue;
-        mpt_accel::Box tb = mpt_accel::empty_box();
-        uint32_t ntri = 0, nsph = 0;
-        for (uint32_t k = 0; k < d.count; ++k) {
-            const float* r = dprims.data() + (size_t)(d.first + k) * 12;
-            if (bits_to_int(r[3]) & 1) {
-                ntri++;
-                const float v[3][3] = {{r[0], r[1], r[2]}, {r[0] + r[4], r[1] + r[5], r[2] + r[6]}, {r[0] + r[8], r[1] + r[9], r[2] + r[10]}};
-                for (auto& q : v) {
-                    mpt_accel::Box c;
-                    memcpy(c.lo, q, 12);
-                    memcpy(c.hi, q, 12);
-                    mpt_accel::grow(tb, c);
-                }
-            } else {
-                nsph++;
-            }
-        }
-        if (ntri == 0 && use_always) {
-            sphere_only_dn.push_back(i);
-            continue;
-        }
-        mpt_accel::Item it;
-        memcpy(it.box.lo, d.bmin, 12);
-        memcpy(it.box.hi, d.bmax, 12);
-        if (nsph != 0 && use_always) {  // a sphere's leaf-mates: v0 + e is not exactly the vertex, hence the generous margin
-            float ext = 0.0f;
-            for (int a = 0; a < 3; ++a) ext = std::max(ext, tb.hi[a] - tb.lo[a]);
-            for (int a = 0; a < 3; ++a) {
-                it.box.lo[a] = std::max(d.bmin[a], tb.lo[a] - 0.05f * ext - pad);
-                it.box.hi[a] = std::min(d.bmax[a], tb.hi[a] + 0.05f * ext + pad);
-            }
-        }
-        for (int a = 0; a < 3; ++a) {
-            it.box.lo[a] -= pad;
-            it.box.hi[a] += pad;
-        }
-        it.count = d.count;
-        it.key = i;
-        items.push_back(it);
-        item_dn.push_back(i);
-    }
-    const mpt_accel::Topology topo = mpt_accel::build_topology(items);
-
-    // 4. ONE primitive array for both structures: leaves without an item (spheres only) first — the reference-order
-    //    kernels test them for almost every ray, so they belong to the LDS-staged prefix — then the items in the
-    //    breadth-first order of the own tree (shallow leaves first).
-    std::vector<uint32_t> first_of(items.size(), 0);
-    {
-        std::vector<float> ordered(dprims.size());
-        uint32_t at = 0;
-        auto place = [&](DNode& d) {
-            memcpy(ordered.data() + (size_t)at * 12, dprims.data() + (size_t)d.first * 12, (size_t)d.count * 48);
-            d.first = at;
-            at += d.count;
-        };
-        for (uint32_t i : sphere_only_dn) place(dn[i]);
-        for (uint32_t it : topo.item_order) {
-            place(dn[item_dn[it]]);
-            first_of[it] = dn[item_dn[it]].first;
-        }
-        dprims.swap(ordered);
-    }
-    const std::vector<float> acc_nodes = mpt_accel::emit(topo, items, first_of);
-    if (use_always)
-        for (size_t i = 0; i < dprims.size() / 12; ++i) {
-            const float* r = dprims.data() + i * 12;
-            if (bits_to_int(r[3]) & 1) continue;
-            float rec[20];
-            memcpy(rec, r, 48);
-            const uint32_t k = (uint32_t)(always.size() / 20), leaf = (uint32_t)bits_to_int(r[3]) >> 1;
-            rec[5] = int_to_bits((int)i);  // own position in the primitive array = what the walk reports as the winner
-            rec[6] = int_to_bits((int)k);
-            memcpy(rec + 12, refleaf.data() + 8 * (size_t)leaf, 32);  // the box of its reference leaf, for the final check
-            always.insert(always.end(), rec, rec + 20);
-            dprims[i * 12 + 6] = int_to_bits((int)k);  // the primitive record points back at its always-list entry
-        }
-
-    // 5. reference-order structure: breadth-first permutation of the threaded nodes (top of the tree first -> LDS).
-    std::vector<uint32_t> depth(ND, 0);
-    {
-        // depth by walking positions: children of internal at pos are pos+1 (right) and sub_end[pos+1] (left)
-        std::vector<uint32_t> pdepth(NV, 0);
-        for (uint32_t pos = 0; pos < NV; ++pos) {
-            uint32_t a = pos_to_dn[pos];
-            if (!dn[a].leaf) {
-                uint32_t r = pos + 1;
-                if (r < NV) {
-                    pdepth[r] = pdepth[pos] + 1;
-                    uint32_t l = sub_end[r];
-                    if (l < NV && l < sub_end[pos]) pdepth[l] = pdepth[pos] + 1;
-                }
-            }
-            for (uint32_t k = a; k < pos_to_dn[pos + 1]; ++k) depth[k] = pdepth[pos];
-        }
-    }
-    std::vector<uint32_t> perm(ND);  // new index -> dn index
-    for (uint32_t i = 0; i < ND; ++i) perm[i] = i;
-    std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return depth[a] < depth[b]; });
-    // the root must stay at index 0 (depth 0, unique) — guaranteed by the stable sort
-    std::vector<uint32_t> inv(ND + 1);
-    for (uint32_t i = 0; i < ND; ++i) inv[perm[i]] = i;
-    inv[ND] = ND;  // terminator
-    std::vector<float> dnodes((size_t)ND * 8);
-    for (uint32_t i = 0; i < ND; ++i) {
-        const DNode& d = dn[perm[i]];
-        float* o = dnodes.data() + 8 * (size_t)i;
-        memcpy(o, d.bmin, 12);
-        memcpy(o + 4, d.bmax, 12);
-        if (d.leaf) {  // hit link = "hold this leaf" (MPT_NODE_HOLD | first << 4 | count - 1), miss link = the next node either way
-            o[3] = int_to_bits((int)(0x80000000u | (d.first * 16u + (d.count - 1u))));
-            o[7] = int_to_bits((int)inv[d.hit]);
-        } else {
-            o[3] = int_to_bits((int)inv[d.hit]);
-            o[7] = int_to_bits((int)inv[d.miss]);
-        }
-    }
-
     SceneState s;   // (the scene before stays in place until this one is complete)
-    auto up = [&](float4** dst, const std::vector<float>& v, size_t min_floats) -> hipError_t {
-        hipError_t e = s.own(dst, std::max(v.size(), min_floats) * 4);
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpy(*dst, v.data(), v.size() * 4, hipMemcpyHostToDevice);
-    };
-    HIPCHK(up(&s.d_nodes, dnodes, 8));
-    HIPCHK(up(&s.d_prims, dprims, 12));
-    HIPCHK(up(&s.d_mats, mat_table, 8));
-    HIPCHK(up(&s.d_acc_nodes, acc_nodes, MPT_ACCEL_NODE_FLOATS));
-    HIPCHK(up(&s.d_refleaf, refleaf, 8));
-    HIPCHK(up(&s.d_always, always, 20));
-    s.n_nodes = ND;
-    s.n_prims = (uint32_t)(dprims.size() / 12);
-    s.n_mats = (uint32_t)(mat_table.size() / 8);
-    s.n_acc_nodes = (uint32_t)(acc_nodes.size() / MPT_ACCEL_NODE_FLOATS);
-    s.n_always = (uint32_t)(always.size() / 20);
-    s.n_ref_leaves = (uint32_t)(refleaf.size() / 8);
+    const struct {
+        float4** dst;
+        uint32_t* count;
+        const std::vector<float>& v;
+        size_t rec_floats;   // floats per record; an empty array still gets an allocation of one record
+    } arrays[6] = {{&s.d_nodes, &s.n_nodes, lay.nodes, 8},
+                   {&s.d_prims, &s.n_prims, lay.prims, 12},
+                   {&s.d_mats, &s.n_mats, lay.mats, 8},
+                   {&s.d_acc_nodes, &s.n_acc_nodes, lay.acc_nodes, MPT_ACCEL_NODE_FLOATS},
+                   {&s.d_refleaf, &s.n_ref_leaves, lay.refleaf, 8},
+                   {&s.d_always, &s.n_always, lay.always, 20}};
+    for (const auto& a : arrays) {
+        HIPCHK(s.own(a.dst, std::max(a.v.size(), a.rec_floats) * 4));
+        if (!a.v.empty()) HIPCHK(hipMemcpy(*a.dst, a.v.data(), a.v.size() * 4, hipMemcpyHostToDevice));
+        *a.count = (uint32_t)(a.v.size() / a.rec_floats);
+    }
     {
         int rrc = make_prim_refbox(ctx, s);
         if (rrc) return rrc;
     }
-    s.acc_depth = topo.depth;
-    s.tri_extent = tri_extent;
-    s.acc_ok = nested && use_always;
-    s.acc_why = !nested ? "a child box is not inside its parent's box" : !use_always ? "more than 16 spheres" : "";
+    s.acc_depth = lay.acc_depth;
+    s.tri_extent = lay.tri_extent;
+    s.acc_ok = lay.acc_ok();
+    s.acc_why = lay.acc_why();
     install_scene(ctx, std::move(s));
     return MPT_OK;
 }
@@ -1327,28 +1003,32 @@ static hipError_t next_event(Lane& L, hipEvent_t* e) {
     return hipSuccess;
 }
 
-// Runs one pass of S samples/pixel over this rank's tiles (or the override's); leaves the per-path results in d_slots.
-static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t sample_begin, uint32_t S, PassParams& pp,
-                    uint32_t& n_local_tiles, bool time_kernels, const TileOverride* ovr = nullptr) {
-    const uint32_t tiles_x = (ctx->W + 7) / 8;
-    const uint32_t nr = (uint32_t)p->shard_count, rk = (uint32_t)p->shard_rank;
-    const int tile_mode = tile_order_of(ctx, p);
-    {
-        int trc = ensure_tile_order(ctx, rk, nr, tile_mode, n_local_tiles);
-        if (trc) return trc;
-    }
-    if (ovr) n_local_tiles = ovr->n;
-    const uint64_t pass_paths = (uint64_t)n_local_tiles * S * 64ull;
-    if (pass_paths >= pass_path_limit(p->pipeline)) return fail(ctx, MPT_ERR_INVALID_ARG, "pass too large (internal)");
+// ---- one pass, step by step (run_pass below drives them in this order) ---------------------------------------------------------------
+// What a pass launches: decided by select_trace_kernel and launch_geometry, used by the two launch functions.
+struct PassLaunch {
+    int pipeline = 0;                 // resolved (resolve_pipeline)
+    const TraceKernel* k = nullptr;
+    bool corun = false;               // the variant of the wave-local kernel that leaves room for a resolve: the pass may overlap the one before
+    int ot_point = 0;                 // closest-first pipeline: its operating point (ordered_point)
+    int wg = 0, grid = 0;
+    size_t lds = 0;
+    AccelDev accel = {};              // closest-first pipeline only
+    WlLean lean_args = {0u, 0u, 0u};  // lean kernels only
+};
+
+// The result slots one iteration of the wavefront pipeline retires, in items of 64 (the other pipelines size k_begin_pass's cursors by it)
+static uint32_t pass_slots(const mpt_render_params* p, uint64_t pass_paths) {
     uint32_t slots = p->slots_per_iter ? p->slots_per_iter : (16u << 20);
     uint32_t slots_items = std::max<uint32_t>(64, (slots + 63) / 64);
     if ((uint64_t)slots_items * 64 > pass_paths + 64) slots_items = (uint32_t)((pass_paths + 63) / 64);
     if (slots_items < 8) slots_items = 8;
-    int rc = ensure_workspace(ctx, L, slots_items, std::max<uint64_t>(pass_paths, 64), p->pipeline == MPT_PIPE_WAVEFRONT);
-    if (rc) return rc;
-    if (p->rng_mode == MPT_RNG_LITERAL && (rc = ensure_pixel_seeds(ctx))) return rc;
+    return slots_items;
+}
 
-    const int pipeline = resolve_pipeline(ctx, p->pipeline, p->rng_mode);
+// The kernels' view of the pass: scene, the lane's buffers, camera, tile walk, sample range and shading parameters.
+static int fill_pass_params(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t sample_begin, uint32_t S, int tile_mode,
+                            const TileOverride* ovr, PassParams& pp) {
+    const uint32_t tiles_x = (ctx->W + 7) / 8;
     pp.scene = scene_dev(ctx);
     for (int i = 0; i < 2; ++i) pp.q[i] = QueueDev{L.q_od[i].get(), L.q_dt[i].get(), L.q_tl[i].get(), L.q_ia[i].get()};
     pp.shard_cap = L.shard_cap;
@@ -1370,8 +1050,8 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     pp.s_shift = (S & (S - 1)) == 0 ? (uint32_t)__builtin_ctz(S) : 0xFFu;
     pp.tile_xy = ovr ? ovr->tiles : ctx->d_tile_xy.get();
     pp.sample_begin = sample_begin;
-    pp.rank = rk;
-    pp.nranks = nr;
+    pp.rank = (uint32_t)p->shard_rank;
+    pp.nranks = (uint32_t)p->shard_count;
     {   // path -> pixel by arithmetic when the tiles are walked in row-major order: T / tiles_x = umulhi(T, ceil(2^32 / tiles_x)) is exact
         // while T * tiles_x < 2^32 (error term T * (tiles_x - 1) / (tiles_x * 2^32) < 1 / tiles_x); otherwise the table
         const uint64_t tiles = (uint64_t)tiles_x * ((ctx->H + 7) / 8);
@@ -1388,63 +1068,70 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     uint32_t* dev_done = nullptr;
     HIPCHK(hipHostGetDevicePointer((void**)&dev_done, L.h_done.get(), 0));
     pp.host_done = dev_done;
+    return MPT_OK;
+}
 
-    if (pass_paths == 0) return MPT_OK;
-    // test mode: poison the per-path result slots so that a path that is lost shows up as NaN in the image
-    if (count_flag(p)) HIPCHK(hipMemsetAsync(L.d_slots.get(), 0xFF, pass_paths * 16, L.stream.get()));
-
-    size_t lds = (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA;
-    int per_cu = 0;
-    const bool all_lds = ctx->n_lds_nodes == ctx->n_nodes;
-    // a render that overlaps others (mpt_render_async) runs the variant of the wave-local kernel that leaves room on the CU for the
-    // resolve of the render before it (k_wavelocal_corun); only then may the end of one pass overlap the start of the next (below)
-    const bool corun = (ctx->lane_order & 4) && !ctx->sync_render && pipeline == MPT_PIPE_WAVELOCAL && !count_flag(p);
-    const int ot_point = pipeline == MPT_PIPE_ORDERED ? ordered_point(ctx, count_flag(p)) : 0;
-    // Philox + Lambert without counters, inside the ranges of the lean kernels' 24-bit index arithmetic: the lean variant of the same kernel
-    WlLean lean_args = {0u, 0u, 0u};
-    const bool lean = pipeline == MPT_PIPE_WAVELOCAL && ctx->wl_lean &&
-                      wl_lean_ok(ctx->n_prims, n_local_tiles, tiles_x, ctx->W, ctx->H, nr, S, pp.tile_magic, p->rng_mode, p->bsdf_mode, count_flag(p), &lean_args) &&
-                      lean_cdiv_ok(ctx->lean_cdiv, pp.W, pp.H, [&](float W, float H, uint32_t* bad) { return lean_cdiv_device_check(ctx, L.stream.get(), W, H, bad); });
-    const void* kfun = pipeline == MPT_PIPE_MEGAKERNEL ? mega_kernel(count_flag(p), all_lds)
-                       : pipeline == MPT_PIPE_WAVELOCAL ? wavelocal_kernel(count_flag(p), all_lds, corun, lean)
-                       : pipeline == MPT_PIPE_ORDERED  ? ordered_kernel(count_flag(p), ctx->ot_pt[ot_point].lds_nodes == ctx->n_acc_nodes, ot_point == 1)
-                                                        : step_kernel(count_flag(p), all_lds);
-    // workgroup size = the kernel's launch bound (mpt_kernels.h: 768 for the wave-local kernel; mpt_ordered.h: 256 or 768 by operating point)
-    const int wg_max = pipeline == MPT_PIPE_WAVELOCAL ? MPT_WL_THREADS(all_lds) : pipeline == MPT_PIPE_ORDERED ? (int)ctx->ot_pt[ot_point].threads : 1024;
-    const int wg = pipeline == MPT_PIPE_ORDERED ? wg_max : ctx->wg_size > 0 && ctx->wg_size <= wg_max ? ctx->wg_size : wg_max;
-    AccelDev accel = {};
-    if (pipeline == MPT_PIPE_ORDERED) {
-        lds = ordered_views(ctx, ot_point, ctx->ot_stack_depth, pp.scene, accel);
-        if (!ordered_layout_ok(pp.scene, accel, (uint32_t)wg, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+// Which kernel of the table runs the pass, and at what workgroup size.
+static int select_trace_kernel(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t n_local_tiles, const PassParams& pp, PassLaunch& g) {
+    const bool count = count_flag(p);
+    bool all_lds = ctx->n_lds_nodes == ctx->n_nodes;
+    int variant = TK_PLAIN;
+    if (g.pipeline == MPT_PIPE_WAVELOCAL) {
+        // a render that overlaps others (mpt_render_async) runs the variant of the wave-local kernel that leaves room on the CU for the
+        // resolve of the render before it (k_wavelocal_corun); only then may the end of one pass overlap the start of the next (order_behind_previous_trace)
+        g.corun = (ctx->lane_order & 4) && !ctx->sync_render && !count;
+        // Philox + Lambert without counters, inside the ranges of the lean kernels' 24-bit index arithmetic: the lean variant of the same kernel
+        const bool lean = ctx->wl_lean &&
+                          wl_lean_ok(ctx->n_prims, n_local_tiles, pp.tiles_x, ctx->W, ctx->H, pp.nranks, pp.S, pp.tile_magic, p->rng_mode, p->bsdf_mode, count, &g.lean_args) &&
+                          lean_cdiv_ok(ctx->lean_cdiv, pp.W, pp.H, [&](float W, float H, uint32_t* bad) { return lean_cdiv_device_check(ctx, L.stream.get(), W, H, bad); });
+        variant = (g.corun ? TK_CORUN : 0) | (lean ? TK_LEAN : 0);
+    } else if (g.pipeline == MPT_PIPE_ORDERED) {
+        g.ot_point = ordered_point(ctx, count);
+        all_lds = ctx->ot_pt[g.ot_point].lds_nodes == ctx->n_acc_nodes;
+        variant = g.ot_point == 1 ? TK_SIX : TK_PLAIN;
     }
-    if (ctx->occ_fun == kfun && ctx->occ_lds == lds) {
+    g.k = trace_kernel(g.pipeline, count, all_lds, variant);
+    if (!g.k) return fail(ctx, MPT_ERR_INVALID_ARG, "no trace kernel for this pass (internal)");
+    g.wg = g.pipeline != MPT_PIPE_ORDERED && ctx->wg_size > 0 && ctx->wg_size <= g.k->wg_max ? ctx->wg_size : g.k->wg_max;
+    return MPT_OK;
+}
+
+// LDS bytes per workgroup, workgroups per CU (the occupancy query is cached by kernel and LDS size) and the grid.  For the closest-first
+// kernel this also makes its views of the scene (pp.scene, g.accel) and checks that the regions of its LDS image do not overlap.
+static int launch_geometry(mpt_ctx* ctx, PassParams& pp, PassLaunch& g) {
+    g.lds = (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA;
+    if (g.pipeline == MPT_PIPE_ORDERED) {
+        g.lds = ordered_views(ctx, g.ot_point, ctx->ot_stack_depth, pp.scene, g.accel);
+        if (!ordered_layout_ok(pp.scene, g.accel, (uint32_t)g.wg, g.lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+    }
+    int per_cu = 0;
+    if (ctx->occ_fun == g.k->fn && ctx->occ_lds == g.lds) {
         per_cu = ctx->occ_per_cu;
     } else {
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfun, wg, lds));
-        ctx->occ_fun = kfun;
-        ctx->occ_lds = lds;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, g.k->fn, g.wg, g.lds));
+        ctx->occ_fun = g.k->fn;
+        ctx->occ_lds = g.lds;
         ctx->occ_per_cu = per_cu;
     }
     if (per_cu < 1) return fail(ctx, MPT_ERR_HIP, "kernel does not fit on a CU");
-    if (getenv("MPT_DEBUG_LAUNCH")) {
-        const char* kname = pipeline == MPT_PIPE_MEGAKERNEL ? "k_megakernel" : pipeline == MPT_PIPE_ORDERED ? "k_ordered" : pipeline != MPT_PIPE_WAVELOCAL ? "k_step"
-                            : lean ? (corun ? "k_wavelocal_lean_corun" : "k_wavelocal_lean") : (corun ? "k_wavelocal_corun" : "k_wavelocal");
-        fprintf(stderr, "[mpt] pipeline %d: %d workgroups of %d per CU, %zu B of LDS each, kernel %s\n", pipeline, per_cu, wg, lds, kname);
-    }
+    if (getenv("MPT_DEBUG_LAUNCH"))
+        fprintf(stderr, "[mpt] pipeline %d: %d workgroups of %d per CU, %zu B of LDS each, kernel %s\n", g.pipeline, per_cu, g.wg, g.lds, g.k->name);
     if (ctx->wgs_per_cu > 0 && per_cu > ctx->wgs_per_cu) per_cu = ctx->wgs_per_cu;
-    const int grid = ctx->prop.multiProcessorCount * per_cu;
-    hipStream_t st = L.stream.get();
-    *L.h_done.get() = 0;
-    // Trace kernels are persistent and sized for the whole chip: two of them must never be DISPATCHED side by side (each would hold
-    // half of the workgroup slots for its whole life — measured: 21.7 ms per 256-spp step instead of 16.8), and which of two pending
-    // launches the hardware starts is not ours to choose.  Two ways to keep them apart:
-    //  * the chain: a trace kernel waits for the event behind the one enqueued before it, on whichever lane — strictly one after the
-    //    other; what the second lane overlaps is the resolve of the render before, the statistics copy, the host;
-    //  * the gate (renders of k_wavelocal_corun): this launch is SUBMITTED only once the trace kernel before it has announced that
-    //    all its workgroups are resident (announce_resident; the host waits here, at most for the render that is running) — from then
-    //    on this kernel's workgroups can only take the places the others give up as they finish: the end of one pass overlaps the
-    //    start of the next, and the resolve runs in the room the variant leaves.  Without the announcement within 200 ms (a kernel
-    //    that does not announce, a foreign kernel holding the chip): the chain.
+    g.grid = ctx->prop.multiProcessorCount * per_cu;
+    return MPT_OK;
+}
+
+// Trace kernels are persistent and sized for the whole chip: two of them must never be DISPATCHED side by side (each would hold
+// half of the workgroup slots for its whole life — measured: 21.7 ms per 256-spp step instead of 16.8), and which of two pending
+// launches the hardware starts is not ours to choose.  Two ways to keep them apart:
+//  * the chain: a trace kernel waits for the event behind the one enqueued before it, on whichever lane — strictly one after the
+//    other; what the second lane overlaps is the resolve of the render before, the statistics copy, the host;
+//  * the gate (renders of k_wavelocal_corun): this launch is SUBMITTED only once the trace kernel before it has announced that
+//    all its workgroups are resident (announce_resident; the host waits here, at most for the render that is running) — from then
+//    on this kernel's workgroups can only take the places the others give up as they finish: the end of one pass overlaps the
+//    start of the next, and the resolve runs in the room the variant leaves.  Without the announcement within 200 ms (a kernel
+//    that does not announce, a foreign kernel holding the chip): the chain.
+static int order_behind_previous_trace(mpt_ctx* ctx, Lane& L, bool corun) {
     bool need_chain = (ctx->lane_order & 1) != 0;
     if (corun && ctx->last_trace_lane && ctx->last_trace_lane != &L) {
         Lane& O = *ctx->last_trace_lane;
@@ -1464,71 +1151,80 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         }
         need_chain = !resident;
     }
-    if (need_chain && ctx->last_traced && ctx->last_traced != L.ev_traced.get()) HIPCHK(hipStreamWaitEvent(st, ctx->last_traced, 0));
-    pp.launch_id = 0u;
-    if (pipeline == MPT_PIPE_WAVELOCAL || pipeline == MPT_PIPE_ORDERED) {
-        if (++ctx->launch_seq == 0u) ctx->launch_seq = 1u;
-        pp.launch_id = ctx->launch_seq;
+    if (need_chain && ctx->last_traced && ctx->last_traced != L.ev_traced.get()) HIPCHK(hipStreamWaitEvent(L.stream.get(), ctx->last_traced, 0));
+    return MPT_OK;
+}
+
+// A lane's ring allocation, grown to `waves` waves (never shrunk): waves * per_wave records of 16 bytes in each of `arrays` arrays, and
+// `extra` bytes behind them.  The records are indexed with 31 bits.
+template <class Rings>
+static int grow_rings(mpt_ctx* ctx, DevMem<float4>& mem, Rings& ring, size_t& ring_waves, size_t waves, size_t per_wave, size_t arrays, size_t extra) {
+    if (waves <= ring_waves) return MPT_OK;
+    ring = Rings{};
+    ring_waves = 0;
+    const size_t n = waves * per_wave;
+    if (n >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "too many waves for the ring index (internal)");
+    HIPCHK(mem.alloc(arrays * n * 16 + extra));
+    ring = Rings{mem.get(), (uint32_t)n};
+    ring_waves = waves;
+    return MPT_OK;
+}
+// The rings of the pass's pipeline: the wave-local kernels' five arrays + room for the MPT_DEBUG_WAVE_TIMES records, or the closest-first kernel's
+static int ensure_rings(mpt_ctx* ctx, Lane& L, int pipeline, size_t waves) {
+    if (pipeline == MPT_PIPE_WAVELOCAL)
+        return grow_rings(ctx, L.ring_mem, L.ring, L.ring_waves, waves, (size_t)MPT_WL_LEVELS * MPT_WL_RING, 5, waves * 128 + 1024);
+    return grow_rings(ctx, L.ot_ring_mem, L.ot_ring, L.ot_ring_waves, waves, (size_t)MPT_OT_RINGS * MPT_WL_RING, MPT_OT_RING_ARRAYS, 0);
+}
+
+// One launch of the pass's kernel — when kernels are timed, between two events of the lane's pool, which go to `timed` (they are read
+// after the ONE sync of mpt_render / mpt_draw).
+static int launch_timed(mpt_ctx* ctx, Lane& L, const PassLaunch& g, void** args, bool time_kernels, std::vector<std::pair<hipEvent_t, hipEvent_t>>& timed) {
+    hipStream_t st = L.stream.get();
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (time_kernels) {
+        HIPCHK(next_event(L, &e0));
+        HIPCHK(next_event(L, &e1));
+        HIPCHK(hipEventRecord(e0, st));
     }
-    L.announced_id = pp.launch_id;
-    hipLaunchKernelGGL(k_begin_pass, dim3(1), dim3(64), 0, st, L.d_desc.get(), L.d_ctr.get(), (uint32_t)pass_paths, slots_items,
-                       (volatile uint32_t*)dev_done, pipeline == MPT_PIPE_WAVEFRONT ? 0 : 1);
-    if (pipeline != MPT_PIPE_WAVEFRONT) {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (time_kernels) {  // events from the lane's pool; they are read after the ONE sync of mpt_render / mpt_draw
-            HIPCHK(next_event(L, &e0));
-            HIPCHK(next_event(L, &e1));
-            HIPCHK(hipEventRecord(e0, st));
-        }
-        if (pipeline == MPT_PIPE_WAVELOCAL || pipeline == MPT_PIPE_ORDERED) {
-            const size_t waves = (size_t)grid * (wg / 64);
-            if (pipeline == MPT_PIPE_WAVELOCAL && waves > L.ring_waves) {
-                L.ring = WaveRings{};
-                L.ring_waves = 0;
-                const size_t n = waves * MPT_WL_LEVELS * MPT_WL_RING;
-                if (n >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "too many waves for the ring index (internal)");
-                HIPCHK(L.ring_mem.alloc(5 * n * 16 + waves * 128 + 1024));  // five arrays + room for the MPT_DEBUG_WAVE_TIMES records
-                L.ring = WaveRings{L.ring_mem.get(), (uint32_t)n};
-                L.ring_waves = waves;
-            }
-            uint32_t wl_block = ctx->wl_block, wl_min = ctx->wl_min, wl_div = ctx->wl_div;
-            if (wl_min == 0u) {   // (a wave's share of the pass / 16 Ki path ids, in steps of 64, between 64 and 256)
-                const uint64_t share = pass_paths / std::max<size_t>(1, waves);
-                wl_min = 64u * (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, share >> 14));
-            }
-            if (pipeline == MPT_PIPE_ORDERED) {
-                if (waves > L.ot_ring_waves) {
-                    L.ot_ring = OtRings{};
-                    L.ot_ring_waves = 0;
-                    const size_t n = waves * MPT_OT_RINGS * MPT_WL_RING;
-                    if (n >= (1ull << 31)) return fail(ctx, MPT_ERR_INVALID_ARG, "too many waves for the ring index (internal)");
-                    HIPCHK(L.ot_ring_mem.alloc(MPT_OT_RING_ARRAYS * n * 16));
-                    L.ot_ring = OtRings{L.ot_ring_mem.get(), (uint32_t)n};
-                    L.ot_ring_waves = waves;
-                }
-                void* args[] = {(void*)&pp, (void*)&accel, (void*)&L.ot_ring, (void*)&ctx->ot_budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div};
-                HIPCHK(hipLaunchKernel(kfun, dim3(grid), dim3(wg), args, lds, st));
-            } else {
-                void* args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div, (void*)&lean_args};   // (the last: lean kernels only)
-                HIPCHK(hipLaunchKernel(kfun, dim3(grid), dim3(wg), args, lds, st));
-            }
-        } else {
-            void* args[] = {(void*)&pp};
-            HIPCHK(hipLaunchKernel(kfun, dim3(grid), dim3(wg), args, lds, st));
-        }
-        if (time_kernels) {
-            HIPCHK(hipEventRecord(e1, st));
-            L.pending_timed.emplace_back(e0, e1);
-        }
-        if (ctx->lane_order & 5) {   // (always, unless MPT_LANE_ORDER=0)
-            HIPCHK(hipEventRecord(L.ev_traced.get(), st));
-            ctx->last_traced = L.ev_traced.get();
-            ctx->last_trace_lane = &L;
-        }
-        ctx->stats.iterations += 1;
-        return MPT_OK;
+    HIPCHK(hipLaunchKernel(g.k->fn, dim3(g.grid), dim3(g.wg), args, g.lds, st));
+    if (time_kernels) {
+        HIPCHK(hipEventRecord(e1, st));
+        timed.emplace_back(e0, e1);
     }
-    // wavefront: enqueue iterations in batches; the device publishes `done` to pinned host memory
+    return MPT_OK;
+}
+
+// Megakernel, wave-local and closest-first pipelines: ONE launch for the whole pass; nothing is waited for.
+static int launch_persistent(mpt_ctx* ctx, Lane& L, PassLaunch& g, PassParams& pp, uint64_t pass_paths, bool time_kernels) {
+    int rc;
+    if (g.pipeline == MPT_PIPE_MEGAKERNEL) {
+        void* args[] = {(void*)&pp};
+        if ((rc = launch_timed(ctx, L, g, args, time_kernels, L.pending_timed))) return rc;
+    } else {
+        const size_t waves = (size_t)g.grid * (g.wg / 64);
+        if ((rc = ensure_rings(ctx, L, g.pipeline, waves))) return rc;
+        uint32_t wl_block = ctx->wl_block, wl_min = ctx->wl_min, wl_div = ctx->wl_div;
+        if (wl_min == 0u) {   // (a wave's share of the pass / 16 Ki path ids, in steps of 64, between 64 and 256)
+            const uint64_t share = pass_paths / std::max<size_t>(1, waves);
+            wl_min = 64u * (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, share >> 14));
+        }
+        void* ordered_args[] = {(void*)&pp, (void*)&g.accel, (void*)&L.ot_ring, (void*)&ctx->ot_budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div};
+        void* wavelocal_args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div, (void*)&g.lean_args};   // (the last: lean kernels only)
+        if ((rc = launch_timed(ctx, L, g, g.pipeline == MPT_PIPE_ORDERED ? ordered_args : wavelocal_args, time_kernels, L.pending_timed))) return rc;
+    }
+    if (ctx->lane_order & 5) {   // (always, unless MPT_LANE_ORDER=0)
+        HIPCHK(hipEventRecord(L.ev_traced.get(), L.stream.get()));
+        ctx->last_traced = L.ev_traced.get();
+        ctx->last_trace_lane = &L;
+    }
+    ctx->stats.iterations += 1;
+    return MPT_OK;
+}
+
+// Wavefront pipeline: k_step + k_advance per bounce generation, enqueued in batches; the device publishes `done` to pinned host memory.
+// Waits for the pass and reads its statistics back.
+static int launch_wavefront(mpt_ctx* ctx, Lane& L, const PassLaunch& g, PassParams& pp, int max_depth, uint64_t pass_paths, uint32_t slots_items, bool time_kernels) {
+    hipStream_t st = L.stream.get();
     std::vector<std::pair<hipEvent_t, hipEvent_t>> timed;
     uint32_t parity = 0;
     uint64_t launched = 0;
@@ -1536,26 +1232,15 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     // 1.7 rays per path here, and the queue drains over at most max_depth further iterations.  All of them
     // are enqueued without a host round trip (an iteration that finds no work exits at once); the device
     // publishes `done` to pinned host memory and the host only tops up if the estimate was short.
-    const uint64_t est = (pass_paths * 7 / 4) / ((uint64_t)slots_items * 64) + (uint64_t)p->max_depth + 2;
+    const uint64_t est = (pass_paths * 7 / 4) / ((uint64_t)slots_items * 64) + (uint64_t)max_depth + 2;
     const uint64_t hard_cap = est * 8 + 64;
     uint64_t batch = est;
     for (;;) {
         for (uint64_t b = 0; b < batch; ++b) {
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (time_kernels) {
-                HIPCHK(next_event(L, &e0));
-                HIPCHK(next_event(L, &e1));
-                HIPCHK(hipEventRecord(e0, st));
-            }
-            {
-                void* args[] = {(void*)&pp, (void*)&parity};
-                HIPCHK(hipLaunchKernel(kfun, dim3(grid), dim3(wg), args, lds, st));
-            }
-            if (time_kernels) {
-                HIPCHK(hipEventRecord(e1, st));
-                timed.emplace_back(e0, e1);
-            }
-            hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, L.d_desc.get(), L.d_ctr.get(), (volatile uint32_t*)dev_done);
+            void* args[] = {(void*)&pp, (void*)&parity};
+            const int rc = launch_timed(ctx, L, g, args, time_kernels, timed);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, st, L.d_desc.get(), L.d_ctr.get(), pp.host_done);
             parity ^= 1u;
             launched++;
         }
@@ -1567,21 +1252,55 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
         if (launched > hard_cap) return fail(ctx, MPT_ERR_HIP, "pass did not drain (internal)");
         batch = 4;
     }
-    {
-        PassDesc hd;
-        HIPCHK(hipMemcpy(&hd, L.d_desc.get(), sizeof hd, hipMemcpyDeviceToHost));
-        // only the iterations that had work count as launches of the dominant kernel
-        const uint64_t real = hd.iterations;
-        for (size_t i = 0; i < timed.size() && i < real; ++i) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, timed[i].first, timed[i].second));
-            ctx->stats.trace_kernel_ms += ms;
-            if (getenv("MPT_DEBUG_ITERS")) fprintf(stderr, "[mpt] iter %zu: %.3f ms\n", i, ms);
-        }
-        if (time_kernels) ctx->stats.trace_launches += real;
-        ctx->stats.iterations += real;
+    PassDesc hd;
+    HIPCHK(hipMemcpy(&hd, L.d_desc.get(), sizeof hd, hipMemcpyDeviceToHost));
+    // only the iterations that had work count as launches of the dominant kernel
+    const uint64_t real = hd.iterations;
+    for (size_t i = 0; i < timed.size() && i < real; ++i) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, timed[i].first, timed[i].second));
+        ctx->stats.trace_kernel_ms += ms;
+        if (getenv("MPT_DEBUG_ITERS")) fprintf(stderr, "[mpt] iter %zu: %.3f ms\n", i, ms);
     }
+    if (time_kernels) ctx->stats.trace_launches += real;
+    ctx->stats.iterations += real;
     return MPT_OK;
+}
+
+// Runs one pass of S samples/pixel over this rank's tiles (or the override's); leaves the per-path results in d_slots.
+static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t sample_begin, uint32_t S, PassParams& pp,
+                    uint32_t& n_local_tiles, bool time_kernels, const TileOverride* ovr = nullptr) {
+    const int tile_mode = tile_order_of(ctx, p);
+    int rc = ensure_tile_order(ctx, (uint32_t)p->shard_rank, (uint32_t)p->shard_count, tile_mode, n_local_tiles);
+    if (rc) return rc;
+    if (ovr) n_local_tiles = ovr->n;
+    const uint64_t pass_paths = (uint64_t)n_local_tiles * S * 64ull;
+    if (pass_paths >= pass_path_limit(p->pipeline)) return fail(ctx, MPT_ERR_INVALID_ARG, "pass too large (internal)");
+    const uint32_t slots_items = pass_slots(p, pass_paths);
+    if ((rc = ensure_workspace(ctx, L, slots_items, std::max<uint64_t>(pass_paths, 64), p->pipeline == MPT_PIPE_WAVEFRONT))) return rc;
+    if (p->rng_mode == MPT_RNG_LITERAL && (rc = ensure_pixel_seeds(ctx))) return rc;
+    if ((rc = fill_pass_params(ctx, L, p, sample_begin, S, tile_mode, ovr, pp))) return rc;
+    if (pass_paths == 0) return MPT_OK;
+    // test mode: poison the per-path result slots so that a path that is lost shows up as NaN in the image
+    if (count_flag(p)) HIPCHK(hipMemsetAsync(L.d_slots.get(), 0xFF, pass_paths * 16, L.stream.get()));
+
+    PassLaunch g;
+    g.pipeline = resolve_pipeline(ctx, p->pipeline, p->rng_mode);
+    if ((rc = select_trace_kernel(ctx, L, p, n_local_tiles, pp, g))) return rc;
+    if ((rc = launch_geometry(ctx, pp, g))) return rc;
+
+    *L.h_done.get() = 0;
+    if ((rc = order_behind_previous_trace(ctx, L, g.corun))) return rc;
+    pp.launch_id = 0u;
+    if (g.pipeline == MPT_PIPE_WAVELOCAL || g.pipeline == MPT_PIPE_ORDERED) {
+        if (++ctx->launch_seq == 0u) ctx->launch_seq = 1u;
+        pp.launch_id = ctx->launch_seq;
+    }
+    L.announced_id = pp.launch_id;
+    hipLaunchKernelGGL(k_begin_pass, dim3(1), dim3(64), 0, L.stream.get(), L.d_desc.get(), L.d_ctr.get(), (uint32_t)pass_paths, slots_items, pp.host_done,
+                       g.pipeline == MPT_PIPE_WAVEFRONT ? 0 : 1);
+    if (g.pipeline == MPT_PIPE_WAVEFRONT) return launch_wavefront(ctx, L, g, pp, p->max_depth, pass_paths, slots_items, time_kernels);
+    return launch_persistent(ctx, L, g, pp, pass_paths, time_kernels);
 }
 
 // Statistics: the pass descriptor of a lane is copied to pinned memory behind the lane's last kernel
@@ -2646,231 +2365,7 @@ extern "C" int mpt_kat_rcp(mpt_ctx* ctx, uint64_t* out4) {
 }
 
 // ---- multi-GPU: RCCL reduce of the HDR sum (include/mpt.h) ----------------------------------------------------------
-#include <dlfcn.h>
-#include <rccl/rccl.h>
-namespace {
-struct RcclApi {
-    void* lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*CommAbort)(ncclComm_t) = nullptr;
-    ncclResult_t (*Reduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-};
-static RcclApi g_rccl;
-static const char* rccl_load() {  // nullptr = ok, else what failed
-    if (g_rccl.lib) return nullptr;
-    void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-    if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h) h = dlopen("/opt/rocm/lib/librccl.so", RTLD_NOW | RTLD_LOCAL);
-    if (!h) return "librccl.so not found";
-    RcclApi a;
-    a.lib = h;
-#define MPT_SYM(field, name)                                 \
-    *(void**)(&a.field) = dlsym(h, name);                    \
-    if (!a.field) {                                          \
-        dlclose(h);                                          \
-        return "librccl.so lacks " name;                     \
-    }
-    MPT_SYM(GetUniqueId, "ncclGetUniqueId")
-    MPT_SYM(CommInitAll, "ncclCommInitAll")
-    MPT_SYM(CommInitRank, "ncclCommInitRank")
-    MPT_SYM(CommDestroy, "ncclCommDestroy")
-    MPT_SYM(CommAbort, "ncclCommAbort")
-    MPT_SYM(Reduce, "ncclReduce")
-    MPT_SYM(GroupStart, "ncclGroupStart")
-    MPT_SYM(GroupEnd, "ncclGroupEnd")
-    MPT_SYM(GetErrorString, "ncclGetErrorString")
-#undef MPT_SYM
-    g_rccl = a;
-    return nullptr;
-}
-}  // namespace
-static_assert(sizeof(ncclUniqueId) == MPT_COMM_ID_BYTES, "MPT_COMM_ID_BYTES must match ncclUniqueId");
+#include "mpt_comm.h"
 
-struct mpt_comm {
-    std::vector<mpt_ctx*> ctxs;      // local contexts (all N in one process, or this rank's one)
-    std::vector<ncclComm_t> comms;   // one per local context; empty when nranks == 1
-    int nranks = 1, first_rank = 0;  // global size; global rank of ctxs[0]
-    bool aborted = false;            // a local failure aborted the communicators: nothing more can be reduced
-    std::string err;
-};
-
-extern "C" const char* mpt_comm_last_error(const mpt_comm* c) { return c ? c->err.c_str() : "null communicator"; }
-
-extern "C" int mpt_comm_unique_id(void* id_out) {
-    if (!id_out) return MPT_ERR_INVALID_ARG;
-    if (rccl_load()) return MPT_ERR_HIP;
-    ncclUniqueId id;
-    if (g_rccl.GetUniqueId(&id) != ncclSuccess) return MPT_ERR_HIP;
-    memcpy(id_out, &id, sizeof id);
-    return MPT_OK;
-}
-
-extern "C" int mpt_comm_create_all(mpt_ctx* const* ctxs, int n, mpt_comm** out) {
-    if (!out) return MPT_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!ctxs || n < 1) return MPT_ERR_INVALID_ARG;
-    for (int i = 0; i < n; ++i)
-        if (!ctxs[i]) return MPT_ERR_INVALID_ARG;
-    try {
-        std::unique_ptr<mpt_comm> c(new mpt_comm());
-        c->ctxs.assign(ctxs, ctxs + n);
-        c->nranks = n;
-        if (n > 1) {
-            if (const char* why = rccl_load()) return fail(ctxs[0], MPT_ERR_HIP, why);
-            std::vector<int> devs(n);
-            for (int i = 0; i < n; ++i) devs[i] = ctxs[i]->device;
-            c->comms.resize(n);
-            ncclResult_t r = g_rccl.CommInitAll(c->comms.data(), n, devs.data());
-            if (r != ncclSuccess) return fail(ctxs[0], MPT_ERR_HIP, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r));
-        }
-        *out = c.release();
-        return MPT_OK;
-    } catch (...) {
-        return MPT_ERR_HIP;
-    }
-}
-
-extern "C" int mpt_comm_create_rank(mpt_ctx* ctx, int rank, int nranks, const void* id, mpt_comm** out) {
-    if (!out) return MPT_ERR_INVALID_ARG;
-    *out = nullptr;
-    if (!ctx || nranks < 1 || rank < 0 || rank >= nranks || (nranks > 1 && !id)) return MPT_ERR_INVALID_ARG;
-    try {
-        std::unique_ptr<mpt_comm> c(new mpt_comm());
-        c->ctxs.push_back(ctx);
-        c->nranks = nranks;
-        c->first_rank = rank;
-        if (nranks > 1) {
-            if (const char* why = rccl_load()) return fail(ctx, MPT_ERR_HIP, why);
-            if (hipSetDevice(ctx->device) != hipSuccess) return fail(ctx, MPT_ERR_HIP, "hipSetDevice failed");
-            ncclUniqueId uid;
-            memcpy(&uid, id, sizeof uid);
-            c->comms.resize(1);
-            ncclResult_t r = g_rccl.CommInitRank(&c->comms[0], nranks, uid, rank);
-            if (r != ncclSuccess) return fail(ctx, MPT_ERR_HIP, std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r));
-        }
-        *out = c.release();
-        return MPT_OK;
-    } catch (...) {
-        return MPT_ERR_HIP;
-    }
-}
-
-// A rank that cannot enter the collective must not leave its peers waiting in it: the local communicators are aborted
-// (ncclCommAbort), which makes the peers' ncclReduce fail instead of hanging on their GPUs.  The job is over then — the
-// communicator cannot be used again (mpt_reduce_sum returns MPT_ERR_NOT_READY on it), the caller tears down and restarts.
-static void comm_abort(mpt_comm* c) {
-    for (ncclComm_t& k : c->comms) {
-        if (k && g_rccl.CommAbort) g_rccl.CommAbort(k);
-        k = nullptr;
-    }
-    c->aborted = true;
-}
-
-extern "C" int mpt_reduce_sum(mpt_comm* c, int root) {
-    if (!c || root < 0 || root >= c->nranks) return MPT_ERR_INVALID_ARG;
-    if (c->aborted) {
-        c->err = "communicator was aborted by an earlier failure";
-        return MPT_ERR_NOT_READY;
-    }
-    // every local context: collect the renders in flight (their resolves have then updated the HDR sum)
-    int local_rc = MPT_OK;
-    for (mpt_ctx* ctx : c->ctxs) {
-        int rc = drain_submit(ctx);
-        if (!rc) rc = wait_impl(ctx);
-        if (rc) {
-            c->err = ctx->err;
-            local_rc = rc;
-            break;
-        }
-        if (!ctx->d_sum || ctx->W != c->ctxs[0]->W || ctx->H != c->ctxs[0]->H) {
-            c->err = "contexts of a communicator must be sized alike (mpt_resize)";
-            local_rc = MPT_ERR_NOT_READY;
-            break;
-        }
-    }
-    if (local_rc) {
-        if (c->nranks > 1) comm_abort(c);
-        return local_rc;
-    }
-    if (c->nranks == 1) return MPT_OK;  // one GPU holds the whole image already
-    const size_t count = (size_t)c->ctxs[0]->W * c->ctxs[0]->H * 4;
-    ncclResult_t r = g_rccl.GroupStart();
-    if (r == ncclSuccess) {   // (GroupEnd always follows a successful GroupStart)
-        for (size_t i = 0; i < c->ctxs.size() && r == ncclSuccess; ++i) {
-            mpt_ctx* ctx = c->ctxs[i];
-            if (hipSetDevice(ctx->device) != hipSuccess) r = ncclUnhandledCudaError;
-            else r = g_rccl.Reduce(ctx->d_sum, ctx->d_sum, count, ncclFloat32, ncclSum, root, c->comms[i], ctx->stream);
-        }
-        ncclResult_t e = g_rccl.GroupEnd();
-        if (r == ncclSuccess) r = e;
-    }
-    if (r != ncclSuccess) {
-        c->err = std::string("ncclReduce: ") + g_rccl.GetErrorString(r);
-        comm_abort(c);
-        return MPT_ERR_HIP;
-    }
-    for (mpt_ctx* ctx : c->ctxs) {
-        if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            c->err = "stream synchronisation after ncclReduce failed";
-            comm_abort(c);
-            return MPT_ERR_HIP;
-        }
-    }
-    return MPT_OK;
-}
-
-extern "C" int mpt_comm_destroy(mpt_comm* c) {
-    if (!c) return MPT_ERR_INVALID_ARG;
-    for (ncclComm_t k : c->comms)
-        if (k && g_rccl.CommDestroy) g_rccl.CommDestroy(k);
-    delete c;
-    return MPT_OK;
-}
-
-#ifdef MPT_OT_TIMES
-extern "C" int mpt_debug_ot_times(unsigned long long* out40, int reset) {   // [0,24) g_ot_times, [24,40) g_ot_walk
-    hipError_t e = hipMemcpyFromSymbol(out40, HIP_SYMBOL(g_ot_times), 24 * 8);
-    if (e == hipSuccess) e = hipMemcpyFromSymbol(out40 + 24, HIP_SYMBOL(g_ot_walk), 16 * 8);
-    if (e == hipSuccess && reset) {
-        unsigned long long z[24] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_ot_times), z, sizeof z);
-        if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(g_ot_walk), z, 16 * 8);
-    }
-    return (int)e;
-}
-#endif
-
-#ifdef MPT_CLOCK_STAMP
-extern "C" int mpt_debug_clock(unsigned long long* out2, int reset) {   // sums over waves: shader cycles, 100 MHz ticks
-    hipError_t e = hipMemcpyFromSymbol(out2, HIP_SYMBOL(g_clock), 16);
-    if (e == hipSuccess && reset) {
-        unsigned long long z[2] = {};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_clock), z, 16);
-    }
-    return (int)e;
-}
-#endif
-
-#ifdef MPT_DEBUG_WAVE_TIMES
-static mpt_ctx* g_dbg_ctx = nullptr;
-extern "C" void mpt_debug_bind(mpt_ctx* ctx) { g_dbg_ctx = ctx; }
-extern "C" int mpt_debug_reset() {   // zero the diagnostics block behind lane 0's rings
-    mpt_ctx* ctx = g_dbg_ctx;
-    const Lane& L = ctx->lane[0];
-    if (!L.ring.base) return -1;
-    const size_t off = L.ring_waves * MPT_WL_LEVELS * MPT_WL_RING;
-    return (int)hipMemset((char*)L.ring.tv() + off * 16, 0, L.ring_waves * 128 + 1024);
-}
-extern "C" int mpt_debug_wave_times(unsigned long long* out, int n) {
-    mpt_ctx* ctx = g_dbg_ctx;
-    const Lane& L = ctx->lane[0];
-    const size_t off = L.ring_waves * MPT_WL_LEVELS * MPT_WL_RING;
-    return (int)hipMemcpy(out, (const char*)L.ring.tv() + off * 16, (size_t)n * 128 + 1024, hipMemcpyDeviceToHost);
-}
-#endif
+// ---- diagnostics of the instrumented builds ------------------------------------------------------------------------------------------
+#include "mpt_debug.h"

@@ -1,5 +1,5 @@
 // mpt_lean_cdiv.h — the per-context record of whether the lean wave-local kernels' division by the image's width and height is exact at
-// the context's size.  Pure host code (no HIP): mpt_hip.hip calls it in run_pass with the device check, tests/lean_math/ compiles it
+// the context's size.  Pure host code (no HIP): mpt_hip.hip calls it in select_trace_kernel (a step of run_pass) with the device check, tests/lean_math/ compiles it
 // alone with the check stubbed.
 //
 // gen_primary<true> divides the sub-pixel jitter x = k 2^-24 - 0.5 by W and H with cdiv_chain (mpt_device.h): five instructions that are

@@ -1,5 +1,5 @@
 // mpt_wl_lean.h — when the lean wave-local trace kernels (k_wavelocal_lean*, mpt_kernels.h) may run a pass, and the constants their
-// integer arithmetic needs.  Pure host code (no HIP): mpt_hip.hip calls it in run_pass, tests/wl_lean/ compiles it alone.
+// integer arithmetic needs.  Pure host code (no HIP): mpt_hip.hip calls it in select_trace_kernel (a step of run_pass), tests/wl_lean/ compiles it alone.
 //
 // The lean kernels are the step loop of k_wavelocal with the render mode decided at compile time (Philox RNG, Lambert bounce, no work
 // counters) and with every index computed by full-rate 24-bit instructions instead of 32 x 32 and 64-bit multiplies.  The instruction

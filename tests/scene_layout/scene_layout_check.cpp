@@ -1,0 +1,363 @@
+// Stand-alone check of mpt_upload_scene's host side (metalpathtracer_amd/csrc/mpt_scene_layout.h) and of the comma-list knobs
+// (mpt_env.h): hand-made trees that reach every branch of the layout, every rejection with its message, and the fill rules of the lists.
+// With arguments — `golden bvh prims mats idx` (raw files) — it lays that scene out and prints the digest of each array by
+// mpt_scene_digest's formula and the seven counts.  Built with AddressSanitizer and UndefinedBehaviorSanitizer and run by
+// tests/test_scene_layout_cpu.py; every input array is a std::vector of exactly its size, so a read past an end is reported.
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "mpt_env.h"
+#include "mpt_scene_layout.h"
+
+using mpt_layout::bits_to_int;
+using mpt_layout::int_to_bits;
+using mpt_layout::SceneLayout;
+
+static int failures = 0;
+#define CHECK(cond)                                                         \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);   \
+            ++failures;                                                     \
+        }                                                                   \
+    } while (0)
+
+// The caller's arrays in the reference's format: node = (bmin, leftFirst) (bmax, count) with count > 0 for a leaf of primitives
+// prim_idx[leftFirst ..], else left child = leftFirst and right child = -count; primitive = 12 floats with the type in [3]
+// (0 sphere: centre, radius in [4]; 1 triangle: three vertices in [0..2], [4..6], [8..10]); one material of 8 floats per primitive.
+struct Scene {
+    std::vector<float> bvh, prims, mats;
+    std::vector<int32_t> idx;
+    uint64_t N() const { return bvh.size() / 8; }
+    uint64_t P() const { return prims.size() / 12; }
+    void node(float lo, float hi, int left_first, int count) {
+        const float n[8] = {lo, lo, lo, int_to_bits(left_first), hi, hi, hi, int_to_bits(count)};
+        bvh.insert(bvh.end(), n, n + 8);
+    }
+    void prim(float type, float x) {   // a small triangle (or a sphere of radius 0.25) at (x, x, x), inside [0, 100]^3; identity index
+        const float p[12] = {x, x, x, type, type == 1.0f ? x + 0.5f : 0.25f, x, x, 0, x, x + 0.5f, x, 0};
+        prims.insert(prims.end(), p, p + 12);
+        const float m[8] = {0.5f, 0.25f, 0.125f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f};
+        mats.insert(mats.end(), m, m + 8);
+        idx.push_back((int32_t)idx.size());
+    }
+    int layout(SceneLayout& out, std::string& err) const {
+        return mpt_layout::layout_scene(bvh.data(), N(), prims.data(), mats.data(), idx.data(), P(), out, err);
+    }
+};
+// n_tri triangles then n_sph spheres in ONE leaf that is the root
+static Scene one_leaf(int n_tri, int n_sph = 0) {
+    Scene s;
+    for (int i = 0; i < n_tri; ++i) s.prim(1.0f, 1.0f + (float)i);
+    for (int i = 0; i < n_sph; ++i) s.prim(0.0f, 50.0f + (float)i);
+    s.node(0.0f, 100.0f, 0, n_tri + n_sph);
+    return s;
+}
+// root -> left leaf 1 (the first n_left primitives), right leaf 2 (the rest)
+static Scene two_leaves(int n_left, int n_right) {
+    Scene s;
+    for (int i = 0; i < n_left + n_right; ++i) s.prim(1.0f, 1.0f + (float)i);
+    s.node(0.0f, 100.0f, 1, -2);
+    s.node(0.0f, 50.0f, 0, n_left);
+    s.node(0.0f, 100.0f, n_left, n_right);
+    return s;
+}
+
+static uint32_t word(const std::vector<float>& v, size_t i) { return (uint32_t)bits_to_int(v[i]); }
+
+// what every accepted layout must satisfy: sizes, the threaded links, every primitive in exactly one leaf, material indices in range
+static void check_well_formed(const Scene& s, const SceneLayout& L, uint32_t expect_nodes) {
+    CHECK(L.nodes.size() == (size_t)expect_nodes * 8 && L.prims.size() % 12 == 0 && L.mats.size() % 8 == 0 && L.refleaf.size() % 8 == 0);
+    CHECK(L.acc_nodes.size() % MPT_ACCEL_NODE_FLOATS == 0 && L.acc_nodes.size() >= MPT_ACCEL_NODE_FLOATS && L.always.size() % 20 == 0);
+    const uint32_t ND = (uint32_t)(L.nodes.size() / 8), P = (uint32_t)(L.prims.size() / 12);
+    std::vector<int> covered(P, 0);
+    for (uint32_t i = 0; i < ND; ++i) {
+        const uint32_t a = word(L.nodes, 8 * i + 3), b = word(L.nodes, 8 * i + 7);
+        CHECK(b <= ND);
+        if (a & 0x80000000u) {   // leaf: first << 4 | count - 1
+            const uint32_t first = (a & 0x7FFFFFFFu) >> 4, count = (a & 15u) + 1u;
+            CHECK(first + count <= P);
+            for (uint32_t k = first; k < first + count && k < P; ++k) covered[k]++;
+        } else {
+            CHECK(a < ND);
+        }
+    }
+    std::multiset<int> ids;
+    for (uint32_t k = 0; k < P; ++k) {
+        CHECK(covered[k] == 1);
+        CHECK(word(L.prims, 12 * k + 7) < L.mats.size() / 8);
+        CHECK((word(L.prims, 12 * k + 3) >> 1) < L.refleaf.size() / 8);
+        ids.insert(bits_to_int(L.prims[12 * k + 11]));
+    }
+    CHECK(ids == std::multiset<int>(s.idx.begin(), s.idx.end()));   // (every test scene names each primitive once)
+}
+
+static void hand_made_trees() {
+    std::string err;
+    {   // a single-leaf root with one triangle
+        const Scene s = one_leaf(1);
+        SceneLayout L;
+        CHECK(s.layout(L, err) == MPT_OK);
+        check_well_formed(s, L, 1);
+        CHECK(word(L.nodes, 3) == 0x80000000u && word(L.nodes, 7) == 1u);   // holds primitive 0, count 1; then the end
+        CHECK(L.prims.size() == 12 && L.mats.size() == 8 && L.refleaf.size() == 8 && L.always.empty() && L.acc_nodes.size() == MPT_ACCEL_NODE_FLOATS);
+        CHECK(L.nested && L.use_always && L.acc_ok() && std::string(L.acc_why()).empty() && L.acc_depth == 1);
+        CHECK(L.tri_extent == 1.5f);
+        CHECK(L.prims[4] == 0.5f && L.prims[5] == 0.0f && L.prims[9] == 0.5f);   // edges, not vertices
+    }
+    for (int n : {16, 17, 33}) {   // the chain splits at 16; the links are k + 1
+        const Scene s = one_leaf(n);
+        SceneLayout L;
+        CHECK(s.layout(L, err) == MPT_OK);
+        const uint32_t chain = (uint32_t)(n + 15) / 16;
+        check_well_formed(s, L, chain);
+        for (uint32_t k = 0; k < chain && L.nodes.size() == (size_t)chain * 8; ++k) {
+            const uint32_t a = word(L.nodes, 8 * k + 3);
+            CHECK((a & 0x80000000u) && (a & 15u) + 1u == (k + 1 < chain ? 16u : (uint32_t)n - 16u * (chain - 1)));
+            CHECK(word(L.nodes, 8 * k + 7) == k + 1);
+        }
+        CHECK(L.refleaf.size() == 8);   // one reference leaf, however long its chain
+    }
+    {   // a primitive whose type is neither 0 nor 1: a sphere of radius NaN
+        Scene s = one_leaf(2);
+        s.prims[12 + 3] = 2.0f;
+        SceneLayout L;
+        CHECK(s.layout(L, err) == MPT_OK);
+        check_well_formed(s, L, 1);
+        CHECK(L.always.size() == 20);
+        int seen = 0;
+        for (size_t k = 0; k < L.prims.size() / 12; ++k)
+            if (bits_to_int(L.prims[12 * k + 11]) == 1) {
+                seen++;
+                CHECK((word(L.prims, 12 * k + 3) & 1u) == 0u && std::isnan(L.prims[12 * k + 4]) && word(L.prims, 12 * k + 6) == 0u);
+                CHECK(word(L.always, 5) == k && word(L.always, 6) == 0u && std::isnan(L.always[4]));
+                CHECK(L.always[12] == 0.0f && L.always[16] == 100.0f);   // the box of its reference leaf
+            }
+        CHECK(seen == 1);
+    }
+    {   // 16 spheres, then 17
+        const Scene a = one_leaf(1, 16), b = one_leaf(1, 17);
+        SceneLayout L;
+        CHECK(a.layout(L, err) == MPT_OK);
+        check_well_formed(a, L, 2);
+        CHECK(L.use_always && L.acc_ok() && L.always.size() == 16 * 20 && std::string(L.acc_why()).empty());
+        SceneLayout M;
+        CHECK(b.layout(M, err) == MPT_OK);
+        check_well_formed(b, M, 2);
+        CHECK(!M.use_always && !M.acc_ok() && M.always.empty() && std::string(M.acc_why()) == "more than 16 spheres");
+    }
+    {   // a child box poking out of its parent by one ulp
+        Scene s = two_leaves(1, 1);
+        SceneLayout L;
+        CHECK(s.layout(L, err) == MPT_OK);
+        check_well_formed(s, L, 3);
+        CHECK(L.nested && L.acc_ok());
+        CHECK(word(L.nodes, 3) == 1u && word(L.nodes, 7) == 3u);   // root: hit -> the right leaf (visited first), miss -> the end
+        s.bvh[8 * 2 + 4] = std::nextafterf(100.0f, 200.0f);
+        SceneLayout M;
+        CHECK(s.layout(M, err) == MPT_OK);
+        CHECK(!M.nested && !M.acc_ok() && std::string(M.acc_why()) == "a child box is not inside its parent's box");
+        s.bvh[8 * 2 + 4] = 100.0f;
+        s.bvh[8 * 1 + 1] = -std::nextafterf(0.0f, 1.0f);   // ... and the other child, below
+        SceneLayout M2;
+        CHECK(s.layout(M2, err) == MPT_OK);
+        CHECK(!M2.nested);
+    }
+    {   // unreachable nodes (with links that would be refused if they were read)
+        Scene s = two_leaves(2, 3);
+        s.node(0.0f, 1.0f, 77, -99);
+        s.node(0.0f, 1.0f, -5, 1000);
+        SceneLayout L;
+        CHECK(s.N() == 5 && s.layout(L, err) == MPT_OK);
+        check_well_formed(s, L, 3);
+    }
+    {   // materials: dedup is by bits, numbered by first occurrence in leaf order
+        Scene s = one_leaf(3);
+        s.mats[8 * 2 + 3] = -0.0f;
+        SceneLayout L;
+        CHECK(s.layout(L, err) == MPT_OK);
+        check_well_formed(s, L, 1);
+        CHECK(L.mats.size() == 16 && word(L.mats, 3) == 0u && word(L.mats, 8 + 3) == 0x80000000u);
+        for (size_t k = 0; k < L.prims.size() / 12; ++k) CHECK(word(L.prims, 12 * k + 7) == (bits_to_int(L.prims[12 * k + 11]) == 2 ? 1u : 0u));
+    }
+}
+
+static void refused(const Scene& s, const char* why, int line) {
+    SceneLayout L;
+    std::string err;
+    const int rc = s.layout(L, err);
+    if (rc != MPT_ERR_BAD_SCENE || err != why) {
+        std::printf("FAILED %s:%d: status %d, message \"%s\" (expected \"%s\")\n", __FILE__, line, rc, err.c_str(), why);
+        ++failures;
+    }
+}
+#define REFUSED(scene, why) refused(scene, why, __LINE__)
+
+static void rejections() {
+    const char* not_a_tree = "BVH is not a tree (cycle or index out of range)";
+    {   // a child link to an ancestor: root -> right leaf 2, left node 1 -> right leaf 3, left 0
+        Scene s = two_leaves(1, 1);
+        s.prim(1.0f, 9.0f);
+        s.node(0.0f, 50.0f, 2, 1);
+        s.bvh[8 * 1 + 3] = int_to_bits(0);
+        s.bvh[8 * 1 + 7] = int_to_bits(-3);
+        REFUSED(s, not_a_tree);
+        s.bvh[8 * 1 + 3] = int_to_bits(2);   // ... and to a node another parent already has
+        REFUSED(s, not_a_tree);
+    }
+    {
+        Scene s = two_leaves(1, 1);
+        s.bvh[7] = int_to_bits(-3);   // a child index == N
+        REFUSED(s, not_a_tree);
+        s.bvh[7] = int_to_bits(INT32_MIN);   // right child 2^31
+        REFUSED(s, not_a_tree);
+        s.bvh[7] = int_to_bits(-2);
+        s.bvh[3] = int_to_bits(3);   // the left one
+        REFUSED(s, not_a_tree);
+    }
+    {
+        Scene s = two_leaves(1, 1);
+        s.bvh[7] = int_to_bits(0);
+        REFUSED(s, "internal node with right child 0");
+    }
+    {
+        Scene s = two_leaves(1, 1);
+        s.bvh[3] = int_to_bits(-1);
+        REFUSED(s, "negative left child");
+    }
+    {
+        Scene s = two_leaves(1, 1);
+        s.bvh[8 * 2 + 3] = int_to_bits(-1);   // a leaf's first < 0
+        REFUSED(s, "leaf primitive range out of bounds");
+        s.bvh[8 * 2 + 3] = int_to_bits(1);
+        s.bvh[8 * 2 + 7] = int_to_bits(2);   // first + count == n_prims + 1
+        REFUSED(s, "leaf primitive range out of bounds");
+        s.bvh[8 * 2 + 7] = int_to_bits(INT32_MAX);
+        REFUSED(s, "leaf primitive range out of bounds");
+    }
+    for (int32_t bad : {-1, 2, INT32_MIN, INT32_MAX}) {   // prim_idx entries: -1, == n_prims, the extremes
+        Scene s = two_leaves(1, 1);
+        s.idx[1] = bad;
+        REFUSED(s, "primitive index out of range");
+    }
+    {   // several faults: the first in the reference's visit order (root, right subtree, left subtree) is the one reported
+        Scene s = two_leaves(1, 1);
+        s.bvh[8 * 1 + 3] = int_to_bits(-1);   // left leaf: bad range
+        s.idx[1] = -1;                        // right leaf: bad primitive index, found only after the whole walk
+        REFUSED(s, "leaf primitive range out of bounds");
+        s.bvh[3] = int_to_bits(-1);           // root: negative left child, met after the right leaf
+        s.bvh[8 * 2 + 7] = int_to_bits(5);    // right leaf: bad range, met first
+        REFUSED(s, "leaf primitive range out of bounds");
+        s.bvh[8 * 2 + 7] = int_to_bits(1);
+        REFUSED(s, "negative left child");
+    }
+}
+
+static bool same(const uint32_t* got, std::initializer_list<uint32_t> want) { return std::equal(want.begin(), want.end(), got); }
+
+static void list_knobs() {
+    const char* longer = "1,2,3,4,5,6";
+    uint32_t v[4];
+    // MPT_BUDGETS: missing entries are twice the one before, starting from 4; none below 1
+    fill_budgets("", v, 4);
+    CHECK(same(v, {8, 16, 32, 64}));
+    fill_budgets("7", v, 4);
+    CHECK(same(v, {7, 14, 28, 56}));
+    fill_budgets("7,", v, 4);
+    CHECK(same(v, {7, 14, 28, 56}));
+    fill_budgets("7,9,x", v, 4);
+    CHECK(same(v, {7, 9, 18, 36}));
+    fill_budgets(longer, v, 4);
+    CHECK(same(v, {1, 2, 3, 4}));
+    fill_budgets("0,0", v, 4);
+    CHECK(same(v, {1, 1, 2, 4}));
+    // MPT_MIN_ACTIVE: missing entries repeat the last one given; none above 64
+    fill_min_active("", v, 4);
+    CHECK(same(v, {0, 0, 0, 0}));
+    fill_min_active("7", v, 4);
+    CHECK(same(v, {7, 7, 7, 7}));
+    fill_min_active("7,", v, 4);
+    CHECK(same(v, {7, 7, 7, 7}));
+    fill_min_active("7,9,x", v, 4);
+    CHECK(same(v, {7, 9, 9, 9}));
+    fill_min_active(longer, v, 4);
+    CHECK(same(v, {1, 2, 3, 4}));
+    fill_min_active("100,3", v, 4);
+    CHECK(same(v, {64, 3, 3, 3}));
+    // MPT_OT_BUDGETS / MPT_OT_MIN_ACTIVE: stop at the first missing entry (the rings left out keep their defaults)
+    uint32_t guard[5] = {99, 99, 99, 99, 99};
+    CHECK(parse_uint_list("", guard, 4) == 0 && same(guard, {99, 99, 99, 99, 99}));
+    CHECK(parse_uint_list("7", guard, 4) == 1 && same(guard, {7, 99, 99, 99, 99}));
+    CHECK(parse_uint_list("7,", guard, 4) == 1 && same(guard, {7, 99, 99, 99, 99}));
+    CHECK(parse_uint_list("7,9,x", guard, 4) == 2 && same(guard, {7, 9, 99, 99, 99}));
+    CHECK(parse_uint_list(longer, guard, 4) == 4 && same(guard, {1, 2, 3, 4, 99}));
+    CHECK(parse_uint_list(longer, guard, 0) == 0);
+}
+
+template <class T>
+static std::vector<T> read_file(const char* path) {
+    std::vector<T> v;
+    if (FILE* f = std::fopen(path, "rb")) {
+        std::fseek(f, 0, SEEK_END);
+        const long bytes = std::ftell(f);
+        std::fseek(f, 0, SEEK_SET);
+        v.resize((size_t)bytes / sizeof(T));
+        if (std::fread(v.data(), sizeof(T), v.size(), f) != v.size()) v.clear();
+        std::fclose(f);
+    }
+    return v;
+}
+// mpt_scene_digest's formula (k_digest): sum over i of splitmix64(i << 32 | word[i])
+static uint64_t digest(const std::vector<float>& a) {
+    uint64_t acc = 0;
+    for (uint64_t i = 0; i < a.size(); ++i) {
+        uint64_t z = (i << 32 | word(a, i)) + 0x9E3779B97F4A7C15ull;
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        acc += z ^ (z >> 31);
+    }
+    return acc;
+}
+static int golden(char** files) {
+    Scene s;
+    s.bvh = read_file<float>(files[0]);
+    s.prims = read_file<float>(files[1]);
+    s.mats = read_file<float>(files[2]);
+    s.idx = read_file<int32_t>(files[3]);
+    SceneLayout L;
+    std::string err;
+    if (s.N() == 0 || s.P() == 0 || s.mats.size() != s.P() * 8 || s.idx.size() != s.P() || s.layout(L, err) != MPT_OK) {
+        std::printf("FAILED: %s\n", err.empty() ? "unreadable input" : err.c_str());
+        return 1;
+    }
+    const struct {
+        const char* name;
+        uint64_t v;
+    } out[] = {{"nodes", digest(L.nodes)}, {"prims", digest(L.prims)}, {"mats", digest(L.mats)}, {"own", digest(L.acc_nodes)},
+               {"refleaf", digest(L.refleaf)}, {"always", digest(L.always)}, {"n_nodes", L.nodes.size() / 8}, {"n_prims", L.prims.size() / 12},
+               {"n_mats", L.mats.size() / 8}, {"n_own", L.acc_nodes.size() / MPT_ACCEL_NODE_FLOATS}, {"n_leaves", L.refleaf.size() / 8},
+               {"n_always", L.always.size() / 20}, {"depth", L.acc_depth}};
+    for (const auto& o : out) std::printf("%s %016llx\n", o.name, (unsigned long long)o.v);
+    std::printf("acc_ok %d\n", L.acc_ok() ? 1 : 0);
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 6 && std::strcmp(argv[1], "golden") == 0) return golden(argv + 2);
+    hand_made_trees();
+    rejections();
+    list_knobs();
+    if (failures) {
+        std::printf("%d check(s) failed\n", failures);
+        return 1;
+    }
+    std::printf("all passed\n");
+    return 0;
+}

@@ -144,6 +144,24 @@ def test_device_build_writes_the_recorded_arrays(gpu_ctx, name, builder, monkeyp
             assert got == want, "%s: other arrays: %s" % (env, [n for n, a, b in zip(names, got, want) if a != b])
 
 
+@pytest.mark.parametrize("name", ["scene.xml", "cornell.xml", "glass.xml", "bunny20.xml"])
+def test_upload_writes_the_recorded_arrays(gpu_ctx, name):
+    """The other route to a scene on the device: the host layer's tree through mpt_upload_scene.  Every array it puts there has the digest
+    recorded in tests/golden/upload_digests.json by tools/gpu_scene_digest.py --upload --write at commit be3643d, the last one whose
+    mpt_upload_scene made the layout inside mpt_hip.hip (it is mpt_scene_layout.h's since; tests/test_scene_layout_cpu.py checks the six
+    host-made arrays against the same file without a GPU, the per-primitive leaf boxes are made on the device and checked only here).  A
+    second upload gives the same, and an uploaded scene has no reference-format tree on the device."""
+    import json, os
+    from conftest import ROOT, host_scene
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "upload_digests.json")))[name]
+    names = "nodes prims mats own refleaf refbox always ref_bvh ref_idx n_nodes n_prims n_mats n_own n_leaves n_always depth".split()
+    for k in range(2):
+        gpu_ctx.upload_scene(*host_scene(name)[1])
+        got = _digest(gpu_ctx)
+        assert len(got) == 16 and got == want, "upload %d: other arrays: %s" % (k, [n for n, a, b in zip(names, got, want) if a != b])
+        assert int(got[7], 16) == 0 and int(got[8], 16) == 0
+
+
 def test_device_builds_of_two_contexts_at_once_and_of_alternating_sizes_write_the_recorded_arrays():
     """The builder's pooled state under the uses a host program makes of it.  (a) Two contexts of one GPU build in two threads at the same
     time, five times each — every build has its own scratch pool, pinned words, second stream and output block, and only the epoch

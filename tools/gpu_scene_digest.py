@@ -1,5 +1,7 @@
 """Digests of every device array mpt_build_and_upload makes (mpt_scene_digest), per scene and builder — what "the same arrays" means when
-the builder's code changes.   usage: python tools/gpu_scene_digest.py [--write tests/golden/devbuild_digests.json] [--check FILE] [--time]"""
+the builder's code changes.   usage: python tools/gpu_scene_digest.py [--write tests/golden/devbuild_digests.json] [--check FILE] [--time]
+With --upload: the mpt_upload_scene route instead (host.Scene -> buildBVH() -> upload_scene -> mpt_scene_digest) for the four asset scenes,
+keyed by scene name:   python tools/gpu_scene_digest.py --upload [--write tests/golden/upload_digests.json] [--check FILE]"""
 import json, os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -17,11 +19,27 @@ def scenes(tmp):
     yield "config4", config4_scene.write(tmp)
 
 
+def upload_digests(ctx):
+    out = {}
+    for name in ("scene.xml", "cornell.xml", "glass.xml", "bunny20.xml"):
+        sc = host.Scene()
+        st, log = host.SceneLoader.LoadSceneFromXML(os.path.join(ROOT, "assets", name), sc, os.path.join(ROOT, "assets"))
+        assert st == 0, log
+        sc.buildBVH()
+        ctx.upload_scene(*sc.buffers())
+        d = ctx.scene_digest()
+        ctx.upload_scene(*sc.buffers())
+        assert ctx.scene_digest() == d, "%s: a second upload gave other arrays" % name
+        out[name] = ["%016x" % v for v in d]
+        print("%-18s upload %8d prims  %s" % (name, sc.getPrimitiveCount(), " ".join("%016x" % v for v in d[:9])), flush=True)
+    return out
+
+
 def main():
     out = {}
     tmp = tempfile.mkdtemp()
     ctx = capi.Context(0)
-    for name, xml in scenes(tmp):
+    for name, xml in scenes(tmp) if "--upload" not in sys.argv else ():
         sc = host.Scene()
         st, log = host.SceneLoader.LoadSceneFromXML(xml, sc, os.path.join(ROOT, "assets"))
         assert st == 0, log
@@ -37,6 +55,8 @@ def main():
             out["%s/%s" % (name, builder)] = ["%016x" % v for v in d]
             print("%-18s %-5s %8d prims  wall %6.2f ms  device %6.2f ms  %s" % (name, builder, int(np.asarray(prims).size) // 12, best * 1e3, ms, " ".join("%016x" % v for v in d[:9])), flush=True)
     os.environ.pop("MPT_GPU_BUILD", None)
+    if "--upload" in sys.argv:
+        out = upload_digests(ctx)
     ctx.close()
     if "--write" in sys.argv:
         json.dump(out, open(sys.argv[sys.argv.index("--write") + 1], "w"), indent=1, sort_keys=True)
