@@ -273,6 +273,15 @@ int mpt_build_info(mpt_ctx* ctx, uint64_t out[8]);
  * same input must give the same 16 words (the tests' "same arrays" check covers what mpt_download_bvh does not return).
  * No reference counterpart (the reference builds once, on the host: R/Scene/Scene.h:71-93).                                */
 int mpt_scene_digest(mpt_ctx* ctx, uint64_t out[16]);
+/* Diagnostics: one of those nine device arrays copied to the host as 32-bit words (a device-to-host copy on the context's stream,
+ * synchronised; no kernel, the scene is untouched).  which = 0..8 in the order of out[0..8] above, with the same word counts: 8 per
+ * threaded node, 12 per primitive record, 8 per material, 28 per own node, 8 per reference leaf, 8 per primitive (leaf boxes), 20 per
+ * always-list entry, 8 per reference-format node, 1 per reference-format index.  *n_words_out is always written: the array's size, 0
+ * for an array the scene does not have (the reference-format tree after mpt_upload_scene; MPT_OK) and 0 with the errors that know
+ * no size.  out = NULL with capacity_words = 0 is a size query.  MPT_ERR_NOT_READY without a scene; MPT_ERR_INVALID_ARG, with out
+ * untouched, for a bad which, a null n_words_out or a capacity below the array's size.  tests/scene_check.py checks every
+ * invariant the arrays carry.                                                                                               */
+int mpt_read_scene_array(mpt_ctx* ctx, int which, uint32_t* out, uint64_t capacity_words, uint64_t* n_words_out);
 
 /* ---- multi-GPU: tile shards + ONE RCCL reduce of the HDR sum over xGMI ---------------------------------
  * The reference is single-GPU (it presents straight to the drawable, R/Renderer/Renderer.cpp:303-307); this is the

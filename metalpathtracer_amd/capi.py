@@ -28,7 +28,7 @@ SYMBOLS = (
     "mpt_resize", "mpt_draw", "mpt_render", "mpt_render_async", "mpt_wait", "mpt_async_info", "mpt_sum_buffer", "mpt_set_sum_buffer", "mpt_clear_sum",
     "mpt_read_frame", "mpt_read_sum", "mpt_write_sum", "mpt_get_stats", "mpt_reset_stats", "mpt_stream", "mpt_synchronize",
     "mpt_trace_rays", "mpt_trace_rays_ordered", "mpt_accel_info", "mpt_kat_pcg", "mpt_kat_philox", "mpt_kat_sincos", "mpt_kat_rcp",
-    "mpt_build_bvh", "mpt_build_and_upload", "mpt_download_bvh", "mpt_gpu_leaf_max", "mpt_build_info", "mpt_scene_digest", "mpt_comm_unique_id", "mpt_comm_create_all", "mpt_comm_create_rank", "mpt_reduce_sum", "mpt_comm_destroy",
+    "mpt_build_bvh", "mpt_build_and_upload", "mpt_download_bvh", "mpt_gpu_leaf_max", "mpt_build_info", "mpt_scene_digest", "mpt_read_scene_array", "mpt_comm_unique_id", "mpt_comm_create_all", "mpt_comm_create_rank", "mpt_reduce_sum", "mpt_comm_destroy",
     "mpt_comm_last_error", "mpt_read_aovs", "mpt_denoise", "mpt_read_denoised", "mpt_denoised_buffer", "mpt_denoise_image",
     "mpt_read_moments", "mpt_render_adaptive", "mpt_read_tile_samples",
     "mpt_temporal_accumulate", "mpt_read_temporal", "mpt_temporal_buffer", "mpt_temporal_reset", "mpt_denoise_temporal",
@@ -40,6 +40,10 @@ SYMBOLS = (
     "mpt_light_info", "mpt_read_lights", "mpt_direct_lighting", "mpt_read_direct", "mpt_direct_buffer", "mpt_direct_image",
     "mpt_render_nee", "mpt_set_light_sampling", "mpt_get_light_sampling",
 )
+
+# mpt_scene_digest's words: the nine device arrays (mpt_read_scene_array's `which`), then the seven counts
+SCENE_ARRAYS = ("nodes", "prims", "mats", "own", "refleaf", "refbox", "always", "ref_bvh", "ref_idx")
+SCENE_COUNTS = ("n_nodes", "n_prims", "n_mats", "n_own", "n_leaves", "n_always", "depth")
 
 DENOISE_SUM, DENOISE_FRAME = 0, 1
 DENOISE_MAX_ITERATIONS = 8
@@ -335,6 +339,7 @@ def load():
     L.mpt_gpu_leaf_max.argtypes = [C.c_uint64]
     L.mpt_build_info.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.mpt_scene_digest.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.mpt_read_scene_array.argtypes = [vp, C.c_int, up, C.c_uint64, C.POINTER(C.c_uint64)]
     L.mpt_comm_unique_id.argtypes = [vp]
     L.mpt_comm_create_all.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
     L.mpt_comm_create_rank.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
@@ -774,6 +779,20 @@ class Context:
         out = (C.c_uint64 * 16)()
         self._chk(self.L.mpt_scene_digest(self.h, out), "mpt_scene_digest")
         return [int(v) for v in out]
+
+    def read_scene_array(self, which):
+        """mpt_read_scene_array: device array `which` (0..8, the order of SCENE_ARRAYS) as uint32 words; empty where the scene has none."""
+        n = C.c_uint64()
+        self._chk(self.L.mpt_read_scene_array(self.h, int(which), None, 0, C.byref(n)), "mpt_read_scene_array")
+        out = np.zeros(n.value, np.uint32)
+        if n.value:
+            self._chk(self.L.mpt_read_scene_array(self.h, int(which), _up(out), n.value, C.byref(n)), "mpt_read_scene_array")
+        return out
+
+    def read_scene(self):
+        """Every device array of the scene and the counts: ({name: uint32 words} over SCENE_ARRAYS, {name: int} over SCENE_COUNTS)."""
+        arrays = {name: self.read_scene_array(k) for k, name in enumerate(SCENE_ARRAYS)}
+        return arrays, dict(zip(SCENE_COUNTS, self.scene_digest()[9:]))
 
     def accel_info(self):
         out = (C.c_uint64 * 8)()

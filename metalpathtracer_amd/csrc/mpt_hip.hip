@@ -2286,17 +2286,46 @@ __global__ void k_digest(const uint32_t* w, uint64_t n_words, unsigned long long
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if ((threadIdx.x & 63u) == 0) atomicAdd(out, acc);
 }
+// The nine device arrays of the scene as 32-bit words, in the order of mpt_scene_digest's first nine words (and of mpt_read_scene_array's `which`)
+struct SceneArray {
+    const void* p;
+    uint64_t words;
+};
+static void scene_arrays(const mpt_ctx* ctx, SceneArray a[9]) {
+    const bool built = ctx->d_ref_bvh != nullptr;
+    const SceneArray v[9] = {
+        {ctx->d_nodes, (uint64_t)ctx->n_nodes * 8}, {ctx->d_prims, (uint64_t)ctx->n_prims * 12}, {ctx->d_mats, (uint64_t)ctx->n_mats * 8},
+        {ctx->d_acc_nodes, (uint64_t)ctx->n_acc_nodes * MPT_OT_NODE_STRIDE * 4}, {ctx->d_refleaf, (uint64_t)ctx->n_ref_leaves * 8},
+        {ctx->d_refbox, ctx->d_refbox ? (uint64_t)ctx->n_prims * 8 : 0u}, {ctx->d_always, (uint64_t)ctx->n_always * 20},
+        {ctx->d_ref_bvh, built ? (uint64_t)ctx->n_ref_nodes * 8 : 0u}, {ctx->d_ref_idx, built ? (uint64_t)ctx->n_prims : 0u}};
+    for (int k = 0; k < 9; ++k) a[k] = v[k];
+}
+extern "C" int mpt_read_scene_array(mpt_ctx* ctx, int which, uint32_t* out, uint64_t capacity_words, uint64_t* n_words_out) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx) return MPT_ERR_INVALID_ARG;
+        if (n_words_out) *n_words_out = 0;
+        if (!n_words_out || which < 0 || which > 8) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_read_scene_array: bad array number or null n_words_out");
+        if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
+        SceneArray a[9];
+        scene_arrays(ctx, a);
+        const uint64_t words = a[which].p ? a[which].words : 0u;
+        *n_words_out = words;
+        if (!out && capacity_words == 0) return MPT_OK;   // the size query
+        if (!out || capacity_words < words) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_read_scene_array: out is null or too small");
+        if (words == 0) return MPT_OK;
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipMemcpyAsync(out, a[which].p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MPT_OK;
+    });
+}
 extern "C" int mpt_scene_digest(mpt_ctx* ctx, uint64_t out[16]) {
     return guarded(ctx, [&]() -> int {
         if (!ctx || !out) return MPT_ERR_INVALID_ARG;
         if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
         HIPCHK(hipSetDevice(ctx->device));
-        const bool built = ctx->d_ref_bvh != nullptr;
-        struct Arr { const void* p; uint64_t words; } a[9] = {
-            {ctx->d_nodes, (uint64_t)ctx->n_nodes * 8}, {ctx->d_prims, (uint64_t)ctx->n_prims * 12}, {ctx->d_mats, (uint64_t)ctx->n_mats * 8},
-            {ctx->d_acc_nodes, (uint64_t)ctx->n_acc_nodes * MPT_OT_NODE_STRIDE * 4}, {ctx->d_refleaf, (uint64_t)ctx->n_ref_leaves * 8},
-            {ctx->d_refbox, ctx->d_refbox ? (uint64_t)ctx->n_prims * 8 : 0u}, {ctx->d_always, (uint64_t)ctx->n_always * 20},
-            {ctx->d_ref_bvh, built ? (uint64_t)ctx->n_ref_nodes * 8 : 0u}, {ctx->d_ref_idx, built ? (uint64_t)ctx->n_prims : 0u}};
+        SceneArray a[9];
+        scene_arrays(ctx, a);
         DevMem<> d;
         HIPCHK(d.alloc(16 * 8));
         HIPCHK(hipMemsetAsync(d.get(), 0, 16 * 8, ctx->stream));

@@ -1,7 +1,8 @@
 // Stand-alone check of mpt_upload_scene's host side (metalpathtracer_amd/csrc/mpt_scene_layout.h) and of the comma-list knobs
 // (mpt_env.h): hand-made trees that reach every branch of the layout, every rejection with its message, and the fill rules of the lists.
 // With arguments — `golden bvh prims mats idx` (raw files) — it lays that scene out and prints the digest of each array by
-// mpt_scene_digest's formula and the seven counts.  Built with AddressSanitizer and UndefinedBehaviorSanitizer and run by
+// mpt_scene_digest's formula and the seven counts; `dump dir bvh prims mats idx` writes the arrays themselves (tests/test_scene_check_cpu.py).
+// Built with AddressSanitizer and UndefinedBehaviorSanitizer and run by
 // tests/test_scene_layout_cpu.py; every input array is a std::vector of exactly its size, so a read past an end is reported.
 #include <cmath>
 #include <cstdint>
@@ -349,8 +350,41 @@ static int golden(char** files) {
     return 0;
 }
 
+// `dump dir bvh prims mats idx`: the six arrays of that scene's layout as raw files dir/<name> (32-bit words) and dir/counts: the seven
+// counts of mpt_scene_digest as uint64, then acc_ok — what tests/scene_check.py checks on the CPU
+static int dump(const char* dir, char** files) {
+    Scene s;
+    s.bvh = read_file<float>(files[0]);
+    s.prims = read_file<float>(files[1]);
+    s.mats = read_file<float>(files[2]);
+    s.idx = read_file<int32_t>(files[3]);
+    SceneLayout L;
+    std::string err;
+    if (s.N() == 0 || s.P() == 0 || s.mats.size() != s.P() * 8 || s.idx.size() != s.P() || s.layout(L, err) != MPT_OK) {
+        std::printf("FAILED: %s\n", err.empty() ? "unreadable input" : err.c_str());
+        return 1;
+    }
+    const struct {
+        const char* name;
+        const std::vector<float>* v;
+    } arrays[] = {{"nodes", &L.nodes}, {"prims", &L.prims}, {"mats", &L.mats}, {"own", &L.acc_nodes}, {"refleaf", &L.refleaf}, {"always", &L.always}};
+    auto write = [&](const char* name, const void* p, size_t bytes) {
+        FILE* f = std::fopen((std::string(dir) + "/" + name).c_str(), "wb");
+        const bool ok = f && (bytes == 0 || std::fwrite(p, 1, bytes, f) == bytes);   // (an empty vector's data() may be null)
+        if (f) std::fclose(f);
+        if (!ok) std::printf("FAILED: cannot write %s\n", name);
+        return ok;
+    };
+    for (const auto& a : arrays)
+        if (!write(a.name, a.v->data(), a.v->size() * 4)) return 1;
+    const uint64_t counts[8] = {L.nodes.size() / 8, L.prims.size() / 12, L.mats.size() / 8, L.acc_nodes.size() / MPT_ACCEL_NODE_FLOATS,
+                                L.refleaf.size() / 8, L.always.size() / 20, L.acc_depth, L.acc_ok() ? 1u : 0u};
+    return write("counts", counts, sizeof counts) ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
     if (argc == 6 && std::strcmp(argv[1], "golden") == 0) return golden(argv + 2);
+    if (argc == 7 && std::strcmp(argv[1], "dump") == 0) return dump(argv[2], argv + 3);
     hand_made_trees();
     rejections();
     list_knobs();

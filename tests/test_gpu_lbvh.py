@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import scene_path
+from scene_cases import BOUNDARY_CASES, boundary_scene, degenerate_scene
 from oracle import binding as ob
 
 pytestmark = pytest.mark.gpu
@@ -370,18 +371,7 @@ def test_build_and_upload_survives_degenerate_input(gpu_ctx):
     the reference-order walk on the device equals the oracle on the downloaded tree."""
     rng = np.random.default_rng(21)
     n = 257
-    prims = np.zeros((n, 12), np.float32)
-    prims[:, 3] = 1.0
-    v0 = rng.uniform(-4, 4, (n, 3))
-    prims[:, 0:3], prims[:, 4:7], prims[:, 8:11] = v0, v0 + rng.uniform(-1, 1, (n, 3)), v0 + rng.uniform(-1, 1, (n, 3))
-    prims[5, 4] = np.nan
-    prims[6, 0:3] = np.inf
-    prims[7, 8] = -np.inf
-    prims[8, 4:7] = prims[8, 0:3]                                  # zero area
-    prims[9, 4:7] = prims[9, 8:11] = prims[9, 0:3]                # a point
-    prims[0, 3], prims[0, 4:12] = 0.0, 0.0                          # a sphere of radius 0
-    mats = np.zeros((n, 8), np.float32)
-    mats[:, 0:3] = 0.5
+    prims, mats = degenerate_scene(rng, n)
     for variant in ("mixed", "identical"):
         p = prims.copy()
         if variant == "identical":
@@ -527,18 +517,8 @@ def test_builders_at_the_kernels_size_boundaries(gpu_ctx, builder, monkeypatch):
     the oracle's closest hit on the downloaded tree."""
     monkeypatch.setenv("MPT_GPU_BUILD", builder)
     rng = np.random.default_rng(23)
-    cases = [(5, 0), (8, 1), (9, 0), (17, 16), (33, 17), (257, 1), (2047, 0), (2048, 3), (2049, 16), (4100, 1), (8191, 0), (8192, 2), (8300, 17)]
-    for n, n_sph in cases:
-        prims = np.zeros((n, 12), np.float32)
-        prims[:, 3] = 1.0
-        v0 = rng.uniform(-20, 20, (n, 3))
-        prims[:, 0:3], prims[:, 4:7], prims[:, 8:11] = v0, v0 + rng.uniform(-1, 1, (n, 3)), v0 + rng.uniform(-1, 1, (n, 3))
-        prims[:n_sph, 3], prims[:n_sph, 4:12] = 0.0, 0.0
-        prims[:n_sph, 4] = rng.uniform(0.5, 3.0, n_sph)
-        if n_sph:
-            prims[0, 0:3], prims[0, 4] = (0.0, -1000.0, 0.0), 980.0     # a ground sphere far larger than the rest
-        mats = np.zeros((n, 8), np.float32)
-        mats[:, 0:3] = 0.5
+    for n, n_sph in BOUNDARY_CASES:
+        prims, mats = boundary_scene(rng, n, n_sph)
         gpu_ctx.build_and_upload(prims, mats)
         bvh, idx = gpu_ctx.download_bvh()
         _check_tree(bvh.reshape(-1, 8), idx, prims)
