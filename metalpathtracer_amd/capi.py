@@ -413,6 +413,15 @@ def _up(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
+def _ray_batch(origins, directions, tmax=None):
+    """What the ray queries pass on: contiguous float32 origins, directions [n, 3], tmax [n] (broadcast; None = no limit), and n."""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    t = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+    return o, d, t, n
+
+
 def gpu_leaf_max(n_prims):
     """mpt_gpu_leaf_max: the leaf limit of the GPU builders for a scene of n_prims primitives (6 below 8192, 2 from there on)."""
     return int(load().mpt_gpu_leaf_max(int(n_prims)))
@@ -581,9 +590,7 @@ class Context:
         return self.L.mpt_stream(self.h)
 
     def trace_rays(self, origins, directions):
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
-        n = o.shape[0]
+        o, d, _, n = _ray_batch(origins, directions)
         t = np.empty(n, np.float32)
         prim = np.empty(n, np.int32)
         nrm = np.empty((n, 3), np.float32)
@@ -594,9 +601,7 @@ class Context:
 
     def trace_rays_ordered(self, origins, directions):
         """Closest hit through the closest-first walk of PIPE_ORDERED; also returns the per-ray re-trace flags."""
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
-        n = o.shape[0]
+        o, d, _, n = _ray_batch(origins, directions)
         t = np.empty(n, np.float32)
         prim = np.empty(n, np.int32)
         nrm = np.empty((n, 3), np.float32)
@@ -609,10 +614,7 @@ class Context:
     def trace_occluded(self, origins, directions, tmax=None, walk=WALK_AUTO):
         """mpt_trace_occluded: is anything in the way before tmax (per ray; None = no limit)?  Returns (occluded [n] bool,
         flags [n] uint32 as trace_rays_ordered's)."""
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
-        n = o.shape[0]
-        t = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        o, d, t, n = _ray_batch(origins, directions, tmax)
         occ = np.empty(n, np.uint8)
         flags = np.empty(n, np.uint32)
         self._chk(self.L.mpt_trace_occluded(self.h, _fp(o), _fp(d), None if t is None else _fp(t), n, int(walk),
@@ -621,10 +623,7 @@ class Context:
 
     def time_trace(self, origins, directions, tmax=None, warmup=3, reps=20):
         """mpt_time_trace: HIP-event ms per launch, [reps, 4] = (closest reference, any-hit reference, closest own, any-hit own)."""
-        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
-        n = o.shape[0]
-        t = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        o, d, t, n = _ray_batch(origins, directions, tmax)
         ms = np.zeros((int(reps), 4), np.float64)
         self._chk(self.L.mpt_time_trace(self.h, _fp(o), _fp(d), None if t is None else _fp(t), n, int(warmup), int(reps),
                                         ms.ctypes.data_as(C.POINTER(C.c_double))), "mpt_time_trace")

@@ -2,7 +2,7 @@
 // management, upload of a scene (its conversion into the device layout — threaded breadth-first BVH, leaf-ordered
 // primitives, de-duplicated materials — is pure host code in mpt_scene_layout.h), pass scheduling and kernel launches.
 // The kernels themselves are in mpt_kernels.h, their building blocks in mpt_device.h; the host side of the
-// post-processing stages is mpt_post.h, the RCCL reduce mpt_comm.h, both included below.
+// post-processing stages is mpt_post.h, the ray queries mpt_query.h, the RCCL reduce mpt_comm.h, all included below.
 //
 // One mpt_render = one pass per <= 2^30 paths: k_begin_pass, ONE k_wavelocal launch (default pipeline; the global
 // wavefront launches k_step + k_advance per bounce generation instead), k_resolve_sum, one host synchronisation.
@@ -24,6 +24,7 @@
 #include <memory>
 #include <exception>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mpt.h"
@@ -805,7 +806,7 @@ static SceneDev scene_dev(const mpt_ctx* ctx) {
 
 // The closest-first kernel's view: own nodes / always list / primitives / materials / stacks in LDS; the threaded
 // reference-order nodes stay in global memory (ring E and the test hook walk them from there).
-static size_t ordered_views(const mpt_ctx* ctx, int point, uint32_t stack_depth, SceneDev& s, AccelDev& a) {
+static size_t ordered_views(const mpt_ctx* ctx, int point, SceneDev& s, AccelDev& a) {
     const mpt_ctx::OtPoint& pt = ctx->ot_pt[point];
     const uint32_t threads = pt.threads;
     s = scene_dev(ctx);
@@ -823,11 +824,11 @@ static size_t ordered_views(const mpt_ctx* ctx, int point, uint32_t stack_depth,
     s.lds_mat_off = s.lds_prim_off + 3u * s.n_lds_prims;
     const uint32_t image4 = mpt_lds_image_end_f4(s.lds_mat_off);   // (material table + the kernel's configuration block: the one definition of mpt_kernels.h)
     a.lds_stack_off = image4 * 16u;
-    a.stack_depth = stack_depth;
+    a.stack_depth = ctx->ot_stack_depth;
     a.eps_abs = ctx->acc_eps_abs;
     a.cull_rel = ctx->acc_cull_rel;
     a.o_limit = ctx->tri_extent > 0.0f ? 64.0f * ctx->tri_extent : INFINITY;  // no triangles: no tree, nothing to bound
-    return (size_t)a.lds_stack_off + (size_t)threads * stack_depth * 8u;
+    return (size_t)a.lds_stack_off + (size_t)threads * a.stack_depth * 8u;
 }
 // The regions of k_ordered's LDS image in the order the kernel addresses them: nodes, always list, primitives, materials, configuration
 // block, per-lane stacks.  None may overlap the next and the last must end inside the launch's allocation (the check that would have
@@ -840,6 +841,51 @@ static bool ordered_layout_ok(const SceneDev& s, const AccelDev& a, uint32_t thr
     return nodes_end <= a.lds_always_off && always_end <= s.lds_prim_off && prims_end <= s.lds_mat_off && mats_end <= cfg_begin &&
            cfg_end * 16u <= a.lds_stack_off && (a.lds_stack_off & 7u) == 0u && stack_end <= lds_bytes && a.stack_depth >= 2u && a.stack_depth <= MPT_OT_PARK &&
            (uint64_t)a.n_nodes < (1ull << 24) /* MPT_OT_SIGNSEL: node offsets by a 24-bit multiply */;
+}
+
+// the closest-first pipeline needs nested boxes and few spheres (mpt_upload_scene); otherwise the reference-order
+// wave-local pipeline renders the same image
+// MPT_PIPE_AUTO never picks the closest-first pipeline for the literal RNG: that mode exists to reproduce the reference's
+// frames, arithmetic artefacts included, and only the reference's own visit order does that for every ray (include/mpt.h).
+static int resolve_pipeline(const mpt_ctx* ctx, int pipeline, int rng_mode = MPT_RNG_PHILOX) {
+    if (pipeline == MPT_PIPE_AUTO)
+        pipeline = ctx->n_prims >= MPT_AUTO_ORDERED_PRIMS && rng_mode != MPT_RNG_LITERAL ? MPT_PIPE_ORDERED : MPT_PIPE_WAVELOCAL;
+    if (pipeline == MPT_PIPE_ORDERED && !ctx->acc_ok) pipeline = MPT_PIPE_WAVELOCAL;
+    return pipeline;
+}
+// MPT_WALK_* -> does the own tree answer?  (-1: a bad value)
+static int resolve_walk(const mpt_ctx* ctx, int32_t walk) {
+    if (walk == MPT_WALK_REFERENCE) return 0;
+    if (walk == MPT_WALK_OWN) return ctx->acc_ok ? 1 : 0;
+    if (walk == MPT_WALK_AUTO) return resolve_pipeline(ctx, MPT_PIPE_AUTO) == MPT_PIPE_ORDERED ? 1 : 0;
+    return -1;
+}
+static bool walk_valid(int32_t walk) { return walk == MPT_WALK_REFERENCE || walk == MPT_WALK_OWN || walk == MPT_WALK_AUTO; }
+// the reference-order kernels' LDS image (size_lds_images), and whether it holds the whole tree (the ALL_LDS instantiations)
+static size_t ref_lds_bytes(const mpt_ctx* ctx) { return (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA; }
+static bool ref_all_lds(const mpt_ctx* ctx) { return ctx->n_lds_nodes == ctx->n_nodes; }
+
+// A walk choice made launchable: the views of the scene the kernel takes, the dynamic LDS bytes of a workgroup and which of the
+// three instantiations (MPT_AO_*, mpt_ao.h) walks it.  Every launch that lets a tree answer a ray gets these from walk_views: the
+// trace kernels of a pass (launch_geometry), the per-tile shadow-ray kernels (tile_walk_launch, mpt_post.h), the ray queries (mpt_query.h).
+struct WalkViews {
+    SceneDev sc;
+    AccelDev ac;   // the own tree only
+    size_t lds;
+    int which;
+};
+// own: the closest-first kernel's image at operating point `point`, checked for workgroups of `threads` (the one-ray-per-lane and per-tile
+// kernels take point 0, the five-wave one's: workgroups of 256); else the reference-order tree, wholly or partly in LDS.
+static int walk_views(mpt_ctx* ctx, bool own, int point, uint32_t threads, WalkViews& v) {
+    if (!own) {
+        v = WalkViews{scene_dev(ctx), AccelDev{}, ref_lds_bytes(ctx), ref_all_lds(ctx) ? MPT_AO_REF_ALL_LDS : MPT_AO_REF};
+        return MPT_OK;
+    }
+    v.ac = AccelDev{};
+    v.lds = ordered_views(ctx, point, v.sc, v.ac);
+    v.which = MPT_AO_OWN;
+    if (!ordered_layout_ok(v.sc, v.ac, threads, v.lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
+    return MPT_OK;
 }
 // Fragment.metal:29 + Random.h:32-35: per-pixel u32 seed of the literal RNG.  The float sin-hash is
 // chaotic in the last ulp of sin(), so it is evaluated once on the host with the
@@ -967,17 +1013,6 @@ static inline uint64_t pass_path_limit(int pipeline) {
 
 static inline bool count_flag(const mpt_render_params* p) { return (p->flags & MPT_FLAG_COUNT_WORK) != 0; }
 
-// the closest-first pipeline needs nested boxes and few spheres (mpt_upload_scene); otherwise the reference-order
-// wave-local pipeline renders the same image
-// MPT_PIPE_AUTO never picks the closest-first pipeline for the literal RNG: that mode exists to reproduce the reference's
-// frames, arithmetic artefacts included, and only the reference's own visit order does that for every ray (include/mpt.h).
-static int resolve_pipeline(const mpt_ctx* ctx, int pipeline, int rng_mode = MPT_RNG_PHILOX) {
-    if (pipeline == MPT_PIPE_AUTO)
-        pipeline = ctx->n_prims >= MPT_AUTO_ORDERED_PRIMS && rng_mode != MPT_RNG_LITERAL ? MPT_PIPE_ORDERED : MPT_PIPE_WAVELOCAL;
-    if (pipeline == MPT_PIPE_ORDERED && !ctx->acc_ok) pipeline = MPT_PIPE_WAVELOCAL;
-    return pipeline;
-}
-
 // The order in which a pass walks the rank's tiles: what MPT_TILE_ORDER says, else row-major — or, for the six-wave operating point of
 // the closest-first kernel, one vertical stripe of the image per claim range = per XCD (ensure_tile_order, mode 3: measured together).
 static int tile_order_of(const mpt_ctx* ctx, const mpt_render_params* p) {
@@ -1074,7 +1109,7 @@ static int fill_pass_params(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, u
 // Which kernel of the table runs the pass, and at what workgroup size.
 static int select_trace_kernel(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t n_local_tiles, const PassParams& pp, PassLaunch& g) {
     const bool count = count_flag(p);
-    bool all_lds = ctx->n_lds_nodes == ctx->n_nodes;
+    bool all_lds = ref_all_lds(ctx);
     int variant = TK_PLAIN;
     if (g.pipeline == MPT_PIPE_WAVELOCAL) {
         // a render that overlaps others (mpt_render_async) runs the variant of the wave-local kernel that leaves room on the CU for the
@@ -1097,13 +1132,14 @@ static int select_trace_kernel(mpt_ctx* ctx, Lane& L, const mpt_render_params* p
 }
 
 // LDS bytes per workgroup, workgroups per CU (the occupancy query is cached by kernel and LDS size) and the grid.  For the closest-first
-// kernel this also makes its views of the scene (pp.scene, g.accel) and checks that the regions of its LDS image do not overlap.
+// kernel this also makes its views of the scene (pp.scene, g.accel), checked by walk_views.
 static int launch_geometry(mpt_ctx* ctx, PassParams& pp, PassLaunch& g) {
-    g.lds = (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA;
-    if (g.pipeline == MPT_PIPE_ORDERED) {
-        g.lds = ordered_views(ctx, g.ot_point, ctx->ot_stack_depth, pp.scene, g.accel);
-        if (!ordered_layout_ok(pp.scene, g.accel, (uint32_t)g.wg, g.lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-    }
+    WalkViews v;
+    const int vrc = walk_views(ctx, g.pipeline == MPT_PIPE_ORDERED, g.ot_point, (uint32_t)g.wg, v);
+    if (vrc) return vrc;
+    pp.scene = v.sc;   // (the reference-order pipelines: scene_dev(ctx), as fill_pass_params left it)
+    g.accel = v.ac;
+    g.lds = v.lds;
     int per_cu = 0;
     if (ctx->occ_fun == g.k->fn && ctx->occ_lds == g.lds) {
         per_cu = ctx->occ_per_cu;
@@ -1625,136 +1661,6 @@ static int render_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const 
     return MPT_OK;
 }
 
-// ---- unit-test entry points -----------------------------------------------------------------------------------
-static int trace_rays_impl(mpt_ctx* ctx, const float* o, const float* d, uint64_t n, float* t_out,
-                              int32_t* prim_out, float* normal_out, int32_t* front_out) {
-    if (!ctx || !o || !d || !t_out || !prim_out || !normal_out || !front_out || n == 0 || n > (1ull << 30))
-        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
-    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
-    HIPCHK(hipSetDevice(ctx->device));
-    DevMem<> d_o, d_d, d_t, d_n, d_p, d_f;
-    HIPCHK(d_o.alloc(n * 12));
-    HIPCHK(d_d.alloc(n * 12));
-    HIPCHK(d_t.alloc(n * 4));
-    HIPCHK(d_n.alloc(n * 12));
-    HIPCHK(d_p.alloc(n * 4));
-    HIPCHK(d_f.alloc(n * 4));
-    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
-    SceneDev sc = scene_dev(ctx);
-    hipLaunchKernelGGL(k_trace_rays, dim3((uint32_t)((n + 255) / 256)), dim3(256), (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA,
-                       ctx->stream, sc, (const float*)d_o.get(), (const float*)d_d.get(), (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(), (float*)d_n.get(), (int*)d_f.get());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(t_out, d_t.get(), n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(prim_out, d_p.get(), n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(normal_out, d_n.get(), n * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(front_out, d_f.get(), n * 4, hipMemcpyDeviceToHost));
-    return MPT_OK;
-}
-
-static int trace_rays_ordered_impl(mpt_ctx* ctx, const float* o, const float* d, uint64_t n, float* t_out, int32_t* prim_out,
-                                   float* normal_out, int32_t* front_out, uint32_t* flags_out) {
-    if (!ctx || !o || !d || !t_out || !prim_out || !normal_out || !front_out || !flags_out || n == 0 || n > (1ull << 22))
-        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument (at most 2^22 rays per call)");
-    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
-    if (!ctx->acc_ok) return fail(ctx, MPT_ERR_BAD_SCENE, "closest-first walk unavailable for this scene: " + ctx->acc_why);
-    HIPCHK(hipSetDevice(ctx->device));
-    DevMem<> d_o, d_d, d_t, d_n, d_p, d_f, d_g;
-    const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    HIPCHK(d_o.alloc(n * 12));
-    HIPCHK(d_d.alloc(n * 12));
-    HIPCHK(d_t.alloc(n * 4));
-    HIPCHK(d_n.alloc(n * 12));
-    HIPCHK(d_p.alloc(n * 4));
-    HIPCHK(d_f.alloc(n * 4));
-    HIPCHK(d_g.alloc(n * 4));
-    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
-    SceneDev sc;
-    AccelDev ac;
-    const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the five-wave operating point's image: workgroups of 256)
-    if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-    hipLaunchKernelGGL(k_trace_rays_ordered, dim3(blocks), dim3(256), lds, ctx->stream, sc, ac, (const float*)d_o.get(), (const float*)d_d.get(),
-                       (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(), (float*)d_n.get(), (int*)d_f.get(), (uint32_t*)d_g.get());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(t_out, d_t.get(), n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(prim_out, d_p.get(), n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(normal_out, d_n.get(), n * 12, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(front_out, d_f.get(), n * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(flags_out, d_g.get(), n * 4, hipMemcpyDeviceToHost));
-    return MPT_OK;
-}
-
-template <typename F>
-static int kat_run(mpt_ctx* ctx, const void* const* in, const size_t* in_bytes, int n_in, void* const* out,
-                   const size_t* out_bytes, int n_out, F launch) {
-    HIPCHK(hipSetDevice(ctx->device));
-    std::vector<DevMem<>> bi(n_in), bo(n_out);
-    std::vector<void*> di(n_in), dout(n_out);
-    for (int i = 0; i < n_in; ++i) {
-        HIPCHK(bi[i].alloc(in_bytes[i]));
-        di[i] = bi[i].get();
-        HIPCHK(hipMemcpy(di[i], in[i], in_bytes[i], hipMemcpyHostToDevice));
-    }
-    for (int i = 0; i < n_out; ++i) {
-        HIPCHK(bo[i].alloc(out_bytes[i]));
-        dout[i] = bo[i].get();
-    }
-    launch(di, dout);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < n_out; ++i) HIPCHK(hipMemcpy(out[i], dout[i], out_bytes[i], hipMemcpyDeviceToHost));
-    return MPT_OK;
-}
-
-static int kat_pcg_impl(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* h, float* f) {
-    if (!ctx || !seeds || !h || !f || n == 0 || n > (1u << 28)) return MPT_ERR_INVALID_ARG;
-    const void* in[] = {seeds};
-    size_t ib[] = {n * 4};
-    void* out[] = {h, f};
-    size_t ob[] = {n * 4, n * 4};
-    return kat_run(ctx, in, ib, 1, out, ob, 2, [&](std::vector<void*>& di, std::vector<void*>& dout) {
-        hipLaunchKernelGGL(k_kat_pcg, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const uint32_t*)di[0], (uint32_t)n, (uint32_t*)dout[0], (float*)dout[1]);
-    });
-}
-static int kat_philox_impl(mpt_ctx* ctx, const uint32_t* c, const uint32_t* k, uint64_t n, uint32_t* o) {
-    if (!ctx || !c || !k || !o || n == 0 || n > (1u << 26)) return MPT_ERR_INVALID_ARG;
-    const void* in[] = {c, k};
-    size_t ib[] = {n * 16, n * 8};
-    void* out[] = {o};
-    size_t ob[] = {n * 16};
-    return kat_run(ctx, in, ib, 2, out, ob, 1, [&](std::vector<void*>& di, std::vector<void*>& dout) {
-        hipLaunchKernelGGL(k_kat_philox, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const uint32_t*)di[0], (const uint32_t*)di[1], (uint32_t)n, (uint32_t*)dout[0]);
-    });
-}
-static int kat_sincos_impl(mpt_ctx* ctx, const float* u, uint64_t n, float* s, float* c) {
-    if (!ctx || !u || !s || !c || n == 0 || n > (1u << 28)) return MPT_ERR_INVALID_ARG;
-    const void* in[] = {u};
-    size_t ib[] = {n * 4};
-    void* out[] = {s, c};
-    size_t ob[] = {n * 4, n * 4};
-    return kat_run(ctx, in, ib, 1, out, ob, 2, [&](std::vector<void*>& di, std::vector<void*>& dout) {
-        hipLaunchKernelGGL(k_kat_sincos, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const float*)di[0], (uint32_t)n, (float*)dout[0], (float*)dout[1]);
-    });
-}
-static int kat_rcp_impl(mpt_ctx* ctx, uint64_t* out4) {
-    if (!ctx || !out4) return MPT_ERR_INVALID_ARG;
-    const uint64_t zero[4] = {0, 0, 0, 0};
-    const void* in[] = {zero};
-    size_t ib[] = {sizeof zero};
-    void* out[] = {out4};
-    size_t ob[] = {sizeof zero};
-    return kat_run(ctx, in, ib, 1, out, ob, 1, [&](std::vector<void*>& di, std::vector<void*>& dout) {
-        (void)hipMemcpyAsync(dout[0], di[0], sizeof zero, hipMemcpyDeviceToDevice, ctx->stream);   // (an error shows in hipGetLastError of kat_run)
-        hipLaunchKernelGGL(k_kat_rcp, dim3(65536), dim3(256), 0, ctx->stream, (unsigned long long*)dout[0]);
-    });
-}
-
 // The binary tree of the GPU builders (mpt_lbvh.h).  Default: top-down binned SAH over the primitives (as good a tree as the host's
 // binned builder).  MPT_GPU_BUILD = ploc: the clustering pass (25 % faster to build, renders 1-7 % slower); lbvh: the plain Karras tree.
 static int gpu_builder() {
@@ -2035,14 +1941,6 @@ extern "C" int mpt_draw(mpt_ctx* ctx, const mpt_render_params* p) {
     return guarded(ctx, [&] { return draw_impl(ctx, p); });
 }
 
-extern "C" int mpt_trace_rays(mpt_ctx* ctx, const float* o, const float* d, uint64_t n, float* t_out, int32_t* prim_out, float* normal_out, int32_t* front_out) {
-    return guarded(ctx, [&] { return trace_rays_impl(ctx, o, d, n, t_out, prim_out, normal_out, front_out); });
-}
-
-extern "C" int mpt_trace_rays_ordered(mpt_ctx* ctx, const float* o, const float* d, uint64_t n, float* t_out, int32_t* prim_out, float* normal_out, int32_t* front_out, uint32_t* flags_out) {
-    return guarded(ctx, [&] { return trace_rays_ordered_impl(ctx, o, d, n, t_out, prim_out, normal_out, front_out, flags_out); });
-}
-
 extern "C" int mpt_accel_info(mpt_ctx* ctx, uint64_t out[8]) {
     if (!ctx || !out) return MPT_ERR_INVALID_ARG;
     if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
@@ -2054,131 +1952,11 @@ extern "C" int mpt_accel_info(mpt_ctx* ctx, uint64_t out[8]) {
 
 extern "C" int mpt_gpu_leaf_max(uint64_t n_prims) { return gpu_leaf_max(n_prims); }
 
-// ---- shadow rays (mpt_anyhit.h, mpt_ao.h; the specification is in include/mpt.h) ----------------------------------------------------
-// MPT_WALK_* -> does the own tree answer?  (-1: a bad value)
-static int resolve_walk(const mpt_ctx* ctx, int32_t walk) {
-    if (walk == MPT_WALK_REFERENCE) return 0;
-    if (walk == MPT_WALK_OWN) return ctx->acc_ok ? 1 : 0;
-    if (walk == MPT_WALK_AUTO) return resolve_pipeline(ctx, MPT_PIPE_AUTO) == MPT_PIPE_ORDERED ? 1 : 0;
-    return -1;
-}
-static bool walk_valid(int32_t walk) { return walk == MPT_WALK_REFERENCE || walk == MPT_WALK_OWN || walk == MPT_WALK_AUTO; }
-static size_t ref_lds_bytes(const mpt_ctx* ctx) { return (size_t)ctx->n_lds_nodes * 32 + (size_t)ctx->n_lds_prims * 48 + MPT_LDS_EXTRA; }
-
-static int trace_occluded_impl(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, int32_t walk, uint8_t* occ_out,
-                               uint32_t* flags_out) {
-    if (!ctx || !o || !d || !occ_out || n == 0 || n > (1ull << 22) || !walk_valid(walk))
-        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument (at most 2^22 rays per call, walk = MPT_WALK_*)");
-    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
-    HIPCHK(hipSetDevice(ctx->device));
-    const bool own = resolve_walk(ctx, walk) == 1;
-    DevMem<> d_o, d_d, d_t, d_occ, d_g;
-    HIPCHK(d_o.alloc(n * 12));
-    HIPCHK(d_d.alloc(n * 12));
-    HIPCHK(d_occ.alloc(n));
-    HIPCHK(d_g.alloc(n * 4));
-    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
-    if (tmax) {
-        HIPCHK(d_t.alloc(n * 4));
-        HIPCHK(hipMemcpy(d_t.get(), tmax, n * 4, hipMemcpyHostToDevice));
-    }
-    const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    if (own) {
-        SceneDev sc;
-        AccelDev ac;
-        const size_t lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the image of k_trace_rays_ordered: workgroups of 256)
-        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        hipLaunchKernelGGL(k_occluded_own, dim3(blocks), dim3(256), lds, ctx->stream, sc, ac, (const float*)d_o.get(), (const float*)d_d.get(),
-                           (const float*)d_t.get(), (uint32_t)n, (uint8_t*)d_occ.get(), (uint32_t*)d_g.get());
-    } else {
-        HIPCHK(hipMemsetAsync(d_g.get(), 0, n * 4, ctx->stream));
-        const SceneDev sc = scene_dev(ctx);
-        if (ctx->n_lds_nodes == ctx->n_nodes)
-            hipLaunchKernelGGL(k_occluded_ref<true>, dim3(blocks), dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, (const float*)d_o.get(), (const float*)d_d.get(),
-                               (const float*)d_t.get(), (uint32_t)n, (uint8_t*)d_occ.get());
-        else
-            hipLaunchKernelGGL(k_occluded_ref<false>, dim3(blocks), dim3(256), ref_lds_bytes(ctx), ctx->stream, sc, (const float*)d_o.get(), (const float*)d_d.get(),
-                               (const float*)d_t.get(), (uint32_t)n, (uint8_t*)d_occ.get());
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipMemcpy(occ_out, d_occ.get(), n, hipMemcpyDeviceToHost));
-    if (flags_out) HIPCHK(hipMemcpy(flags_out, d_g.get(), n * 4, hipMemcpyDeviceToHost));
-    return MPT_OK;
-}
-
-// Measurement hook (tools/ao_timing.py): the four one-ray-per-lane kernels on the SAME rays, uploaded once, launched in turn — closest hit
-// in reference order (k_trace_rays), any hit in reference order, closest hit through the own tree (k_trace_rays_ordered), any hit through
-// the own tree — `warmup` untimed rounds, then `reps` rounds with a pair of HIP events around every launch.
-static int time_trace_impl(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, uint32_t warmup, uint32_t reps, double* ms_out) {
-    if (!ctx || !o || !d || !ms_out || n == 0 || n > (1ull << 22) || reps == 0 || reps > 1000u || warmup > 1000u)
-        return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument (at most 2^22 rays, 1..1000 repetitions)");
-    if (!ctx->have_scene) return fail(ctx, MPT_ERR_NOT_READY, "no scene");
-    HIPCHK(hipSetDevice(ctx->device));
-    DevMem<> d_o, d_d, d_tm, d_t, d_n, d_p, d_f, d_g, d_occ;
-    for (DevMem<>* b : {&d_o, &d_d, &d_n}) HIPCHK(b->alloc(n * 12));
-    for (DevMem<>* b : {&d_t, &d_p, &d_f, &d_g, &d_occ}) HIPCHK(b->alloc(n * 4));
-    HIPCHK(hipMemcpy(d_o.get(), o, n * 12, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_d.get(), d, n * 12, hipMemcpyHostToDevice));
-    if (tmax) {
-        HIPCHK(d_tm.alloc(n * 4));
-        HIPCHK(hipMemcpy(d_tm.get(), tmax, n * 4, hipMemcpyHostToDevice));
-    }
-    const SceneDev sc = scene_dev(ctx);
-    SceneDev osc = sc;
-    AccelDev ac = {};
-    size_t olds = 0;
-    if (ctx->acc_ok) {
-        olds = ordered_views(ctx, 0, ctx->ot_stack_depth, osc, ac);
-        if (!ordered_layout_ok(osc, ac, 256u, olds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-    }
-    const dim3 grid((uint32_t)((n + 255) / 256)), block(256);
-    const float *po = (const float*)d_o.get(), *pd = (const float*)d_d.get(), *pt = (const float*)d_tm.get();
-    const bool all_lds = ctx->n_lds_nodes == ctx->n_nodes;
-    Event e0, e1;
-    HIPCHK(e0.create(hipEventCreate));
-    HIPCHK(e1.create(hipEventCreate));
-    for (uint32_t r = 0; r < warmup + reps; ++r)
-        for (int kind = 0; kind < 4; ++kind) {
-            double* slot = r >= warmup ? ms_out + 4 * (size_t)(r - warmup) + kind : nullptr;
-            if (kind >= 2 && !ctx->acc_ok) {
-                if (slot) *slot = 0.0;
-                continue;
-            }
-            HIPCHK(hipEventRecord(e0.get(), ctx->stream));
-            if (kind == 0)
-                hipLaunchKernelGGL(k_trace_rays, grid, block, ref_lds_bytes(ctx), ctx->stream, sc, po, pd, (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(),
-                                   (float*)d_n.get(), (int*)d_f.get());
-            else if (kind == 1 && all_lds)
-                hipLaunchKernelGGL(k_occluded_ref<true>, grid, block, ref_lds_bytes(ctx), ctx->stream, sc, po, pd, pt, (uint32_t)n, (uint8_t*)d_occ.get());
-            else if (kind == 1)
-                hipLaunchKernelGGL(k_occluded_ref<false>, grid, block, ref_lds_bytes(ctx), ctx->stream, sc, po, pd, pt, (uint32_t)n, (uint8_t*)d_occ.get());
-            else if (kind == 2)
-                hipLaunchKernelGGL(k_trace_rays_ordered, grid, block, olds, ctx->stream, osc, ac, po, pd, (uint32_t)n, (float*)d_t.get(), (int*)d_p.get(),
-                                   (float*)d_n.get(), (int*)d_f.get(), (uint32_t*)d_g.get());
-            else
-                hipLaunchKernelGGL(k_occluded_own, grid, block, olds, ctx->stream, osc, ac, po, pd, pt, (uint32_t)n, (uint8_t*)d_occ.get(), (uint32_t*)d_g.get());
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(e1.get(), ctx->stream));
-            HIPCHK(hipEventSynchronize(e1.get()));
-            float ms = 0.0f;
-            HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
-            if (slot) *slot = (double)ms;
-        }
-    return MPT_OK;
-}
-
-extern "C" int mpt_trace_occluded(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, int32_t walk, uint8_t* occluded_out,
-                                  uint32_t* flags_out) {
-    return guarded(ctx, [&] { return trace_occluded_impl(ctx, o, d, tmax, n, walk, occluded_out, flags_out); });
-}
-extern "C" int mpt_time_trace(mpt_ctx* ctx, const float* o, const float* d, const float* tmax, uint64_t n, uint32_t warmup, uint32_t reps, double* ms_out) {
-    return guarded(ctx, [&] { return time_trace_impl(ctx, o, d, tmax, n, warmup, reps, ms_out); });
-}
-
 // ---- the post-processing stages: guide pass and denoiser, ambient occlusion, temporal accumulation, SVGF, display ----------------------
 #include "mpt_post.h"
+
+// ---- the ray queries: closest hit and any hit for caller rays, their timing hook, the known-answer kernels --------------------------
+#include "mpt_query.h"
 
 // ---- next-event estimation (mpt_nee.h; the estimator is specified in include/mpt.h) -------------------------------------------------
 // One launch of k_nee<WALK> over the whole image on ctx->stream, synchronous like mpt_render: the renders in flight are collected first,
@@ -2375,22 +2153,6 @@ extern "C" int mpt_build_and_upload(mpt_ctx* ctx, const float* prims, const floa
 
 extern "C" int mpt_download_bvh(mpt_ctx* ctx, float* bvh_out, uint64_t bvh_capacity_nodes, uint64_t* n_nodes_out, int32_t* prim_idx_out) {
     return guarded(ctx, [&] { return download_bvh_impl(ctx, bvh_out, bvh_capacity_nodes, n_nodes_out, prim_idx_out); });
-}
-
-extern "C" int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* h, float* f) {
-    return guarded(ctx, [&] { return kat_pcg_impl(ctx, seeds, n, h, f); });
-}
-
-extern "C" int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* c, const uint32_t* k, uint64_t n, uint32_t* o) {
-    return guarded(ctx, [&] { return kat_philox_impl(ctx, c, k, n, o); });
-}
-
-extern "C" int mpt_kat_sincos(mpt_ctx* ctx, const float* u, uint64_t n, float* s, float* c) {
-    return guarded(ctx, [&] { return kat_sincos_impl(ctx, u, n, s, c); });
-}
-
-extern "C" int mpt_kat_rcp(mpt_ctx* ctx, uint64_t* out4) {
-    return guarded(ctx, [&] { return kat_rcp_impl(ctx, out4); });
 }
 
 // ---- multi-GPU: RCCL reduce of the HDR sum (include/mpt.h) ----------------------------------------------------------

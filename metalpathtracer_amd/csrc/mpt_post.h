@@ -47,16 +47,10 @@ template <class Pass>
 using WalkKernel = void (*)(SceneDev, AccelDev, Pass);
 template <class Pass>
 static int tile_walk_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, int32_t walk, const WalkKernel<Pass> k[3], const Pass& P) {
-    SceneDev sc = scene_dev(ctx);
-    AccelDev ac = {};
-    size_t lds = ref_lds_bytes(ctx);
-    int which = ctx->n_lds_nodes == ctx->n_nodes ? MPT_AO_REF_ALL_LDS : MPT_AO_REF;
-    if (resolve_walk(ctx, walk) == 1) {
-        lds = ordered_views(ctx, 0, ctx->ot_stack_depth, sc, ac);   // (the image of k_trace_rays_ordered: workgroups of 256)
-        if (!ordered_layout_ok(sc, ac, 256u, lds)) return fail(ctx, MPT_ERR_INVALID_ARG, "LDS layout of the closest-first kernel overlaps (internal)");
-        which = MPT_AO_OWN;
-    }
-    hipLaunchKernelGGL(k[which], tile_grid(W, H), dim3(256), lds, ctx->stream, sc, ac, P);
+    WalkViews v;
+    const int rc = walk_views(ctx, resolve_walk(ctx, walk) == 1, 0, 256u, v);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k[v.which], tile_grid(W, H), dim3(256), v.lds, ctx->stream, v.sc, v.ac, P);
     HIPCHK(hipGetLastError());
     return MPT_OK;
 }
@@ -74,8 +68,9 @@ static int stage_in(mpt_ctx* ctx, DevMem<T>& d, const void* host, size_t bytes) 
     return MPT_OK;
 }
 // buffers of `bytes` each that the kernels fill (a stage's own, too)
-static int scratch(mpt_ctx* ctx, size_t bytes, std::initializer_list<DevMem<float4>*> bufs) {
-    for (DevMem<float4>* b : bufs) HIPCHK(b->alloc(bytes));
+template <class T>
+static int scratch(mpt_ctx* ctx, size_t bytes, std::initializer_list<DevMem<T>*> bufs) {
+    for (DevMem<T>* b : bufs) HIPCHK(b->alloc(bytes));
     return MPT_OK;
 }
 // device -> host array, enqueued (the caller synchronises once, behind its last copy); an output the caller did not ask for is skipped
