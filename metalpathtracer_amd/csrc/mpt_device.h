@@ -326,8 +326,27 @@ struct Prim3 {
 #endif
 typedef const __attribute__((address_space(3))) char* LdsBytes;
 __device__ __forceinline__ uint32_t mul_u24(uint32_t a, uint32_t b) { return (uint32_t)__umul24(a, b); }   // v_mul_u32_u24: low 32 bits of the product of the low 24 bits (__umul24 returns int: a product >= 2^31 must not meet a signed shift)
-template <bool LEAN = false>
-__device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uint32_t i) {
+// LEAN, camera-relative sphere terms (MPT_LEAN_CAMSPHERE): a primary ray starts at the camera, the same bits in every lane of every
+// primary step of a launch, so oc = o - c and cc = dot3(oc, oc) - r * r of the sphere test are functions of (camera, sphere) alone: 10
+// of the test's 19 vector instructions.  The lean kernels write them once per workgroup into the unused words of the sphere records of
+// their LDS image (stage_nodes_lean, mpt_kernels.h: p2.xyz = oc, p1.z = cc; sphere_cam_terms below is the one expression of both), and
+// the walk of a primary step (PRIMARY, an instantiation of its own) reads them there.  A sphere record that such a walk reads from global memory gets
+// the same two terms here, in the branch that separates the two sources, so leaf_test's sphere branch has one form per walk.  The
+// global array and every other reader of a record (the walks of ring steps, finish_hit, the materials) are as they were.
+// (MPT_LEAN_CAMSPHERE=0: pricing build without it — profiles/r17_lean_primary.txt)
+#ifndef MPT_LEAN_CAMSPHERE
+#define MPT_LEAN_CAMSPHERE 1
+#endif
+__device__ __forceinline__ void sphere_cam_terms(F3 o, float4 p0, float4& p1, float4& p2) {   // the operators and the order of leaf_test
+    const F3 oc = o - f3(p0.x, p0.y, p0.z);
+    const float radius = p1.x;
+    p1.z = dot3(oc, oc) - radius * radius;
+    p2.x = oc.x;
+    p2.y = oc.y;
+    p2.z = oc.z;
+}
+template <bool LEAN = false, bool PRIMARY = false>   // PRIMARY: `o` is the camera, and a sphere record comes back with oc and cc in it
+__device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uint32_t i, F3 o = F3{0.0f, 0.0f, 0.0f}) {
     Prim3 r;
     if (LEAN && MPT_LEAN_INT24) {
         const uint32_t off = mul_u24(i, 48u);
@@ -342,6 +361,7 @@ __device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uin
             r.p0 = q[0];
             r.p1 = q[1];
             r.p2 = q[2];
+            if (MPT_LEAN_CAMSPHERE && PRIMARY && prim_type(r.p0) == 0) sphere_cam_terms(o, r.p0, r.p1, r.p2);
         }
         return r;
     }
@@ -360,13 +380,14 @@ __device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uin
 }
 
 // Primitives of one leaf, in index order — PathTracing.h:106-186.
-template <bool COUNT, bool LEAN = false>
+template <bool COUNT, bool LEAN = false, bool PRIMARY = false>
 __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint32_t first, uint32_t count, F3 o, F3 d,
                                           float& best_t, int& best_prim, WorkCount& wc) {
+    constexpr bool cam_terms = LEAN && MPT_LEAN_INT24 && MPT_LEAN_CAMSPHERE && PRIMARY;   // a sphere record carries oc and cc (load_prim)
     for (uint32_t k = 0; k < count; ++k) {
         // the three 16-byte loads of a primitive are issued together (the third is used by triangles only, but a
         // load that waits for the type check costs a second L2 round trip per primitive)
-        const Prim3 pr = load_prim<LEAN>(sc, lds, first + k);
+        const Prim3 pr = load_prim<LEAN, cam_terms>(sc, lds, first + k, o);
         const float4 p0 = pr.p0, p1 = pr.p1, p2 = pr.p2;
         if (COUNT) {
             wc.prim_tests++;
@@ -396,7 +417,7 @@ __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint
         } else if (ptype == 0) {  // PathTracing.h:120-142 sphere, near root only
             F3 c = f3(p0.x, p0.y, p0.z);
             float radius = p1.x;
-            F3 oc = o - c;
+            const F3 oc = cam_terms ? f3(p2.x, p2.y, p2.z) : o - c;
             float a = dot3(d, d);
             float b = dot3(oc, d);
             // b >= 0 (the centre lies behind the ray): the root (-b - sqrt(disc)) / a is <= 0 whatever disc is and fails
@@ -404,7 +425,7 @@ __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint
             // nothing (a NaN b compares false and takes the full path).
             // one level of branching (the square root and the division are skipped by whole waves), the rest as selects:
             // every nested if costs the scalar unit ~6 instructions of exec-mask bookkeeping
-            const float cc = dot3(oc, oc) - radius * radius;
+            const float cc = cam_terms ? p1.z : dot3(oc, oc) - radius * radius;
             const float disc = b * b - a * cc;
             if (!(b >= 0.0f) && disc > 0.0f) {
                 const float sq = sqrtf(disc);
@@ -432,11 +453,15 @@ __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint
 #define MPT_LEAF_EARLY 8u
 #endif
 #define MPT_NODE_HOLD 0x80000000u   // hit link of a leaf record: HOLD | first << 4 | (count - 1)
+#ifndef MPT_LEAN_ONECMP
+#define MPT_LEAN_ONECMP 1
+#endif
 // LEAN: 32-bit primitive addressing (load_prim).  (The box loop's fminf(best_t, ..) canonicalises best_t on every trip — v_max_f32 t, t, t —
 // although best_t does not change inside the loop.  Making it canonical once per round, best_t = fminf(best_t, INFINITY) in front of
 // the loop, does not remove that instruction: the compiler decides "known canonical" per basic block, and the loop body is a block of
 // its own.  Tried and left out, profiles/r15_fast_kernel.txt.)
-template <bool COUNT, bool ALL_LDS, bool BUDGETED, bool LEAN = false>
+// PRIMARY (lean kernels): every ray of the call starts at the launch's camera, and sphere records carry the camera-relative terms (load_prim).
+template <bool COUNT, bool ALL_LDS, bool BUDGETED, bool LEAN = false, bool PRIMARY = false>
 __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes lds_nodes, F3 o, F3 d, uint32_t& node,
                                                    float& best_t, int& best_prim, uint32_t budget, WorkCount& wc,
                                                    uint32_t min_active = 0u) {
@@ -463,13 +488,17 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
     for (;;) {
         uint32_t skip = 0;
         // (at least 1: "no lane searching" then leaves the loop by the same comparison as the early leave below)
-        const uint32_t n_entered0 = (uint32_t)__popcll(__ballot(i < n_nodes)), n_entered = max(n_entered0, 1u);
+        unsigned long long search_mask = __ballot(i < n_nodes);   // the lanes with i < n_nodes, from the end of a trip to the head of the next
+        const uint32_t n_entered0 = (uint32_t)__popcll(search_mask), n_entered = max(n_entered0, 1u);
 #ifdef MPT_DEBUG_WAVE_TIMES
         uint32_t my_trips = 0, round_trips = 0;
 #endif
         uint32_t n_searching = n_entered0;
         while (n_searching * MPT_LEAF_EARLY >= n_entered && (!BUDGETED || trips < budget)) {
-            const bool searching = i < n_nodes;
+            // LEAN: `searching` is the ballot the trip before (or the entry) took, handed back to the lanes — the compiler does not merge a
+            // compare that feeds a ballot with the same compare feeding the exec mask, so the plain form issues it twice per trip
+            // (MPT_LEAN_ONECMP=0: pricing build — profiles/r17_lean_primary.txt)
+            const bool searching = LEAN && MPT_LEAN_ONECMP ? __builtin_amdgcn_inverse_ballot_w64(search_mask) : i < n_nodes;
             // When fewer than 1/8 of the lanes that entered this search are still looking for their next leaf, the
             // others — who hold a leaf — stop waiting: the leaf phase runs now and the searchers resume afterwards
             // from where they are (each lane still sees its own sequence of tests).  In the deep rings most box-loop
@@ -479,7 +508,9 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
             my_trips += searching ? 1u : 0u;
             round_trips++;
 #endif
-            const uint32_t j = i < n_nodes - 1u ? i : n_nodes - 1u;
+            // (the clamp keeps a lane that is not searching inside the array; only searching lanes read, and the compiler drops it where it
+            //  sees `searching` as the compare.  Behind the handed-back ballot it cannot see that, so the lean form says it: j = i.)
+            const uint32_t j = LEAN && MPT_LEAN_ONECMP ? i : (i < n_nodes - 1u ? i : n_nodes - 1u);
             float4 n0 = make_float4(0, 0, 0, 0), n1 = n0;
             bool box = false;
             // Lanes that are not searching sit the trip out under the exec mask (one s_and_saveexec / s_or per trip): they issue
@@ -520,7 +551,8 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
             i = searching ? next : i;
             skip = searching ? B : skip;
             if (BUDGETED) trips++;
-            n_searching = (uint32_t)__popcll(__ballot(i < n_nodes));
+            search_mask = __ballot(i < n_nodes);
+            n_searching = (uint32_t)__popcll(search_mask);
         }
 #ifdef MPT_DEBUG_WAVE_TIMES
         if (COUNT) {
@@ -532,7 +564,7 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         if ((i & MPT_NODE_HOLD) != 0u) {
             const uint32_t enc = i & ~MPT_NODE_HOLD;
             if (COUNT && first_active_lane()) wc.outer_iters++;
-            leaf_test<COUNT, LEAN>(sc, lds_nodes, enc >> 4, (enc & 15u) + 1u, o, d, best_t, best_prim, wc);
+            leaf_test<COUNT, LEAN, PRIMARY>(sc, lds_nodes, enc >> 4, (enc & 15u) + 1u, o, d, best_t, best_prim, wc);
             i = skip;
         }
         MPT_TOC(wc.t_leaf, tic_);

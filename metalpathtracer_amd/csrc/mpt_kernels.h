@@ -250,6 +250,26 @@ __device__ __forceinline__ void stage_nodes(const SceneDev& sc, float4* lds) {
     __syncthreads();
 }
 
+// The lean wave-local kernels' image: the same copy, with every LDS-resident sphere record carrying the camera-relative terms of its
+// test in the words the record does not use (p2.xyz = cam - c, p1.z = dot3(oc, oc) - r * r: sphere_cam_terms, mpt_device.h).  One
+// thread copies a whole record, so the patch is in the copy and needs no barrier of its own.  `cam` is the launch's camera, the bits
+// the LDS camera block hands to gen_primary as a primary ray's origin: the terms belong to the launch, nothing is kept in the context.
+__device__ __forceinline__ void stage_nodes_lean(const SceneDev& sc, float4* lds, F3 cam) {
+    const uint32_t n4 = sc.n_lds_nodes * 2u;
+    for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) lds[i] = sc.nodes[i];
+    for (uint32_t i = threadIdx.x; i < sc.n_lds_prims; i += blockDim.x) {
+        const float4 p0 = sc.prims[3u * i];
+        float4 p1 = sc.prims[3u * i + 1u], p2 = sc.prims[3u * i + 2u];
+        if (prim_type(p0) == 0) sphere_cam_terms(cam, p0, p1, p2);
+        float4* q = lds + sc.lds_prim_off + 3u * i;
+        q[0] = p0;
+        q[1] = p1;
+        q[2] = p2;
+    }
+    for (uint32_t i = threadIdx.x; i < sc.n_lds_mats * 2u; i += blockDim.x) lds[sc.lds_mat_off + i] = sc.mats[i];
+    __syncthreads();
+}
+
 // Wave-uniform work fetch of the GLOBAL wavefront (k_step): a wave claims a run of consecutive 64-slot items from its
 // home group's cursor (then steals from the other groups).  The run length is guided — remaining / (2 * waves) clamped
 // to [1, 16] — so the bulk of an iteration costs few atomics and the tail stays fine-grained.  (k_wavelocal / k_ordered
@@ -749,7 +769,8 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             w[21] = lean.s_shift;
         }
     }
-    stage_nodes(pp.scene, lds_nodes_raw);
+    if (LEAN && MPT_LEAN_CAMSPHERE) stage_nodes_lean(pp.scene, lds_nodes_raw, pp.cam);
+    else stage_nodes(pp.scene, lds_nodes_raw);
     MPT_CLOCK_BEGIN();
     const LdsNodes lds_nodes = (LdsNodes)lds_nodes_raw;
     const __attribute__((address_space(3))) uint32_t* lds_cfg_u32 = (const __attribute__((address_space(3))) uint32_t*)(lds_nodes + cfg_off + 4u);
@@ -1041,6 +1062,9 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             if (budgeted)
                 done = closest_hit_resume<COUNT, ALL_LDS, true, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
                                                                      budget, wc, min_active);
+            else if (LEAN && MPT_LEAN_CAMSPHERE && level < 0)   // a primary step: every origin is the camera (the staged sphere terms)
+                done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN, true>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
+                                                                            0xFFFFFFFFu, wc);
             else
                 done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
                                                                       0xFFFFFFFFu, wc);
