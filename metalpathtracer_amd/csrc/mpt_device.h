@@ -461,6 +461,26 @@ __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint
 // the loop, does not remove that instruction: the compiler decides "known canonical" per basic block, and the loop body is a block of
 // its own.  Tried and left out, profiles/r15_fast_kernel.txt.)
 // PRIMARY (lean kernels): every ray of the call starts at the launch's camera, and sphere records carry the camera-relative terms (load_prim).
+//
+// One trip's box test: n0 = (lo planes, hit link), n1 = (hi planes, miss link), id = 1 / d.  (A function of its own so that
+// tests/lean_entry/ can put it next to the entry guard of mpt_lean_entry.h; the kernels' instructions are what they were.)
+// (Tried for the lean kernels and taken out again, profiles/r18_lean_entry.txt: the far terms through fminf first — one v_min3_f32 —
+// and best_t joining by a bare asm v_min_f32, which drops the v_max_f32 t, t, t in front of fminf(best_t, ..): 27 -> 26 vector
+// instructions per trip plus an s_nop behind the asm, 0.06 ms of 14.4, inside the run-to-run spread.)
+__device__ __forceinline__ bool slab_hit(float4 n0, float4 n1, F3 o, float idx, float idy, float idz, float best_t) {
+    float t0 = (n0.x - o.x) * idx, t1 = (n1.x - o.x) * idx;
+    float lo = fmaxf(0.0001f, idx < 0.0f ? t1 : t0);
+    float hi = fminf(best_t, idx < 0.0f ? t0 : t1);
+    t0 = (n0.y - o.y) * idy;
+    t1 = (n1.y - o.y) * idy;
+    lo = fmaxf(lo, idy < 0.0f ? t1 : t0);
+    hi = fminf(hi, idy < 0.0f ? t0 : t1);
+    t0 = (n0.z - o.z) * idz;
+    t1 = (n1.z - o.z) * idz;
+    lo = fmaxf(lo, idz < 0.0f ? t1 : t0);
+    hi = fminf(hi, idz < 0.0f ? t0 : t1);
+    return hi > lo;
+}
 template <bool COUNT, bool ALL_LDS, bool BUDGETED, bool LEAN = false, bool PRIMARY = false>
 __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes lds_nodes, F3 o, F3 d, uint32_t& node,
                                                    float& best_t, int& best_prim, uint32_t budget, WorkCount& wc,
@@ -528,18 +548,7 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
                 }
                 // PathTracing.h:52-72 slab test with tMin = 1e-4, tMax = best t.  The per-axis early-outs
                 // are equivalent to one test after the third axis (tMin only grows, tMax only shrinks).
-                float t0 = (n0.x - o.x) * idx, t1 = (n1.x - o.x) * idx;
-                float lo = fmaxf(0.0001f, idx < 0.0f ? t1 : t0);
-                float hi = fminf(best_t, idx < 0.0f ? t0 : t1);
-                t0 = (n0.y - o.y) * idy;
-                t1 = (n1.y - o.y) * idy;
-                lo = fmaxf(lo, idy < 0.0f ? t1 : t0);
-                hi = fminf(hi, idy < 0.0f ? t0 : t1);
-                t0 = (n0.z - o.z) * idz;
-                t1 = (n1.z - o.z) * idz;
-                lo = fmaxf(lo, idz < 0.0f ? t1 : t0);
-                hi = fminf(hi, idz < 0.0f ? t0 : t1);
-                box = hi > lo;
+                box = slab_hit(n0, n1, o, idx, idy, idz, best_t);
             }
             const uint32_t A = __float_as_uint(n0.w), B = __float_as_uint(n1.w);  // links: box hit / box missed
             if (COUNT) {

@@ -12,6 +12,7 @@
 
 #include "mpt_device.h"
 #include "mpt_wl_lean.h"
+#include "mpt_lean_entry.h"
 
 // Minimum waves per SIMD the two secondary trace kernels (k_step, k_megakernel) are compiled for (2nd __launch_bounds__
 // argument): 8 waves/SIMD (<= 64 VGPRs, 2 x 1024-thread workgroups per CU next to 2 x 57 KB of LDS).  k_wavelocal has
@@ -568,7 +569,7 @@ __device__ __forceinline__ uint32_t wave_rank(unsigned long long m) {
 #endif
 #define MPT_WL_RING 512u       // records per ring
 #define MPT_LDS_MATS_N 32u     // materials staged in LDS (= MPT_LDS_MATS of mpt_hip.hip): the configuration block of k_wavelocal / k_ordered starts behind them
-#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes): camera in float4 0..3, then 32 words (budgets 0..15, claim parameters 16..19).
+#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes): camera in float4 0..3, then 32 words (budgets 0..15, claim parameters 16..19); float4 10..11: the lean kernels' entry terms (mpt_lean_entry.h).
                                // The host reserves it (MPT_LDS_EXTRA, ordered_views): k_ordered's stacks start right behind it.
 // Where the configuration block starts in a workgroup's LDS (float4 index), for the kernels AND for the host code that lays the
 // image out and sizes the launch (mpt_hip.hip: MPT_LDS_EXTRA, ordered_views) — one definition.  Round 4's development build of
@@ -759,7 +760,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             w[8u + k] = budgets.min_active[k];
         }
         // ... and what only a CLAIM of path ids needs (words 16..19 of the block's 32: static_assert below)
-        static_assert(4u * (MPT_LDS_CFG_F4 - 4u) >= 22u, "configuration block too small");
+        static_assert(4u * (10u - 4u) >= 22u && MPT_LDS_CFG_F4 >= 12u, "configuration block too small");   // words 0..21 end inside float4 9; float4 10 and 11 hold the lean kernels' entry terms
         w[16] = wl_block;
         w[17] = wl_min;
         w[18] = wl_div * (((uint32_t)(gridDim.x * (blockDim.x >> 6)) + MPT_NGROUP - 1u) / MPT_NGROUP);   // wl_div * waves per claim range
@@ -767,6 +768,13 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         if (LEAN) {   // the division by a sample count that is no power of two (path_to_pixel<true>)
             w[20] = lean.s_mul;
             w[21] = lean.s_shift;
+        }
+        if (LEAN && MPT_LEAN_ENTRY) {   // where fresh queries enter the tree (mpt_lean_entry.h): float4 10 and 11 of the block, behind the words above
+            const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // (a tree without nodes: A0 = 0 switches the item off, nothing is read)
+            const bool tree = pp.scene.n_nodes != 0u;
+            const LeanEntry e = lean_entry_terms(tree ? pp.scene.nodes[0] : none, tree ? pp.scene.nodes[1] : none, pp.scene.n_nodes, pp.cam.x, pp.cam.y, pp.cam.z);
+            lds_nodes_raw[cfg_off + 10] = make_float4(e.ilo[0], e.ilo[1], e.ilo[2], __uint_as_float(e.entry));
+            lds_nodes_raw[cfg_off + 11] = make_float4(e.ihi[0], e.ihi[1], e.ihi[2], __uint_as_float(e.entry_primary));
         }
     }
     if (LEAN && MPT_LEAN_CAMSPHERE) stage_nodes_lean(pp.scene, lds_nodes_raw, pp.cam);
@@ -1044,6 +1052,20 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             if (!shade_bounce<LEAN>(pp.scene, lds_nodes, pp.sp, g, ps, hit_t, hit_prim)) {   // the path ends here (depth limit, material guard)
                 store_slot(pp.slots, ps.path, clamp01(ps.L.x), clamp01(ps.L.y), clamp01(ps.L.z), clamp01(ps.La));
                 valid = false;
+            }
+        }
+        // LEAN: a fresh query whose box test of the root is known to pass starts at the root's hit link (mpt_lean_entry.h): a primary
+        // ray when the launch's camera is inside the shrunk root box (one word for the wave), a bounce ray — shade_bounce has left it
+        // in `ps` — when its origin is; both only with |d| <= 2 on every axis.  Per lane: a wave saves the trip when its fresh lanes agree.
+        if (LEAN && MPT_LEAN_ENTRY && fresh) {
+            const bool d_ok = fmaxf(fmaxf(fabsf(ps.d.x), fabsf(ps.d.y)), fabsf(ps.d.z)) <= MPT_LEAN_ENTRY_DMAX;
+            if (level < 0) {
+                const uint32_t entry_primary = ((const __attribute__((address_space(3))) uint32_t*)(lds_nodes + cfg_off + 11u))[3];
+                node = d_ok ? entry_primary : 0u;
+            } else {
+                const v4f elo = lds_nodes[cfg_off + 10u], ehi = lds_nodes[cfg_off + 11u];
+                const bool in = elo.x <= ps.o.x && ps.o.x <= ehi.x && elo.y <= ps.o.y && ps.o.y <= ehi.y && elo.z <= ps.o.z && ps.o.z <= ehi.z;
+                node = in && d_ok ? __float_as_uint(elo.w) : 0u;
             }
         }
         // the last ring never has a budget; a ring whose budget is "none" runs the plain (unsynchronised) loop

@@ -1,0 +1,41 @@
+"""Where a fresh query of the lean wave-local kernels enters the tree (lean_entry_terms, metalpathtracer_amd/csrc/mpt_lean_entry.h), on the CPU.
+
+tests/lean_entry/lean_entry_check.cpp is a stand-alone program that includes the header.  It checks the off-switch at each edge — the
+root is a leaf record, A0 = 0, A0 = n_nodes, a box thinner than 4m (and one exactly 4m thick, accepted), planes at 1.6e7 where an ulp
+exceeds 2m, a NaN or infinite plane, the camera exactly on ilo / ihi (inside) and one ulp outside each — and then the implication the
+kernels rely on, in float32 with the IEEE 1 / d: for 2^21 origins per box (in the shrunk box, on its faces, between the two boxes, on the
+root's faces, around it) and directions with exact zeros, -0, denormals, tiny components, |d| = 2 and components past 2, whenever the
+guard says skip the root's slab test says hit and the minimum of its far terms exceeds 0.0001f.  Four boxes the function accepts, among
+them scene.xml's [-1e4, 1e4] x [-2e4, 60] x [-1e4, 1e4].  The program asserts that at least half of the origins are inside the shrunk
+box and that the guard says skip for at least a fifth, so it cannot pass by declining.
+
+Built twice with the host compiler, plain and with AddressSanitizer + UndefinedBehaviorSanitizer, and run directly; nothing is loaded
+into Python."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+from conftest import ROOT
+
+SRC = os.path.join(ROOT, "tests", "lean_entry", "lean_entry_check.cpp")
+FLAGS = ["-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", "-I" + os.path.join(ROOT, "metalpathtracer_amd", "csrc")]
+
+
+@pytest.mark.parametrize("sanitize", [False, True], ids=["plain", "asan-ubsan"])
+def test_entry_terms_edges_and_implication(tmp_path, sanitize):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "lean_entry_check")
+    extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []
+    subprocess.run([cxx] + FLAGS + extra + [SRC, "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr)
+    assert r.returncode == 0 and "all passed" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
+    boxes = re.findall(r"box \d: (\d+) origins, (\d+) inside the shrunk box, (\d+) skipped, (\d+) failures, least far term (\S+)", r.stdout)
+    assert len(boxes) >= 3
+    for n, inside, skipped, bad, least in boxes:
+        assert int(n) >= 10 ** 6 and 2 * int(inside) >= int(n) and int(skipped) > 0 and int(bad) == 0 and float(least) > 1e-4
