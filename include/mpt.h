@@ -389,7 +389,7 @@ typedef struct mpt_adaptive_info {
     uint32_t _pad;
 } mpt_adaptive_info;
 int mpt_render_adaptive(mpt_ctx* ctx, const mpt_render_params* p, const mpt_adaptive_params* a, mpt_adaptive_info* out);
-/* Samples per tile of the last mpt_render_adaptive: ceil(W/8) * ceil(H/8) uint32, row-major tiles (zeros before the first one;
+/* Samples per tile of the last mpt_render_adaptive (or mpt_render_nee_adaptive): ceil(W/8) * ceil(H/8) uint32, row-major tiles (zeros before the first one;
  * MPT_ERR_NOT_READY before mpt_resize).                                                                                       */
 int mpt_read_tile_samples(mpt_ctx* ctx, uint32_t* counts);
 
@@ -584,8 +584,8 @@ enum { MPT_DISPLAY_SUM = 0,       /* HDR sum / samples (IEEE division by (float)
        MPT_DISPLAY_DENOISED = 2,  /* what mpt_read_denoised returns (mpt_denoise / mpt_denoise_temporal)                              */
        MPT_DISPLAY_TEMPORAL = 3,  /* rgb of the mpt_temporal_* history                                                                */
        MPT_DISPLAY_SVGF = 4,      /* rgb of mpt_read_svgf                                                                             */
-       MPT_DISPLAY_ADAPTIVE = 5 };/* HDR sum / (float)count(tile) of the last mpt_render_adaptive, the tile of pixel (x, y) being
-                                     (y / 8) * ceil(W / 8) + x / 8; a count of 0 gives 0                                              */
+       MPT_DISPLAY_ADAPTIVE = 5 };/* HDR sum / (float)count(tile) of the last mpt_render_adaptive or mpt_render_nee_adaptive, the tile
+                                     of pixel (x, y) being (y / 8) * ceil(W / 8) + x / 8; a count of 0 gives 0                        */
 enum { MPT_TONE_CLAMP = 0, MPT_TONE_REINHARD = 1, MPT_TONE_ACES = 2 };
 enum { MPT_TRANSFER_SRGB = 0, MPT_TRANSFER_GAMMA22 = 1, MPT_TRANSFER_LINEAR = 2 };
 #define MPT_DISPLAY_DEFAULT_WHITE 4.0f
@@ -769,7 +769,8 @@ int mpt_direct_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float*
  * pipeline and slots_per_iter are ignored.  It writes none of: the frame targets, the moments, the denoised buffer, the temporal, SVGF,
  * display, AO and direct state.  mpt_get_stats: paths and rays grow by the info's, trace_kernel_ms and total_ms are set as after an
  * mpt_render, trace_launches = 1.
- * OUT OF SCOPE: moments (MPT_FLAG_MOMENTS), shards, the asynchronous lane and adaptive rendering over this estimator.
+ * OUT OF SCOPE: moments (MPT_FLAG_MOMENTS), shards, the asynchronous lane and adaptive rendering over this estimator (that is a call of
+ * its own with its own kernel: mpt_render_nee_adaptive, below).
  * MPT_ERR_INVALID_ARG, with nothing rendered: a null p or n, MPT_RNG_LITERAL, MPT_BSDF_SCATTER_ALL (its direction pdf is not the cosine
  * pdf), shard_count != 1 or shard_rank != 0, flags != 0, sample_count == 0, max_depth < 1, a bad walk, a NaN clamp, and mpt_render's
  * upper limits: max_depth > 32, sample_begin + sample_count > 2^27.  MPT_ERR_NOT_READY before scene, uniforms and size.  MPT_ERR_BAD_SCENE from the light table, as mpt_direct_lighting.
@@ -813,6 +814,35 @@ typedef struct mpt_nee_info {
     double device_ms;    /* HIP-event time of the trace kernel (table build not included)                                               */
 } mpt_nee_info;
 int mpt_render_nee(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out /* may be NULL */);
+
+/* ---- adaptive sampling over the NEE estimator: every 8x8 tile decides on the device ---------------------------------------------------
+ * No reference counterpart.  mpt_render_nee_adaptive spends mpt_render_nee's samples the way mpt_render_adaptive allocates them: with
+ * b = p->sample_begin and N = p->sample_count the most samples any tile gets, every tile renders samples [b, b + count(tile)) of the
+ * estimator above, count(tile) being where the stopping rule of the adaptive section first holds along its schedule
+ *   n_0 = min(min_samples, N),  n_{k+1} = min(n_k + batch_samples, N)   (the tile goes on iff error > threshold and n_k < N),
+ * with the rule's arithmetic unchanged: double precision from the float32 sum and the float32 moments of the n_k samples the tile holds
+ * (so, as there, a tile without any variance — error exactly 0 — stops at n_0 even under threshold 0).
+ * The moments are those of MPT_FLAG_MOMENTS, m2 += (v.x^2, v.y^2, v.z^2, l^2) per sample value v in sample order, one IEEE operation at a
+ * time.  The wave that renders a tile keeps both in registers and applies the rule itself: ONE kernel launch, no host passes.
+ *
+ * The call is synchronous.  It waits for the renders queued and in flight (reporting a failed mpt_render_async), builds the light table
+ * if stale, clears the HDR sum (the caller's storage of mpt_set_sum_buffer included), the moments buffer (allocated if absent) and the
+ * tile counts, and launches the kernel.  The light-sampling mode is read at the start, as mpt_render_nee reads it.  From p and n it reads
+ * what mpt_render_nee reads; a's zeros select the defaults of mpt_adaptive_params.
+ * Afterwards each tile holds, bit for bit, the sum that mpt_render_nee of [b, b + count(tile)) adds to a cleared sum (same walk, clamp,
+ * BSDF mode and light sampling); mpt_read_tile_samples gives the counts and mpt_read_moments the moments of exactly those samples.
+ * MPT_DISPLAY_ADAPTIVE, mpt_denoise with the adaptive mean and mpt_read_sum read the same buffers and work unchanged.  Like
+ * mpt_render_nee it writes none of: the frame targets, the denoised buffer, the temporal, SVGF, display, AO and direct state.
+ * out (may be NULL): samples = pixel samples inside the image; passes = the schedule steps the farthest tile took, the first included;
+ * tiles_converged / tiles_at_max as after mpt_render_adaptive — all derived from the tile counts after the kernel.
+ * nee_out (may be NULL) and mpt_get_stats: as after mpt_render_nee (paths and rays grow, the timing fields are set, trace_launches = 1).
+ * OUT OF SCOPE: shards and more than one GPU, the asynchronous lane, checkpoints of an adaptive render, camera paths.
+ * MPT_ERR_INVALID_ARG, with nothing rendered and nothing cleared: every refusal of mpt_render_nee (a null p or n, MPT_RNG_LITERAL,
+ * MPT_BSDF_SCATTER_ALL, shards, flags != 0, max_depth < 1 or > 32, a bad walk, a NaN clamp, sample_begin + sample_count > 2^27) and every
+ * refusal of mpt_render_adaptive (a null a, min_samples == 1, a negative or NaN threshold, N < 2).  MPT_ERR_NOT_READY before scene,
+ * uniforms and size; MPT_ERR_BAD_SCENE from the light table, as mpt_direct_lighting.                                                   */
+int mpt_render_nee_adaptive(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, const mpt_adaptive_params* a,
+                            mpt_adaptive_info* out /* may be NULL */, mpt_nee_info* nee_out /* may be NULL */);
 
 /* ---- light sampling: a sphere light by the solid angle it subtends ---------------------------------------------------------------------
  * A property of the context, host state only: how mpt_direct_lighting, mpt_direct_image and mpt_render_nee sample a SPHERE light.  It is

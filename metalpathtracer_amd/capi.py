@@ -38,7 +38,7 @@ SYMBOLS = (
     "mpt_display_image",
     "mpt_trace_occluded", "mpt_time_trace", "mpt_ambient_occlusion", "mpt_read_ao", "mpt_ao_buffer", "mpt_ao_image",
     "mpt_light_info", "mpt_read_lights", "mpt_direct_lighting", "mpt_read_direct", "mpt_direct_buffer", "mpt_direct_image",
-    "mpt_render_nee", "mpt_set_light_sampling", "mpt_get_light_sampling",
+    "mpt_render_nee", "mpt_set_light_sampling", "mpt_get_light_sampling", "mpt_render_nee_adaptive",
 )
 
 # mpt_scene_digest's words: the nine device arrays (mpt_read_scene_array's `which`), then the seven counts
@@ -395,6 +395,8 @@ def load():
     L.mpt_direct_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.mpt_direct_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(DirectParams), fp, up, up]
     L.mpt_render_nee.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(NeeInfo)]
+    L.mpt_render_nee_adaptive.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(AdaptiveParams),
+                                          C.POINTER(AdaptiveInfo), C.POINTER(NeeInfo)]
     L.mpt_set_light_sampling.argtypes = [vp, C.c_int32]
     L.mpt_get_light_sampling.argtypes = [vp, C.POINTER(C.c_int32)]
     _lib = L
@@ -723,6 +725,18 @@ class Context:
         info = NeeInfo()
         self._chk(self.L.mpt_render_nee(self.h, C.byref(p), C.byref(n), C.byref(info)), "mpt_render_nee")
         return info.as_dict()
+
+    def render_nee_adaptive(self, threshold, min_samples=0, batch_samples=0, luminance_floor=0.0, walk=WALK_AUTO, clamp=0.0, **params):
+        """mpt_render_nee_adaptive: render_nee's estimator with render_adaptive's allocation, every 8x8 tile deciding on the device in
+        one launch; sample_count (params) is the most samples a tile gets.  Clears the sum, the moments and the tile counts first.
+        Returns {"adaptive": the mpt_adaptive_info, "nee": the mpt_nee_info}, each as a dict."""
+        p = self.params(**params)
+        n = NeeParams(int(walk), float(clamp))
+        a = AdaptiveParams(int(min_samples), int(batch_samples), float(threshold), float(luminance_floor))
+        info, nee = AdaptiveInfo(), NeeInfo()
+        self._chk(self.L.mpt_render_nee_adaptive(self.h, C.byref(p), C.byref(n), C.byref(a), C.byref(info), C.byref(nee)),
+                  "mpt_render_nee_adaptive")
+        return {"adaptive": info.as_dict(), "nee": nee.as_dict()}
 
     def set_light_sampling(self, mode):
         """mpt_set_light_sampling: LIGHT_SAMPLING_AREA (the default) or LIGHT_SAMPLING_CONE — how direct_lighting, direct_image and

@@ -397,6 +397,22 @@ mpt_nee_info Renderer::renderNee(uint32_t spp, int32_t depth, int32_t walk, floa
     sumSamples_ += spp;
     return info;
 }
+mpt_adaptive_info Renderer::renderNeeAdaptive(uint32_t maxSamples, int32_t depth, const mpt_adaptive_params& a, int32_t walk, float clamp,
+                                              uint32_t sampleBegin, mpt_nee_info* neeInfo) {
+    uniforms_.primitiveCount = scene_->getPrimitiveCount();
+    uniforms_.triangleCount = scene_->getTriangleCount();
+    check(mpt_set_uniforms(ctx_, &uniforms_), "mpt_set_uniforms");
+    mpt_render_params p = params_;
+    p.max_depth = depth;
+    p.sample_begin = sampleBegin;
+    p.sample_count = maxSamples;
+    const mpt_nee_params n = {walk, clamp};
+    mpt_adaptive_info info;
+    check(mpt_render_nee_adaptive(ctx_, &p, &n, &a, &info, neeInfo), "mpt_render_nee_adaptive");
+    lastSource_ = MPT_DENOISE_SUM;
+    sumSamples_ = 0;   // (the tiles hold different counts, as after renderAdaptive)
+    return info;
+}
 void Renderer::setLightSampling(int mode) { check(mpt_set_light_sampling(ctx_, static_cast<int32_t>(mode)), "mpt_set_light_sampling"); }
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;

@@ -90,6 +90,10 @@ public:
     // mpt_render_nee: renderBatch's samples [sampleBegin, sampleBegin + spp) onto the HDR sum with a light sample and MIS at every Lambert
     // vertex, at max_depth `depth`, both kinds of ray through `walk` (MPT_WALK_*), per-sample clamp `clamp` (<= 0: none)
     mpt_nee_info renderNee(uint32_t spp, int32_t depth, int32_t walk = MPT_WALK_AUTO, float clamp = 0.0f, uint32_t sampleBegin = 0);
+    // mpt_render_nee_adaptive: renderNee's estimator, [sampleBegin, sampleBegin + maxSamples) at most per tile, every tile stopped on the
+    // device by renderAdaptive's rule (a); the sum is cleared first, readAdaptiveMean gives the image; neeInfo, if given, gets the NEE counts
+    mpt_adaptive_info renderNeeAdaptive(uint32_t maxSamples, int32_t depth, const mpt_adaptive_params& a, int32_t walk = MPT_WALK_AUTO,
+                                        float clamp = 0.0f, uint32_t sampleBegin = 0, mpt_nee_info* neeInfo = nullptr);
     // mpt_set_light_sampling: how renderDirectLighting and renderNee sample a sphere light (MPT_LIGHT_SAMPLING_AREA, the default, or
     // MPT_LIGHT_SAMPLING_CONE); a bad mode throws and changes nothing
     void setLightSampling(int mode);

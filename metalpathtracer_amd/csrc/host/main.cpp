@@ -45,6 +45,7 @@ static void usage() {
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]] [--ao N [--ao-radius R]]\n"
         "           [--direct N [--direct-walk reference|own|auto]]\n"
         "           [--nee [--nee-walk reference|own|auto] [--nee-clamp C]]\n"
+        "           [--nee-adaptive THRESHOLD [--nee-walk ...] [--nee-clamp C] [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--light-sampling area|cone]\n"
         "           [--adaptive THRESHOLD [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--temporal [--temporal-history N] [--temporal-spp K]]\n"
@@ -96,7 +97,17 @@ static void usage() {
         "                    estimator and its clamp (header MPTNEE1) and is resumed only by an --nee run with the same clamp, a plain one\n"
         "                    only by a plain run.  Not with --adaptive, --gpus > 1, --camera-path (hence --temporal, --svgf), --frames,\n"
         "                    --ao, --direct, --rng literal or --bsdf scatter-all\n"
-        "  --light-sampling  with --direct or --nee: how a sphere light is sampled (mpt_set_light_sampling, include/mpt.h) — area: uniformly\n"
+        "  --nee-adaptive T  render the still image with the estimator of --nee and the allocation of --adaptive in ONE kernel launch\n"
+        "                    (mpt_render_nee_adaptive, include/mpt.h): the wave that renders an 8x8 tile keeps its pixels' sums and second\n"
+        "                    moments in registers and applies the stopping rule of --adaptive itself, after --adaptive-min samples and then\n"
+        "                    every --adaptive-batch, up to --spp.  Takes --nee-walk, --nee-clamp and --light-sampling as --nee does,\n"
+        "                    --adaptive-min, --adaptive-batch and --adaptive-floor as --adaptive does, --denoise and the display flags over\n"
+        "                    the per-pixel mean, which --out gets; the JSON line gains the \"adaptive\" and the \"nee\" object.  A flag of\n"
+        "                    its own because --nee --adaptive stays refused: those two calls keep their contracts (mpt_render_nee adds to\n"
+        "                    the sum and writes no moments, mpt_render_adaptive drives the plain path loop in host passes).  Not with --nee,\n"
+        "                    --adaptive, --gpus > 1, --camera-path, --frames, --checkpoint, --resume, --ao, --direct, --rng literal or\n"
+        "                    --bsdf scatter-all\n"
+        "  --light-sampling  with --direct, --nee or --nee-adaptive: how a sphere light is sampled (mpt_set_light_sampling, include/mpt.h) — area: uniformly\n"
         "                    over its whole surface (the default); cone: uniformly in the cone of directions it subtends from the\n"
         "                    shading point, so that every sample meets the light.  Triangle lights are sampled the same either way.  The\n"
         "                    \"direct\" / \"nee\" JSON object gains \"light_sampling\"; a checkpoint of an --nee render with cone sampling\n"
@@ -386,6 +397,7 @@ int main(int argc, char** argv) {
     bool nee = false, haveNeeOpt = false;   // --nee; --nee-walk / --nee-clamp were given
     int32_t neeWalk = MPT_WALK_AUTO;
     float neeClamp = 0.0f;
+    bool neeAdaptive = false;   // --nee-adaptive T (the threshold goes into adp, as --adaptive's)
     bool haveLightSampling = false;   // --light-sampling was given
     int lightSampling = MPT_LIGHT_SAMPLING_AREA;
     bool display = false;   // a display flag was given: .ppm files come from mpt_display
@@ -467,6 +479,10 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
         else if (a == "--adaptive") {
             adaptive = true;
+            adp.threshold = static_cast<float>(std::atof(next()));
+        }
+        else if (a == "--nee-adaptive") {
+            neeAdaptive = true;
             adp.threshold = static_cast<float>(std::atof(next()));
         }
         else if (a == "--temporal") temporal = true;
@@ -559,11 +575,21 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "mpt_render: --key, --percentile and --adaptation go with --auto-exposure\n");
         return 2;
     }
-    if (haveLightSampling && !nee && !haveDirect) {
-        std::fprintf(stderr, "mpt_render: --light-sampling goes with --direct or --nee\n");
+    if (neeAdaptive) {   // (first: whatever it meets, the message names this flag)
+        const char* why = nee ? "--nee" : adaptive ? "--adaptive" : neeClamp != neeClamp ? "a --nee-clamp that is no number" : gpus > 1 ? "--gpus > 1"
+                          : !cameraPath.empty() ? "--camera-path" : frames > 0 ? "--frames" : !checkpoint.empty() ? "--checkpoint"
+                          : !resume.empty() ? "--resume" : haveAo || haveAoRadius ? "--ao" : haveDirect || haveDirectWalk ? "--direct"
+                          : prm.rng_mode == MPT_RNG_LITERAL ? "--rng literal" : prm.bsdf_mode == MPT_BSDF_SCATTER_ALL ? "--bsdf scatter-all" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: --nee-adaptive cannot be combined with %s\n", why);
+            return 2;
+        }
+    }
+    if (haveLightSampling && !nee && !haveDirect && !neeAdaptive) {
+        std::fprintf(stderr, "mpt_render: --light-sampling goes with --direct, --nee or --nee-adaptive\n");
         return 2;
     }
-    if (nee || haveNeeOpt) {
+    if (!neeAdaptive && (nee || haveNeeOpt)) {
         const char* why = !nee ? "a run without --nee" : neeClamp != neeClamp ? "a --nee-clamp that is no number" : adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1"
                           : !cameraPath.empty() ? "--camera-path" : frames > 0 ? "--frames" : haveAo || haveAoRadius ? "--ao"
                           : haveDirect || haveDirectWalk ? "--direct"
@@ -672,8 +698,10 @@ int main(int argc, char** argv) {
                           direct, (unsigned long long)info.pixels_surface, (unsigned long long)info.rays, (unsigned long long)info.rays_occluded,
                           (unsigned long long)info.lights, info.device_ms);
             extraJson = buf + samplingJson + "}";
-        } else if (adaptive) {
-            const mpt_adaptive_info info = r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);
+        } else if (adaptive || neeAdaptive) {
+            mpt_nee_info neeInfo = {};
+            const mpt_adaptive_info info = neeAdaptive ? r.renderNeeAdaptive(static_cast<uint32_t>(spp), depth, adp, neeWalk, neeClamp, 0, &neeInfo)
+                                                       : r.renderAdaptive(0, static_cast<uint32_t>(spp), adp);
             if (!display || denoise) r.readAdaptiveMean(img);
             if (display && !denoise) present(r, shown, MPT_DISPLAY_ADAPTIVE);
             if (denoise) {   // the mean through the filter kernels, with the context's guides (mpt_read_aovs + mpt_denoise_image)
@@ -696,6 +724,13 @@ int main(int argc, char** argv) {
                           info.passes, (unsigned long long)info.samples, info.tiles_converged, info.tiles_at_max,
                           pixels > 0 ? static_cast<double>(info.samples) / pixels : 0.0);
             extraJson = buf;
+            if (neeAdaptive) {
+                char nbuf[320];
+                std::snprintf(nbuf, sizeof nbuf, ", \"nee\": {\"paths\": %llu, \"rays\": %llu, \"shadow_rays\": %llu, \"shadow_rays_occluded\": %llu, \"lights\": %llu, \"device_ms\": %.3f",
+                              (unsigned long long)neeInfo.paths, (unsigned long long)neeInfo.rays, (unsigned long long)neeInfo.shadow_rays,
+                              (unsigned long long)neeInfo.shadow_rays_occluded, (unsigned long long)neeInfo.lights, neeInfo.device_ms);
+                extraJson += nbuf + samplingJson + "}";
+            }
         } else if (!cameraPath.empty()) {
             if (temporal) r.setTemporalParams(tpp);
             if (svgf) {

@@ -24,8 +24,24 @@ __device__ __forceinline__ double adaptive_lum(float r, float g, float b) {
     return ((double)0.2126f * (double)r + (double)0.7152f * (double)g) + (double)0.0722f * (double)b;
 }
 
+// The stopping rule per pixel, written once (k_adaptive_eval below and the NEE render that decides in the wave, mpt_nee_adaptive.h):
+// the relative standard error of the mean luminance of a pixel that holds n_samples samples, from its float32 sum and the luminance
+// moment m2.w, in double precision.
+__device__ __forceinline__ double adaptive_pixel_error(const float4& s4, float m2w, uint32_t n_samples, double luminance_floor) {
+    const double n = (double)n_samples;
+    const double s = adaptive_lum(s4.x, s4.y, s4.z);
+    const double mean = s / n;
+    const double var = fmax(0.0, ((double)m2w - s * mean) / (n - 1.0));
+    return sqrt(var / n) / fmax(mean, luminance_floor);
+}
+// The tile's error: the maximum over the wave's lanes (cross-lane shuffles; every lane gets it).
+__device__ __forceinline__ double adaptive_tile_error(double err) {
+    for (int off = 32; off > 0; off >>= 1) err = fmax(err, __shfl_xor(err, off));
+    return err;
+}
+
 // One wave64 per list entry.  err = sqrt(var / n) / max(mean, floor) per pixel inside the image (0 outside), the tile's error is the
-// wave maximum (cross-lane shuffles); lane 0 writes the tile's count and whether it stays active (error > threshold and n < N).
+// wave maximum; lane 0 writes the tile's count and whether it stays active (error > threshold and n < N).
 __global__ __launch_bounds__(256) void k_adaptive_eval(AdaptiveEval a) {
     const uint32_t e = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
     if (e >= a.n_list) return;   // (wave-uniform)
@@ -35,13 +51,9 @@ __global__ __launch_bounds__(256) void k_adaptive_eval(AdaptiveEval a) {
     if (px < a.width && py < a.height) {
         const size_t i = (size_t)py * a.width + px;
         const float4 s4 = a.sum[i], q4 = a.m2[i];
-        const double n = (double)a.n;
-        const double s = adaptive_lum(s4.x, s4.y, s4.z);
-        const double mean = s / n;
-        const double var = fmax(0.0, ((double)q4.w - s * mean) / (n - 1.0));
-        err = sqrt(var / n) / fmax(mean, a.luminance_floor);
+        err = adaptive_pixel_error(s4, q4.w, a.n, a.luminance_floor);
     }
-    for (int off = 32; off > 0; off >>= 1) err = fmax(err, __shfl_xor(err, off));
+    err = adaptive_tile_error(err);
     if (lane == 0u) {
         a.tile_count[(size_t)ty * a.tiles_x + tx] = a.n;
         a.flag[e] = err > a.threshold && a.n < a.n_max ? 1u : 0u;

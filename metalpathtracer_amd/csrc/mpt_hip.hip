@@ -48,6 +48,7 @@
 #include "mpt_ao.h"
 #include "mpt_direct.h"
 #include "mpt_nee.h"
+#include "mpt_nee_adaptive.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -546,7 +547,10 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
                           (const void*)k_direct<MPT_AO_REF_ALL_LDS>, (const void*)k_direct<MPT_AO_OWN>, (const void*)k_nee<MPT_AO_REF>,
                           (const void*)k_nee<MPT_AO_REF_ALL_LDS>, (const void*)k_nee<MPT_AO_OWN>, (const void*)k_direct_cone<MPT_AO_REF>,
                           (const void*)k_direct_cone<MPT_AO_REF_ALL_LDS>, (const void*)k_direct_cone<MPT_AO_OWN>, (const void*)k_nee_cone<MPT_AO_REF>,
-                          (const void*)k_nee_cone<MPT_AO_REF_ALL_LDS>, (const void*)k_nee_cone<MPT_AO_OWN>})
+                          (const void*)k_nee_cone<MPT_AO_REF_ALL_LDS>, (const void*)k_nee_cone<MPT_AO_OWN>, (const void*)k_nee_adaptive<MPT_AO_REF>,
+                          (const void*)k_nee_adaptive<MPT_AO_REF_ALL_LDS>, (const void*)k_nee_adaptive<MPT_AO_OWN>,
+                          (const void*)k_nee_adaptive_cone<MPT_AO_REF>, (const void*)k_nee_adaptive_cone<MPT_AO_REF_ALL_LDS>,
+                          (const void*)k_nee_adaptive_cone<MPT_AO_OWN>})
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = ctx.release();
     return MPT_OK;
@@ -1961,19 +1965,28 @@ extern "C" int mpt_gpu_leaf_max(uint64_t n_prims) { return gpu_leaf_max(n_prims)
 // ---- next-event estimation (mpt_nee.h; the estimator is specified in include/mpt.h) -------------------------------------------------
 // One launch of k_nee<WALK> over the whole image on ctx->stream, synchronous like mpt_render: the renders in flight are collected first,
 // the light table is built if stale, the kernel adds its samples onto the HDR sum in place.
-static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
+// The two NEE renders (mpt_render_nee and mpt_render_nee_adaptive, mpt_nee_adaptive.h) share their host steps:
+//   nee_check_params  what both refuse in p and n, before anything is waited for or touched
+//   nee_ready         the renders in flight collected, the context ready, the light table built, the four totals zeroed on the stream
+//   nee_fill_pass     the NeePass of p and n
+//   nee_launch        the kernel of the walk and of `cone` between the two timing events
+//   nee_collect       the totals read back (this synchronises), the statistics and the info
+static int nee_check_params(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n) {
     if (!ctx) return MPT_ERR_INVALID_ARG;
     if (!p || !n) return fail(ctx, MPT_ERR_INVALID_ARG, "null render or NEE params");
-    if (p->rng_mode != MPT_RNG_PHILOX) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: rng_mode must be MPT_RNG_PHILOX");
+    if (p->rng_mode != MPT_RNG_PHILOX) return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: rng_mode must be MPT_RNG_PHILOX");
     if (p->bsdf_mode != MPT_BSDF_LAMBERT && p->bsdf_mode != MPT_BSDF_SCATTER)
-        return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: bsdf_mode must be MPT_BSDF_LAMBERT or MPT_BSDF_SCATTER");
-    if (p->shard_count != 1 || p->shard_rank != 0) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: no shards");
-    if (p->flags != 0u) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: flags must be 0");
+        return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: bsdf_mode must be MPT_BSDF_LAMBERT or MPT_BSDF_SCATTER");
+    if (p->shard_count != 1 || p->shard_rank != 0) return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: no shards");
+    if (p->flags != 0u) return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: flags must be 0");
     if (p->sample_count == 0u || (uint64_t)p->sample_begin + p->sample_count > (1ull << 27))
-        return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: sample_count 0 or samples beyond 2^27");
-    if (p->max_depth < 1 || p->max_depth > 32) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: max_depth outside 1..32");
-    if (!walk_valid(n->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: bad walk");
-    if (n->clamp != n->clamp) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee: NaN clamp");
+        return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: sample_count 0 or samples beyond 2^27");
+    if (p->max_depth < 1 || p->max_depth > 32) return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: max_depth outside 1..32");
+    if (!walk_valid(n->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: bad walk");
+    if (n->clamp != n->clamp) return fail(ctx, MPT_ERR_INVALID_ARG, "NEE render: NaN clamp");
+    return MPT_OK;
+}
+static int nee_ready(mpt_ctx* ctx) {
     int rc = wait_impl(ctx);
     if (rc) return rc;
     if (!ctx->have_scene || !ctx->have_uniforms || !ctx->W) return fail(ctx, MPT_ERR_NOT_READY, "scene, uniforms or size not set");
@@ -1988,9 +2001,11 @@ static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_n
         HIPCHK(ns.e1.create(hipEventCreate));
     }
     HIPCHK(hipMemsetAsync(ns.totals.get(), 0, 32, ctx->stream));
-    NeePass P = {};
+    return MPT_OK;
+}
+static void nee_fill_pass(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, NeePass& P) {
     P.sum = ctx->d_sum;
-    P.totals = ns.totals.get();
+    P.totals = ctx->nee.totals.get();
     P.lights = ctx->lights.rec.get();
     P.cdf = ctx->lights.cdf.get();
     P.ids = ctx->lights.d_ids.get();
@@ -1998,17 +2013,23 @@ static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_n
     float key[14];
     guide_key(ctx->u, key);
     pass_frame(P, key, ctx->W, ctx->H, *p);
-    P.fW = key[12];   // uniforms.screenSize itself, as gen_primary divides by it (the check above compares it with (W, H) as integers)
+    P.fW = key[12];   // uniforms.screenSize itself, as gen_primary divides by it (nee_ready compares it with (W, H) as integers)
     P.fH = key[13];
     P.bsdf_mode = p->bsdf_mode;
     P.max_depth = p->max_depth;
     P.primitive_count = (uint32_t)std::min<uint64_t>(ctx->u.primitiveCount, 0xFFFFFFFFull);
     P.clamp = n->clamp > 0.0f ? n->clamp : INFINITY;
-    static const WalkKernel<NeePass> area[3] = {k_nee<MPT_AO_REF>, k_nee<MPT_AO_REF_ALL_LDS>, k_nee<MPT_AO_OWN>},
-                                     cone[3] = {k_nee_cone<MPT_AO_REF>, k_nee_cone<MPT_AO_REF_ALL_LDS>, k_nee_cone<MPT_AO_OWN>};
-    HIPCHK(hipEventRecord(ns.e0.get(), ctx->stream));
-    if ((rc = tile_walk_launch(ctx, ctx->W, ctx->H, n->walk, ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE ? cone : area, P))) return rc;
-    HIPCHK(hipEventRecord(ns.e1.get(), ctx->stream));
+}
+template <class Pass>
+static int nee_launch(mpt_ctx* ctx, int32_t walk, bool cone, const WalkKernel<Pass> k_area[3], const WalkKernel<Pass> k_cone[3], const Pass& P) {
+    HIPCHK(hipEventRecord(ctx->nee.e0.get(), ctx->stream));
+    const int rc = tile_walk_launch(ctx, ctx->W, ctx->H, walk, cone ? k_cone : k_area, P);
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(ctx->nee.e1.get(), ctx->stream));
+    return MPT_OK;
+}
+static int nee_collect(mpt_ctx* ctx, mpt_nee_info* out) {
+    NeeState& ns = ctx->nee;
     unsigned long long totals[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(totals, ns.totals.get(), 32, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2029,8 +2050,73 @@ static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_n
     }
     return MPT_OK;
 }
+static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
+    int rc = nee_check_params(ctx, p, n);
+    if (rc) return rc;
+    if ((rc = nee_ready(ctx))) return rc;
+    NeePass P = {};
+    nee_fill_pass(ctx, p, n, P);
+    static const WalkKernel<NeePass> area[3] = {k_nee<MPT_AO_REF>, k_nee<MPT_AO_REF_ALL_LDS>, k_nee<MPT_AO_OWN>},
+                                     cone[3] = {k_nee_cone<MPT_AO_REF>, k_nee_cone<MPT_AO_REF_ALL_LDS>, k_nee_cone<MPT_AO_OWN>};
+    if ((rc = nee_launch(ctx, n->walk, ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE, area, cone, P))) return rc;
+    return nee_collect(ctx, out);
+}
 extern "C" int mpt_render_nee(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
     return guarded(ctx, [&] { return render_nee_impl(ctx, p, n, out); });
+}
+
+// mpt_render_nee_adaptive: ONE launch of k_nee_adaptive<WALK> over the whole image.  Every wave renders its tile up to the quota of
+// mpt_render_adaptive's schedule, applies the stopping rule itself and goes on or stops (mpt_nee_adaptive.h); the host clears the three
+// buffers before the launch and derives the info from the tile counts after it.
+static int render_nee_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, const mpt_adaptive_params* a,
+                                    mpt_adaptive_info* out, mpt_nee_info* nee_out) {
+    int rc = nee_check_params(ctx, p, n);
+    if (rc) return rc;
+    if (!a) return fail(ctx, MPT_ERR_INVALID_ARG, "null adaptive params");
+    const uint32_t N = p->sample_count;
+    if (a->min_samples == 1u || !(a->threshold >= 0.0f) || N < 2u)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "bad adaptive params (min_samples 1, threshold < 0 or NaN, or sample_count < 2)");
+    const bool cone = ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE;   // (read at the start, as mpt_render_nee reads it)
+    if ((rc = nee_ready(ctx))) return rc;
+    const uint32_t tiles_x = (ctx->W + 7) / 8, tiles_y = (ctx->H + 7) / 8, tiles = tiles_x * tiles_y;
+    if ((rc = ensure_adaptive_buffers(ctx, tiles))) return rc;
+    if (!ctx->d_m2) HIPCHK(ctx->d_m2.alloc((size_t)ctx->W * ctx->H * 16));   // (cleared with the sum, next)
+    if ((rc = clear_sum_impl(ctx))) return rc;
+    HIPCHK(hipMemsetAsync(ctx->ad.tile_count.get(), 0, (size_t)tiles * 4, ctx->stream));
+    NeeAdaptivePass A = {};
+    nee_fill_pass(ctx, p, n, A.nee);
+    A.m2 = ctx->d_m2.get();
+    A.tile_count = ctx->ad.tile_count.get();
+    A.tiles_x = tiles_x;
+    A.min_samples = a->min_samples ? a->min_samples : MPT_ADAPTIVE_DEFAULT_MIN_SAMPLES;
+    A.batch = a->batch_samples ? a->batch_samples : MPT_ADAPTIVE_DEFAULT_BATCH;
+    A.threshold = a->threshold;
+    A.floor = a->luminance_floor > 0.0f ? a->luminance_floor : MPT_ADAPTIVE_DEFAULT_LUMINANCE_FLOOR;
+    static const WalkKernel<NeeAdaptivePass> k_area[3] = {k_nee_adaptive<MPT_AO_REF>, k_nee_adaptive<MPT_AO_REF_ALL_LDS>,
+                                                          k_nee_adaptive<MPT_AO_OWN>},
+                                             k_cone[3] = {k_nee_adaptive_cone<MPT_AO_REF>, k_nee_adaptive_cone<MPT_AO_REF_ALL_LDS>,
+                                                          k_nee_adaptive_cone<MPT_AO_OWN>};
+    if ((rc = nee_launch(ctx, n->walk, cone, k_area, k_cone, A))) return rc;
+    if ((rc = nee_collect(ctx, nee_out))) return rc;
+    std::vector<uint32_t> counts(tiles);
+    HIPCHK(hipMemcpy(counts.data(), ctx->ad.tile_count.get(), (size_t)tiles * 4, hipMemcpyDeviceToHost));
+    const uint32_t n0 = std::min(A.min_samples, N);
+    mpt_adaptive_info info = {};
+    for (uint32_t t = 0; t < tiles; ++t) {
+        const uint32_t tx = t % tiles_x, ty = t / tiles_x, c = counts[t];
+        const uint64_t px = (uint64_t)std::min<uint32_t>(8u, ctx->W - tx * 8u) * std::min<uint32_t>(8u, ctx->H - ty * 8u);
+        info.samples += px * c;
+        (c == N ? info.tiles_at_max : info.tiles_converged)++;
+        // the schedule steps this tile took, the first included: n_0, then batches up to its count
+        const uint32_t steps = c <= n0 ? 1u : 1u + (uint32_t)(((uint64_t)(c - n0) + A.batch - 1u) / A.batch);
+        info.passes = std::max(info.passes, steps);
+    }
+    if (out) *out = info;
+    return MPT_OK;
+}
+extern "C" int mpt_render_nee_adaptive(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, const mpt_adaptive_params* a,
+                                       mpt_adaptive_info* out, mpt_nee_info* nee_out) {
+    return guarded(ctx, [&] { return render_nee_adaptive_impl(ctx, p, n, a, out, nee_out); });
 }
 // How mpt_direct_lighting, mpt_direct_image and mpt_render_nee sample a sphere light: host state of the context alone — no scene call,
 // mpt_resize or mpt_clear_sum touches it, and the light table does not depend on it.

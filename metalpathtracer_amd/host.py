@@ -27,6 +27,7 @@ SYMBOLS = (
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
     "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_render_nee", "mpt_renderer_set_light_sampling",
+    "mpt_renderer_render_nee_adaptive",
 )
 
 _lib = None
@@ -87,6 +88,8 @@ def load():
     L.mpt_renderer_direct_lighting.argtypes = [vp, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.POINTER(capi.DirectInfo)]
     L.mpt_renderer_render_nee.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.NeeInfo)]
     L.mpt_renderer_set_light_sampling.argtypes = [vp, C.c_int32]
+    L.mpt_renderer_render_nee_adaptive.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.AdaptiveParams),
+                                                   C.POINTER(capi.AdaptiveInfo), C.POINTER(capi.NeeInfo)]
     _lib = L
     return L
 
@@ -414,6 +417,16 @@ class Renderer:
         info = capi.NeeInfo()
         self._chk(self.L.mpt_renderer_render_nee(self.h, int(spp), int(depth), int(walk), float(clamp), C.byref(info)), "renderNee")
         return info.as_dict()
+
+    def renderNeeAdaptive(self, max_samples, depth, threshold, min_samples=0, batch_samples=0, luminance_floor=0.0, walk=capi.WALK_AUTO,
+                          clamp=0.0):
+        """mpt_renderer_render_nee_adaptive: renderNee's estimator, at most max_samples per 8x8 tile, every tile stopped on the device by
+        renderAdaptive's rule (counts per tile: readTileSamples).  Returns {"adaptive": ..., "nee": ...}, the two infos as dicts."""
+        a = capi.AdaptiveParams(int(min_samples), int(batch_samples), float(threshold), float(luminance_floor))
+        info, nee = capi.AdaptiveInfo(), capi.NeeInfo()
+        self._chk(self.L.mpt_renderer_render_nee_adaptive(self.h, int(max_samples), int(depth), int(walk), float(clamp), C.byref(a),
+                                                          C.byref(info), C.byref(nee)), "renderNeeAdaptive")
+        return {"adaptive": info.as_dict(), "nee": nee.as_dict()}
 
     def setLightSampling(self, mode):
         """mpt_renderer_set_light_sampling: capi.LIGHT_SAMPLING_AREA (the default) or capi.LIGHT_SAMPLING_CONE for renderDirectLighting
