@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mpt_lean_entry.h"   // MPT_NODE_TAIL and the bound of the tail leaf's guard
+
 #define MPT_WAVE 64
 #define MPT_NSHARD 16
 #define MPT_NGROUP 8          // work-cursor groups (one per XCD under round-robin placement)
@@ -481,10 +483,16 @@ __device__ __forceinline__ bool slab_hit(float4 n0, float4 n1, F3 o, float idx, 
     hi = fminf(hi, idz < 0.0f ? t0 : t1);
     return hi > lo;
 }
+// LEAN and ALL_LDS, the tail leaf (MPT_LEAN_TAIL, mpt_lean_entry.h): in the staged image every link to the walk's last node T is the
+// marker MPT_NODE_TAIL, "done" for the loop below.  The lanes that hold it test T once behind the loop: its box only where the guard
+// does not already know the answer, then its primitives — one leaf for all of them, so first and count are scalars.  `tail_cfg`: the four
+// float4 the workgroup staged for it, (tlo, T's leaf word) (thi, tail_primary) and T's two plane records.  A launch with the item off has
+// no marker in its image and never enters the branch.
+static_assert(MPT_LEAN_LEAF_BIT == MPT_NODE_HOLD && MPT_NODE_TAIL < MPT_NODE_HOLD, "mpt_lean_entry.h: the leaf bit and the tail marker");
 template <bool COUNT, bool ALL_LDS, bool BUDGETED, bool LEAN = false, bool PRIMARY = false>
 __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes lds_nodes, F3 o, F3 d, uint32_t& node,
                                                    float& best_t, int& best_prim, uint32_t budget, WorkCount& wc,
-                                                   uint32_t min_active = 0u) {
+                                                   uint32_t min_active = 0u, LdsNodes tail_cfg = nullptr) {
     float idx, idy, idz;
     mpt_rcp3(d.x, d.y, d.z, idx, idy, idz);   // PathTracing.h:61 (per call there): 1.0 / r.direction[i]
     const uint32_t n_nodes = sc.n_nodes, n_lds = sc.n_lds_nodes;
@@ -584,6 +592,34 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         // ... and, in a budgeted step, while enough lanes are still working: the stragglers of a step are parked and
         // meet other stragglers in the next ring instead of holding 64 lanes for their long walks
         if (BUDGETED && (uint32_t)__popcll(going) < min_active) break;
+    }
+    if (LEAN && ALL_LDS && MPT_LEAN_ENTRY && MPT_LEAN_TAIL) {   // (the block is staged with the entry terms: wavelocal_body)
+        if (i == MPT_NODE_TAIL) {
+            const bool d_ok = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)) <= MPT_LEAN_ENTRY_DMAX;
+            bool hit;   // T's box test answers hit: known (`certain`), or made
+            uint32_t leaf;
+            if (PRIMARY) {   // the origin is the launch's camera: one word says whether it is inside [tlo, thi]
+                const __attribute__((address_space(3))) uint32_t* w = (const __attribute__((address_space(3))) uint32_t*)tail_cfg;
+                leaf = w[3];
+                hit = d_ok && w[7] != 0u;
+            } else {
+                const v4f tlo = tail_cfg[0], thi = tail_cfg[1];
+                leaf = __float_as_uint(tlo.w);
+                hit = d_ok && tlo.x <= o.x && o.x <= thi.x && tlo.y <= o.y && o.y <= thi.y && tlo.z <= o.z && o.z <= thi.z;
+            }
+#if !defined(MPT_LEAN_TAIL_NO_SLAB)   // (a test's build without the branch: tests/test_gpu_lean_tail.py must then fail)
+            if (__ballot(!hit) != 0ull) {
+                if (!hit) {
+                    const v4f a = tail_cfg[2], b = tail_cfg[3];
+                    hit = slab_hit(make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), o, idx, idy, idz, best_t);
+                }
+            }
+#endif
+            if (hit) {
+                const uint32_t enc = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf) & ~MPT_NODE_HOLD;
+                leaf_test<COUNT, LEAN, PRIMARY>(sc, lds_nodes, enc >> 4, (enc & 15u) + 1u, o, d, best_t, best_prim, wc);
+            }
+        }
     }
     node = i;
     return i >= n_nodes;
@@ -706,6 +742,9 @@ template <bool LEAN = false>
 __device__ __forceinline__ bool shade_bounce(const SceneDev& sc, LdsNodes lds, const ShadeParams& sp, const PathRngDev& g,
                                              PathState& ps, float t, int prim) {
     if (prim < 0) {  // PathTracing.h:225-232 sky
+        // (LEAN: ps.d left normalize3, so dot3(ps.d, ps.d) is within a few ulps of 1, where 1 / sqrt is a short integer function of the bits.
+        //  Built behind a wave-uniform guard, enumerated exact, and taken out again: 0.04 ms of 13.9, inside the run-to-run spread —
+        //  profiles/r20_lean_tail.txt.)
         F3 ud = normalize3<LEAN>(ps.d);
         float tt = 0.5f * (ud.y + 1.0f);
         F3 sky = f3(1.0f + (0.6f - 1.0f) * tt, 1.0f + (0.7f - 1.0f) * tt, 1.0f + (1.0f - 1.0f) * tt);

@@ -569,7 +569,7 @@ __device__ __forceinline__ uint32_t wave_rank(unsigned long long m) {
 #endif
 #define MPT_WL_RING 512u       // records per ring
 #define MPT_LDS_MATS_N 32u     // materials staged in LDS (= MPT_LDS_MATS of mpt_hip.hip): the configuration block of k_wavelocal / k_ordered starts behind them
-#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes): camera in float4 0..3, then 32 words (budgets 0..15, claim parameters 16..19); float4 10..11: the lean kernels' entry terms (mpt_lean_entry.h).
+#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes): camera in float4 0..3, then 32 words (budgets 0..15, claim parameters 16..19); float4 10..11: the lean kernels' entry terms, 12..15: their tail leaf (mpt_lean_entry.h).
                                // The host reserves it (MPT_LDS_EXTRA, ordered_views): k_ordered's stacks start right behind it.
 // Where the configuration block starts in a workgroup's LDS (float4 index), for the kernels AND for the host code that lays the
 // image out and sizes the launch (mpt_hip.hip: MPT_LDS_EXTRA, ordered_views) — one definition.  Round 4's development build of
@@ -773,12 +773,41 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // (a tree without nodes: A0 = 0 switches the item off, nothing is read)
             const bool tree = pp.scene.n_nodes != 0u;
             const LeanEntry e = lean_entry_terms(tree ? pp.scene.nodes[0] : none, tree ? pp.scene.nodes[1] : none, pp.scene.n_nodes, pp.cam.x, pp.cam.y, pp.cam.z);
-            lds_nodes_raw[cfg_off + 10] = make_float4(e.ilo[0], e.ilo[1], e.ilo[2], __uint_as_float(e.entry));
-            lds_nodes_raw[cfg_off + 11] = make_float4(e.ihi[0], e.ihi[1], e.ihi[2], __uint_as_float(e.entry_primary));
+            // the tail leaf (MPT_LEAN_TAIL, mpt_lean_entry.h): float4 12..15 — (tlo, T's leaf word) (thi, tail_primary) and T's own two records for the
+            // lanes that make its box test, with T (0: the item is off) in the place of its miss link, which no box test reads
+            uint32_t entry = e.entry, entry_primary = e.entry_primary;
+            if (ALL_LDS && MPT_LEAN_TAIL) {
+                static_assert(MPT_LDS_CFG_F4 >= 16u, "configuration block too small");
+                const LeanTail t = lean_tail_terms(pp.scene.nodes, pp.scene.n_nodes, pp.cam.x, pp.cam.y, pp.cam.z);
+                lds_nodes_raw[cfg_off + 12] = make_float4(t.tlo[0], t.tlo[1], t.tlo[2], __uint_as_float(t.leaf));
+                lds_nodes_raw[cfg_off + 13] = make_float4(t.thi[0], t.thi[1], t.thi[2], __uint_as_float(t.tail_primary));
+                float4 t0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t1 = t0;   // (values, not a choice between two addresses)
+                if (t.node != 0u) {
+                    t0 = pp.scene.nodes[2u * t.node];
+                    t1 = pp.scene.nodes[2u * t.node + 1u];
+                }
+                t1.w = __uint_as_float(t.node);
+                lds_nodes_raw[cfg_off + 14] = t0;
+                lds_nodes_raw[cfg_off + 15] = t1;
+                // a fresh query that enters at T enters at the marker
+                if (t.node != 0u && entry == t.node) entry = MPT_NODE_TAIL;
+                if (t.node != 0u && entry_primary == t.node) entry_primary = MPT_NODE_TAIL;
+            }
+            lds_nodes_raw[cfg_off + 10] = make_float4(e.ilo[0], e.ilo[1], e.ilo[2], __uint_as_float(entry));
+            lds_nodes_raw[cfg_off + 11] = make_float4(e.ihi[0], e.ihi[1], e.ihi[2], __uint_as_float(entry_primary));
         }
     }
     if (LEAN && MPT_LEAN_CAMSPHERE) stage_nodes_lean(pp.scene, lds_nodes_raw, pp.cam);
     else stage_nodes(pp.scene, lds_nodes_raw);
+    if (LEAN && ALL_LDS && MPT_LEAN_ENTRY && MPT_LEAN_TAIL) {   // every link to T in the image becomes the marker (the global array stays as it is)
+        const uint32_t tail_node = __float_as_uint(lds_nodes_raw[cfg_off + 15].w);
+        if (tail_node != 0u) {
+            uint32_t* links = (uint32_t*)lds_nodes_raw;
+            for (uint32_t k = threadIdx.x; k < pp.scene.n_lds_nodes * 2u; k += blockDim.x)
+                if (links[4u * k + 3u] == tail_node) links[4u * k + 3u] = MPT_NODE_TAIL;
+        }
+        __syncthreads();
+    }
     MPT_CLOCK_BEGIN();
     const LdsNodes lds_nodes = (LdsNodes)lds_nodes_raw;
     const __attribute__((address_space(3))) uint32_t* lds_cfg_u32 = (const __attribute__((address_space(3))) uint32_t*)(lds_nodes + cfg_off + 4u);
@@ -1083,13 +1112,13 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             bool done;
             if (budgeted)
                 done = closest_hit_resume<COUNT, ALL_LDS, true, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                     budget, wc, min_active);
+                                                                     budget, wc, min_active, lds_nodes + cfg_off + 12u);
             else if (LEAN && MPT_LEAN_CAMSPHERE && level < 0)   // a primary step: every origin is the camera (the staged sphere terms)
                 done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN, true>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                            0xFFFFFFFFu, wc);
+                                                                            0xFFFFFFFFu, wc, 0u, lds_nodes + cfg_off + 12u);
             else
                 done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                      0xFFFFFFFFu, wc);
+                                                                      0xFFFFFFFFu, wc, 0u, lds_nodes + cfg_off + 12u);
             MPT_TOC(reg_trace, tic_);
 #ifdef MPT_DEBUG_WAVE_TIMES
             if (COUNT) {  // per-level divergence diagnostics: [level + 1][steps, box trips, box lane work, prim trips, prim lane work]

@@ -74,3 +74,79 @@ MPT_LEAN_ENTRY_HD inline LeanEntry lean_entry_terms(const V4& n0, const V4& n1, 
     e.entry_primary = on && cam_in ? A0 : 0u;
     return e;
 }
+
+// ---- the tail leaf (MPT_LEAN_TAIL) ----------------------------------------------------------------------------------------------------
+// The last node of every complete walk, T: start at the root's hit link A0 and follow miss links while they name a node.  When the
+// device builder has hoisted the spheres (k_sah_to_radix_hoisted) T is their leaf record, the left child of the root, and the walk pops
+// the right child first: every walk that is not cut ends with T's box test, T's primitives, "done".  The lean kernels whose whole tree
+// is in LDS (ALL_LDS) replace every link to T in their staged image by the marker MPT_NODE_TAIL — a value >= n_nodes and below the
+// leaf bit, so "done" for the box loop and never parked — and closest_hit_resume tests T once, after its loop, for the lanes that hold
+// the marker: the same tests in the same order with the same best_t, at the width of those lanes and without the loop's rounds.
+// T's box test is made there only by lanes for which it is not known to answer "hit": by the argument at the top of this file, with T's
+// planes in the place of the root's, origins inside [tlo, thi] = [lo + 2m, hi - 2m] with |d_a| <= 2 hit (best_t at T is +inf or passed
+// `tt > 0.0001f`, as for a fresh query; a NaN direction never reaches the marker).
+// The item is on for a launch when the root is internal, T != 0, T is a leaf record whose miss link ends the walk (it does, by the
+// way T is found), n_nodes is below the marker (the link that ends a walk in the device's tree is n_nodes itself, mpt_scene_layout.h,
+// so no link of the tree is the marker by accident) and T's planes pass the staging check of lean_entry_terms.  Off: node = 0,
+// nothing is patched and the kernels run as without the item.
+// (MPT_LEAN_TAIL=0: pricing build of the lean kernels without it — profiles/r20_lean_tail.txt)
+#ifndef MPT_LEAN_TAIL
+#define MPT_LEAN_TAIL 1
+#endif
+#define MPT_NODE_TAIL 0x40000000u      // a link to T in the staged image
+#define MPT_LEAN_LEAF_BIT 0x80000000u  // MPT_NODE_HOLD (mpt_device.h): the hit link of a leaf record
+
+struct LeanTail {
+    float tlo[3], thi[3];      // origins with tlo <= o <= thi on every axis need no box test of T (none when the item is off)
+    uint32_t node;             // T, or 0 when the item is off
+    uint32_t leaf;             // T's hit link: MPT_NODE_HOLD | first << 4 | (count - 1); 0 when off
+    uint32_t tail_primary;     // 1 when the camera is such an origin, else 0
+};
+
+// nodes: the threaded tree as the device stores it, two V4 per node — (lo, hit link as bits) (hi, miss link as bits).
+template <class V4>
+MPT_LEAN_ENTRY_HD inline LeanTail lean_tail_terms(const V4* nodes, uint32_t n_nodes, float cam_x, float cam_y, float cam_z) {
+    const float m = MPT_LEAN_ENTRY_M, inf = __builtin_huge_valf();
+    const float cam[3] = {cam_x, cam_y, cam_z};
+    LeanTail t;
+    for (int a = 0; a < 3; ++a) {
+        t.tlo[a] = inf;
+        t.thi[a] = -inf;
+    }
+    t.node = t.leaf = t.tail_primary = 0u;
+    if (n_nodes == 0u || n_nodes >= MPT_NODE_TAIL) return t;
+    uint32_t T, B, steps = 0u;
+    const float a0 = nodes[0].w;
+    __builtin_memcpy(&T, &a0, sizeof T);
+    if (T == 0u || T >= n_nodes) return t;   // the root is a leaf record (or a tree of one box)
+    for (;; ++steps) {
+        const float b = nodes[2u * T + 1u].w;
+        __builtin_memcpy(&B, &b, sizeof B);
+        if (B >= n_nodes) break;
+        if (B == 0u || steps == n_nodes) return t;   // (links that never end: not a tree this code knows)
+        T = B;
+    }
+    uint32_t leaf;
+    const float l = nodes[2u * T].w;
+    __builtin_memcpy(&leaf, &l, sizeof leaf);
+    if ((leaf & MPT_LEAN_LEAF_BIT) == 0u) return t;   // T is internal (a chain node)
+    const float lo[3] = {nodes[2u * T].x, nodes[2u * T].y, nodes[2u * T].z}, hi[3] = {nodes[2u * T + 1u].x, nodes[2u * T + 1u].y, nodes[2u * T + 1u].z};
+    float tlo[3], thi[3];
+    bool on = true, cam_in = true;
+    for (int a = 0; a < 3; ++a) {
+        tlo[a] = lo[a] + 2.0f * m;
+        thi[a] = hi[a] - 2.0f * m;
+        // (written so that a NaN anywhere switches the item off)
+        on = on && (lo[a] - tlo[a] <= -m) && (hi[a] - thi[a] >= m) && tlo[a] <= thi[a];
+        cam_in = cam_in && tlo[a] <= cam[a] && cam[a] <= thi[a];
+    }
+    if (!on) return t;
+    for (int a = 0; a < 3; ++a) {
+        t.tlo[a] = tlo[a];
+        t.thi[a] = thi[a];
+    }
+    t.node = T;
+    t.leaf = leaf;
+    t.tail_primary = cam_in ? 1u : 0u;
+    return t;
+}
