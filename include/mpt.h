@@ -892,6 +892,50 @@ enum { MPT_LIGHT_SAMPLING_AREA = 0, MPT_LIGHT_SAMPLING_CONE = 1 };
 int mpt_set_light_sampling(mpt_ctx* ctx, int32_t mode);
 int mpt_get_light_sampling(mpt_ctx* ctx, int32_t* mode);
 
+/* ---- light candidates: resampled light sampling (RIS) ---------------------------------------------------------------------------------
+ * A property of the context, host state only, with the life of mpt_set_light_sampling: from how many CANDIDATES m a light sample of
+ * mpt_direct_lighting, mpt_direct_image and mpt_render_nee is resampled.  It is read at the start of each of the three calls, survives
+ * mpt_resize, mpt_upload_scene, mpt_build_and_upload and mpt_clear_sum and does not make the light table stale.  m = 1 (the default)
+ * is the contract of the sections above and launches their kernels: every result is theirs bit for bit.  m = 0, m >
+ * MPT_LIGHT_CANDIDATES_MAX or a null pointer: MPT_ERR_INVALID_ARG, nothing changed.  mpt_render_nee_adaptive with m > 1 returns
+ * MPT_ERR_INVALID_ARG with nothing rendered and nothing cleared (OUT OF SCOPE: that kernel has its own copy of the round).
+ * tests/ris_ref.py restates the rule in numpy.
+ *
+ * m >= 2.  A light sample is drawn blind — a light by power, a point uniformly on it — and a full any-hit walk is paid for whatever
+ * comes out.  Here m candidates are drawn that way, each is weighted by the light it would deliver unshadowed, one is kept in
+ * proportion to that weight in a streaming reservoir of one, and ONE shadow ray is traced.  float32, one IEEE operation at a time in the
+ * order written.  Everything not named below is the m = 1 contract under the light-sampling mode in effect: the selection by cdf, the
+ * sample geometry of a triangle and of a sphere (area or cone), the skip rule, tmax = dist * 0.9990234375f, sampled, pb, the weight of
+ * an emitter a bounce finds, the clamp, the sample order, the sky.
+ *
+ * Direct pass.  Per surface pixel and sample s: wsum = 0, nothing taken.  For j = 0 .. m-1, ascending:
+ *   r_j = philox4x32_10(counter = (py*W+px, s, 0xFFFFFFFD, j), key)       (j = 0 is the m = 1 block; word 2 = 0xFFFFFFFD is nobody else's)
+ *   candidate j: light k_j from u01(r_j.x), its point or direction from (u01(r_j.y), u01(r_j.z)), formed from o and n exactly as the
+ *     m = 1 sample: ok_j (the sample would not be skipped), wi_j, dist_j and its factor
+ *       fac_j = ((cos_s * cos_l) / d2) * inv_pdf[k_j]      a triangle; a sphere under AREA
+ *       fac_j = cos_s * J                                  a sphere under CONE
+ *   l_j = (0.2126f * Le.r + 0.7152f * Le.g) + 0.0722f * Le.b               (Le of light k_j, from the table)
+ *   w_j = l_j * fac_j;  the candidate COUNTS iff ok_j && w_j > 0 && w_j < +inf (a NaN does not); one that does not changes nothing
+ *   a candidate that counts: wsum = wsum + w_j; it is TAKEN iff nothing has been taken yet or u01(r_j.w) * wsum < w_j (r.w is the one
+ *     word the m = 1 sample leaves unused); taking it keeps wi_j, dist_j, Le_j and l_j as (wi_y, dist_y, Le_y, l_y)
+ * The sample is SKIPPED (no ray, not counted) unless a candidate was taken.  Otherwise traced += 1 and the shadow ray is
+ * any-hit(o, wi_y, dist_y * 0.9990234375f); not occluded: unoccluded += 1, Fy = (wsum / (float)m) / l_y,
+ * S += (Le_y.r * Fy, Le_y.g * Fy, Le_y.b * Fy).  rgba, the counts, the totals and the result's lifetime are unchanged.
+ *
+ * mpt_render_nee.  At a Lambert vertex where a light sample is attempted, the same loop over the blocks philox(p, s, b, 1 + j) (every
+ * other block has word 3 = 0; j = 0 is the m = 1 block), from the origin o' and the normal n.  The candidate's factor is the m_j of the
+ * m = 1 rule — the factor times its power-heuristic weight wl against pbs, in the area or the cone form — and w_j = l_j * m_j; counting,
+ * taking and skipping as above.  shadow_rays grows by one per vertex that took a candidate.  Not occluded:
+ *   Fy = (wsum / (float)m) / l_y,   L.c += ((thr.c * albedo.c) * 0.31830987f) * (Le_y.c * Fy)
+ * added where the m = 1 contribution is added.  sampled = attempt and pb are unchanged, and the emitter branch is the m = 1 branch.
+ *
+ * UNBIASED.  The target is p^ = l * fac (l * fac * wl in the render), the source pdf p is the m = 1 pdf, w_j = p^ / p, and the estimate
+ * is f(y) / p^(y) * (1/m) sum w_j with f = Le * fac * V: resampled importance sampling (Talbot et al. 2005), unbiased as p^ > 0
+ * wherever f != 0.  In the render the two MIS weights stay functions of the sampled point alone and still sum to 1.                   */
+#define MPT_LIGHT_CANDIDATES_MAX 32u
+int mpt_set_light_candidates(mpt_ctx* ctx, uint32_t m);   /* 1..MPT_LIGHT_CANDIDATES_MAX; default 1 */
+int mpt_get_light_candidates(mpt_ctx* ctx, uint32_t* m);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

@@ -109,6 +109,11 @@ int mpt_renderer_render_nee(mpt_renderer* r, uint32_t spp, int32_t depth, int32_
 /* mpt_set_light_sampling (include/mpt.h) on the renderer's context: MPT_LIGHT_SAMPLING_AREA (the default) or MPT_LIGHT_SAMPLING_CONE for
  * the two calls above.  A bad mode: MPT_ERR_INVALID_ARG, nothing changed.                                                             */
 int mpt_renderer_set_light_sampling(mpt_renderer* r, int32_t mode);
+/* mpt_set_light_candidates / mpt_get_light_candidates (include/mpt.h) on the renderer's context: from how many candidates, 1 (the
+ * default) to MPT_LIGHT_CANDIDATES_MAX, a light sample of the same two calls is resampled.  m outside that range or a null pointer:
+ * MPT_ERR_INVALID_ARG, nothing changed.  mpt_renderer_render_nee_adaptive refuses m > 1.                                              */
+int mpt_renderer_set_light_candidates(mpt_renderer* r, uint32_t m);
+int mpt_renderer_get_light_candidates(mpt_renderer* r, uint32_t* m);
 /* mpt_render_nee_adaptive (include/mpt.h) for the renderer's camera and render parameters: samples [0, max_samples) at most per 8x8 tile
  * at max_depth `depth`, stopped per tile on the device by the rule of p.  The sum is cleared first; the counts per tile are
  * mpt_read_tile_samples' on mpt_renderer_context.  out and nee_out may be NULL.                                                       */

@@ -39,6 +39,7 @@ SYMBOLS = (
     "mpt_trace_occluded", "mpt_time_trace", "mpt_ambient_occlusion", "mpt_read_ao", "mpt_ao_buffer", "mpt_ao_image",
     "mpt_light_info", "mpt_read_lights", "mpt_direct_lighting", "mpt_read_direct", "mpt_direct_buffer", "mpt_direct_image",
     "mpt_render_nee", "mpt_set_light_sampling", "mpt_get_light_sampling", "mpt_render_nee_adaptive",
+    "mpt_set_light_candidates", "mpt_get_light_candidates",
 )
 
 # mpt_scene_digest's words: the nine device arrays (mpt_read_scene_array's `which`), then the seven counts
@@ -67,6 +68,7 @@ AO_MAX_SAMPLES = 1024
 DIRECT_MAX_SAMPLES = 1024
 LIGHTS_MAX = 65536
 LIGHT_SAMPLING_AREA, LIGHT_SAMPLING_CONE = 0, 1
+LIGHT_CANDIDATES_MAX = 32
 
 
 class MptError(RuntimeError):
@@ -399,6 +401,8 @@ def load():
                                           C.POINTER(AdaptiveInfo), C.POINTER(NeeInfo)]
     L.mpt_set_light_sampling.argtypes = [vp, C.c_int32]
     L.mpt_get_light_sampling.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.mpt_set_light_candidates.argtypes = [vp, C.c_uint32]
+    L.mpt_get_light_candidates.argtypes = [vp, C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -748,6 +752,16 @@ class Context:
         mode = C.c_int32(-1)
         self._chk(self.L.mpt_get_light_sampling(self.h, C.byref(mode)), "mpt_get_light_sampling")
         return mode.value
+
+    def set_light_candidates(self, m):
+        """mpt_set_light_candidates: from how many candidates (1..LIGHT_CANDIDATES_MAX; 1, the default, is no resampling) a light
+        sample of direct_lighting, direct_image and render_nee is resampled."""
+        self._chk(self.L.mpt_set_light_candidates(self.h, int(m)), "mpt_set_light_candidates")
+
+    def get_light_candidates(self):
+        m = C.c_uint32(0)
+        self._chk(self.L.mpt_get_light_candidates(self.h, C.byref(m)), "mpt_get_light_candidates")
+        return m.value
 
     def build_bvh(self, prims):
         """GPU LBVH over the packed primitive array (12 floats each) -> (bvh [N, 8] f32, prim_idx [P] i32, device ms)."""

@@ -414,6 +414,12 @@ mpt_adaptive_info Renderer::renderNeeAdaptive(uint32_t maxSamples, int32_t depth
     return info;
 }
 void Renderer::setLightSampling(int mode) { check(mpt_set_light_sampling(ctx_, static_cast<int32_t>(mode)), "mpt_set_light_sampling"); }
+void Renderer::setLightCandidates(uint32_t m) { check(mpt_set_light_candidates(ctx_, m), "mpt_set_light_candidates"); }
+uint32_t Renderer::lightCandidates() {
+    uint32_t m = 0;
+    check(mpt_get_light_candidates(ctx_, &m), "mpt_get_light_candidates");
+    return m;
+}
 void Renderer::writeSum(const std::vector<float>& rgba) {
     const size_t n = static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4;
     if (rgba.size() != n) throw std::runtime_error("writeSum: the array does not have the size of the frame");

@@ -97,6 +97,10 @@ public:
     // mpt_set_light_sampling: how renderDirectLighting and renderNee sample a sphere light (MPT_LIGHT_SAMPLING_AREA, the default, or
     // MPT_LIGHT_SAMPLING_CONE); a bad mode throws and changes nothing
     void setLightSampling(int mode);
+    // mpt_set_light_candidates: from how many candidates (1, the default, to MPT_LIGHT_CANDIDATES_MAX) a light sample of the same two
+    // calls is resampled; a bad count throws and changes nothing.  renderNeeAdaptive refuses more than 1.
+    void setLightCandidates(uint32_t m);
+    uint32_t lightCandidates();
 
 private:
     void check(int status, const char* where);

@@ -354,6 +354,14 @@ int mpt_renderer_set_light_sampling(mpt_renderer* r, int32_t mode) {
     if (!r) return MPT_ERR_INVALID_ARG;
     return mpt_set_light_sampling(r->r->context(), mode);   // (the status itself: a bad mode is MPT_ERR_INVALID_ARG)
 }
+int mpt_renderer_set_light_candidates(mpt_renderer* r, uint32_t m) {
+    if (!r) return MPT_ERR_INVALID_ARG;
+    return mpt_set_light_candidates(r->r->context(), m);   // (the status itself: a bad count is MPT_ERR_INVALID_ARG)
+}
+int mpt_renderer_get_light_candidates(mpt_renderer* r, uint32_t* m) {
+    if (!r) return MPT_ERR_INVALID_ARG;
+    return mpt_get_light_candidates(r->r->context(), m);
+}
 int mpt_renderer_render_nee_adaptive(mpt_renderer* r, uint32_t max_samples, int32_t depth, int32_t walk, float clamp,
                                      const mpt_adaptive_params* p, mpt_adaptive_info* out, mpt_nee_info* nee_out) {
     if (!r || !p) return MPT_ERR_INVALID_ARG;

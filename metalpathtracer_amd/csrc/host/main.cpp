@@ -112,6 +112,12 @@ static void usage() {
         "                    shading point, so that every sample meets the light.  Triangle lights are sampled the same either way.  The\n"
         "                    \"direct\" / \"nee\" JSON object gains \"light_sampling\"; a checkpoint of an --nee render with cone sampling\n"
         "                    has the header MPTNEE2 and is resumed only by such a run, one with area sampling (MPTNEE1) only by such a run\n"
+        "  --light-candidates M  with --direct or --nee: resample every light sample from M candidates, 1..32 (mpt_set_light_candidates,\n"
+        "                    include/mpt.h) — M lights and points are drawn as the one sample is, each weighted by the light it would deliver\n"
+        "                    unshadowed, one kept in proportion to that weight, and one shadow ray traced for it.  1 (the default) is no\n"
+        "                    resampling: every file and every line is what it is without the flag.  The \"direct\" / \"nee\" JSON object gains\n"
+        "                    \"light_candidates\"; a checkpoint of an --nee render with M > 1 has the header MPTNEE3 (its last fields the\n"
+        "                    sampling and M) and is resumed only by a run with the same M and sampling.  With --nee-adaptive only M = 1\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
@@ -400,6 +406,8 @@ int main(int argc, char** argv) {
     bool neeAdaptive = false;   // --nee-adaptive T (the threshold goes into adp, as --adaptive's)
     bool haveLightSampling = false;   // --light-sampling was given
     int lightSampling = MPT_LIGHT_SAMPLING_AREA;
+    bool haveLightCandidates = false;   // --light-candidates was given
+    int lightCandidates = 1;
     bool display = false;   // a display flag was given: .ppm files come from mpt_display
     DisplayOut shown;
     std::memset(&shown.params, 0, sizeof shown.params);   // (clamp, srgb, and 0 = the defaults of include/mpt.h)
@@ -475,6 +483,14 @@ int main(int argc, char** argv) {
             }
             lightSampling = std::strcmp(v, "cone") == 0 ? MPT_LIGHT_SAMPLING_CONE : MPT_LIGHT_SAMPLING_AREA;
             haveLightSampling = true;
+        }
+        else if (a == "--light-candidates") {
+            lightCandidates = std::atoi(next());
+            if (lightCandidates < 1 || lightCandidates > static_cast<int>(MPT_LIGHT_CANDIDATES_MAX)) {
+                std::fprintf(stderr, "mpt_render: --light-candidates takes a count in 1..32\n");
+                return 2;
+            }
+            haveLightCandidates = true;
         }
         else if (a == "--denoise-iterations") dnp.iterations = std::atoi(next());
         else if (a == "--adaptive") {
@@ -589,6 +605,11 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "mpt_render: --light-sampling goes with --direct, --nee or --nee-adaptive\n");
         return 2;
     }
+    if (haveLightCandidates && (neeAdaptive ? lightCandidates > 1 : !nee && !haveDirect)) {
+        std::fprintf(stderr, neeAdaptive ? "mpt_render: --light-candidates above 1 cannot be combined with --nee-adaptive\n"
+                                         : "mpt_render: --light-candidates goes with --direct or --nee\n");
+        return 2;
+    }
     if (!neeAdaptive && (nee || haveNeeOpt)) {
         const char* why = !nee ? "a run without --nee" : neeClamp != neeClamp ? "a --nee-clamp that is no number" : adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1"
                           : !cameraPath.empty() ? "--camera-path" : frames > 0 ? "--frames" : haveAo || haveAoRadius ? "--ao"
@@ -662,6 +683,7 @@ int main(int argc, char** argv) {
         Renderer r(device, scene, assetRoot, bvh);
         r.setRenderParams(prm);
         if (haveLightSampling) r.setLightSampling(lightSampling);
+        if (haveLightCandidates) r.setLightCandidates(static_cast<uint32_t>(lightCandidates));
         // the reference hard-codes Camera::reset(); the flags overwrite the same globals before the viewport is built
         if (havePos) Camera::position = mpt::float3(camPos[0], camPos[1], camPos[2]);
         if (haveDir) Camera::forward = mpt::normalize(mpt::float3(camDir[0], camDir[1], camDir[2]));
@@ -673,8 +695,10 @@ int main(int argc, char** argv) {
         float scale = 1.0f;
         std::string extraJson;
         // (the "direct" / "nee" object names the sampling only when the flag was given: without it the line is what it was)
-        const std::string samplingJson = !haveLightSampling ? "" : lightSampling == MPT_LIGHT_SAMPLING_CONE ? ", \"light_sampling\": \"cone\"" : ", \"light_sampling\": \"area\"";
-        const bool neeCone = nee && lightSampling == MPT_LIGHT_SAMPLING_CONE;
+        const std::string samplingJson = std::string(!haveLightSampling ? "" : lightSampling == MPT_LIGHT_SAMPLING_CONE ? ", \"light_sampling\": \"cone\"" : ", \"light_sampling\": \"area\"") +
+                                         (haveLightCandidates ? ", \"light_candidates\": " + std::to_string(lightCandidates) : std::string());
+        const bool neeRis = nee && lightCandidates > 1;   // (resampled: the header MPTNEE3 names the sampling and the candidates)
+        const bool neeCone = nee && !neeRis && lightSampling == MPT_LIGHT_SAMPLING_CONE;
         auto t0 = std::chrono::steady_clock::now();
         if (ao > 0) {   // grey (ao, ao, ao, 1) through the writer the radiance goes through
             const mpt_ao_info info = r.renderAmbientOcclusion(static_cast<uint32_t>(ao), aoRadius);
@@ -783,16 +807,20 @@ int main(int argc, char** argv) {
                 unsigned long long sh = 0;
                 // (an --nee sum is another estimator's: its header is "MPTNEE1 ... scene-hash clamp-bits\n", which the plain format does not
                 //  parse and the other way round, so neither run continues the other's sum, nor an --nee run one of another clamp; with
-                //  cone sampling of the sphere lights it is "MPTNEE2 ... clamp-bits sampling\n": the two samplings do not mix either)
+                //  cone sampling of the sphere lights it is "MPTNEE2 ... clamp-bits sampling\n": the two samplings do not mix either; with
+                //  more than one light candidate it is "MPTNEE3 ... clamp-bits sampling candidates\n")
                 unsigned cb = 0;
-                int ls = 0;
-                const bool parsed = f && (neeCone ? std::fscanf(f, "MPTNEE2 %d %d %u %u %d %d %d %llx %x %d", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb, &ls) == 10 &&
+                int ls = 0, lc = 0;
+                const bool parsed = f && (neeRis ? std::fscanf(f, "MPTNEE3 %d %d %u %u %d %d %d %llx %x %d %d", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb, &ls, &lc) == 11 &&
+                                                       ls == lightSampling && lc == lightCandidates
+                                          : neeCone ? std::fscanf(f, "MPTNEE2 %d %d %u %u %d %d %d %llx %x %d", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb, &ls) == 10 &&
                                                         ls == lightSampling
                                           : nee ? std::fscanf(f, "MPTNEE1 %d %d %u %u %d %d %d %llx %x", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh, &cb) == 9
                                               : std::fscanf(f, "MPTSUM2 %d %d %u %u %d %d %d %llx", &w, &h, &have, &sd, &rngm, &dep, &bs, &sh) == 8);
                 if (!parsed || std::fgetc(f) != '\n') {
                     if (f) std::fclose(f);
-                    throw std::runtime_error("cannot read the checkpoint " + resume + (neeCone ? " as one of an --nee render with cone light sampling"
+                    throw std::runtime_error("cannot read the checkpoint " + resume + (neeRis ? " as one of an --nee render with these light candidates and this light sampling"
+                                                                                     : neeCone ? " as one of an --nee render with cone light sampling"
                                                                                      : nee   ? " as one of an --nee render with area light sampling" : " as one of a plain render"));
                 }
                 if (nee && cb != neeClampBits) {
@@ -824,7 +852,10 @@ int main(int argc, char** argv) {
                 const std::string tmp = checkpoint + ".tmp";
                 FILE* f = std::fopen(tmp.c_str(), "wb");
                 if (!f) throw std::runtime_error("cannot write " + tmp);
-                if (neeCone)
+                if (neeRis)
+                    std::fprintf(f, "MPTNEE3 %d %d %u %u %d %d %d %llx %x %d %d\n", width, height, have + static_cast<uint32_t>(spp), seed, prm.rng_mode, depth,
+                                 prm.bsdf_mode, sceneHash, neeClampBits, lightSampling, lightCandidates);
+                else if (neeCone)
                     std::fprintf(f, "MPTNEE2 %d %d %u %u %d %d %d %llx %x %d\n", width, height, have + static_cast<uint32_t>(spp), seed, prm.rng_mode, depth,
                                  prm.bsdf_mode, sceneHash, neeClampBits, lightSampling);
                 else if (nee)

@@ -49,6 +49,7 @@
 #include "mpt_direct.h"
 #include "mpt_nee.h"
 #include "mpt_nee_adaptive.h"
+#include "mpt_ris.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -367,6 +368,7 @@ struct mpt_ctx : SceneState {
     DirectState di;
     NeeState nee;
     int32_t light_sampling = MPT_LIGHT_SAMPLING_AREA;   // mpt_set_light_sampling: host state, read at the start of the three calls that sample lights
+    uint32_t light_candidates = 1u;                     // mpt_set_light_candidates: host state with the same life, read at the same three places
     int dp_px = 4;                  // MPT_DISPLAY_PX: pixels per thread of k_dp_present, 1 or 4 (the same bytes)
     bool dp_hist_agg = true;        // MPT_DISPLAY_HIST=plain: k_dp_histogram without the aggregation within the wave
 };
@@ -2053,12 +2055,21 @@ static int nee_collect(mpt_ctx* ctx, mpt_nee_info* out) {
 static int render_nee_impl(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
     int rc = nee_check_params(ctx, p, n);
     if (rc) return rc;
+    const uint32_t m = ctx->light_candidates;   // (read at the start)
     if ((rc = nee_ready(ctx))) return rc;
     NeePass P = {};
     nee_fill_pass(ctx, p, n, P);
     static const WalkKernel<NeePass> area[3] = {k_nee<MPT_AO_REF>, k_nee<MPT_AO_REF_ALL_LDS>, k_nee<MPT_AO_OWN>},
                                      cone[3] = {k_nee_cone<MPT_AO_REF>, k_nee_cone<MPT_AO_REF_ALL_LDS>, k_nee_cone<MPT_AO_OWN>};
-    if ((rc = nee_launch(ctx, n->walk, ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE, area, cone, P))) return rc;
+    const bool use_cone = ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE;
+    if (m == 1u) {   // today's kernels, bit for bit
+        if ((rc = nee_launch(ctx, n->walk, use_cone, area, cone, P))) return rc;
+    } else {         // the same render with the vertex's light sample resampled from m candidates (mpt_ris.h)
+        static const WalkKernel<NeeRisPass> ris_area[3] = {k_nee_ris<MPT_AO_REF>, k_nee_ris<MPT_AO_REF_ALL_LDS>, k_nee_ris<MPT_AO_OWN>},
+                                            ris_cone[3] = {k_nee_ris_cone<MPT_AO_REF>, k_nee_ris_cone<MPT_AO_REF_ALL_LDS>, k_nee_ris_cone<MPT_AO_OWN>};
+        NeeRisPass R = {P, m};
+        if ((rc = nee_launch(ctx, n->walk, use_cone, ris_area, ris_cone, R))) return rc;
+    }
     return nee_collect(ctx, out);
 }
 extern "C" int mpt_render_nee(mpt_ctx* ctx, const mpt_render_params* p, const mpt_nee_params* n, mpt_nee_info* out) {
@@ -2073,6 +2084,8 @@ static int render_nee_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, co
     int rc = nee_check_params(ctx, p, n);
     if (rc) return rc;
     if (!a) return fail(ctx, MPT_ERR_INVALID_ARG, "null adaptive params");
+    if (ctx->light_candidates != 1u)   // (k_nee_adaptive has its own copy of the round: resampling is not in it)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee_adaptive: light candidates must be 1 (mpt_set_light_candidates)");
     const uint32_t N = p->sample_count;
     if (a->min_samples == 1u || !(a->threshold >= 0.0f) || N < 2u)
         return fail(ctx, MPT_ERR_INVALID_ARG, "bad adaptive params (min_samples 1, threshold < 0 or NaN, or sample_count < 2)");
@@ -2133,6 +2146,23 @@ extern "C" int mpt_get_light_sampling(mpt_ctx* ctx, int32_t* mode) {
     return guarded(ctx, [&]() -> int {
         if (!ctx || !mode) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
         *mode = ctx->light_sampling;
+        return MPT_OK;
+    });
+}
+// How many candidates a light sample of those three calls is resampled from: host state with the life of the light-sampling mode.
+extern "C" int mpt_set_light_candidates(mpt_ctx* ctx, uint32_t m) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx) return MPT_ERR_INVALID_ARG;
+        if (m == 0u || m > MPT_LIGHT_CANDIDATES_MAX)
+            return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_set_light_candidates: m must be in 1..MPT_LIGHT_CANDIDATES_MAX (32)");
+        ctx->light_candidates = m;
+        return MPT_OK;
+    });
+}
+extern "C" int mpt_get_light_candidates(mpt_ctx* ctx, uint32_t* m) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx || !m) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+        *m = ctx->light_candidates;
         return MPT_OK;
     });
 }

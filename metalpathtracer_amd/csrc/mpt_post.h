@@ -585,7 +585,14 @@ static int direct_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad,
     pass_frame(P, key, W, H, *p);
     static const WalkKernel<DirectPass> area[3] = {k_direct<MPT_AO_REF>, k_direct<MPT_AO_REF_ALL_LDS>, k_direct<MPT_AO_OWN>},
                                         cone[3] = {k_direct_cone<MPT_AO_REF>, k_direct_cone<MPT_AO_REF_ALL_LDS>, k_direct_cone<MPT_AO_OWN>};
-    return tile_walk_launch(ctx, W, H, p->walk, ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE ? cone : area, P);
+    const bool use_cone = ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE;
+    if (ctx->light_candidates == 1u) return tile_walk_launch(ctx, W, H, p->walk, use_cone ? cone : area, P);   // today's kernels, bit for bit
+    // the same pass with every sample resampled from the candidates (mpt_ris.h)
+    static const WalkKernel<DirectRisPass> ris_area[3] = {k_direct_ris<MPT_AO_REF>, k_direct_ris<MPT_AO_REF_ALL_LDS>, k_direct_ris<MPT_AO_OWN>},
+                                           ris_cone[3] = {k_direct_ris_cone<MPT_AO_REF>, k_direct_ris_cone<MPT_AO_REF_ALL_LDS>,
+                                                          k_direct_ris_cone<MPT_AO_OWN>};
+    const DirectRisPass R = {P, ctx->light_candidates};
+    return tile_walk_launch(ctx, W, H, p->walk, use_cone ? ris_cone : ris_area, R);
 }
 static StageResult di_result(const mpt_ctx* c) {
     return stage_result(c, stage_valid(c, c->di), c->di.out.get(), 16, "no mpt_direct_lighting result for this scene and size");

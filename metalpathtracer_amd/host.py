@@ -27,7 +27,7 @@ SYMBOLS = (
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
     "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_render_nee", "mpt_renderer_set_light_sampling",
-    "mpt_renderer_render_nee_adaptive",
+    "mpt_renderer_render_nee_adaptive", "mpt_renderer_set_light_candidates", "mpt_renderer_get_light_candidates",
 )
 
 _lib = None
@@ -88,6 +88,8 @@ def load():
     L.mpt_renderer_direct_lighting.argtypes = [vp, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.POINTER(capi.DirectInfo)]
     L.mpt_renderer_render_nee.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.NeeInfo)]
     L.mpt_renderer_set_light_sampling.argtypes = [vp, C.c_int32]
+    L.mpt_renderer_set_light_candidates.argtypes = [vp, C.c_uint32]
+    L.mpt_renderer_get_light_candidates.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.mpt_renderer_render_nee_adaptive.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.AdaptiveParams),
                                                    C.POINTER(capi.AdaptiveInfo), C.POINTER(capi.NeeInfo)]
     _lib = L
@@ -432,6 +434,16 @@ class Renderer:
         """mpt_renderer_set_light_sampling: capi.LIGHT_SAMPLING_AREA (the default) or capi.LIGHT_SAMPLING_CONE for renderDirectLighting
         and renderNee."""
         self._chk(self.L.mpt_renderer_set_light_sampling(self.h, int(mode)), "setLightSampling")
+
+    def setLightCandidates(self, m):
+        """mpt_renderer_set_light_candidates: from how many candidates (1..capi.LIGHT_CANDIDATES_MAX; 1, the default, is no resampling)
+        a light sample of renderDirectLighting and renderNee is resampled."""
+        self._chk(self.L.mpt_renderer_set_light_candidates(self.h, int(m)), "setLightCandidates")
+
+    def lightCandidates(self):
+        m = C.c_uint32(0)
+        self._chk(self.L.mpt_renderer_get_light_candidates(self.h, C.byref(m)), "lightCandidates")
+        return m.value
 
     def scene(self):
         return Scene(_borrowed=self.L.mpt_renderer_scene(self.h))
