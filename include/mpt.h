@@ -898,7 +898,7 @@ int mpt_get_light_sampling(mpt_ctx* ctx, int32_t* mode);
  * mpt_resize, mpt_upload_scene, mpt_build_and_upload and mpt_clear_sum and does not make the light table stale.  m = 1 (the default)
  * is the contract of the sections above and launches their kernels: every result is theirs bit for bit.  m = 0, m >
  * MPT_LIGHT_CANDIDATES_MAX or a null pointer: MPT_ERR_INVALID_ARG, nothing changed.  mpt_render_nee_adaptive with m > 1 returns
- * MPT_ERR_INVALID_ARG with nothing rendered and nothing cleared (OUT OF SCOPE: that kernel has its own copy of the round).
+ * MPT_ERR_INVALID_ARG with nothing rendered and nothing cleared (OUT OF SCOPE: the adaptive loop draws one sample per vertex).
  * tests/ris_ref.py restates the rule in numpy.
  *
  * m >= 2.  A light sample is drawn blind — a light by power, a point uniformly on it — and a full any-hit walk is paid for whatever

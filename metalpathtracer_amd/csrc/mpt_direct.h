@@ -2,9 +2,12 @@
 //   k_light_collect   one thread per device primitive: the emissive ones are appended to a list (the host sorts it into the light table)
 //   k_direct<WALK>    per surface pixel, N points on the lights drawn by power, one shadow ray each through an any-hit walk
 //   k_direct_cone<WALK>  the same pass with a sphere light sampled in the cone it subtends (MPT_LIGHT_SAMPLING_CONE); both kernels are
-//                     direct_pass<WALK, CONE>, which differ in the sphere sample alone
+//                     direct_pass<WALK, CONE, false>, which differ in the sphere sample alone
+//   direct_pass<WALK, CONE, RIS>   the pass, written once: the prologue over the guide buffers, the rounds, the image, the counts and the
+//                     totals; RIS = true is k_direct_ris / k_direct_ris_cone (mpt_ris.h), whose round takes ris_pick's sample for the one draw
 //   table_search, light_sample<CONE>   one sample of the light table — the selection, the point or direction on the light, the skip
-//                     predicate — for direct_pass and for nee_render (mpt_nee.h): the only copy
+//                     predicate — for direct_pass, the NEE round (mpt_nee.h) and ris_pick: the only copy
+//   direct_light_factor<CONE>      the estimator's factor of such a sample, for direct_pass and ris_pick<CONE, false>
 // The pass is specified exactly in include/mpt.h (mpt_direct_params) and restated in numpy in tests/direct_ref.py; DESIGN.md §16 has the
 // table, the lane mapping and the registers.
 #pragma once
@@ -167,14 +170,28 @@ struct DirectPass {
     uint32_t seed_lo, seed_hi;
 };
 
+// The estimator's factor of a light sample: (cos_s cos_l / d2) inv_pdf for a point of an area, cos_s J for a direction of a cone.  The only
+// copy: direct_pass forms it for its one draw, ris_pick<CONE, false> (mpt_ris.h) for every candidate.
+template <bool CONE>
+__device__ __forceinline__ float direct_light_factor(LightSample ls) {   // (by value: by reference the cone kernels come out with another register count)
+    return !CONE || ls.tri ? ((ls.cos_s * ls.cos_l) / ls.d2) * ls.inv_pdf : ls.cos_s * ls.J;
+}
+// (mpt_ris.h, which is included after mpt_nee.h and this header: the round's sample of k_direct_ris)
+struct RisPick;
+template <bool CONE, bool NEE>
+__device__ __forceinline__ RisPick ris_pick(const float4* lights, const float* cdf, uint32_t last, uint32_t search_steps, uint32_t M, uint32_t c0,
+                                            uint32_t c1, uint32_t c2, uint32_t c3, uint32_t seed_lo, uint32_t seed_hi, F3 o, F3 n, bool active);
+
 // Lane mapping.  A workgroup of four waves takes a 16 x 16 pixel block, each wave one 8 x 8 tile of it (as k_ao), ONE LANE PER PIXEL, and
 // a round per sample: all 64 lanes trace sample s of their own pixels together.  The shadow rays of neighbouring pixels towards a handful
 // of lights start next to each other and point the same way, so a round's walk is coherent as it is, and a pixel's sum runs in sample
 // order in its one lane: no cross-lane work.  A round in which no lane has a ray skips the walk; a tile without a surface pixel
 // returns after writing its constants.  The table is fetched per lane from global memory (it is small and stays in L2).
 // CONE: a sphere light is sampled by cone_cap / cone_sample (light_sample<true>); a triangle light, the selection and everything else are the same.
-template <int WALK, bool CONE>
-__device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass P) {
+// RIS: the round's sample is not the one draw but ris_pick's choice among `candidates` draws (k_direct_ris, mpt_ris.h): one shadow ray per
+// round as before, and the prologue over the guide buffers, the image, the counts and the totals are these for both.
+template <int WALK, bool CONE, bool RIS>
+__device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass P, uint32_t candidates) {
     const TileWalk T = tile_walk<WALK>(sc, ac);
     const uint32_t lane = T.lane, tx0 = T.tx0, ty0 = T.ty0;
     if (tx0 >= P.W || ty0 >= P.H) return;   // (wave-uniform: the tile lies outside the image)
@@ -211,26 +228,45 @@ __device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass
     uint32_t n_traced = 0u, n_unoccluded = 0u;
     F3 S = f3(0.0f, 0.0f, 0.0f);
     // (the count is wave-uniform and stays in the scalar file: formed from n_lights - 1, which `last` above has put in a vector register,
-    // it would follow it there and take a vector register across the walk)
+    // it would follow it there and take a vector register across the walk; the candidate loop is a uniform loop)
     const uint32_t search_steps = __builtin_amdgcn_readfirstlane(table_search_steps(P.n_lights));
+    const uint32_t M = RIS ? __builtin_amdgcn_readfirstlane(candidates) : 1u;
     const uint32_t rounds = P.n_lights != 0u ? P.sample_count : 0u;   // (no lights: nothing to sample, every surface pixel is black)
     for (uint32_t s = 0; s < rounds; ++s) {
-        const U4 r = philox4x32_10<true>(pixel, sample_begin + s, 0xFFFFFFFDu, 0u, P.seed_lo, P.seed_hi);
-        const float u = u01(r.x);   // the smallest k with u < cdf[k] (u < 1 = cdf[last])
-        const uint32_t k = table_search(last, search_steps, [&](uint32_t mid) { return u < cdf[mid]; });
-        const LightSample ls = light_sample<CONE>(lights, k, o, n, u01(r.y), u01(r.z));
-        // the sample's factor: CONE forms it here, so one value crosses the walk; AREA forms it behind the walk, for the rays that arrive
-        float fac = 0.0f;
-        if (CONE) fac = ls.tri ? ((ls.cos_s * ls.cos_l) / ls.d2) * ls.inv_pdf : ls.cos_s * ls.J;
-        const bool live = surface && ls.ok;
+        // the round's sample: its shadow ray (wi, tmax), whether the lane traces it, and what it adds where the ray arrives
+        F3 wi, C;
+        float tmax, fac = 0.0f;
+        bool live;
+        LightSample ls;   // (the one draw: not used under RIS)
+        if constexpr (RIS) {   // the pick of M candidates, its contribution finished here so that wi, tmax and C cross the walk
+            const auto y = ris_pick<CONE, false>(lights, cdf, last, search_steps, M, pixel, sample_begin + s, 0xFFFFFFFDu, 0u, P.seed_lo,
+                                                 P.seed_hi, o, n, surface);
+            wi = y.wi;
+            tmax = y.tmax;
+            C = y.C;
+            live = y.taken;
+        } else {
+            const U4 r = philox4x32_10<true>(pixel, sample_begin + s, 0xFFFFFFFDu, 0u, P.seed_lo, P.seed_hi);
+            const float u = u01(r.x);   // the smallest k with u < cdf[k] (u < 1 = cdf[last])
+            const uint32_t k = table_search(last, search_steps, [&](uint32_t mid) { return u < cdf[mid]; });
+            ls = light_sample<CONE>(lights, k, o, n, u01(r.y), u01(r.z));
+            // the sample's factor: CONE forms it here, so one value crosses the walk; AREA forms it behind the walk, for the rays that arrive
+            if (CONE) fac = direct_light_factor<CONE>(ls);
+            wi = ls.wi;
+            tmax = ls.dist * 0.9990234375f;
+            live = surface && ls.ok;
+        }
         if (__ballot(live) == 0ull) continue;   // (wave-uniform)
-        const bool hit = any_hit<WALK>(sc, ac, T, o, ls.wi, ls.dist * 0.9990234375f, live);
+        const bool hit = any_hit<WALK>(sc, ac, T, o, wi, tmax, live);
         if (live) {
             n_traced += 1u;
             if (!hit) {
                 n_unoccluded += 1u;
-                if (!CONE) fac = ((ls.cos_s * ls.cos_l) / ls.d2) * ls.inv_pdf;
-                S = S + f3(ls.Le.x * fac, ls.Le.y * fac, ls.Le.z * fac);
+                if constexpr (!RIS) {
+                    if (!CONE) fac = direct_light_factor<CONE>(ls);
+                    C = f3(ls.Le.x * fac, ls.Le.y * fac, ls.Le.z * fac);
+                }
+                S = S + C;
             }
         }
     }
@@ -252,9 +288,9 @@ __device__ __forceinline__ void direct_pass(SceneDev sc, AccelDev ac, DirectPass
 }
 template <int WALK>
 __global__ __launch_bounds__(256) void k_direct(SceneDev sc, AccelDev ac, DirectPass P) {
-    direct_pass<WALK, false>(sc, ac, P);
+    direct_pass<WALK, false, false>(sc, ac, P, 1u);
 }
 template <int WALK>
 __global__ __launch_bounds__(256) void k_direct_cone(SceneDev sc, AccelDev ac, DirectPass P) {
-    direct_pass<WALK, true>(sc, ac, P);
+    direct_pass<WALK, true, false>(sc, ac, P, 1u);
 }

@@ -2084,7 +2084,7 @@ static int render_nee_adaptive_impl(mpt_ctx* ctx, const mpt_render_params* p, co
     int rc = nee_check_params(ctx, p, n);
     if (rc) return rc;
     if (!a) return fail(ctx, MPT_ERR_INVALID_ARG, "null adaptive params");
-    if (ctx->light_candidates != 1u)   // (k_nee_adaptive has its own copy of the round: resampling is not in it)
+    if (ctx->light_candidates != 1u)   // (the adaptive loop draws k_nee's one sample: a loop with ris_pick in it is not written yet)
         return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_render_nee_adaptive: light candidates must be 1 (mpt_set_light_candidates)");
     const uint32_t N = p->sample_count;
     if (a->min_samples == 1u || !(a->threshold >= 0.0f) || N < 2u)
