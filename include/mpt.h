@@ -283,6 +283,13 @@ int mpt_scene_digest(mpt_ctx* ctx, uint64_t out[16]);
  * invariant the arrays carry.                                                                                               */
 int mpt_read_scene_array(mpt_ctx* ctx, int which, uint32_t* out, uint64_t capacity_words, uint64_t* n_words_out);
 
+/* Diagnostics: the per-tile class words of the lean wave-local kernels (csrc/mpt_lean_tiles.h) that render lane `lane` (0 or 1; -1: the lane
+ * of the last trace kernel) holds from its last pass, if that pass ran those kernels: tiles_x * tiles_y words in row-major tile order, bit 31 = skip, bits 0..15 = mask, 0 = general.
+ * Waits for the renders in flight.  *n_words_out is always written (0: the lane has no table — another kernel ran, or
+ * MPT_LEAN_TILES=0); out = NULL with capacity_words = 0 is a size query.  *builds_out (may be NULL): how often this context has
+ * built a table so far.  MPT_ERR_INVALID_ARG for a bad lane, a null n_words_out or a capacity below the size.                  */
+int mpt_read_lean_tile_classes(mpt_ctx* ctx, int lane, uint32_t* out, uint64_t capacity_words, uint64_t* n_words_out, uint64_t* builds_out);
+
 /* ---- multi-GPU: tile shards + ONE RCCL reduce of the HDR sum over xGMI ---------------------------------
  * The reference is single-GPU (it presents straight to the drawable, R/Renderer/Renderer.cpp:303-307); this is the
  * product's extension.  Every GPU renders the 8x8 pixel tiles t % N == rank (mpt_render_params.shard_rank / shard_count)

@@ -28,7 +28,7 @@ SYMBOLS = (
     "mpt_resize", "mpt_draw", "mpt_render", "mpt_render_async", "mpt_wait", "mpt_async_info", "mpt_sum_buffer", "mpt_set_sum_buffer", "mpt_clear_sum",
     "mpt_read_frame", "mpt_read_sum", "mpt_write_sum", "mpt_get_stats", "mpt_reset_stats", "mpt_stream", "mpt_synchronize",
     "mpt_trace_rays", "mpt_trace_rays_ordered", "mpt_accel_info", "mpt_kat_pcg", "mpt_kat_philox", "mpt_kat_sincos", "mpt_kat_rcp",
-    "mpt_build_bvh", "mpt_build_and_upload", "mpt_download_bvh", "mpt_gpu_leaf_max", "mpt_build_info", "mpt_scene_digest", "mpt_read_scene_array", "mpt_comm_unique_id", "mpt_comm_create_all", "mpt_comm_create_rank", "mpt_reduce_sum", "mpt_comm_destroy",
+    "mpt_build_bvh", "mpt_build_and_upload", "mpt_download_bvh", "mpt_gpu_leaf_max", "mpt_build_info", "mpt_scene_digest", "mpt_read_scene_array", "mpt_read_lean_tile_classes", "mpt_comm_unique_id", "mpt_comm_create_all", "mpt_comm_create_rank", "mpt_reduce_sum", "mpt_comm_destroy",
     "mpt_comm_last_error", "mpt_read_aovs", "mpt_denoise", "mpt_read_denoised", "mpt_denoised_buffer", "mpt_denoise_image",
     "mpt_read_moments", "mpt_render_adaptive", "mpt_read_tile_samples",
     "mpt_temporal_accumulate", "mpt_read_temporal", "mpt_temporal_buffer", "mpt_temporal_reset", "mpt_denoise_temporal",
@@ -342,6 +342,8 @@ def load():
     L.mpt_build_info.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.mpt_scene_digest.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.mpt_read_scene_array.argtypes = [vp, C.c_int, up, C.c_uint64, C.POINTER(C.c_uint64)]
+    if hasattr(L, "mpt_read_lean_tile_classes"):   # (MPT_LIB may name a build from before the entry point)
+        L.mpt_read_lean_tile_classes.argtypes = [vp, C.c_int, up, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.mpt_comm_unique_id.argtypes = [vp]
     L.mpt_comm_create_all.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp)]
     L.mpt_comm_create_rank.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
@@ -815,6 +817,15 @@ class Context:
         if n.value:
             self._chk(self.L.mpt_read_scene_array(self.h, int(which), _up(out), n.value, C.byref(n)), "mpt_read_scene_array")
         return out
+
+    def read_lean_tile_classes(self, lane=-1):
+        """mpt_read_lean_tile_classes: (the class words of render lane `lane` (-1: the last one that traced) as uint32, row-major by tile; tables built by this context so far)."""
+        n, builds = C.c_uint64(), C.c_uint64()
+        self._chk(self.L.mpt_read_lean_tile_classes(self.h, int(lane), None, 0, C.byref(n), C.byref(builds)), "mpt_read_lean_tile_classes")
+        out = np.zeros(n.value, np.uint32)
+        if n.value:
+            self._chk(self.L.mpt_read_lean_tile_classes(self.h, int(lane), _up(out), n.value, C.byref(n), C.byref(builds)), "mpt_read_lean_tile_classes")
+        return out, builds.value
 
     def read_scene(self):
         """Every device array of the scene and the counts: ({name: uint32 words} over SCENE_ARRAYS, {name: int} over SCENE_COUNTS)."""

@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "mpt_lean_entry.h"   // MPT_NODE_TAIL and the bound of the tail leaf's guard
+#include "mpt_lean_tiles.h"   // the class word of a primary step's tile
 
 #define MPT_WAVE 64
 #define MPT_NSHARD 16
@@ -492,17 +493,24 @@ static_assert(MPT_LEAN_LEAF_BIT == MPT_NODE_HOLD && MPT_NODE_TAIL < MPT_NODE_HOL
 template <bool COUNT, bool ALL_LDS, bool BUDGETED, bool LEAN = false, bool PRIMARY = false>
 __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes lds_nodes, F3 o, F3 d, uint32_t& node,
                                                    float& best_t, int& best_prim, uint32_t budget, WorkCount& wc,
-                                                   uint32_t min_active = 0u, LdsNodes tail_cfg = nullptr) {
-    float idx, idy, idz;
-    mpt_rcp3(d.x, d.y, d.z, idx, idy, idz);   // PathTracing.h:61 (per call there): 1.0 / r.direction[i]
+                                                   uint32_t min_active = 0u, LdsNodes tail_cfg = nullptr, uint32_t tile_class = 0u) {
+    // PRIMARY, ALL_LDS: `tile_class` is the class word of the step's tile (mpt_lean_tiles.h, wave-uniform; 0: general).  A `skip` tile's rays
+    // miss every box between the entry and T, so its walk is the epilogue below alone — T's spheres, those of the word's mask — and a
+    // tile with an empty mask is done at once: no reciprocals, no loop, one copy of the epilogue for both kinds of tile.
+    constexpr bool TILES = PRIMARY && LEAN && ALL_LDS && MPT_LEAN_TILES && MPT_LEAN_ENTRY && MPT_LEAN_TAIL;
+    const bool tile_skip = TILES && (tile_class & MPT_LEAN_TILES_SKIP) != 0u && (MPT_LEAN_TILES_MASK || (tile_class & MPT_LEAN_TILES_MASK_BITS) == 0u);
+    float idx = 0.0f, idy = 0.0f, idz = 0.0f;
     const uint32_t n_nodes = sc.n_nodes, n_lds = sc.n_lds_nodes;
+    uint32_t i = (tile_class & MPT_LEAN_TILES_MASK_BITS) != 0u ? MPT_NODE_TAIL : n_nodes;   // (a skip tile's)
+    if (!tile_skip) {
+    mpt_rcp3(d.x, d.y, d.z, idx, idy, idz);   // PathTracing.h:61 (per call there): 1.0 / r.direction[i]
     // A direction with a NaN component (normalize of a zero vector: e.g. a refraction at the critical angle whose
     // discriminant rounds below zero) hits nothing — every sphere / triangle test mixes all three components and ends
     // in a comparison with NaN, which is false — but its slab tests PASS every box (min / max drop the NaN operand), so
     // the reference walks the whole tree: 0.5 s for one such ray on a 1 M-triangle scene, with every other wave of
     // the launch waiting for it.  The result of that walk is "miss"; return it without walking.  (The work counters
     // then lack this walk; the oracle, which restates the reference, makes it.)
-    uint32_t i = (d.x != d.x || d.y != d.y || d.z != d.z) ? n_nodes : node;
+    i = (d.x != d.x || d.y != d.y || d.z != d.z) ? n_nodes : node;
     // The box-test loop is written for the SCALAR unit: one per CU, shared by the four SIMDs, and as busy as the vector
     // units in this kernel (rocprofv3: 0.50 SALU per VALU instruction; a loop with per-lane exits costs ~28 scalar
     // instructions of exec-mask bookkeeping per trip).  So the loop is wave-uniform — every lane runs every trip, lanes
@@ -593,6 +601,7 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         // meet other stragglers in the next ring instead of holding 64 lanes for their long walks
         if (BUDGETED && (uint32_t)__popcll(going) < min_active) break;
     }
+    }
     if (LEAN && ALL_LDS && MPT_LEAN_ENTRY && MPT_LEAN_TAIL) {   // (the block is staged with the entry terms: wavelocal_body)
         if (i == MPT_NODE_TAIL) {
             const bool d_ok = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)) <= MPT_LEAN_ENTRY_DMAX;
@@ -617,7 +626,16 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
 #endif
             if (hit) {
                 const uint32_t enc = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf) & ~MPT_NODE_HOLD;
-                leaf_test<COUNT, LEAN, PRIMARY>(sc, lds_nodes, enc >> 4, (enc & 15u) + 1u, o, d, best_t, best_prim, wc);
+                if (TILES) {   // one leaf_test per run of set bits (scalar first and count): a skip tile's mask, else all of T in one run
+                    uint32_t m = tile_skip ? tile_class & MPT_LEAN_TILES_MASK_BITS : (2u << (enc & 15u)) - 1u;
+                    do {
+                        const uint32_t s = (uint32_t)__builtin_ctz(m), run = (uint32_t)__builtin_ctz(~(m >> s));
+                        leaf_test<COUNT, LEAN, PRIMARY>(sc, lds_nodes, (enc >> 4) + s, run, o, d, best_t, best_prim, wc);
+                        m &= ~(((1u << run) - 1u) << s);
+                    } while (m != 0u);
+                } else {
+                    leaf_test<COUNT, LEAN, PRIMARY>(sc, lds_nodes, enc >> 4, (enc & 15u) + 1u, o, d, best_t, best_prim, wc);
+                }
             }
         }
     }

@@ -98,6 +98,14 @@ using mpt_own::Event;
 using mpt_own::HostMem;
 using mpt_own::Stream;
 
+// What a lane's class table was built from: the scene (guide_epoch: bumped by every scene call and every resize, and the node array), the camera as
+// the kernels read it, the image and its tile grid, and the number of words (tiles + the pass's rank count)
+struct LeanTileKey {
+    uint64_t epoch;
+    const void* nodes;
+    LeanTileView view;
+    uint32_t width, height, n_words;
+};
 struct Lane {
     Stream stream;
     DevMem<PassDesc> d_desc;
@@ -119,6 +127,10 @@ struct Lane {
     OtRings ot_ring = {};        // ... and its rings (MPT_OT_RINGS per wave, in ot_ring_mem)
     size_t ot_ring_waves = 0;
     uint32_t announced_id = 0;   // launch id of the lane's last trace kernel that announces its residency (0: none)
+    // the lean ALL_LDS kernels' per-tile class words (mpt_lean_tiles.h), built on this lane's stream when `tile_key` changes: each lane has its own,
+    // so a launch in flight on the other lane never sees its table change
+    DevMem<uint32_t> d_tile_classes;
+    LeanTileKey tile_key = {};
     bool in_flight = false;      // enqueued by mpt_render_async, not yet collected
     bool timed = false;
 };
@@ -347,6 +359,7 @@ struct mpt_ctx : SceneState {
     // 128 / 256 / 512 / 1024 -> 16.79-16.86 / 16.70 / 16.62-16.65 / 16.65 / 17.87 ms, the 1/8 shard's serial step 2.54 / - / 2.71 / 3.36
     uint32_t wl_min = 0, wl_div = 32;
     bool wl_lean = true;               // MPT_WL_LEAN=0: every wave-local pass runs the generic kernels (development knob)
+    bool lean_tiles = true;            // MPT_LEAN_TILES=0: the lean kernels get no class table, every tile is "general" (mpt_lean_tiles.h; development knob)
     LeanCdivCache lean_cdiv;           // is the lean kernels' division by W and H exact at this context's size (mpt_lean_cdiv.h)
     DevMem<uint32_t> d_cdiv_bad;       // the mismatch count of k_lean_cdiv_check
     uint32_t wl_block = MPT_WL_BLOCK;  // path ids a wave claims per atomic (multiple of 64)
@@ -354,6 +367,7 @@ struct mpt_ctx : SceneState {
     size_t lds_budget = 78 * 1024;  // per workgroup; two workgroups per CU share the 160 KiB
     mpt_stats stats = {};
     uint64_t guide_epoch = 1;       // bumped by every scene upload / build and every mpt_resize
+    uint64_t tile_class_builds = 0; // launches of k_lean_tile_classes (ensure_tile_classes)
     GuideState gd;
     DenoiseState dn;
     // adaptive sampling (mpt_adaptive.h): the moments buffer (W x H, allocated by the first render with MPT_FLAG_MOMENTS) and the
@@ -529,6 +543,7 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     if ((e = getenv("MPT_OT_OCC")) && (atoi(e) == 5 || atoi(e) == 6)) ctx->ot_occ = atoi(e);
     if ((e = getenv("MPT_WL_DIV")) && atoi(e) >= 1) ctx->wl_div = (uint32_t)atoi(e);
     if ((e = getenv("MPT_WL_LEAN"))) ctx->wl_lean = atoi(e) != 0;
+    if ((e = getenv("MPT_LEAN_TILES"))) ctx->lean_tiles = atoi(e) != 0;
     if ((e = getenv("MPT_OT_STACK")) && atoi(e) >= 2 && atoi(e) <= (int)MPT_OT_PARK) ctx->ot_stack_depth = (uint32_t)atoi(e);
     unsigned ot[MPT_OT_MLEVELS];   // "a,b,c": one number per tree-walk ring; the rings a list leaves out keep their defaults
     if ((e = getenv("MPT_OT_BUDGETS")))
@@ -1055,6 +1070,8 @@ struct PassLaunch {
     size_t lds = 0;
     AccelDev accel = {};              // closest-first pipeline only
     WlLean lean_args = {0u, 0u, 0u};  // lean kernels only
+    bool lean_all_lds = false;        // a lean kernel with the whole tree in LDS: the ones that read the class table
+    const uint32_t* tile_classes = nullptr;   // ... and the table (ensure_tile_classes; null: every tile is general)
 };
 
 // The result slots one iteration of the wavefront pipeline retires, in items of 64 (the other pipelines size k_begin_pass's cursors by it)
@@ -1126,6 +1143,7 @@ static int select_trace_kernel(mpt_ctx* ctx, Lane& L, const mpt_render_params* p
                           wl_lean_ok(ctx->n_prims, n_local_tiles, pp.tiles_x, ctx->W, ctx->H, pp.nranks, pp.S, pp.tile_magic, p->rng_mode, p->bsdf_mode, count, &g.lean_args) &&
                           lean_cdiv_ok(ctx->lean_cdiv, pp.W, pp.H, [&](float W, float H, uint32_t* bad) { return lean_cdiv_device_check(ctx, L.stream.get(), W, H, bad); });
         variant = (g.corun ? TK_CORUN : 0) | (lean ? TK_LEAN : 0);
+        g.lean_all_lds = lean && all_lds;
     } else if (g.pipeline == MPT_PIPE_ORDERED) {
         g.ot_point = ordered_point(ctx, count);
         all_lds = ctx->ot_pt[g.ot_point].lds_nodes == ctx->n_acc_nodes;
@@ -1197,6 +1215,53 @@ static int order_behind_previous_trace(mpt_ctx* ctx, Lane& L, bool corun) {
     return MPT_OK;
 }
 
+// The class table of a pass of the lean ALL_LDS kernels: built by k_lean_tile_classes on the lane's stream, ahead of the trace kernel, when
+// the lane has none for this scene, camera and image (a batch render: once).  Without the item (MPT_LEAN_TILES=0, a pricing build) the
+// kernels get a null pointer.
+static int ensure_tile_classes(mpt_ctx* ctx, Lane& L, const PassParams& pp, PassLaunch& g) {
+    g.tile_classes = nullptr;
+#if MPT_LEAN_TILES
+    if (!g.lean_all_lds || !ctx->lean_tiles) {   // (the lane's pass runs without a table: what mpt_read_lean_tile_classes reports for it)
+        memset(&L.tile_key, 0, sizeof L.tile_key);
+        return MPT_OK;
+    }
+    const uint32_t tiles_x = pp.tiles_x, tiles_y = (ctx->H + 7) / 8;
+    LeanTileKey key;
+    memset(&key, 0, sizeof key);
+    key.epoch = ctx->guide_epoch;
+    key.nodes = pp.scene.nodes;
+    const F3 v3[4] = {pp.cam, pp.first, pp.vu, pp.vv};
+    float* dst[4] = {key.view.cam, key.view.first, key.view.vu, key.view.vv};
+    for (int k = 0; k < 4; ++k) {
+        dst[k][0] = v3[k].x;
+        dst[k][1] = v3[k].y;
+        dst[k][2] = v3[k].z;
+    }
+    key.view.W = pp.W;
+    key.view.H = pp.H;
+    key.view.tiles_x = tiles_x;
+    key.view.tiles_y = tiles_y;
+    key.width = ctx->W;
+    key.height = ctx->H;
+    key.n_words = tiles_x * tiles_y + pp.nranks;   // (both below 2^24: wl_lean_ok)
+    if (!L.d_tile_classes || memcmp(&key, &L.tile_key, sizeof key) != 0) {
+        if (L.d_tile_classes.bytes() < (size_t)key.n_words * 4) {
+            memset(&L.tile_key, 0, sizeof L.tile_key);
+            HIPCHK(L.d_tile_classes.alloc((size_t)key.n_words * 4));
+        }
+        hipLaunchKernelGGL(k_lean_tile_classes, dim3((key.n_words + 63u) / 64u), dim3(64), 0, L.stream.get(), pp.scene.nodes, pp.scene.n_nodes, pp.scene.prims,
+                           pp.scene.n_prims, key.view, L.d_tile_classes.get(), key.n_words);
+        HIPCHK(hipGetLastError());
+        L.tile_key = key;
+        ctx->tile_class_builds++;
+    }
+    g.tile_classes = L.d_tile_classes.get();
+#else
+    (void)ctx, (void)L, (void)pp;
+#endif
+    return MPT_OK;
+}
+
 // A lane's ring allocation, grown to `waves` waves (never shrunk): waves * per_wave records of 16 bytes in each of `arrays` arrays, and
 // `extra` bytes behind them.  The records are indexed with 31 bits.
 template <class Rings>
@@ -1251,7 +1316,7 @@ static int launch_persistent(mpt_ctx* ctx, Lane& L, PassLaunch& g, PassParams& p
             wl_min = 64u * (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, share >> 14));
         }
         void* ordered_args[] = {(void*)&pp, (void*)&g.accel, (void*)&L.ot_ring, (void*)&ctx->ot_budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div};
-        void* wavelocal_args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div, (void*)&g.lean_args};   // (the last: lean kernels only)
+        void* wavelocal_args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div, (void*)&g.lean_args, (void*)&g.tile_classes};   // (the last two: lean kernels only)
         if ((rc = launch_timed(ctx, L, g, g.pipeline == MPT_PIPE_ORDERED ? ordered_args : wavelocal_args, time_kernels, L.pending_timed))) return rc;
     }
     if (ctx->lane_order & 5) {   // (always, unless MPT_LANE_ORDER=0)
@@ -1330,6 +1395,7 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     g.pipeline = resolve_pipeline(ctx, p->pipeline, p->rng_mode);
     if ((rc = select_trace_kernel(ctx, L, p, n_local_tiles, pp, g))) return rc;
     if ((rc = launch_geometry(ctx, pp, g))) return rc;
+    if ((rc = ensure_tile_classes(ctx, L, pp, g))) return rc;
 
     *L.h_done.get() = 0;
     if ((rc = order_behind_previous_trace(ctx, L, g.corun))) return rc;
@@ -2210,6 +2276,29 @@ extern "C" int mpt_read_scene_array(mpt_ctx* ctx, int which, uint32_t* out, uint
         HIPCHK(hipSetDevice(ctx->device));
         HIPCHK(hipMemcpyAsync(out, a[which].p, words * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
+        return MPT_OK;
+    });
+}
+// Test hook: the class table of render lane `lane` (0 or 1; -1: the lane of the last trace kernel) as the lane's last pass of a lean ALL_LDS kernel left it, its tiles only (row-major,
+// tiles_x * tiles_y words); *builds_out: launches of k_lean_tile_classes in this context so far.  No table: *n_words_out = 0.
+extern "C" int mpt_read_lean_tile_classes(mpt_ctx* ctx, int lane, uint32_t* out, uint64_t capacity_words, uint64_t* n_words_out, uint64_t* builds_out) {
+    return guarded(ctx, [&]() -> int {
+        if (!ctx) return MPT_ERR_INVALID_ARG;
+        if (n_words_out) *n_words_out = 0;
+        if (!n_words_out || lane < -1 || lane > 1) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_read_lean_tile_classes: bad lane or null n_words_out");
+        int rc = drain_submit(ctx);
+        if (rc) return rc;
+        if ((rc = wait_impl(ctx))) return rc;
+        Lane& L = lane >= 0 ? ctx->lane[lane] : ctx->last_trace_lane ? *ctx->last_trace_lane : ctx->lane[0];
+        if (builds_out) *builds_out = ctx->tile_class_builds;
+        const uint64_t words = L.d_tile_classes && L.tile_key.n_words ? (uint64_t)L.tile_key.view.tiles_x * L.tile_key.view.tiles_y : 0u;
+        *n_words_out = words;
+        if (!out && capacity_words == 0) return MPT_OK;   // the size query
+        if (!out || capacity_words < words) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_read_lean_tile_classes: out is null or too small");
+        if (words == 0) return MPT_OK;
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipMemcpyAsync(out, L.d_tile_classes.get(), words * 4, hipMemcpyDeviceToHost, L.stream.get()));
+        HIPCHK(hipStreamSynchronize(L.stream.get()));
         return MPT_OK;
     });
 }

@@ -13,6 +13,7 @@
 #include "mpt_device.h"
 #include "mpt_wl_lean.h"
 #include "mpt_lean_entry.h"
+#include "mpt_lean_tiles.h"
 
 // Minimum waves per SIMD the two secondary trace kernels (k_step, k_megakernel) are compiled for (2nd __launch_bounds__
 // argument): 8 waves/SIMD (<= 64 VGPRs, 2 x 1024-thread workgroups per CU next to 2 x 57 KB of LDS).  k_wavelocal has
@@ -569,7 +570,7 @@ __device__ __forceinline__ uint32_t wave_rank(unsigned long long m) {
 #endif
 #define MPT_WL_RING 512u       // records per ring
 #define MPT_LDS_MATS_N 32u     // materials staged in LDS (= MPT_LDS_MATS of mpt_hip.hip): the configuration block of k_wavelocal / k_ordered starts behind them
-#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes): camera in float4 0..3, then 32 words (budgets 0..15, claim parameters 16..19); float4 10..11: the lean kernels' entry terms, 12..15: their tail leaf (mpt_lean_entry.h).
+#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes): camera in float4 0..3, then 24 words (budgets 0..15, claim parameters 16..19, the lean kernels' sample division 20..21 and class table 22..23); float4 10..11: the lean kernels' entry terms, 12..15: their tail leaf (mpt_lean_entry.h).
                                // The host reserves it (MPT_LDS_EXTRA, ordered_views): k_ordered's stacks start right behind it.
 // Where the configuration block starts in a workgroup's LDS (float4 index), for the kernels AND for the host code that lays the
 // image out and sizes the launch (mpt_hip.hip: MPT_LDS_EXTRA, ordered_views) — one definition.  Round 4's development build of
@@ -702,7 +703,7 @@ struct WaveBudgets {
 #define MPT_WL_WAVES(ALL_LDS) MPT_WL_WAVES_N
 template <bool COUNT, bool ALL_LDS, bool LEAN = false>
 __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveRings& ring, const WaveBudgets& budgets, uint32_t wl_block, uint32_t wl_min,
-                                               uint32_t wl_div, const WlLean& lean = WlLean{0u, 0u, 0u});
+                                               uint32_t wl_div, const WlLean& lean = WlLean{0u, 0u, 0u}, const uint32_t* tile_classes = nullptr);
 template <bool COUNT, bool ALL_LDS>
 __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) void k_wavelocal(PassParams pp, WaveRings ring, WaveBudgets budgets,
                                                                                              uint32_t wl_block, uint32_t wl_min, uint32_t wl_div) {
@@ -731,18 +732,31 @@ void k_wavelocal_corun(PassParams pp, WaveRings ring, WaveBudgets budgets, uint3
 // every floating-point operation a ray sees are the generic kernels'.  Measured: DESIGN.md 5, profiles/r15_fast_kernel.txt.  The names carry "k_wavelocal" (bench.py finds its counter profile by that) and none of the generic kernels' names.
 template <bool ALL_LDS>
 __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) void k_wavelocal_lean(PassParams pp, WaveRings ring, WaveBudgets budgets,
-                                                                                                  uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean) {
-    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean);
+                                                                                                  uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean,
+                                                                                                  const uint32_t* tile_classes) {
+    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean, tile_classes);
 }
 template <bool ALL_LDS>
 __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) __attribute__((amdgpu_num_sgpr(MPT_WL_CORUN_SGPRS)))
-void k_wavelocal_lean_corun(PassParams pp, WaveRings ring, WaveBudgets budgets, uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean) {
-    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean);
+void k_wavelocal_lean_corun(PassParams pp, WaveRings ring, WaveBudgets budgets, uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean,
+                            const uint32_t* tile_classes) {
+    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean, tile_classes);
+}
+// The class table of the lean ALL_LDS kernels (mpt_lean_tiles.h): one thread per word, word T = the class of tile T = ty * tiles_x + tx — the
+// index path_to_pixel<true> computes — and 0 behind the last tile (a rank's last tile index may lie up to nranks - 1 past it; no pixel is there).
+__global__ __launch_bounds__(64) void k_lean_tile_classes(const float4* nodes, uint32_t n_nodes, const float4* prims, uint32_t n_prims, LeanTileView view,
+                                                          uint32_t* out, uint32_t n_words) {
+    const uint32_t T = blockIdx.x * blockDim.x + threadIdx.x;
+    if (T >= n_words) return;
+    const uint32_t ty = T / view.tiles_x, tx = T - ty * view.tiles_x;
+    out[T] = ty < view.tiles_y ? lean_tile_class(nodes, n_nodes, prims, n_prims, view, tx, ty) : 0u;
 }
 template <bool COUNT, bool ALL_LDS, bool LEAN>
 __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveRings& ring, const WaveBudgets& budgets, uint32_t wl_block, uint32_t wl_min,
-                                               uint32_t wl_div, const WlLean& lean) {
+                                               uint32_t wl_div, const WlLean& lean, const uint32_t* tile_classes) {
     static_assert(!(LEAN && COUNT), "the lean body does not count");
+    // the per-tile class words (mpt_lean_tiles.h) are read by the primary steps of the lean kernels whose whole tree is in LDS
+    constexpr bool TILES = LEAN && ALL_LDS && MPT_LEAN_TILES && MPT_LEAN_ENTRY && MPT_LEAN_TAIL && MPT_LEAN_CAMSPHERE;
     extern __shared__ float4 lds_nodes_raw[];
     // what only some steps need goes to LDS, behind the scene image (the 256-byte descriptor area of MPT_LDS_EXTRA), instead of
     // living in scalar registers across the whole step loop: the camera (14 words, primary steps) and the ring budgets (10 words,
@@ -760,7 +774,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             w[8u + k] = budgets.min_active[k];
         }
         // ... and what only a CLAIM of path ids needs (words 16..19 of the block's 32: static_assert below)
-        static_assert(4u * (10u - 4u) >= 22u && MPT_LDS_CFG_F4 >= 12u, "configuration block too small");   // words 0..21 end inside float4 9; float4 10 and 11 hold the lean kernels' entry terms
+        static_assert(4u * (10u - 4u) >= 24u && MPT_LDS_CFG_F4 >= 12u, "configuration block too small");   // words 0..23 fill float4 4..9 (22, 23: the lean kernels' class table); float4 10 and 11 hold the lean kernels' entry terms
         w[16] = wl_block;
         w[17] = wl_min;
         w[18] = wl_div * (((uint32_t)(gridDim.x * (blockDim.x >> 6)) + MPT_NGROUP - 1u) / MPT_NGROUP);   // wl_div * waves per claim range
@@ -768,6 +782,10 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         if (LEAN) {   // the division by a sample count that is no power of two (path_to_pixel<true>)
             w[20] = lean.s_mul;
             w[21] = lean.s_shift;
+        }
+        if (TILES) {   // the class table's address (words 22 and 23, the last of float4 9; null: every tile is general) — read back when a wave changes its tile, so that the step loop keeps no scalar register for it
+            w[22] = (uint32_t)(uintptr_t)tile_classes;
+            w[23] = (uint32_t)((uint64_t)(uintptr_t)tile_classes >> 32);
         }
         if (LEAN && MPT_LEAN_ENTRY) {   // where fresh queries enter the tree (mpt_lean_entry.h): float4 10 and 11 of the block, behind the words above
             const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // (a tree without nodes: A0 = 0 switches the item off, nothing is read)
@@ -826,6 +844,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
     uint32_t seen = 0;                                 // cursor value (virtual index) at this wave's previous claim
     bool exhausted = false;
     uint32_t tile_cached = 0xFFFFFFFFu, tile_xy_cached = 0u;
+    uint32_t tile_class_cached = 0u;   // the cached tile's class word (mpt_lean_tiles.h; 0: general)
     float uvx_cached = 0.0f, uvy_cached = 0.0f;   // pixel_uv of this lane's pixel in the cached tile
     uint32_t n_rays = 0, n_paths = 0;
     WorkCount wc = {};
@@ -974,7 +993,17 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             const bool new_tile = tl != tile_cached;
             if (new_tile) {
                 tile_cached = tl;
-                if (LEAN) {   // the table's entry by (scalar) arithmetic, as path_to_pixel<true>: no load, no table pointer in the loop
+                if (TILES) {   // the tile's class word, kept with the cached tile: a scalar load from a wave-uniform address (the table's address comes
+                               // from LDS here, once per tile change, so that the step loop keeps one scalar register for the word and none for the table)
+                    const uint32_t tlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[22]), thi = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[23]);
+                    tile_class_cached = 0u;
+                    if ((tlo | thi) != 0u) {
+                        typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+                        tile_class_cached = ((ConstWords)(((uint64_t)thi << 32) | tlo))[tl * pp.nranks + pp.rank];
+                    }
+                }
+                if (TILES) {   // (the tile's place: by every step, below)
+                } else if (LEAN) {   // the table's entry by (scalar) arithmetic, as path_to_pixel<true>: no load, no table pointer in the loop
                     const uint32_t T = tl * pp.nranks + pp.rank, ty = (T * lean.tile_mul) >> MPT_WL_LEAN_TILE_SHIFT;
                     tile_xy_cached = (T - ty * pp.tiles_x) | (ty << 16);
                 } else {
@@ -983,7 +1012,13 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             }
             PathState np;   // (every lane's ray is replaced, also in the lanes outside the image, which hold none: nothing of the step before stays live)
             np.path = pchunk * 64u + lane;
-            const uint32_t px = (tile_xy_cached & 0xFFFFu) * 8u + (lane & 7u), py = (tile_xy_cached >> 16) * 8u + (lane >> 3);
+            uint32_t tile_xy = tile_xy_cached;
+            if (TILES) {   // with the class word kept across steps, the tile's place is not: six scalar instructions per primary step buy the scalar
+                           // register back (the bench step's kernel spills 24 with both kept, 23 as before this way — profiles/r23_lean_tiles.txt)
+                const uint32_t T = tl * pp.nranks + pp.rank, ty = (T * lean.tile_mul) >> MPT_WL_LEAN_TILE_SHIFT;
+                tile_xy = (T - ty * pp.tiles_x) | (ty << 16);
+            }
+            const uint32_t px = (tile_xy & 0xFFFFu) * 8u + (lane & 7u), py = (tile_xy >> 16) * 8u + (lane >> 3);
             CamView cv;
             {
                 const v4f c0 = lds_nodes[cfg_off], c1 = lds_nodes[cfg_off + 1u], c2 = lds_nodes[cfg_off + 2u], c3 = lds_nodes[cfg_off + 3u];
@@ -1114,8 +1149,9 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 done = closest_hit_resume<COUNT, ALL_LDS, true, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
                                                                      budget, wc, min_active, lds_nodes + cfg_off + 12u);
             else if (LEAN && MPT_LEAN_CAMSPHERE && level < 0)   // a primary step: every origin is the camera (the staged sphere terms)
+                // (with the tile's class word: a `skip` tile's walk is the tail leaf's masked spheres alone, mpt_lean_tiles.h)
                 done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN, true>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                            0xFFFFFFFFu, wc, 0u, lds_nodes + cfg_off + 12u);
+                                                                            0xFFFFFFFFu, wc, 0u, lds_nodes + cfg_off + 12u, TILES ? tile_class_cached : 0u);
             else
                 done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
                                                                       0xFFFFFFFFu, wc, 0u, lds_nodes + cfg_off + 12u);
