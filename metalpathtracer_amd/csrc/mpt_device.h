@@ -18,6 +18,7 @@
 
 #include "mpt_lean_entry.h"   // MPT_NODE_TAIL and the bound of the tail leaf's guard
 #include "mpt_lean_tiles.h"   // the class word of a primary step's tile
+#include "mpt_lds_cfg.h"      // the tail leaf's slots in the configuration block
 
 #define MPT_WAVE 64
 #define MPT_NSHARD 16
@@ -109,12 +110,8 @@ __device__ __forceinline__ F3 normalize3(F3 a) {
 // 2^-96 <= x < inf (sqrt_core_exact) the bits are sqrtf's.  Measured over all 2^32 operands, not argued (tests/test_gpu_lean_math.py).
 // normalize3<true> needs ONE wave-uniform guard (one ballot, as mpt_rcp) for both the root and the reciprocal: 2^-96 <= l2 <= 2^126 puts
 // the root into [2^-48, 2^63], well inside the range of rcp_chain; a wave with a lane outside takes today's expression.  That is 7 vector
-// instructions and the reciprocal's own guard less per normalize.  MPT_LEAN_SQRT=0: pricing build of the lean kernels with the parent's
-// normalize.  (The two bare square roots — leaf_test's sphere, random_unit_vector — need a guard of their own for the same core; priced,
-// it did not pay and is not here: profiles/r16_lean_math.txt.)
-#ifndef MPT_LEAN_SQRT
-#define MPT_LEAN_SQRT 1
-#endif
+// instructions and the reciprocal's own guard less per normalize (priced: profiles/r16_lean_math.txt).  (The two bare square roots —
+// leaf_test's sphere, random_unit_vector — need a guard of their own for the same core; priced, it did not pay and is not here: same file.)
 #define MPT_SQRT_LO 0x1p-96f
 #define MPT_NORM_HI 0x1p126f
 __device__ __forceinline__ float sqrt_core(float x) {
@@ -130,7 +127,7 @@ __device__ __forceinline__ bool norm_core_exact(float l2) { return l2 >= MPT_SQR
 __device__ __forceinline__ float inv_len_core(float l2) { return rcp_chain(sqrt_core(l2)); }   // 1.0f / sqrtf(l2) where norm_core_exact(l2)
 template <bool LEAN>
 __device__ __forceinline__ F3 normalize3(F3 a) {
-    if (LEAN && MPT_LEAN_SQRT) {
+    if (LEAN) {
         const float l2 = dot3(a, a);
         if (__builtin_expect(__ballot(!norm_core_exact(l2)) == 0ull, 1)) return a * inv_len_core(l2);
         return a * mpt_rcp(sqrtf(l2));
@@ -142,10 +139,7 @@ __device__ __forceinline__ F3 normalize3(F3 a) {
 // proper: one multiply and four fused multiply-adds, cdiv_chain().  v_div_scale and v_div_fixup around them do nothing for the operands
 // gen_primary has (1 <= W < 2^24, x = k 2^-24 - 0.5): MEASURED per (W, H) by k_lean_cdiv_check over all 2^24 numerators before a context
 // takes the lean kernels at that size (mpt_lean_cdiv.h), and for a list of sizes by tests/test_gpu_lean_math.py.
-// MPT_LEAN_CDIV=0: pricing build, the parent's two divisions.
-#ifndef MPT_LEAN_CDIV
-#define MPT_LEAN_CDIV 1
-#endif
+// Priced against the two divisions: profiles/r16_lean_math.txt.
 __device__ __forceinline__ float cdiv_recip(float W) {
     const float r0 = __builtin_amdgcn_rcpf(W);
     const float e = fmaf(-W, r0, 1.0f);
@@ -222,6 +216,7 @@ __device__ __forceinline__ void sincos_2pi(float u, float& s_out, float& c_out) 
 // (a generic pointer selected between LDS and global turns into flat_load: measured 0 LDS reads per ray).
 typedef float v4f __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(3))) v4f* LdsNodes;
+typedef const __attribute__((address_space(3))) uint32_t* LdsWords;
 
 // ---- scene on the device ----------------------------------------------------------------------------
 // Threaded BVH node, 32 bytes (same size as the reference's, SURVEY App. D buf 0):
@@ -312,6 +307,27 @@ struct WorkCount {
 #define MPT_TIC(var) do { } while (0)
 #define MPT_TOC(acc, var) do { } while (0)
 #endif
+// The box loop's own diagnostics (MPT_DEBUG_WAVE_TIMES with counting): the trips of one round that a lane sat out, booked as "holding a
+// leaf" or "done".  A product build's members do nothing.
+struct BoxLoopIdle {
+#ifdef MPT_DEBUG_WAVE_TIMES
+    uint32_t my_trips = 0, round_trips = 0;
+    __device__ __forceinline__ void trip(bool searching) {
+        my_trips += searching ? 1u : 0u;
+        round_trips++;
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ void book(bool holds_leaf, WorkCount& wc) const {
+        if (!COUNT) return;
+        if (holds_leaf) wc.wait_leaf += round_trips - my_trips;
+        else wc.wait_done += round_trips - my_trips;   // finished, out of budget, or cut by the early leave
+    }
+#else
+    __device__ __forceinline__ void trip(bool) {}
+    template <bool COUNT>
+    __device__ __forceinline__ void book(bool, WorkCount&) const {}
+#endif
+};
 
 // One primitive record (3 x 16 B).  Primitives are stored by leaf depth (shallow leaves first); the first
 // n_lds_prims of them are staged in LDS behind the node image.  On scene.xml 65 % of all primitive tests hit the three
@@ -323,23 +339,17 @@ struct Prim3 {
 // multiply, added to the scalar base (global: base in scalar registers + 32-bit vector offset; LDS: a 32-bit address anyway) — the
 // generic form multiplies in 64 bits (v_mad_u64_u32, quarter rate).  The host admits a scene only when i < 2^24 for every record
 // (wl_lean_ok, mpt_wl_lean.h), so i * 48 < 2^32: the same address, the same record.
-// (MPT_LEAN_INT24=0: pricing build of the lean kernels without the 24-bit index arithmetic — profiles/r15_fast_kernel.txt)
-#ifndef MPT_LEAN_INT24
-#define MPT_LEAN_INT24 1
-#endif
+// (priced against the 64-bit form: profiles/r15_fast_kernel.txt)
 typedef const __attribute__((address_space(3))) char* LdsBytes;
 __device__ __forceinline__ uint32_t mul_u24(uint32_t a, uint32_t b) { return (uint32_t)__umul24(a, b); }   // v_mul_u32_u24: low 32 bits of the product of the low 24 bits (__umul24 returns int: a product >= 2^31 must not meet a signed shift)
-// LEAN, camera-relative sphere terms (MPT_LEAN_CAMSPHERE): a primary ray starts at the camera, the same bits in every lane of every
+// LEAN, camera-relative sphere terms: a primary ray starts at the camera, the same bits in every lane of every
 // primary step of a launch, so oc = o - c and cc = dot3(oc, oc) - r * r of the sphere test are functions of (camera, sphere) alone: 10
 // of the test's 19 vector instructions.  The lean kernels write them once per workgroup into the unused words of the sphere records of
 // their LDS image (stage_nodes_lean, mpt_kernels.h: p2.xyz = oc, p1.z = cc; sphere_cam_terms below is the one expression of both), and
 // the walk of a primary step (PRIMARY, an instantiation of its own) reads them there.  A sphere record that such a walk reads from global memory gets
 // the same two terms here, in the branch that separates the two sources, so leaf_test's sphere branch has one form per walk.  The
 // global array and every other reader of a record (the walks of ring steps, finish_hit, the materials) are as they were.
-// (MPT_LEAN_CAMSPHERE=0: pricing build without it — profiles/r17_lean_primary.txt)
-#ifndef MPT_LEAN_CAMSPHERE
-#define MPT_LEAN_CAMSPHERE 1
-#endif
+// (priced: profiles/r17_lean_primary.txt)
 __device__ __forceinline__ void sphere_cam_terms(F3 o, float4 p0, float4& p1, float4& p2) {   // the operators and the order of leaf_test
     const F3 oc = o - f3(p0.x, p0.y, p0.z);
     const float radius = p1.x;
@@ -351,7 +361,7 @@ __device__ __forceinline__ void sphere_cam_terms(F3 o, float4 p0, float4& p1, fl
 template <bool LEAN = false, bool PRIMARY = false>   // PRIMARY: `o` is the camera, and a sphere record comes back with oc and cc in it
 __device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uint32_t i, F3 o = F3{0.0f, 0.0f, 0.0f}) {
     Prim3 r;
-    if (LEAN && MPT_LEAN_INT24) {
+    if (LEAN) {
         const uint32_t off = mul_u24(i, 48u);
         if (i < sc.n_lds_prims) {
             const LdsNodes q = (LdsNodes)((LdsBytes)lds + (sc.lds_prim_off * 16u + off));
@@ -364,7 +374,7 @@ __device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uin
             r.p0 = q[0];
             r.p1 = q[1];
             r.p2 = q[2];
-            if (MPT_LEAN_CAMSPHERE && PRIMARY && prim_type(r.p0) == 0) sphere_cam_terms(o, r.p0, r.p1, r.p2);
+            if (PRIMARY && prim_type(r.p0) == 0) sphere_cam_terms(o, r.p0, r.p1, r.p2);
         }
         return r;
     }
@@ -386,7 +396,7 @@ __device__ __forceinline__ Prim3 load_prim(const SceneDev& sc, LdsNodes lds, uin
 template <bool COUNT, bool LEAN = false, bool PRIMARY = false>
 __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint32_t first, uint32_t count, F3 o, F3 d,
                                           float& best_t, int& best_prim, WorkCount& wc) {
-    constexpr bool cam_terms = LEAN && MPT_LEAN_INT24 && MPT_LEAN_CAMSPHERE && PRIMARY;   // a sphere record carries oc and cc (load_prim)
+    constexpr bool cam_terms = LEAN && PRIMARY;   // a sphere record carries oc and cc (load_prim)
     for (uint32_t k = 0; k < count; ++k) {
         // the three 16-byte loads of a primitive are issued together (the third is used by triangles only, but a
         // load that waits for the type check costs a second L2 round trip per primitive)
@@ -456,9 +466,6 @@ __device__ __forceinline__ void leaf_test(const SceneDev& sc, LdsNodes lds, uint
 #define MPT_LEAF_EARLY 8u
 #endif
 #define MPT_NODE_HOLD 0x80000000u   // hit link of a leaf record: HOLD | first << 4 | (count - 1)
-#ifndef MPT_LEAN_ONECMP
-#define MPT_LEAN_ONECMP 1
-#endif
 // LEAN: 32-bit primitive addressing (load_prim).  (The box loop's fminf(best_t, ..) canonicalises best_t on every trip — v_max_f32 t, t, t —
 // although best_t does not change inside the loop.  Making it canonical once per round, best_t = fminf(best_t, INFINITY) in front of
 // the loop, does not remove that instruction: the compiler decides "known canonical" per basic block, and the loop body is a block of
@@ -484,10 +491,10 @@ __device__ __forceinline__ bool slab_hit(float4 n0, float4 n1, F3 o, float idx, 
     hi = fminf(hi, idz < 0.0f ? t0 : t1);
     return hi > lo;
 }
-// LEAN and ALL_LDS, the tail leaf (MPT_LEAN_TAIL, mpt_lean_entry.h): in the staged image every link to the walk's last node T is the
+// LEAN and ALL_LDS, the tail leaf (mpt_lean_entry.h): in the staged image every link to the walk's last node T is the
 // marker MPT_NODE_TAIL, "done" for the loop below.  The lanes that hold it test T once behind the loop: its box only where the guard
 // does not already know the answer, then its primitives — one leaf for all of them, so first and count are scalars.  `tail_cfg`: the four
-// float4 the workgroup staged for it, (tlo, T's leaf word) (thi, tail_primary) and T's two plane records.  A launch with the item off has
+// float4 the workgroup staged for it at CFG_F4_TAIL of its configuration block (mpt_lds_cfg.h).  A launch with the item off has
 // no marker in its image and never enters the branch.
 static_assert(MPT_LEAN_LEAF_BIT == MPT_NODE_HOLD && MPT_NODE_TAIL < MPT_NODE_HOLD, "mpt_lean_entry.h: the leaf bit and the tail marker");
 template <bool COUNT, bool ALL_LDS, bool BUDGETED, bool LEAN = false, bool PRIMARY = false>
@@ -497,8 +504,8 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
     // PRIMARY, ALL_LDS: `tile_class` is the class word of the step's tile (mpt_lean_tiles.h, wave-uniform; 0: general).  A `skip` tile's rays
     // miss every box between the entry and T, so its walk is the epilogue below alone — T's spheres, those of the word's mask — and a
     // tile with an empty mask is done at once: no reciprocals, no loop, one copy of the epilogue for both kinds of tile.
-    constexpr bool TILES = PRIMARY && LEAN && ALL_LDS && MPT_LEAN_TILES && MPT_LEAN_ENTRY && MPT_LEAN_TAIL;
-    const bool tile_skip = TILES && (tile_class & MPT_LEAN_TILES_SKIP) != 0u && (MPT_LEAN_TILES_MASK || (tile_class & MPT_LEAN_TILES_MASK_BITS) == 0u);
+    constexpr bool TILES = PRIMARY && LEAN && ALL_LDS;
+    const bool tile_skip = TILES && (tile_class & MPT_LEAN_TILES_SKIP) != 0u;
     float idx = 0.0f, idy = 0.0f, idz = 0.0f;
     const uint32_t n_nodes = sc.n_nodes, n_lds = sc.n_lds_nodes;
     uint32_t i = (tile_class & MPT_LEAN_TILES_MASK_BITS) != 0u ? MPT_NODE_TAIL : n_nodes;   // (a skip tile's)
@@ -526,27 +533,22 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         // (at least 1: "no lane searching" then leaves the loop by the same comparison as the early leave below)
         unsigned long long search_mask = __ballot(i < n_nodes);   // the lanes with i < n_nodes, from the end of a trip to the head of the next
         const uint32_t n_entered0 = (uint32_t)__popcll(search_mask), n_entered = max(n_entered0, 1u);
-#ifdef MPT_DEBUG_WAVE_TIMES
-        uint32_t my_trips = 0, round_trips = 0;
-#endif
+        BoxLoopIdle idle;
         uint32_t n_searching = n_entered0;
         while (n_searching * MPT_LEAF_EARLY >= n_entered && (!BUDGETED || trips < budget)) {
             // LEAN: `searching` is the ballot the trip before (or the entry) took, handed back to the lanes — the compiler does not merge a
             // compare that feeds a ballot with the same compare feeding the exec mask, so the plain form issues it twice per trip
-            // (MPT_LEAN_ONECMP=0: pricing build — profiles/r17_lean_primary.txt)
-            const bool searching = LEAN && MPT_LEAN_ONECMP ? __builtin_amdgcn_inverse_ballot_w64(search_mask) : i < n_nodes;
+            // (priced: profiles/r17_lean_primary.txt)
+            const bool searching = LEAN ?__builtin_amdgcn_inverse_ballot_w64(search_mask) : i < n_nodes;
             // When fewer than 1/8 of the lanes that entered this search are still looking for their next leaf, the
             // others — who hold a leaf — stop waiting: the leaf phase runs now and the searchers resume afterwards
             // from where they are (each lane still sees its own sequence of tests).  In the deep rings most box-loop
             // lane slots were such waits (utilisation 19-42 %); 28.7 -> 27.4 ms, thresholds 1/6 .. 1/32 all help.
             // (this is the loop condition)
-#ifdef MPT_DEBUG_WAVE_TIMES
-            my_trips += searching ? 1u : 0u;
-            round_trips++;
-#endif
+            idle.trip(searching);
             // (the clamp keeps a lane that is not searching inside the array; only searching lanes read, and the compiler drops it where it
             //  sees `searching` as the compare.  Behind the handed-back ballot it cannot see that, so the lean form says it: j = i.)
-            const uint32_t j = LEAN && MPT_LEAN_ONECMP ? i : (i < n_nodes - 1u ? i : n_nodes - 1u);
+            const uint32_t j = LEAN ? i : (i < n_nodes - 1u ? i : n_nodes - 1u);
             float4 n0 = make_float4(0, 0, 0, 0), n1 = n0;
             bool box = false;
             // Lanes that are not searching sit the trip out under the exec mask (one s_and_saveexec / s_or per trip): they issue
@@ -579,12 +581,7 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
             search_mask = __ballot(i < n_nodes);
             n_searching = (uint32_t)__popcll(search_mask);
         }
-#ifdef MPT_DEBUG_WAVE_TIMES
-        if (COUNT) {
-            if ((i & MPT_NODE_HOLD) != 0u) wc.wait_leaf += round_trips - my_trips;
-            else wc.wait_done += round_trips - my_trips;   // finished, out of budget, or cut by the early leave
-        }
-#endif
+        idle.template book<COUNT>((i & MPT_NODE_HOLD) != 0u, wc);
         MPT_TOC(wc.t_box, tic_);
         if ((i & MPT_NODE_HOLD) != 0u) {
             const uint32_t enc = i & ~MPT_NODE_HOLD;
@@ -602,24 +599,24 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         if (BUDGETED && (uint32_t)__popcll(going) < min_active) break;
     }
     }
-    if (LEAN && ALL_LDS && MPT_LEAN_ENTRY && MPT_LEAN_TAIL) {   // (the block is staged with the entry terms: wavelocal_body)
+    if (LEAN && ALL_LDS) {   // (the block is staged with the entry terms: wavelocal_body)
         if (i == MPT_NODE_TAIL) {
             const bool d_ok = fmaxf(fmaxf(fabsf(d.x), fabsf(d.y)), fabsf(d.z)) <= MPT_LEAN_ENTRY_DMAX;
             bool hit;   // T's box test answers hit: known (`certain`), or made
             uint32_t leaf;
             if (PRIMARY) {   // the origin is the launch's camera: one word says whether it is inside [tlo, thi]
-                const __attribute__((address_space(3))) uint32_t* w = (const __attribute__((address_space(3))) uint32_t*)tail_cfg;
-                leaf = w[3];
-                hit = d_ok && w[7] != 0u;
+                const LdsWords w = (LdsWords)tail_cfg;
+                leaf = w[CFG_TAIL_W_LEAF];
+                hit = d_ok && w[CFG_TAIL_W_PRIMARY] != 0u;
             } else {
-                const v4f tlo = tail_cfg[0], thi = tail_cfg[1];
+                const v4f tlo = tail_cfg[CFG_TAIL_LO], thi = tail_cfg[CFG_TAIL_HI];
                 leaf = __float_as_uint(tlo.w);
                 hit = d_ok && tlo.x <= o.x && o.x <= thi.x && tlo.y <= o.y && o.y <= thi.y && tlo.z <= o.z && o.z <= thi.z;
             }
 #if !defined(MPT_LEAN_TAIL_NO_SLAB)   // (a test's build without the branch: tests/test_gpu_lean_tail.py must then fail)
             if (__ballot(!hit) != 0ull) {
                 if (!hit) {
-                    const v4f a = tail_cfg[2], b = tail_cfg[3];
+                    const v4f a = tail_cfg[CFG_TAIL_N0], b = tail_cfg[CFG_TAIL_N1];
                     hit = slab_hit(make_float4(a.x, a.y, a.z, a.w), make_float4(b.x, b.y, b.z, b.w), o, idx, idy, idz, best_t);
                 }
             }

@@ -440,18 +440,12 @@ static const TraceKernel* trace_kernel(int pipeline, bool count, bool all_lds, i
 // The device check behind lean_cdiv_ok (mpt_lean_cdiv.h): all 2^24 numerators of gen_primary<true> over W and over H, on `st`, waited for.
 // Runs when a context's size has changed since its last lean pass, never inside a render.
 static bool lean_cdiv_device_check(mpt_ctx* ctx, hipStream_t st, float W, float H, uint32_t* mismatches) {
-#if MPT_LEAN_CDIV
     if (!ctx->d_cdiv_bad && ctx->d_cdiv_bad.alloc(sizeof(uint32_t)) != hipSuccess) return false;
     if (hipMemsetAsync(ctx->d_cdiv_bad.get(), 0, sizeof(uint32_t), st) != hipSuccess) return false;
     hipLaunchKernelGGL(k_lean_cdiv_check, dim3(256), dim3(256), 0, st, W, H, ctx->d_cdiv_bad.get());
     if (hipGetLastError() != hipSuccess) return false;
     if (hipMemcpyAsync(mismatches, ctx->d_cdiv_bad.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess) return false;
     return hipStreamSynchronize(st) == hipSuccess;
-#else
-    (void)ctx, (void)st, (void)W, (void)H;
-    *mismatches = 0u;   // (the pricing build without the constant division has nothing to check)
-    return true;
-#endif
 }
 
 #define MPT_LDS_MATS MPT_LDS_MATS_N               // materials staged in LDS (32 B each; mpt_kernels.h)
@@ -1216,11 +1210,10 @@ static int order_behind_previous_trace(mpt_ctx* ctx, Lane& L, bool corun) {
 }
 
 // The class table of a pass of the lean ALL_LDS kernels: built by k_lean_tile_classes on the lane's stream, ahead of the trace kernel, when
-// the lane has none for this scene, camera and image (a batch render: once).  Without the item (MPT_LEAN_TILES=0, a pricing build) the
+// the lane has none for this scene, camera and image (a batch render: once).  Without the item (MPT_LEAN_TILES=0 in the environment) the
 // kernels get a null pointer.
 static int ensure_tile_classes(mpt_ctx* ctx, Lane& L, const PassParams& pp, PassLaunch& g) {
     g.tile_classes = nullptr;
-#if MPT_LEAN_TILES
     if (!g.lean_all_lds || !ctx->lean_tiles) {   // (the lane's pass runs without a table: what mpt_read_lean_tile_classes reports for it)
         memset(&L.tile_key, 0, sizeof L.tile_key);
         return MPT_OK;
@@ -1256,9 +1249,6 @@ static int ensure_tile_classes(mpt_ctx* ctx, Lane& L, const PassParams& pp, Pass
         ctx->tile_class_builds++;
     }
     g.tile_classes = L.d_tile_classes.get();
-#else
-    (void)ctx, (void)L, (void)pp;
-#endif
     return MPT_OK;
 }
 

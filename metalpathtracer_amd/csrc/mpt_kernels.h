@@ -91,15 +91,19 @@ __device__ __forceinline__ uint32_t range_paths(uint32_t n_tiles, uint32_t S, ui
     const uint32_t n_g = n_tiles > g ? (n_tiles - g + MPT_NGROUP - 1u) / MPT_NGROUP : 0u;
     return n_g * S * 64u;
 }
+// chunk = tile * S + sample -> (tile, sample); without a division when the samples per pass are a power of two (the usual case)
+__device__ __forceinline__ void chunk_tile_sample(const PassParams& pp, uint32_t chunk, uint32_t& tile, uint32_t& sample) {
+    if (pp.s_shift != 0xFFu) {
+        tile = chunk >> pp.s_shift;
+        sample = chunk & (pp.S - 1u);
+    } else {
+        tile = chunk / pp.S;
+        sample = chunk - tile * pp.S;
+    }
+}
 __device__ __forceinline__ uint32_t range_chunk_to_path_chunk(const PassParams& pp, uint32_t vchunk, uint32_t g) {
     uint32_t tv, s;
-    if (pp.s_shift != 0xFFu) {
-        tv = vchunk >> pp.s_shift;
-        s = vchunk & (pp.S - 1u);
-    } else {
-        tv = vchunk / pp.S;
-        s = vchunk - tv * pp.S;
-    }
+    chunk_tile_sample(pp, vchunk, tv, s);
     return (tv * MPT_NGROUP + g) * pp.S + s;  // chunk index in the pass's path-id space: tile * S + sample
 }
 
@@ -131,8 +135,7 @@ __device__ __forceinline__ void flush_stats(PassDesc* desc, uint32_t n_rays, uin
 // (mesh) tiles — with row-major order the expensive tiles cluster and the end of a pass is all slow work.
 // LEAN (the lean wave-local kernels below): the same values from full-rate 24-bit multiplies and multiply-shift divisions whose
 // ranges the host has checked for the pass (wl_lean_ok, mpt_wl_lean.h, where each bound is derived); no tile table.  `cfg`: the
-// kernel's configuration words in LDS (words 20, 21 = WlLean::s_mul, s_shift, read only when S is not a power of two).
-typedef const __attribute__((address_space(3))) uint32_t* LdsWords;
+// kernel's configuration words in LDS (CFG_W_S_MUL, CFG_W_S_SHIFT of mpt_lds_cfg.h = WlLean::s_mul, s_shift, read only when S is not a power of two).
 __device__ __forceinline__ uint32_t mul24_shift(uint32_t x, uint32_t m, uint32_t sh) {   // (x * m) >> sh, x and m < 2^24, sh <= 47, result < 2^32
     return (uint32_t)(((uint64_t)(x & 0xFFFFFFu) * (uint64_t)(m & 0xFFFFFFu)) >> sh);
 }
@@ -141,12 +144,12 @@ __device__ __forceinline__ bool path_to_pixel(const PassParams& pp, uint32_t pat
                                               uint32_t& s, uint32_t tile_mul = 0u, LdsWords cfg = nullptr) {
     const uint32_t lane = path & 63u, chunk = path >> 6;
     uint32_t tl;
-    if (LEAN && MPT_LEAN_INT24) {
+    if (LEAN) {
         if (pp.s_shift != 0xFFu) {
             tl = chunk >> pp.s_shift;
             s = chunk & (pp.S - 1u);
         } else {
-            const uint32_t s_mul = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg[20]), s_sh = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg[21]);
+            const uint32_t s_mul = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg[CFG_W_S_MUL]), s_sh = (uint32_t)__builtin_amdgcn_readfirstlane((int)cfg[CFG_W_S_SHIFT]);
             tl = mul24_shift(chunk, s_mul, s_sh);
             s = chunk - mul_u24(tl, pp.S);
         }
@@ -155,13 +158,7 @@ __device__ __forceinline__ bool path_to_pixel(const PassParams& pp, uint32_t pat
         py = ty * 8u + (lane >> 3);
         return px < pp.width && py < pp.height;
     }
-    if (pp.s_shift != 0xFFu) {  // samples per pass is a power of two (the usual case): no division
-        tl = chunk >> pp.s_shift;
-        s = chunk & (pp.S - 1u);
-    } else {
-        tl = chunk / pp.S;
-        s = chunk - tl * pp.S;
-    }
+    chunk_tile_sample(pp, chunk, tl, s);
     if (pp.tile_magic != 0u) {   // (wave-uniform) arithmetic instead of a dependent table load: the hit rings recompute the pixel of every popped record
         const uint32_t T = tl * pp.nranks + pp.rank, ty = __umulhi(T, pp.tile_magic), tx = T - ty * pp.tiles_x;
         px = tx * 8u + (lane & 7u);
@@ -194,7 +191,7 @@ template <bool LEAN = false>   // LEAN: Philox decided at compile time, the pixe
 __device__ __forceinline__ void gen_primary(const PassParams& pp, const CamView& cv, uint32_t px, uint32_t py, float uvx, float uvy, uint32_t sample,
                                             PathState& ps, PathRngDev& g) {
     float xOff, yOff;
-    g.pixel = LEAN && MPT_LEAN_INT24 ? mul_u24(py, pp.width) + px : py * pp.width + px;
+    g.pixel = LEAN ? mul_u24(py, pp.width) + px : py * pp.width + px;
     g.sample = sample;
     if (!LEAN && pp.sp.rng_mode == 0) {
         uint32_t seed = pp.pixel_seed[g.pixel];
@@ -205,7 +202,7 @@ __device__ __forceinline__ void gen_primary(const PassParams& pp, const CamView&
         g.lit_seed = seed;
     } else {
         U4 r = philox4x32_10<true>(g.pixel, sample, 0xFFFFFFFFu, 0u, pp.sp.seed_lo, pp.sp.seed_hi);
-        if (LEAN && MPT_LEAN_CDIV) {   // the division proper, its reciprocal step done once per workgroup (cdiv_chain, mpt_device.h)
+        if (LEAN) {   // the division proper, its reciprocal step done once per workgroup (cdiv_chain, mpt_device.h)
             xOff = cdiv_chain(u01(r.x) - 0.5f, cv.W, cv.rW);
             yOff = cdiv_chain(u01(r.y) - 0.5f, cv.H, cv.rH);
         } else {
@@ -519,20 +516,12 @@ __global__ __launch_bounds__(1024, MPT_MIN_WAVES) void k_megakernel(PassParams p
 // keep them from evicting the ring records the trace kernel is about to pop.
 typedef float v4f_nt __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_slot(float4* slots, uint32_t path, float r, float g, float b, float a) {
-#ifdef MPT_SLOTS_TEMPORAL
-    slots[path] = make_float4(r, g, b, a);
-#else
     v4f_nt v = {r, g, b, a};
     __builtin_nontemporal_store(v, (v4f_nt*)(slots + path));
-#endif
 }
 __device__ __forceinline__ float4 load_slot(const float4* slots, uint32_t idx) {
-#ifdef MPT_SLOTS_TEMPORAL
-    return slots[idx];
-#else
     v4f_nt v = __builtin_nontemporal_load((const v4f_nt*)(slots + idx));
     return make_float4(v.x, v.y, v.z, v.w);
-#endif
 }
 
 __device__ __forceinline__ uint32_t wave_rank(unsigned long long m) {
@@ -549,8 +538,8 @@ __device__ __forceinline__ uint32_t wave_rank(unsigned long long m) {
 //   no ring is ready        -> take the next 8x8-pixel tile sample (64 new paths), generate the primary rays in
 //                              registers, closest hit, one bounce of shading; survivors -> ring 0
 // Compaction into the rings is a wave64 ballot + mbcnt prefix; ring counts are wave-uniform registers: no kernel
-// boundary, no shared counter, no atomic per step.  Records are popped newest first (the "rings" are stacks unless
-// MPT_WL_FIFO is defined): what was pushed a few steps ago is still in L2 / Infinity Cache and the live part of a ring
+// boundary, no shared counter, no atomic per step.  Records are popped newest first (the "rings" are stacks):
+// what was pushed a few steps ago is still in L2 / Infinity Cache and the live part of a ring
 // stays below ~128 records — 6 % faster than first-in-first-out.  The order in which rays are traced does not affect
 // any result: every ray writes only its own path's slot.
 // Why budgets: a wave runs as long as its slowest lane, and bounce rays are heavy-tailed on this kind of scene — 88 %
@@ -570,8 +559,9 @@ __device__ __forceinline__ uint32_t wave_rank(unsigned long long m) {
 #endif
 #define MPT_WL_RING 512u       // records per ring
 #define MPT_LDS_MATS_N 32u     // materials staged in LDS (= MPT_LDS_MATS of mpt_hip.hip): the configuration block of k_wavelocal / k_ordered starts behind them
-#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes): camera in float4 0..3, then 24 words (budgets 0..15, claim parameters 16..19, the lean kernels' sample division 20..21 and class table 22..23); float4 10..11: the lean kernels' entry terms, 12..15: their tail leaf (mpt_lean_entry.h).
+#define MPT_LDS_CFG_F4 16u     // ... and is this many float4 long (256 bytes); every slot in it is named in mpt_lds_cfg.h.
                                // The host reserves it (MPT_LDS_EXTRA, ordered_views): k_ordered's stacks start right behind it.
+static_assert(CFG_F4_END <= MPT_LDS_CFG_F4, "configuration block too small");
 // Where the configuration block starts in a workgroup's LDS (float4 index), for the kernels AND for the host code that lays the
 // image out and sizes the launch (mpt_hip.hip: MPT_LDS_EXTRA, ordered_views) — one definition.  Round 4's development build of
 // k_ordered had two: the kernel wrote the block at lds_mat_off + 2 * MPT_LDS_MATS_N while ordered_views still put the per-lane stacks at
@@ -582,6 +572,79 @@ __host__ __device__ __forceinline__ uint32_t mpt_lds_cfg_off_f4(uint32_t lds_mat
 __host__ __device__ __forceinline__ uint32_t mpt_lds_image_end_f4(uint32_t lds_mat_off) { return mpt_lds_cfg_off_f4(lds_mat_off) + MPT_LDS_CFG_F4; }
 #define MPT_WL_BLOCK 1024u     // upper bound of a path-id claim
 #define MPT_WL_NO_BUDGET 0x7FFFFFFFu  // budgets at or above this mean "run to completion"
+
+// ---- the step pieces k_wavelocal* and k_ordered share (scalars, pointers and const& only: by-value copies of the argument structs
+// once cost k_ordered spilled VGPRs, the comment above it) ------------------------------------------------------------------------
+// What both kernels keep in the block: the camera (primary steps) and what only a CLAIM of path ids needs.  One thread of the
+// workgroup, before the barrier of the image's staging.  `rW`, `rH`: cdiv_recip of W and H for the lean kernels, 0 elsewhere.
+__device__ __forceinline__ void cfg_stage_common(float4* blk, const PassParams& pp, float rW, float rH, uint32_t wl_block, uint32_t wl_min, uint32_t wl_div) {
+    blk[CFG_F4_CAM] = make_float4(pp.cam.x, pp.cam.y, pp.cam.z, pp.W);
+    blk[CFG_F4_FIRST] = make_float4(pp.first.x, pp.first.y, pp.first.z, pp.H);
+    blk[CFG_F4_VU] = make_float4(pp.vu.x, pp.vu.y, pp.vu.z, rW);
+    blk[CFG_F4_VV] = make_float4(pp.vv.x, pp.vv.y, pp.vv.z, rH);
+    uint32_t* w = (uint32_t*)(blk + CFG_F4_WORDS);
+    w[CFG_W_CLAIM_BLOCK] = wl_block;
+    w[CFG_W_CLAIM_MIN] = wl_min;
+    w[CFG_W_CLAIM_DIV] = wl_div * (((uint32_t)(gridDim.x * (blockDim.x >> 6)) + MPT_NGROUP - 1u) / MPT_NGROUP);   // wl_div * waves per claim range
+    w[CFG_W_RANK_TILES] = pp.desc->total_paths / (pp.S * 64u);                                                  // this rank's tiles
+}
+// ... and the camera read back by a primary step (`blk`: the block in LDS)
+__device__ __forceinline__ CamView cfg_cam_view(LdsNodes blk) {
+    const v4f c0 = blk[CFG_F4_CAM], c1 = blk[CFG_F4_FIRST], c2 = blk[CFG_F4_VU], c3 = blk[CFG_F4_VV];
+    CamView cv;
+    cv.cam = f3(c0.x, c0.y, c0.z);
+    cv.first = f3(c1.x, c1.y, c1.z);
+    cv.vu = f3(c2.x, c2.y, c2.z);
+    cv.vv = f3(c3.x, c3.y, c3.z);
+    cv.W = c0.w;
+    cv.H = c1.w;
+    cv.rW = c2.w;
+    cv.rH = c3.w;
+    return cv;
+}
+// Guided self-scheduling of path ids.  The pass's tiles are dealt to MPT_NGROUP interleaved ranges, each with its own cursor on its
+// own line (a single cursor saturates at ~88 claims/us: in the sky part of the image a step takes ~1 us and 8192 waves would queue
+// on it).  A wave claims from its home range (blockIdx % 8: the blocks of one XCD under round-robin placement), then steals from the
+// next ranges.  Claim size = remaining_in_range / (wl_div * waves_per_range) rounded to whole 64-path tile samples and clamped to
+// [wl_min, wl_block]: few atomics while there is plenty of work, fine grain at the end (tile samples differ ~5x in cost between sky
+// and geometry; with remaining/(2*waves) the last wave finished 23 ms after the first, with /16 within ~1 ms).  `seen` is the cursor
+// value of this wave's previous claim: an extra load of the hot cursor line before the atomic made the kernel 4x slower (loads of a
+// line under atomic fire serialise at the memory side).
+// `cfg`: the block's words.  `grp`, `seen`: the wave's claim state.  True: the wave owns the virtual indices [k, min(k + blk, rend)) of
+// range `grp`.  False: every range is exhausted.  All wave-uniform.  (The caller sets its own `cur`, `end` and `exhausted`: a helper
+// that wrote them moved k_ordered's spilled scalars — 76 -> 94 in one instantiation, profiles/r24_trace_refactor.txt.)
+__device__ __forceinline__ bool claim_paths(const PassParams& pp, LdsWords cfg, uint32_t lane, uint32_t& grp, uint32_t& seen, uint32_t& k, uint32_t& blk,
+                                            uint32_t& rend) {
+    bool got = false;
+    k = 0, blk = 0, rend = 0;
+    if (lane == 0) {
+        const uint32_t c_block = cfg[CFG_W_CLAIM_BLOCK], c_min = cfg[CFG_W_CLAIM_MIN], c_div = cfg[CFG_W_CLAIM_DIV], c_tiles = cfg[CFG_W_RANK_TILES];
+        for (uint32_t t = 0; t < MPT_NGROUP && !got; ++t) {
+            const uint32_t re = range_paths(c_tiles, pp.S, grp);
+            const uint32_t left = seen < re ? re - seen : 0u;
+            blk = (left / c_div) & ~63u;
+            blk = blk < c_min ? c_min : (blk > c_block ? c_block : blk);
+            // a range entered by stealing is near its end but `seen` knows nothing about it yet: the first
+            // claim there is the minimum (it returns the cursor, which sizes the following ones)
+            if (t > 0u) blk = c_min;
+            k = atomicAdd(&pp.ctr[MPT_CTR_CURSOR(grp)], blk);
+            if (k < re) {
+                got = true;
+                rend = re;
+            } else {
+                grp = (grp + 1u) & (MPT_NGROUP - 1u);
+                seen = 0;
+            }
+        }
+    }
+    got = __builtin_amdgcn_readfirstlane((int)got) != 0;
+    k = __builtin_amdgcn_readfirstlane(k);
+    blk = __builtin_amdgcn_readfirstlane(blk);
+    rend = __builtin_amdgcn_readfirstlane(rend);
+    grp = __builtin_amdgcn_readfirstlane(grp);
+    seen = k;
+    return got;
+}
 // Ring record (round 4, "the traffic diet"): 48 bytes that every ray needs — od, dt, ia — and 16 more (tl: the light gathered so
 // far) only for the rays that HAVE gathered light: L and alpha are all-zero bits until a path meets an emitter, which most bounce
 // rays of most scenes never have (a flag in ia says whether tl was written; the pop restores exact zeros otherwise).  The sample
@@ -684,21 +747,15 @@ struct WaveBudgets {
 #ifndef MPT_WL_WAVES_N
 #define MPT_WL_WAVES_N 6
 #endif
-// Carried hits (MPT_WL_CARRY, default on).  Ring 0 is a stack and a ring-0 step pops its newest records, so whenever the step after
+// Carried hits.  Ring 0 is a stack and a ring-0 step pops its newest records, so whenever the step after
 // a hit push is a ring-0 step the records just written are read straight back: 48-64 bytes to the fabric (stores are not absorbed
 // by L2) and a dependent load of the same bytes at the head of the next step, for rays that never left the wave.  With the carry
 // the hits of a step stay in the lanes that found them when the next step is known to be a ring-0 step — no ring >= 1 holds a full
 // wave and ring 0 plus these hits does — and that step pops only the 64 - k records it still needs, into the lanes that carry
 // nothing.  "Push k, pop the top 64" and "keep k, pop the top 64 - k" give a step the same 64 rays and leave the same records
 // behind; only the lane a ray sits in differs, and nothing a path computes depends on its lane: every step of the schedule, every
-// count and every slot value stay what they were.  -DMPT_WL_CARRY=0 pushes every hit.  A first-in-first-out ring pops the OLDEST
-// records, so the identity does not hold there.
-#ifndef MPT_WL_CARRY
-#define MPT_WL_CARRY 1
-#endif
-#if MPT_WL_CARRY && defined(MPT_WL_FIFO)
-#error "MPT_WL_CARRY needs ring 0 to be a stack: build MPT_WL_FIFO with -DMPT_WL_CARRY=0"
-#endif
+// count and every slot value stay what they were.  (The identity needs ring 0 to be a stack: a first-in-first-out ring pops the OLDEST
+// records.)
 #define MPT_WL_THREADS(ALL_LDS) MPT_WL_THREADS_N
 #define MPT_WL_WAVES(ALL_LDS) MPT_WL_WAVES_N
 template <bool COUNT, bool ALL_LDS, bool LEAN = false>
@@ -751,74 +808,164 @@ __global__ __launch_bounds__(64) void k_lean_tile_classes(const float4* nodes, u
     const uint32_t ty = T / view.tiles_x, tx = T - ty * view.tiles_x;
     out[T] = ty < view.tiles_y ? lean_tile_class(nodes, n_nodes, prims, n_prims, view, tx, ty) : 0u;
 }
+// The diagnostics of a -DMPT_DEBUG_WAVE_TIMES build (tools/gpu_wave_times.py reads the buffer behind the rings' last array): per wave
+// its timestamps, step counts and shader-clock cycles per region of a step; with counting also, per kind of step, the divergence of the
+// walk and the ring traffic by record.  In a product build every member does nothing and the type holds nothing.
+struct WaveStepDiag {
+    enum Region { SELECT, FETCH, TRACE, SHADE, PUSH, N_REGIONS };
+#ifdef MPT_DEBUG_WAVE_TIMES
+    unsigned long long t_start, t_exh = 0ull, t_claim = 0ull, steps = 0ull, left = 0ull, blk = 0ull;
+    unsigned long long reg[N_REGIONS] = {}, tic_;   // cycles per region
+    WorkCount wc0;
+    __device__ __forceinline__ static uint32_t n_waves() { return gridDim.x * (blockDim.x >> 6); }
+    __device__ __forceinline__ static unsigned long long* buffer(const WaveRings& ring) { return (unsigned long long*)(ring.tv() + (size_t)n_waves() * MPT_WL_LEVELS * MPT_WL_RING); }
+    __device__ __forceinline__ void start() { t_start = __builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ void tic() { tic_ = __builtin_amdgcn_s_memtime(); }
+    __device__ __forceinline__ void toc(Region r) { MPT_TOC(reg[r], tic_); }
+    __device__ __forceinline__ void claimed(bool got, uint32_t asked, const uint32_t* cnt) {
+        if (got) {
+            t_claim = __builtin_amdgcn_s_memrealtime();
+            steps = 0ull;
+            blk = asked;
+        } else {
+            t_exh = __builtin_amdgcn_s_memrealtime();
+            for (uint32_t q = 0; q < MPT_WL_LEVELS; ++q) left |= (unsigned long long)cnt[q] << (12u * q);
+        }
+    }
+    __device__ __forceinline__ void step(bool exhausted, int level) {
+        if (!exhausted) steps += 1ull << (12u * (uint32_t)(level + 1));  // field 0 = primary steps
+    }
+    __device__ __forceinline__ void before_walk(const WorkCount& wc) { wc0 = wc; }
+    template <bool COUNT>
+    __device__ __forceinline__ void after_walk(const WaveRings& ring, int level, const WorkCount& wc, bool done) const {
+        if (!COUNT) return;
+        // per-level divergence diagnostics: [level + 1][steps, box trips, box lane work, prim trips, prim lane work]
+        unsigned long long* lv = buffer(ring) + 16ull * n_waves() + 8ull * (unsigned)(level + 1);
+        if (first_active_lane()) atomicAdd(lv + 0, 1ull);
+        // the per-wave trip counters live in whichever lane was first active at the time: sum over lanes
+        if (wc.node_iters != wc0.node_iters) atomicAdd(lv + 1, (unsigned long long)(wc.node_iters - wc0.node_iters));
+        if (wc.prim_iters != wc0.prim_iters) atomicAdd(lv + 3, (unsigned long long)(wc.prim_iters - wc0.prim_iters));
+        atomicAdd(lv + 2, (unsigned long long)(wc.node_visits - wc0.node_visits));
+        atomicAdd(lv + 4, (unsigned long long)(wc.prim_tests - wc0.prim_tests));
+        atomicAdd(lv + 5, 1ull);  // rays in the step
+        if (wc.wait_leaf != wc0.wait_leaf) atomicAdd(lv + 7, (unsigned long long)(wc.wait_leaf - wc0.wait_leaf));
+        if (done) atomicAdd(lv + 6, 1ull);
+    }
+    template <bool COUNT>
+    __device__ __forceinline__ void traffic(const WaveRings& ring, uint32_t lane, unsigned long long am, unsigned long long pm, bool keep, bool alive, bool parked,
+                                            const PathState& ps) const {
+        if (!COUNT || (am | pm) == 0ull) return;
+        // rows 15 and 14 of the per-step-kind block, the ring traffic by record: row 15 = hits (carried, pushed, carried with light,
+        // pushed with light, steps that carried, steps that pushed), row 14 = parked rays (records, with light, steps)
+        unsigned long long* rt = buffer(ring) + 16ull * n_waves() + 8ull * 14ull;
+        const unsigned long long lit_a = __ballot(alive && ring_has_light(ps)), lit_p = __ballot(parked && ring_has_light(ps));
+        if (lane == 0u) {
+            if (am != 0ull) {
+                atomicAdd(rt + 8 + (keep ? 0 : 1), (unsigned long long)__popcll(am));
+                atomicAdd(rt + 8 + (keep ? 2 : 3), (unsigned long long)__popcll(lit_a));
+                atomicAdd(rt + 8 + (keep ? 4 : 5), 1ull);
+            }
+            if (pm != 0ull) {
+                atomicAdd(rt + 0, (unsigned long long)__popcll(pm));
+                atomicAdd(rt + 1, (unsigned long long)__popcll(lit_p));
+                atomicAdd(rt + 2, 1ull);
+            }
+        }
+    }
+    // per-wave (start, cursor exhausted, end) timestamps, 100 MHz ticks, and the regions' cycles
+    __device__ __forceinline__ void finish(const WaveRings& ring, uint32_t lane, uint32_t wave_id, const WorkCount& wc) const {
+        if (lane != 0) return;
+        unsigned long long* dbg = buffer(ring);
+        dbg[8 * wave_id] = t_start;
+        dbg[8 * wave_id + 1] = t_exh;
+        dbg[8 * wave_id + 2] = __builtin_amdgcn_s_memrealtime();
+        dbg[8 * wave_id + 3] = t_claim;
+        dbg[8 * wave_id + 4] = steps;
+        dbg[8 * wave_id + 5] = left;
+        dbg[8 * wave_id + 6] = blk;
+        unsigned long long* out = dbg + 8ull * n_waves() + 8ull * wave_id;
+        for (int r = 0; r < N_REGIONS; ++r) out[r] = reg[r];
+        out[5] = wc.t_box;
+        out[6] = wc.t_leaf;
+    }
+#else
+    __device__ __forceinline__ void start() {}
+    __device__ __forceinline__ void tic() {}
+    __device__ __forceinline__ void toc(Region) {}
+    __device__ __forceinline__ void claimed(bool, uint32_t, const uint32_t*) {}
+    __device__ __forceinline__ void step(bool, int) {}
+    __device__ __forceinline__ void before_walk(const WorkCount&) {}
+    template <bool COUNT>
+    __device__ __forceinline__ void after_walk(const WaveRings&, int, const WorkCount&, bool) const {}
+    template <bool COUNT>
+    __device__ __forceinline__ void traffic(const WaveRings&, uint32_t, unsigned long long, unsigned long long, bool, bool, bool, const PathState&) const {}
+    __device__ __forceinline__ void finish(const WaveRings&, uint32_t, uint32_t, const WorkCount&) const {}
+#endif
+};
+// The lean kernels' own slots of the block (mpt_lds_cfg.h), by the thread that stages it: where fresh queries enter the tree
+// (mpt_lean_entry.h), and with the whole tree in LDS the tail leaf T — (tlo, T's leaf word) (thi, tail_primary) and T's own two records
+// for the lanes that make its box test, with T (0: the item is off) in the place of its miss link, which no box test reads.
+template <bool ALL_LDS>
+__device__ __forceinline__ void cfg_stage_lean(float4* blk, const PassParams& pp) {
+    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // (a tree without nodes: A0 = 0 switches the item off, nothing is read)
+    const bool tree = pp.scene.n_nodes != 0u;
+    const LeanEntry e = lean_entry_terms(tree ? pp.scene.nodes[0] : none, tree ? pp.scene.nodes[1] : none, pp.scene.n_nodes, pp.cam.x, pp.cam.y, pp.cam.z);
+    uint32_t entry = e.entry, entry_primary = e.entry_primary;
+    if (ALL_LDS) {
+        const LeanTail t = lean_tail_terms(pp.scene.nodes, pp.scene.n_nodes, pp.cam.x, pp.cam.y, pp.cam.z);
+        float4* const tail = blk + CFG_F4_TAIL;
+        tail[CFG_TAIL_LO] = make_float4(t.tlo[0], t.tlo[1], t.tlo[2], __uint_as_float(t.leaf));
+        tail[CFG_TAIL_HI] = make_float4(t.thi[0], t.thi[1], t.thi[2], __uint_as_float(t.tail_primary));
+        float4 t0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t1 = t0;   // (values, not a choice between two addresses)
+        if (t.node != 0u) {
+            t0 = pp.scene.nodes[2u * t.node];
+            t1 = pp.scene.nodes[2u * t.node + 1u];
+        }
+        t1.w = __uint_as_float(t.node);
+        tail[CFG_TAIL_N0] = t0;
+        tail[CFG_TAIL_N1] = t1;
+        // a fresh query that enters at T enters at the marker
+        if (t.node != 0u && entry == t.node) entry = MPT_NODE_TAIL;
+        if (t.node != 0u && entry_primary == t.node) entry_primary = MPT_NODE_TAIL;
+    }
+    blk[CFG_F4_ENTRY_LO] = make_float4(e.ilo[0], e.ilo[1], e.ilo[2], __uint_as_float(entry));
+    blk[CFG_F4_ENTRY_HI] = make_float4(e.ihi[0], e.ihi[1], e.ihi[2], __uint_as_float(entry_primary));
+}
 template <bool COUNT, bool ALL_LDS, bool LEAN>
 __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveRings& ring, const WaveBudgets& budgets, uint32_t wl_block, uint32_t wl_min,
                                                uint32_t wl_div, const WlLean& lean, const uint32_t* tile_classes) {
     static_assert(!(LEAN && COUNT), "the lean body does not count");
     // the per-tile class words (mpt_lean_tiles.h) are read by the primary steps of the lean kernels whose whole tree is in LDS
-    constexpr bool TILES = LEAN && ALL_LDS && MPT_LEAN_TILES && MPT_LEAN_ENTRY && MPT_LEAN_TAIL && MPT_LEAN_CAMSPHERE;
+    constexpr bool TILES = LEAN && ALL_LDS;
     extern __shared__ float4 lds_nodes_raw[];
     // what only some steps need goes to LDS, behind the scene image (the 256-byte descriptor area of MPT_LDS_EXTRA), instead of
     // living in scalar registers across the whole step loop: the camera (14 words, primary steps) and the ring budgets (10 words,
     // ring steps).  The loop needs more scalar registers than the 102 a wave has; every value kept out of it is one spill less.
     const uint32_t cfg_off = mpt_lds_cfg_off_f4(pp.scene.lds_mat_off);   // in float4 units
+    float4* const blk_raw = lds_nodes_raw + cfg_off;
     if (threadIdx.x == 0) {
         announce_resident(pp);
-        lds_nodes_raw[cfg_off + 0] = make_float4(pp.cam.x, pp.cam.y, pp.cam.z, pp.W);
-        lds_nodes_raw[cfg_off + 1] = make_float4(pp.first.x, pp.first.y, pp.first.z, pp.H);
-        lds_nodes_raw[cfg_off + 2] = make_float4(pp.vu.x, pp.vu.y, pp.vu.z, LEAN && MPT_LEAN_CDIV ? cdiv_recip(pp.W) : 0.0f);
-        lds_nodes_raw[cfg_off + 3] = make_float4(pp.vv.x, pp.vv.y, pp.vv.z, LEAN && MPT_LEAN_CDIV ? cdiv_recip(pp.H) : 0.0f);
-        uint32_t* w = (uint32_t*)(lds_nodes_raw + cfg_off + 4);
+        cfg_stage_common(blk_raw, pp, LEAN ? cdiv_recip(pp.W) : 0.0f, LEAN ? cdiv_recip(pp.H) : 0.0f, wl_block, wl_min, wl_div);
+        uint32_t* w = (uint32_t*)(blk_raw + CFG_F4_WORDS);
+        static_assert(MPT_WL_LEVELS <= CFG_MAX_LEVELS, "configuration block: a budget word per ring");
         for (uint32_t k = 0; k < MPT_WL_LEVELS; ++k) {
-            w[k] = budgets.b[k];
-            w[8u + k] = budgets.min_active[k];
+            w[CFG_W_BUDGET + k] = budgets.b[k];
+            w[CFG_W_MIN_ACTIVE + k] = budgets.min_active[k];
         }
-        // ... and what only a CLAIM of path ids needs (words 16..19 of the block's 32: static_assert below)
-        static_assert(4u * (10u - 4u) >= 24u && MPT_LDS_CFG_F4 >= 12u, "configuration block too small");   // words 0..23 fill float4 4..9 (22, 23: the lean kernels' class table); float4 10 and 11 hold the lean kernels' entry terms
-        w[16] = wl_block;
-        w[17] = wl_min;
-        w[18] = wl_div * (((uint32_t)(gridDim.x * (blockDim.x >> 6)) + MPT_NGROUP - 1u) / MPT_NGROUP);   // wl_div * waves per claim range
-        w[19] = pp.desc->total_paths / (pp.S * 64u);                                                   // this rank's tiles
         if (LEAN) {   // the division by a sample count that is no power of two (path_to_pixel<true>)
-            w[20] = lean.s_mul;
-            w[21] = lean.s_shift;
+            w[CFG_W_S_MUL] = lean.s_mul;
+            w[CFG_W_S_SHIFT] = lean.s_shift;
         }
-        if (TILES) {   // the class table's address (words 22 and 23, the last of float4 9; null: every tile is general) — read back when a wave changes its tile, so that the step loop keeps no scalar register for it
-            w[22] = (uint32_t)(uintptr_t)tile_classes;
-            w[23] = (uint32_t)((uint64_t)(uintptr_t)tile_classes >> 32);
+        if (TILES) {   // the class table's address (null: every tile is general) — read back when a wave changes its tile, so that the step loop keeps no scalar register for it
+            w[CFG_W_CLASSES_LO] = (uint32_t)(uintptr_t)tile_classes;
+            w[CFG_W_CLASSES_HI] = (uint32_t)((uint64_t)(uintptr_t)tile_classes >> 32);
         }
-        if (LEAN && MPT_LEAN_ENTRY) {   // where fresh queries enter the tree (mpt_lean_entry.h): float4 10 and 11 of the block, behind the words above
-            const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // (a tree without nodes: A0 = 0 switches the item off, nothing is read)
-            const bool tree = pp.scene.n_nodes != 0u;
-            const LeanEntry e = lean_entry_terms(tree ? pp.scene.nodes[0] : none, tree ? pp.scene.nodes[1] : none, pp.scene.n_nodes, pp.cam.x, pp.cam.y, pp.cam.z);
-            // the tail leaf (MPT_LEAN_TAIL, mpt_lean_entry.h): float4 12..15 — (tlo, T's leaf word) (thi, tail_primary) and T's own two records for the
-            // lanes that make its box test, with T (0: the item is off) in the place of its miss link, which no box test reads
-            uint32_t entry = e.entry, entry_primary = e.entry_primary;
-            if (ALL_LDS && MPT_LEAN_TAIL) {
-                static_assert(MPT_LDS_CFG_F4 >= 16u, "configuration block too small");
-                const LeanTail t = lean_tail_terms(pp.scene.nodes, pp.scene.n_nodes, pp.cam.x, pp.cam.y, pp.cam.z);
-                lds_nodes_raw[cfg_off + 12] = make_float4(t.tlo[0], t.tlo[1], t.tlo[2], __uint_as_float(t.leaf));
-                lds_nodes_raw[cfg_off + 13] = make_float4(t.thi[0], t.thi[1], t.thi[2], __uint_as_float(t.tail_primary));
-                float4 t0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), t1 = t0;   // (values, not a choice between two addresses)
-                if (t.node != 0u) {
-                    t0 = pp.scene.nodes[2u * t.node];
-                    t1 = pp.scene.nodes[2u * t.node + 1u];
-                }
-                t1.w = __uint_as_float(t.node);
-                lds_nodes_raw[cfg_off + 14] = t0;
-                lds_nodes_raw[cfg_off + 15] = t1;
-                // a fresh query that enters at T enters at the marker
-                if (t.node != 0u && entry == t.node) entry = MPT_NODE_TAIL;
-                if (t.node != 0u && entry_primary == t.node) entry_primary = MPT_NODE_TAIL;
-            }
-            lds_nodes_raw[cfg_off + 10] = make_float4(e.ilo[0], e.ilo[1], e.ilo[2], __uint_as_float(entry));
-            lds_nodes_raw[cfg_off + 11] = make_float4(e.ihi[0], e.ihi[1], e.ihi[2], __uint_as_float(entry_primary));
-        }
+        if (LEAN) cfg_stage_lean<ALL_LDS>(blk_raw, pp);
     }
-    if (LEAN && MPT_LEAN_CAMSPHERE) stage_nodes_lean(pp.scene, lds_nodes_raw, pp.cam);
+    if (LEAN) stage_nodes_lean(pp.scene, lds_nodes_raw, pp.cam);
     else stage_nodes(pp.scene, lds_nodes_raw);
-    if (LEAN && ALL_LDS && MPT_LEAN_ENTRY && MPT_LEAN_TAIL) {   // every link to T in the image becomes the marker (the global array stays as it is)
-        const uint32_t tail_node = __float_as_uint(lds_nodes_raw[cfg_off + 15].w);
+    if (LEAN && ALL_LDS) {   // every link to T in the image becomes the marker (the global array stays as it is)
+        const uint32_t tail_node = __float_as_uint(blk_raw[CFG_F4_TAIL + CFG_TAIL_N1].w);
         if (tail_node != 0u) {
             uint32_t* links = (uint32_t*)lds_nodes_raw;
             for (uint32_t k = threadIdx.x; k < pp.scene.n_lds_nodes * 2u; k += blockDim.x)
@@ -828,17 +975,15 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
     }
     MPT_CLOCK_BEGIN();
     const LdsNodes lds_nodes = (LdsNodes)lds_nodes_raw;
-    const __attribute__((address_space(3))) uint32_t* lds_cfg_u32 = (const __attribute__((address_space(3))) uint32_t*)(lds_nodes + cfg_off + 4u);
+    const LdsNodes blk = lds_nodes + cfg_off;                       // the configuration block (mpt_lds_cfg.h)
+    const LdsWords lds_cfg_u32 = (LdsWords)(blk + CFG_F4_WORDS);    // ... and its words
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_id = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-#ifdef MPT_DEBUG_WAVE_TIMES
-    const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
-#endif
     const uint32_t wbase = wave_id * (MPT_WL_LEVELS * MPT_WL_RING);
-    const uint32_t M = MPT_WL_RING - 1u;
-    uint32_t head[MPT_WL_LEVELS], cnt[MPT_WL_LEVELS];  // wave-uniform ring state (fully unrolled accesses)
+    const uint32_t M = MPT_WL_RING - 1u;   // (ring positions wrap: what the "cannot happen" overflow flag below relies on)
+    uint32_t cnt[MPT_WL_LEVELS];  // wave-uniform ring fills: the rings are stacks (fully unrolled accesses)
 #pragma unroll
-    for (uint32_t k = 0; k < MPT_WL_LEVELS; ++k) head[k] = cnt[k] = 0;
+    for (uint32_t k = 0; k < MPT_WL_LEVELS; ++k) cnt[k] = 0;
     uint32_t cur = 0, end = 0;     // wave-uniform private range of path ids (multiples of 64)
     uint32_t grp = blockIdx.x & (MPT_NGROUP - 1u);     // range this wave currently claims from
     uint32_t seen = 0;                                 // cursor value (virtual index) at this wave's previous claim
@@ -848,7 +993,6 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
     float uvx_cached = 0.0f, uvy_cached = 0.0f;   // pixel_uv of this lane's pixel in the cached tile
     uint32_t n_rays = 0, n_paths = 0;
     WorkCount wc = {};
-#if MPT_WL_CARRY
     // the hits the previous step kept in its lanes (the lane mask is this flag's ballot).  What those lanes hold is the step's own
     // `ps`, `best_t` and `best_prim`, which therefore live across the loop's back edge: every step replaces them in every lane that
     // carries nothing, so they occupy no register the walk did not need anyway and nothing is copied.  (A separate copy, written
@@ -857,82 +1001,27 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
     PathState ps = {};
     float best_t = INFINITY;
     int best_prim = -1;
-#endif
-#ifdef MPT_DEBUG_WAVE_TIMES
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    unsigned long long t_exh = 0ull, t_claim = 0ull, dbg_steps = 0ull, dbg_left = 0ull, dbg_blk = 0ull;
-    unsigned long long reg_select = 0, reg_fetch = 0, reg_trace = 0, reg_shade = 0, reg_push = 0;  // cycles per region
-#endif
+    WaveStepDiag diag;
+    diag.start();
     for (;;) {
-        MPT_TIC(tic_);
+        diag.tic();
         // ---- step choice: deepest ring with a full wave of rays; else new paths; else drain ----------------------
         int level = -1;  // -1 = primary step
-#if MPT_WL_CARRY
         const unsigned long long carry = __ballot(kept);   // ring 0 counts with the hits its last step kept: a carry always leads to level 0
         if (cnt[0] + (uint32_t)__popcll(carry) >= 64u) level = 0;
 #pragma unroll
         for (int k = (int)MPT_WL_LEVELS - 1; k >= 1; --k)
             if (level <= 0 && cnt[k] >= 64u) level = k;   // (never with a carry: the carry rule saw every ring >= 1 below 64)
-#else
-#pragma unroll
-        for (int k = (int)MPT_WL_LEVELS - 1; k >= 0; --k)
-            if (level < 0 && cnt[k] >= 64u) level = k;
-#endif
         if (level < 0) {
             if (!exhausted && cur == end) {
-                // Guided self-scheduling of path ids.  The pass's tiles are dealt to MPT_NGROUP interleaved ranges,
-                // each with its own cursor on its own line (a single cursor saturates at ~88 claims/us: in the sky
-                // part of the image a step takes ~1 us and 8192 waves would queue on it).  A wave claims from its
-                // home range (blockIdx % 8: the blocks of one XCD under round-robin placement), then steals from the
-                // next ranges.  Claim size = remaining_in_range / (wl_div * waves_per_range) rounded to whole 64-path
-                // tile samples and clamped to [wl_min, wl_block]: few atomics while there is plenty of work, fine grain
-                // at the end (tile samples differ ~5x in cost between sky and geometry; with remaining/(2*waves) the
-                // last wave finished 23 ms after the first, with /16 within ~1 ms).  `seen` is the cursor value of
-                // this wave's previous claim: an extra load of the hot cursor line before the atomic made the kernel
-                // 4x slower (loads of a line under atomic fire serialise at the memory side).
-                uint32_t k = 0, blk = 0, rend = 0;
-                bool got = false;
-                if (lane == 0) {
-                    const uint32_t c_block = lds_cfg_u32[16], c_min = lds_cfg_u32[17], c_div = lds_cfg_u32[18], c_tiles = lds_cfg_u32[19];   // (claim parameters: from LDS)
-                    for (uint32_t t = 0; t < MPT_NGROUP && !got; ++t) {
-                        const uint32_t re = range_paths(c_tiles, pp.S, grp);
-                        const uint32_t left = seen < re ? re - seen : 0u;
-                        blk = (left / c_div) & ~63u;
-                        blk = blk < c_min ? c_min : (blk > c_block ? c_block : blk);
-                        // a range entered by stealing is near its end but `seen` knows nothing about it yet: the first
-                        // claim there is the minimum (it returns the cursor, which sizes the following ones)
-                        if (t > 0u) blk = c_min;
-                        k = atomicAdd(&pp.ctr[MPT_CTR_CURSOR(grp)], blk);
-                        if (k < re) {
-                            got = true;
-                            rend = re;
-                        } else {
-                            grp = (grp + 1u) & (MPT_NGROUP - 1u);
-                            seen = 0;
-                        }
-                    }
-                }
-                got = __builtin_amdgcn_readfirstlane((int)got) != 0;
-                k = __builtin_amdgcn_readfirstlane(k);
-                blk = __builtin_amdgcn_readfirstlane(blk);
-                rend = __builtin_amdgcn_readfirstlane(rend);
-                grp = __builtin_amdgcn_readfirstlane(grp);
-                seen = k;
-#ifdef MPT_DEBUG_WAVE_TIMES
-                if (got) {
-                    t_claim = __builtin_amdgcn_s_memrealtime();
-                    dbg_steps = 0ull;
-                    dbg_blk = blk;
-                } else {
-                    t_exh = __builtin_amdgcn_s_memrealtime();
-                    for (uint32_t q = 0; q < MPT_WL_LEVELS; ++q) dbg_left |= (unsigned long long)cnt[q] << (12u * q);
-                }
-#endif
+                uint32_t k, blk_asked, rend;
+                const bool got = claim_paths(pp, lds_cfg_u32, lane, grp, seen, k, blk_asked, rend);
+                diag.claimed(got, blk_asked, cnt);
                 if (!got) {
                     exhausted = true;
                 } else {
                     cur = k;
-                    end = (k + blk < rend) ? k + blk : rend;
+                    end = (k + blk_asked < rend) ? k + blk_asked : rend;
                 }
             }
             if (exhausted) {
@@ -950,11 +1039,8 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 level = (int)MPT_WL_LEVELS;  // merged drain step
             }
         }
-#ifdef MPT_DEBUG_WAVE_TIMES
-        if (!exhausted) dbg_steps += 1ull << (12u * (uint32_t)(level + 1));  // field 0 = primary steps
-#endif
-        MPT_TOC(reg_select, tic_);
-#if MPT_WL_CARRY
+        diag.step(exhausted, level);
+        diag.toc(WaveStepDiag::SELECT);
         // a lane that carries a hit holds what a push and a pop of its record would have left there (ring_push_hit / ring_pop_hit):
         // the ray in `ps`, and t and the primitive behind the record's masks
         float hit_t = __uint_as_float(__float_as_uint(best_t) & 0x7FFFFFFFu);
@@ -962,13 +1048,6 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         ps.bounce &= 31u;
         best_t = INFINITY;
         best_prim = -1;
-#else
-        PathState ps;
-        float best_t = INFINITY;
-        int best_prim = -1;
-        float hit_t = 0.0f;
-        int hit_prim = -1;
-#endif
         PathRngDev g;
         bool valid = false;
         uint32_t node = 0;
@@ -983,19 +1062,13 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             const uint32_t pchunk = range_chunk_to_path_chunk(pp, cur >> 6, grp);  // cur is a virtual index of range grp
             cur += 64u;
             uint32_t tl, sidx;
-            if (pp.s_shift != 0xFFu) {
-                tl = pchunk >> pp.s_shift;
-                sidx = pchunk & (pp.S - 1u);
-            } else {
-                tl = pchunk / pp.S;
-                sidx = pchunk - tl * pp.S;
-            }
+            chunk_tile_sample(pp, pchunk, tl, sidx);
             const bool new_tile = tl != tile_cached;
             if (new_tile) {
                 tile_cached = tl;
                 if (TILES) {   // the tile's class word, kept with the cached tile: a scalar load from a wave-uniform address (the table's address comes
                                // from LDS here, once per tile change, so that the step loop keeps one scalar register for the word and none for the table)
-                    const uint32_t tlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[22]), thi = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[23]);
+                    const uint32_t tlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_CLASSES_LO]), thi = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_CLASSES_HI]);
                     tile_class_cached = 0u;
                     if ((tlo | thi) != 0u) {
                         typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
@@ -1019,18 +1092,7 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 tile_xy = (T - ty * pp.tiles_x) | (ty << 16);
             }
             const uint32_t px = (tile_xy & 0xFFFFu) * 8u + (lane & 7u), py = (tile_xy >> 16) * 8u + (lane >> 3);
-            CamView cv;
-            {
-                const v4f c0 = lds_nodes[cfg_off], c1 = lds_nodes[cfg_off + 1u], c2 = lds_nodes[cfg_off + 2u], c3 = lds_nodes[cfg_off + 3u];
-                cv.cam = f3(c0.x, c0.y, c0.z);
-                cv.first = f3(c1.x, c1.y, c1.z);
-                cv.vu = f3(c2.x, c2.y, c2.z);
-                cv.vv = f3(c3.x, c3.y, c3.z);
-                cv.W = c0.w;
-                cv.H = c1.w;
-                cv.rW = c2.w;
-                cv.rH = c3.w;
-            }
+            const CamView cv = cfg_cam_view(blk);
             if (new_tile) pixel_uv(cv, px, py, uvx_cached, uvy_cached);
             if (px < pp.width && py < pp.height) {
                 gen_primary<LEAN>(pp, cv, px, py, uvx_cached, uvy_cached, pp.sample_begin + sidx, np, g);
@@ -1044,15 +1106,10 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
             uint32_t my_ring = 0, my_off = 0;
             bool take = false;
             uint32_t assigned = 0;
-#if MPT_WL_CARRY
             // after a carry (always a ring-0 step) only the lanes that carry nothing pop: 64 - popcount(carry) records, the top of the
             // stack, indexed by a lane's rank among those lanes (= lane when nothing is carried)
             const uint32_t slot = wave_rank(~carry), room = 64u - (uint32_t)__popcll(carry);
             const bool empty = !kept;
-#else
-            const uint32_t slot = lane, room = 64u;
-            const bool empty = true;
-#endif
 #pragma unroll
             for (int k = (int)MPT_WL_LEVELS - 1; k >= 0; --k) {
                 const bool use = (level == (int)MPT_WL_LEVELS) || (level == k);
@@ -1061,22 +1118,14 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 if (empty && slot >= assigned && slot < assigned + tk) {
                     take = true;
                     my_ring = (uint32_t)k;
-#ifdef MPT_WL_FIFO
-                    my_off = (head[k] + (slot - assigned)) & M;
-#else
                     my_off = cnt[k] - tk + (slot - assigned);  // newest records first: they are still in L2
-#endif
                 }
-                (void)k;
-#ifdef MPT_WL_FIFO
-                head[k] = (head[k] + tk) & M;
-#endif
                 cnt[k] -= tk;
                 assigned += tk;
             }
             if (level < (int)MPT_WL_LEVELS) {   // (a ring step: its budget and its minimum of working lanes, from the LDS copy)
-                budget = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[level]);
-                min_active = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[8 + level]);
+                budget = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_BUDGET + level]);
+                min_active = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_MIN_ACTIVE + level]);
             }
             // merged drain step: no trip budget, but the stragglers of a step (fewer than a third of the lanes it
             // started with) go back to the last ring and are traced together once the rest is gone (4.76 -> 4.54 ms
@@ -1097,19 +1146,17 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 }
                 valid = true;
             }
-#if MPT_WL_CARRY
             if (kept) {   // a carried hit: its ray, t and primitive are in place
                 need_shade = true;
                 fresh = true;
                 valid = true;
             }
-#endif
         }
         // ---- the hits popped from ring 0 are shaded first — all 64 lanes of a ring-0 step — and leave their bounce rays in `ps` ------
         if (need_shade) {
             uint32_t px, py, sidx;
-            path_to_pixel<LEAN>(pp, ps.path, px, py, sidx, lean.tile_mul, (LdsWords)lds_cfg_u32);
-            g.pixel = LEAN && MPT_LEAN_INT24 ? mul_u24(py, pp.width) + px : py * pp.width + px;
+            path_to_pixel<LEAN>(pp, ps.path, px, py, sidx, lean.tile_mul, lds_cfg_u32);
+            g.pixel = LEAN ? mul_u24(py, pp.width) + px : py * pp.width + px;
             g.sample = pp.sample_begin + sidx;
             g.lit_seed = 0;
             if (!LEAN && pp.sp.rng_mode == 0) g.lit_seed = pcg_hash(pcg_hash(pp.pixel_seed[g.pixel]));
@@ -1121,13 +1168,13 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         // LEAN: a fresh query whose box test of the root is known to pass starts at the root's hit link (mpt_lean_entry.h): a primary
         // ray when the launch's camera is inside the shrunk root box (one word for the wave), a bounce ray — shade_bounce has left it
         // in `ps` — when its origin is; both only with |d| <= 2 on every axis.  Per lane: a wave saves the trip when its fresh lanes agree.
-        if (LEAN && MPT_LEAN_ENTRY && fresh) {
+        if (LEAN && fresh) {
             const bool d_ok = fmaxf(fmaxf(fabsf(ps.d.x), fabsf(ps.d.y)), fabsf(ps.d.z)) <= MPT_LEAN_ENTRY_DMAX;
             if (level < 0) {
-                const uint32_t entry_primary = ((const __attribute__((address_space(3))) uint32_t*)(lds_nodes + cfg_off + 11u))[3];
+                const uint32_t entry_primary = ((LdsWords)(blk + CFG_F4_ENTRY_HI))[CFG_W_OF_F4];
                 node = d_ok ? entry_primary : 0u;
             } else {
-                const v4f elo = lds_nodes[cfg_off + 10u], ehi = lds_nodes[cfg_off + 11u];
+                const v4f elo = blk[CFG_F4_ENTRY_LO], ehi = blk[CFG_F4_ENTRY_HI];
                 const bool in = elo.x <= ps.o.x && ps.o.x <= ehi.x && elo.y <= ps.o.y && ps.o.y <= ehi.y && elo.z <= ps.o.z && ps.o.z <= ehi.z;
                 node = in && d_ok ? __float_as_uint(elo.w) : 0u;
             }
@@ -1138,39 +1185,23 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                               ((level < (int)MPT_WL_LEVELS - 1 && budget < MPT_WL_NO_BUDGET) || min_active != 0u);
         const int park_ring = level + 1 < (int)MPT_WL_LEVELS ? level + 1 : (int)MPT_WL_LEVELS - 1;  // where unfinished queries go
         bool alive = false, parked = false;
-        MPT_TOC(reg_fetch, tic_);
-#ifdef MPT_DEBUG_WAVE_TIMES
-        const WorkCount wc0 = wc;
-#endif
+        diag.toc(WaveStepDiag::FETCH);
+        diag.before_walk(wc);
         n_rays += (uint32_t)__popcll(__ballot(valid && fresh));  // a resumed query was counted when it started
         if (valid) {
             bool done;
             if (budgeted)
                 done = closest_hit_resume<COUNT, ALL_LDS, true, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                     budget, wc, min_active, lds_nodes + cfg_off + 12u);
-            else if (LEAN && MPT_LEAN_CAMSPHERE && level < 0)   // a primary step: every origin is the camera (the staged sphere terms)
+                                                                     budget, wc, min_active, blk + CFG_F4_TAIL);
+            else if (LEAN && level < 0)   // a primary step: every origin is the camera (the staged sphere terms)
                 // (with the tile's class word: a `skip` tile's walk is the tail leaf's masked spheres alone, mpt_lean_tiles.h)
                 done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN, true>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                            0xFFFFFFFFu, wc, 0u, lds_nodes + cfg_off + 12u, TILES ? tile_class_cached : 0u);
+                                                                            0xFFFFFFFFu, wc, 0u, blk + CFG_F4_TAIL, TILES ? tile_class_cached : 0u);
             else
                 done = closest_hit_resume<COUNT, ALL_LDS, false, LEAN>(pp.scene, lds_nodes, ps.o, ps.d, node, best_t, best_prim,
-                                                                      0xFFFFFFFFu, wc, 0u, lds_nodes + cfg_off + 12u);
-            MPT_TOC(reg_trace, tic_);
-#ifdef MPT_DEBUG_WAVE_TIMES
-            if (COUNT) {  // per-level divergence diagnostics: [level + 1][steps, box trips, box lane work, prim trips, prim lane work]
-                unsigned long long* lv = (unsigned long long*)(ring.tv() + (size_t)n_waves * MPT_WL_LEVELS * MPT_WL_RING) +
-                                         16ull * n_waves + 8ull * (unsigned)(level + 1);
-                if (first_active_lane()) atomicAdd(lv + 0, 1ull);
-                // the per-wave trip counters live in whichever lane was first active at the time: sum over lanes
-                if (wc.node_iters != wc0.node_iters) atomicAdd(lv + 1, (unsigned long long)(wc.node_iters - wc0.node_iters));
-                if (wc.prim_iters != wc0.prim_iters) atomicAdd(lv + 3, (unsigned long long)(wc.prim_iters - wc0.prim_iters));
-                atomicAdd(lv + 2, (unsigned long long)(wc.node_visits - wc0.node_visits));
-                atomicAdd(lv + 4, (unsigned long long)(wc.prim_tests - wc0.prim_tests));
-                atomicAdd(lv + 5, 1ull);  // rays in the step
-                if (wc.wait_leaf != wc0.wait_leaf) atomicAdd(lv + 7, (unsigned long long)(wc.wait_leaf - wc0.wait_leaf));
-                if (done) atomicAdd(lv + 6, 1ull);
-            }
-#endif
+                                                                      0xFFFFFFFFu, wc, 0u, blk + CFG_F4_TAIL);
+            diag.toc(WaveStepDiag::TRACE);
+            diag.template after_walk<COUNT>(ring, level, wc, done);
             if (done) {
                 alive = best_prim >= 0;   // a hit: to ring 0 as it is, shaded by the step that pops it
                 if (!alive) {             // the sky ends the path (PathTracing.h:225-232)
@@ -1181,18 +1212,15 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 parked = true;
             }
         }
-        MPT_TOC(reg_shade, tic_);
+        diag.toc(WaveStepDiag::SHADE);
         const unsigned long long am = __ballot(alive), pm = __ballot(parked);
         if (pm != 0ull) {  // unfinished queries -> next ring, with their traversal state (only from budgeted steps)
-            uint32_t h = 0, c = 0;
+            uint32_t c = 0;
 #pragma unroll
             for (int k = 1; k < (int)MPT_WL_LEVELS; ++k)
-                if (k == park_ring) {
-                    h = head[k];
-                    c = cnt[k];
-                }
+                if (k == park_ring) c = cnt[k];
             if (parked) {
-                const uint32_t at = wbase + (uint32_t)park_ring * MPT_WL_RING + ((h + c + wave_rank(pm)) & M);
+                const uint32_t at = wbase + (uint32_t)park_ring * MPT_WL_RING + ((c + wave_rank(pm)) & M);
                 ring_push_hit(ring, at, ps, 0.0f, 0u);   // (a parked ray: its traversal state is in tv)
                 ring.tv()[at] = make_uint4(node, __float_as_uint(best_t), (uint32_t)best_prim, 0u);
             }
@@ -1201,39 +1229,16 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 if (k == park_ring) cnt[k] = c + (uint32_t)__popcll(pm);
         }
         // survivors are fresh rays -> ring 0 (after the parked rays, whose ring count the carry rule reads)
-#if MPT_WL_CARRY
         // ... unless the next step is a ring-0 step anyway — no ring >= 1 holds a full wave, ring 0 with these hits does: then they stay
         // where they are and that step pops the rest
         bool keep = cnt[0] + (uint32_t)__popcll(am) >= 64u;
 #pragma unroll
         for (int k = 1; k < (int)MPT_WL_LEVELS; ++k) keep = keep && cnt[k] < 64u;
         kept = keep && alive;
-#else
-        const bool keep = false;
-#endif
-#ifdef MPT_DEBUG_WAVE_TIMES
-        if (COUNT && (am | pm) != 0ull) {
-            // rows 15 and 14 of the per-step-kind block, the ring traffic by record: row 15 = hits (carried, pushed, carried with light,
-            // pushed with light, steps that carried, steps that pushed), row 14 = parked rays (records, with light, steps)
-            unsigned long long* rt = (unsigned long long*)(ring.tv() + (size_t)n_waves * MPT_WL_LEVELS * MPT_WL_RING) + 16ull * n_waves + 8ull * 14ull;
-            const unsigned long long lit_a = __ballot(alive && ring_has_light(ps)), lit_p = __ballot(parked && ring_has_light(ps));
-            if (lane == 0u) {
-                if (am != 0ull) {
-                    atomicAdd(rt + 8 + (keep ? 0 : 1), (unsigned long long)__popcll(am));
-                    atomicAdd(rt + 8 + (keep ? 2 : 3), (unsigned long long)__popcll(lit_a));
-                    atomicAdd(rt + 8 + (keep ? 4 : 5), 1ull);
-                }
-                if (pm != 0ull) {
-                    atomicAdd(rt + 0, (unsigned long long)__popcll(pm));
-                    atomicAdd(rt + 1, (unsigned long long)__popcll(lit_p));
-                    atomicAdd(rt + 2, 1ull);
-                }
-            }
-        }
-#endif
+        diag.template traffic<COUNT>(ring, lane, am, pm, keep, alive, parked, ps);
         if (am != 0ull && !keep) {
             if (alive) {
-                const uint32_t at = wbase + ((head[0] + cnt[0] + wave_rank(am)) & M);
+                const uint32_t at = wbase + ((cnt[0] + wave_rank(am)) & M);
                 ring_push_hit(ring, at, ps, best_t, (uint32_t)best_prim);
             }
             cnt[0] += (uint32_t)__popcll(am);
@@ -1242,28 +1247,9 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
 #pragma unroll
         for (uint32_t k = 0; k < MPT_WL_LEVELS; ++k) worst = cnt[k] > worst ? cnt[k] : worst;
         if (worst > MPT_WL_RING) pp.desc->overflow = 1u;  // cannot happen (see capacity note above)
-        MPT_TOC(reg_push, tic_);
+        diag.toc(WaveStepDiag::PUSH);
     }
-#ifdef MPT_DEBUG_WAVE_TIMES  // diagnostics build: per-wave (start, cursor exhausted, end) timestamps, 100 MHz ticks
-    if (lane == 0) {
-        unsigned long long* dbg = (unsigned long long*)(ring.tv() + (size_t)n_waves * MPT_WL_LEVELS * MPT_WL_RING);
-        dbg[8 * wave_id] = t_start;
-        dbg[8 * wave_id + 1] = t_exh;
-        dbg[8 * wave_id + 2] = __builtin_amdgcn_s_memrealtime();
-        dbg[8 * wave_id + 3] = t_claim;
-        dbg[8 * wave_id + 4] = dbg_steps;
-        dbg[8 * wave_id + 5] = dbg_left;
-        dbg[8 * wave_id + 6] = dbg_blk;
-        unsigned long long* reg = dbg + 8ull * n_waves + 8ull * wave_id;
-        reg[0] = reg_select;
-        reg[1] = reg_fetch;
-        reg[2] = reg_trace;
-        reg[3] = reg_shade;
-        reg[4] = reg_push;
-        reg[5] = wc.t_box;
-        reg[6] = wc.t_leaf;
-    }
-#endif
+    diag.finish(ring, lane, wave_id, wc);
     MPT_CLOCK_END();
     flush_stats<COUNT>(pp.desc, lane == 0u ? n_rays : 0u, lane == 0u ? n_paths : 0u, wc);
     note_wave_exit(pp);

@@ -27,13 +27,10 @@
 // |d_a| <= 2 is tested per ray by the kernel (one v_max3_f32 of magnitudes, one compare): normalize3 returns components of magnitude
 // <= 1.23 when the squared length is representable — but (+-inf, +-inf, +-inf) when three non-zero components are so small that it
 // rounds to zero, and then id = 0, every term is +-0 and the root's test answers MISS.
-// (MPT_LEAN_ENTRY=0: pricing build of the lean kernels without it — profiles/r18_lean_entry.txt)
+// (priced: profiles/r18_lean_entry.txt)
 #pragma once
 #include <stdint.h>
 
-#ifndef MPT_LEAN_ENTRY
-#define MPT_LEAN_ENTRY 1
-#endif
 #define MPT_LEAN_ENTRY_M 0x1p-10f
 #define MPT_LEAN_ENTRY_DMAX 2.0f
 #if defined(__HIPCC__)
@@ -75,7 +72,7 @@ MPT_LEAN_ENTRY_HD inline LeanEntry lean_entry_terms(const V4& n0, const V4& n1, 
     return e;
 }
 
-// ---- the tail leaf (MPT_LEAN_TAIL) ----------------------------------------------------------------------------------------------------
+// ---- the tail leaf --------------------------------------------------------------------------------------------------------------------
 // The last node of every complete walk, T: start at the root's hit link A0 and follow miss links while they name a node.  When the
 // device builder has hoisted the spheres (k_sah_to_radix_hoisted) T is their leaf record, the left child of the root, and the walk pops
 // the right child first: every walk that is not cut ends with T's box test, T's primitives, "done".  The lean kernels whose whole tree
@@ -89,10 +86,7 @@ MPT_LEAN_ENTRY_HD inline LeanEntry lean_entry_terms(const V4& n0, const V4& n1, 
 // way T is found), n_nodes is below the marker (the link that ends a walk in the device's tree is n_nodes itself, mpt_scene_layout.h,
 // so no link of the tree is the marker by accident) and T's planes pass the staging check of lean_entry_terms.  Off: node = 0,
 // nothing is patched and the kernels run as without the item.
-// (MPT_LEAN_TAIL=0: pricing build of the lean kernels without it — profiles/r20_lean_tail.txt)
-#ifndef MPT_LEAN_TAIL
-#define MPT_LEAN_TAIL 1
-#endif
+// (priced: profiles/r20_lean_tail.txt)
 #define MPT_NODE_TAIL 0x40000000u      // a link to T in the staged image
 #define MPT_LEAN_LEAF_BIT 0x80000000u  // MPT_NODE_HOLD (mpt_device.h): the hit link of a leaf record
 

@@ -33,9 +33,8 @@
 // General for every tile of the launch: the r18 entry or the tail item is off, or the camera is not inside both shrunk boxes; T holds
 // a primitive that is no sphere; the chain is longer than MPT_LEAN_TILES_CHAIN_MAX; W or H is not the whole number of pixels that the
 // tile counts cover (tiles_x = ceil(W / 8), tiles_y = ceil(H / 8)); a NaN anywhere.
-// (MPT_LEAN_TILES=0: pricing build of the lean kernels without the item; MPT_LEAN_TILES_MASK=0: only `skip` with an empty mask is used;
-//  MPT_LEAN_TILES_CONTROL: a build whose intervals shrink to the tile-centre ray — wrong on purpose, the tests must fail with it.
-//  profiles/r23_lean_tiles.txt)
+// (Priced, `skip` alone and with the masks: profiles/r23_lean_tiles.txt.  MPT_LEAN_TILES_CONTROL: a build whose intervals shrink to the
+//  tile-centre ray — wrong on purpose, the tests must fail with it.)
 #pragma once
 #include <stdint.h>
 #if defined(MPT_LEAN_TILES_CONTROL) && !defined(MPT_LEAN_TILES_TESTING)
@@ -44,12 +43,6 @@
 
 #include "mpt_lean_entry.h"
 
-#ifndef MPT_LEAN_TILES
-#define MPT_LEAN_TILES 1
-#endif
-#ifndef MPT_LEAN_TILES_MASK
-#define MPT_LEAN_TILES_MASK 1
-#endif
 #define MPT_LEAN_TILES_SKIP 0x80000000u
 #define MPT_LEAN_TILES_MASK_BITS 0xFFFFu   // a leaf record holds at most 16 primitives
 #define MPT_LEAN_TILES_CHAIN_MAX 8u

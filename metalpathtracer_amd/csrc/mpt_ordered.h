@@ -88,6 +88,12 @@ __device__ unsigned long long g_ot_times[OT_NREG + 16];   // + steps[RINGS + 1] 
         ot_acc[r] += now_ - ot_t_;                                  \
         ot_t_ = now_;                                               \
     } while (0)
+#define OT_STEP(kind, valid)                                        \
+    do {   /* slots: R (all octants), E, M0.., primary last */      \
+        const uint32_t ot_slot = (kind) == MPT_OT_NONE ? 2u + MPT_OT_MLEVELS : (kind) < MPT_OT_RING_E ? 0u : (kind) - MPT_OT_RING_E + 1u; \
+        ot_steps[ot_slot] += 1;                                     \
+        ot_lanes[ot_slot] += (unsigned long long)__popcll(__ballot(valid)); \
+    } while (0)
 __device__ __forceinline__ void ot_flush_walk_times(const WorkCount& wc, uint32_t lane) {
     unsigned long long v[15] = {wc.ot_node_cycles, wc.ot_leaf_cycles, wc.ot_node_trips, wc.ot_leaf_trips, wc.ot_rounds, wc.ot_node_lanes, wc.ot_leaf_lanes,
                                 wc.ot_lds_nodes, wc.ot_glb_nodes, wc.ot_lds_prims, wc.ot_glb_prims, wc.ot_pops, wc.ot_pop_iters, wc.ot_pop_calls, wc.ot_pop_wave_iters};
@@ -100,6 +106,7 @@ __device__ __forceinline__ void ot_flush_walk_times(const WorkCount& wc, uint32_
 #else
 #define OT_TIC() do { } while (0)
 #define OT_TOC(r) do { } while (0)
+#define OT_STEP(kind, valid) do { } while (0)
 #endif
 
 struct OtRings {              // [n_waves][MPT_OT_RINGS][MPT_WL_RING] records, struct of arrays of 16-byte fields; ONE allocation (one base
@@ -733,27 +740,20 @@ __global__ __launch_bounds__(OCC == MPT_OT6_WAVES ? MPT_OT6_THREADS : MPT_OT_THR
     const uint32_t cfg_off = mpt_lds_cfg_off_f4(pp.scene.lds_mat_off);
     if (threadIdx.x == 0) {
         announce_resident(pp);
-        lds_raw[cfg_off + 0] = make_float4(pp.cam.x, pp.cam.y, pp.cam.z, pp.W);
-        lds_raw[cfg_off + 1] = make_float4(pp.first.x, pp.first.y, pp.first.z, pp.H);
-        lds_raw[cfg_off + 2] = make_float4(pp.vu.x, pp.vu.y, pp.vu.z, 0.0f);
-        lds_raw[cfg_off + 3] = make_float4(pp.vv.x, pp.vv.y, pp.vv.z, 0.0f);
-        uint32_t* w = (uint32_t*)(lds_raw + cfg_off + 4);
+        cfg_stage_common(lds_raw + cfg_off, pp, 0.0f, 0.0f, wl_block, wl_min, wl_div);   // (the stacks start behind the block: ordered_views)
+        uint32_t* w = (uint32_t*)(lds_raw + cfg_off + CFG_F4_WORDS);
+        static_assert(MPT_OT_MLEVELS <= CFG_MAX_LEVELS && CFG_W_MIN_ACTIVE + MPT_OT_MLEVELS <= CFG_W_INPLACE_MIN, "configuration block: the walk rings' words run into the in-place threshold");
         for (uint32_t k = 0; k < MPT_OT_MLEVELS; ++k) {
-            w[k] = budgets.trips[k];
-            w[8u + k] = budgets.min_active[k];
+            w[CFG_W_BUDGET + k] = budgets.trips[k];
+            w[CFG_W_MIN_ACTIVE + k] = budgets.min_active[k];
         }
-        w[15] = budgets.inplace_min;
-        // ... and what only a CLAIM of path ids needs (words 16..19 of the block's 32; the stacks start behind the block: ordered_views)
-        static_assert(4u * (MPT_LDS_CFG_F4 - 4u) >= 20u, "configuration block too small");
-        w[16] = wl_block;
-        w[17] = wl_min;
-        w[18] = wl_div * (((uint32_t)(gridDim.x * (blockDim.x >> 6)) + MPT_NGROUP - 1u) / MPT_NGROUP);   // wl_div * waves per claim range
-        w[19] = pp.desc->total_paths / (pp.S * 64u);                                                   // this rank's tiles
+        w[CFG_W_INPLACE_MIN] = budgets.inplace_min;
     }
     ot_stage(pp.scene, ac, lds_raw);
     MPT_CLOCK_BEGIN();
     const LdsNodes lds = (LdsNodes)lds_raw;
-    const __attribute__((address_space(3))) uint32_t* lds_cfg_u32 = (const __attribute__((address_space(3))) uint32_t*)(lds + cfg_off + 4u);
+    const LdsNodes blk = lds + cfg_off;                             // the configuration block (mpt_lds_cfg.h)
+    const LdsWords lds_cfg_u32 = (LdsWords)(blk + CFG_F4_WORDS);    // ... and its words
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_id = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const OtStack st = ot_stack(ac, lds_raw, wave_id);
@@ -790,38 +790,13 @@ __global__ __launch_bounds__(OCC == MPT_OT6_WAVES ? MPT_OT6_THREADS : MPT_OT_THR
         }
         if (kind == MPT_OT_NONE && (r_fill >= 64u || (MPT_OT_NR > 1u && in_flight > MPT_OT_MAX_INFLIGHT && r_fill != 0u))) kind = r_best;
         if (kind == MPT_OT_NONE) {
-            if (!exhausted && cur == end) {  // guided self-scheduling of path ids, as k_wavelocal (mpt_kernels.h)
-                uint32_t k = 0, blk = 0, rend = 0;
-                bool got = false;
-                if (lane == 0) {
-                    const uint32_t c_block = lds_cfg_u32[16], c_min = lds_cfg_u32[17], c_div = lds_cfg_u32[18], c_tiles = lds_cfg_u32[19];   // (claim parameters: from LDS)
-                    for (uint32_t t = 0; t < MPT_NGROUP && !got; ++t) {
-                        const uint32_t re = range_paths(c_tiles, pp.S, grp);
-                        const uint32_t left = seen < re ? re - seen : 0u;
-                        blk = (left / c_div) & ~63u;
-                        blk = blk < c_min ? c_min : (blk > c_block ? c_block : blk);
-                        if (t > 0u) blk = c_min;
-                        k = atomicAdd(&pp.ctr[MPT_CTR_CURSOR(grp)], blk);
-                        if (k < re) {
-                            got = true;
-                            rend = re;
-                        } else {
-                            grp = (grp + 1u) & (MPT_NGROUP - 1u);
-                            seen = 0;
-                        }
-                    }
-                }
-                got = __builtin_amdgcn_readfirstlane((int)got) != 0;
-                k = __builtin_amdgcn_readfirstlane(k);
-                blk = __builtin_amdgcn_readfirstlane(blk);
-                rend = __builtin_amdgcn_readfirstlane(rend);
-                grp = __builtin_amdgcn_readfirstlane(grp);
-                seen = k;
-                if (!got) {
+            if (!exhausted && cur == end) {
+                uint32_t k, blk_asked, rend;
+                if (!claim_paths(pp, lds_cfg_u32, lane, grp, seen, k, blk_asked, rend)) {
                     exhausted = true;
                 } else {
                     cur = k;
-                    end = (k + blk < rend) ? k + blk : rend;
+                    end = (k + blk_asked < rend) ? k + blk_asked : rend;
                 }
             }
             if (exhausted) {  // drain: partial steps, tree walks and hits first (they feed ring R)
@@ -850,13 +825,7 @@ __global__ __launch_bounds__(OCC == MPT_OT6_WAVES ? MPT_OT6_THREADS : MPT_OT_THR
             const uint32_t pchunk = range_chunk_to_path_chunk(pp, cur >> 6, grp);  // = tile * S + sample
             cur += 64u;
             uint32_t tl, sidx;
-            if (pp.s_shift != 0xFFu) {
-                tl = pchunk >> pp.s_shift;
-                sidx = pchunk & (pp.S - 1u);
-            } else {
-                tl = pchunk / pp.S;
-                sidx = pchunk - tl * pp.S;
-            }
+            chunk_tile_sample(pp, pchunk, tl, sidx);
             if (tl != tile_cached) {
                 tile_cached = tl;
                 tile_xy_cached = (uint32_t)__builtin_amdgcn_readfirstlane((int)pp.tile_xy[tl]);
@@ -864,14 +833,7 @@ __global__ __launch_bounds__(OCC == MPT_OT6_WAVES ? MPT_OT6_THREADS : MPT_OT_THR
             ps.path = pchunk * 64u + lane;
             const uint32_t px = (tile_xy_cached & 0xFFFFu) * 8u + (lane & 7u), py = (tile_xy_cached >> 16) * 8u + (lane >> 3);
             if (px < pp.width && py < pp.height) {
-                CamView cv;
-                const v4f c0 = lds[cfg_off], c1 = lds[cfg_off + 1u], c2 = lds[cfg_off + 2u], c3 = lds[cfg_off + 3u];
-                cv.cam = f3(c0.x, c0.y, c0.z);
-                cv.first = f3(c1.x, c1.y, c1.z);
-                cv.vu = f3(c2.x, c2.y, c2.z);
-                cv.vv = f3(c3.x, c3.y, c3.z);
-                cv.W = c0.w;
-                cv.H = c1.w;
+                const CamView cv = cfg_cam_view(blk);
                 float uvx, uvy;
                 pixel_uv(cv, px, py, uvx, uvy);
                 gen_primary(pp, cv, px, py, uvx, uvy, pp.sample_begin + sidx, ps, g);
@@ -956,11 +918,7 @@ __global__ __launch_bounds__(OCC == MPT_OT6_WAVES ? MPT_OT6_THREADS : MPT_OT_THR
             W = -1;
         }
         OT_TOC(1);
-#ifdef MPT_OT_TIMES
-        const uint32_t ot_slot = kind == MPT_OT_NONE ? 2u + MPT_OT_MLEVELS : kind < MPT_OT_RING_E ? 0u : kind - MPT_OT_RING_E + 1u;
-        ot_steps[ot_slot] += 1;
-        ot_lanes[ot_slot] += (unsigned long long)__popcll(__ballot(valid));
-#endif
+        OT_STEP(kind, valid);
         uint32_t dest = MPT_OT_NONE;      // ring this lane's ray goes to next
         bool shade = false;               // ... or its closest hit is final: one bounce of shading now
         uint32_t walk_kind = MPT_OT_NONE; // wave-uniform: the step walks the tree with this ring's budget
@@ -985,7 +943,7 @@ __global__ __launch_bounds__(OCC == MPT_OT6_WAVES ? MPT_OT6_THREADS : MPT_OT_THR
             }
             // most of the wave has to walk the tree: do it now, as a step of ring M0 would, and save those rays the trip
             // through the ring (80 bytes written and read back per ray)
-            if ((uint32_t)__popcll(__ballot(dest == MPT_OT_RING_M)) >= (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[15])) {
+            if ((uint32_t)__popcll(__ballot(dest == MPT_OT_RING_M)) >= (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_INPLACE_MIN])) {
                 walk_kind = MPT_OT_RING_M;
                 walking = dest == MPT_OT_RING_M;
                 if (walking) dest = MPT_OT_NONE;
@@ -1000,8 +958,8 @@ __global__ __launch_bounds__(OCC == MPT_OT6_WAVES ? MPT_OT6_THREADS : MPT_OT_THR
             // ---- closest-first walk, continued for this ring's budget of node-loop trips ------------------------------
             bool tie = false, done;
             uint32_t budget = 0u, min_active = 0u;
-            budget = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[walk_kind - MPT_OT_RING_M]);
-            min_active = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[8u + walk_kind - MPT_OT_RING_M]);
+            budget = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_BUDGET + walk_kind - MPT_OT_RING_M]);
+            min_active = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_MIN_ACTIVE + walk_kind - MPT_OT_RING_M]);
             // (the drain walks to the end: parking a handful of rays again and again does not pay)
             if (!exhausted && (walk_kind + 1u < MPT_OT_RINGS || min_active != 0u))
                 done = ot_walk<COUNT, true, ALL_LDS>(ac, pp.scene, lds, st, ps.o, ps.d, r, walk_cur, walk_sp, T, W, tie, walk_lost,

@@ -1,4 +1,4 @@
-"""Carried hits of the wave-local kernel (MPT_WL_CARRY, mpt_kernels.h): when the step after a step is going to pop ring 0, the hits
+"""Carried hits of the wave-local kernel (wavelocal_body, mpt_kernels.h): when the step after a step is going to pop ring 0, the hits
 just found stay in their lanes instead of being pushed and popped.  The schedule, the counts and every result bit must be what they
 are without the carry, so the wave-local pipeline (2) is compared with the megakernel (1), which has no rings at all: every float of
 the HDR sum and the `rays` / `paths` counts must be equal.

@@ -1,4 +1,4 @@
-"""Fresh rays of the lean wave-local kernels enter the walk below the root (MPT_LEAN_ENTRY, metalpathtracer_amd/csrc/mpt_lean_entry.h) against
+"""Fresh rays of the lean wave-local kernels enter the walk below the root (the entry node, metalpathtracer_amd/csrc/mpt_lean_entry.h) against
 the generic kernels and the megakernel.
 
 Every case of tests/lean_entry/entry_cases.py is rendered three ways — this build, this build with MPT_WL_LEAN=0 in a fresh child process (the

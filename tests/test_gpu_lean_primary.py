@@ -1,5 +1,5 @@
-"""The camera-relative sphere terms of the lean wave-local kernels (MPT_LEAN_CAMSPHERE, mpt_device.h / mpt_kernels.h) and the carried
-ballot of their box loop (MPT_LEAN_ONECMP), against the generic kernels and the megakernel.
+"""The camera-relative sphere terms of the lean wave-local kernels (sphere_cam_terms, mpt_device.h / mpt_kernels.h) and the carried
+ballot of their box loop (closest_hit_resume<.., LEAN>), against the generic kernels and the megakernel.
 
 A lean kernel stages, once per workgroup, oc = camera - centre and cc = dot3(oc, oc) - r * r into the unused words of every LDS-resident
 sphere record; the walk of a primary step reads them instead of computing them per ray.  Every case of tests/lean_primary/cases.py is

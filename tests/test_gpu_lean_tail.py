@@ -1,4 +1,4 @@
-"""The lean wave-local kernels test the walk's last leaf once, behind the loop (MPT_LEAN_TAIL, metalpathtracer_amd/csrc/mpt_lean_entry.h),
+"""The lean wave-local kernels test the walk's last leaf once, behind the loop (the tail leaf, metalpathtracer_amd/csrc/mpt_lean_entry.h),
 against the generic kernels and the megakernel.
 
 Every case of tests/lean_tail/tail_cases.py is rendered three ways — this build, this build with MPT_WL_LEAN=0 in a fresh child process

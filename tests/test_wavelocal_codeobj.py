@@ -1,6 +1,6 @@
 """CPU-side checks of the BUILT wave-local trace kernels (libmpt_hip.so is cross-compiled for gfx950; no GPU needed).
 
-The kernel sits on a register cliff: 6 waves/SIMD allow 80 VGPRs, and the hits a step keeps in its lanes (MPT_WL_CARRY, mpt_kernels.h)
+The kernel sits on a register cliff: 6 waves/SIMD allow 80 VGPRs, and the hits a step keeps in its lanes (the carry, mpt_kernels.h)
 take the last three.  test_build_asm.py watches the two k_wavelocal<false, ..> instantiations; this file adds the ones pipelined
 renders run (bench.py's timed steps), k_wavelocal_corun<false> and <true>, and reads the kernels' metadata as well as their
 instructions.  It also makes

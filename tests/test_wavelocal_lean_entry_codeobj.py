@@ -1,4 +1,4 @@
-"""CPU-side checks of the BUILT lean wave-local kernels after fresh queries enter the walk below the root (MPT_LEAN_ENTRY,
+"""CPU-side checks of the BUILT lean wave-local kernels after fresh queries enter the walk below the root (the entry node,
 mpt_lean_entry.h), read from libmpt_hip.so the way test_wavelocal_codeobj.py reads the generic ones.
 
 The entry choice adds two LDS reads and a handful of compares per ring-0 step and two more values to the step loop; the operating point

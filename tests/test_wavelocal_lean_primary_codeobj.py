@@ -1,5 +1,5 @@
 """CPU-side checks of the BUILT lean wave-local kernels after the primary walk became an instantiation of its own (camera-relative
-sphere terms, MPT_LEAN_CAMSPHERE: closest_hit_resume<.., LEAN, PRIMARY>, mpt_device.h), read from libmpt_hip.so the way
+sphere terms, sphere_cam_terms: closest_hit_resume<.., LEAN, PRIMARY>, mpt_device.h), read from libmpt_hip.so the way
 test_wavelocal_codeobj.py reads the generic ones.
 
 A third walk in the step loop is more code and more live scalar values; the operating point must hold all the same: <= 80 VGPRs (6

@@ -1,4 +1,4 @@
-"""CPU-side checks of the BUILT lean wave-local kernels after the tail leaf moved behind the walk's loop (MPT_LEAN_TAIL, mpt_lean_entry.h),
+"""CPU-side checks of the BUILT lean wave-local kernels after the tail leaf moved behind the walk's loop (the tail leaf, mpt_lean_entry.h),
 read from libmpt_hip.so the way test_wavelocal_codeobj.py reads the generic ones.  Registers and scratch only.
 
 The epilogue adds a second copy of the leaf test to each of the three walks of the ALL_LDS kernels, and the guard's planes come from

@@ -77,7 +77,7 @@ if flags:
             nm, st_, rays / st_, 100 * dn / max(1, rays), bt / st_, 100 * bw / max(1, 64 * bt), pt / st_, 100 * pw / max(1, 64 * pt),
             100 * (bt * 26 + pt * 70) / tot, 100 * wl / max(1, 64 * bt)))
     # rows 15 and 14 of the block, the ring traffic by record: hits that stayed in their lanes for the ring-0 step that followed
-    # (MPT_WL_CARRY) against hits pushed to ring 0, and the rays parked in ring 1; a record is 48 bytes, 16 more if the path has
+    # (the carry) against hits pushed to ring 0, and the rays parked in ring 1; a record is 48 bytes, 16 more if the path has
     # gathered light, 16 more (the walk state) for a parked ray
     carried, pushed, carried_lit, pushed_lit, carry_steps, push_steps = lv[15, :6]
     parked, parked_lit, park_steps = lv[14, :3]
