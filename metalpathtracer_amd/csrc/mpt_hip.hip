@@ -360,6 +360,7 @@ struct mpt_ctx : SceneState {
     uint32_t wl_min = 0, wl_div = 32;
     bool wl_lean = true;               // MPT_WL_LEAN=0: every wave-local pass runs the generic kernels (development knob)
     bool lean_tiles = true;            // MPT_LEAN_TILES=0: the lean kernels get no class table, every tile is "general" (mpt_lean_tiles.h; development knob)
+    bool lean_sky_resolve = true;      // MPT_LEAN_SKY_RESOLVE=0: the lean kernels trace the sky tiles and the resolve reads their slots (development knob)
     LeanCdivCache lean_cdiv;           // is the lean kernels' division by W and H exact at this context's size (mpt_lean_cdiv.h)
     DevMem<uint32_t> d_cdiv_bad;       // the mismatch count of k_lean_cdiv_check
     uint32_t wl_block = MPT_WL_BLOCK;  // path ids a wave claims per atomic (multiple of 64)
@@ -538,6 +539,7 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
     if ((e = getenv("MPT_WL_DIV")) && atoi(e) >= 1) ctx->wl_div = (uint32_t)atoi(e);
     if ((e = getenv("MPT_WL_LEAN"))) ctx->wl_lean = atoi(e) != 0;
     if ((e = getenv("MPT_LEAN_TILES"))) ctx->lean_tiles = atoi(e) != 0;
+    if ((e = getenv("MPT_LEAN_SKY_RESOLVE"))) ctx->lean_sky_resolve = atoi(e) != 0;
     if ((e = getenv("MPT_OT_STACK")) && atoi(e) >= 2 && atoi(e) <= (int)MPT_OT_PARK) ctx->ot_stack_depth = (uint32_t)atoi(e);
     unsigned ot[MPT_OT_MLEVELS];   // "a,b,c": one number per tree-walk ring; the rings a list leaves out keep their defaults
     if ((e = getenv("MPT_OT_BUDGETS")))
@@ -1066,6 +1068,7 @@ struct PassLaunch {
     WlLean lean_args = {0u, 0u, 0u};  // lean kernels only
     bool lean_all_lds = false;        // a lean kernel with the whole tree in LDS: the ones that read the class table
     const uint32_t* tile_classes = nullptr;   // ... and the table (ensure_tile_classes; null: every tile is general)
+    uint32_t sky_resolve = 0u;        // ... and whether its sky tiles are left to the pass's resolve (run_pass)
 };
 
 // The result slots one iteration of the wavefront pipeline retires, in items of 64 (the other pipelines size k_begin_pass's cursors by it)
@@ -1306,7 +1309,7 @@ static int launch_persistent(mpt_ctx* ctx, Lane& L, PassLaunch& g, PassParams& p
             wl_min = 64u * (uint32_t)std::min<uint64_t>(4, std::max<uint64_t>(1, share >> 14));
         }
         void* ordered_args[] = {(void*)&pp, (void*)&g.accel, (void*)&L.ot_ring, (void*)&ctx->ot_budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div};
-        void* wavelocal_args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div, (void*)&g.lean_args, (void*)&g.tile_classes};   // (the last two: lean kernels only)
+        void* wavelocal_args[] = {(void*)&pp, (void*)&L.ring, (void*)&ctx->budgets, (void*)&wl_block, (void*)&wl_min, (void*)&wl_div, (void*)&g.lean_args, (void*)&g.tile_classes, (void*)&g.sky_resolve};   // (the last three: lean kernels only)
         if ((rc = launch_timed(ctx, L, g, g.pipeline == MPT_PIPE_ORDERED ? ordered_args : wavelocal_args, time_kernels, L.pending_timed))) return rc;
     }
     if (ctx->lane_order & 5) {   // (always, unless MPT_LANE_ORDER=0)
@@ -1365,8 +1368,11 @@ static int launch_wavefront(mpt_ctx* ctx, Lane& L, const PassLaunch& g, PassPara
 }
 
 // Runs one pass of S samples/pixel over this rank's tiles (or the override's); leaves the per-path results in d_slots.
+// `sky_classes` (null: the caller's resolve reads every slot, as k_resolve_frame does): the caller ends the pass in k_resolve_sum or
+// k_resolve_sum_moments and hands them what this leaves there — the pass's class table when its trace kernel elided the sky tiles, which
+// then have NO slot values (a lean kernel with a table, unless MPT_LEAN_SKY_RESOLVE=0), else null.
 static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t sample_begin, uint32_t S, PassParams& pp,
-                    uint32_t& n_local_tiles, bool time_kernels, const TileOverride* ovr = nullptr) {
+                    uint32_t& n_local_tiles, bool time_kernels, const TileOverride* ovr = nullptr, const uint32_t** sky_classes = nullptr) {
     const int tile_mode = tile_order_of(ctx, p);
     int rc = ensure_tile_order(ctx, (uint32_t)p->shard_rank, (uint32_t)p->shard_count, tile_mode, n_local_tiles);
     if (rc) return rc;
@@ -1386,6 +1392,9 @@ static int run_pass(mpt_ctx* ctx, Lane& L, const mpt_render_params* p, uint32_t 
     if ((rc = select_trace_kernel(ctx, L, p, n_local_tiles, pp, g))) return rc;
     if ((rc = launch_geometry(ctx, pp, g))) return rc;
     if ((rc = ensure_tile_classes(ctx, L, pp, g))) return rc;
+    g.sky_resolve = sky_classes && g.tile_classes && ctx->lean_sky_resolve ? 1u : 0u;
+    if (sky_classes) *sky_classes = g.sky_resolve ? g.tile_classes : nullptr;
+    if (getenv("MPT_DEBUG_LAUNCH") && g.sky_resolve) fprintf(stderr, "[mpt] sky tiles: summed by the resolve\n");
 
     *L.h_done.get() = 0;
     if ((rc = order_behind_previous_trace(ctx, L, g.corun))) return rc;
@@ -1518,7 +1527,8 @@ static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p, const Til
         uint32_t S = std::min(s_max, p->sample_count - done);
         PassParams pp;
         uint32_t nlt = 0;
-        rc = run_pass(ctx, L, p, p->sample_begin + done, S, pp, nlt, ctx->time_kernels, ovr);
+        const uint32_t* sky_classes = nullptr;
+        rc = run_pass(ctx, L, p, p->sample_begin + done, S, pp, nlt, ctx->time_kernels, ovr, &sky_classes);
         if (rc) return rc;
         if (nlt) {
             // sum[p] += pass total must happen in submission order on both lanes (float addition does not commute
@@ -1529,9 +1539,9 @@ static int render_async_impl(mpt_ctx* ctx, const mpt_render_params* p, const Til
             const uint32_t narrow = (uint32_t)ctx->prop.multiProcessorCount * (uint32_t)ctx->resolve_wgs_per_cu;
             const uint32_t rgrid = !ctx->sync_render && ctx->resolve_wgs_per_cu > 0 ? std::min(wide, narrow) : wide;
             if (p->flags & MPT_FLAG_MOMENTS)
-                hipLaunchKernelGGL(k_resolve_sum_moments, dim3(rgrid), dim3(256), 0, L.stream.get(), pp, ctx->d_sum, ctx->d_m2.get(), nlt);
+                hipLaunchKernelGGL(k_resolve_sum_moments, dim3(rgrid), dim3(256), 0, L.stream.get(), pp, ctx->d_sum, ctx->d_m2.get(), nlt, sky_classes);
             else
-                hipLaunchKernelGGL(k_resolve_sum, dim3(rgrid), dim3(256), 0, L.stream.get(), pp, ctx->d_sum, nlt);
+                hipLaunchKernelGGL(k_resolve_sum, dim3(rgrid), dim3(256), 0, L.stream.get(), pp, ctx->d_sum, nlt, sky_classes);
             HIPCHK(hipGetLastError());
             HIPCHK(hipEventRecord(L.ev_resolved.get(), L.stream.get()));
             ctx->last_resolved = L.ev_resolved.get();

@@ -571,6 +571,8 @@ static_assert(CFG_F4_END <= MPT_LDS_CFG_F4, "configuration block too small");
 __host__ __device__ __forceinline__ uint32_t mpt_lds_cfg_off_f4(uint32_t lds_mat_off) { return lds_mat_off + 2u * MPT_LDS_MATS_N; }
 __host__ __device__ __forceinline__ uint32_t mpt_lds_image_end_f4(uint32_t lds_mat_off) { return mpt_lds_cfg_off_f4(lds_mat_off) + MPT_LDS_CFG_F4; }
 #define MPT_WL_BLOCK 1024u     // upper bound of a path-id claim
+#define MPT_WL_TILE_ELIDED 0x40000000u   // in a wave's cached copy of a tile's class word (never in the table): a sky tile whose samples the resolve sums
+static_assert((MPT_WL_TILE_ELIDED & (MPT_LEAN_TILES_SKIP | MPT_LEAN_TILES_MASK_BITS)) == 0u, "the elision mark shares a bit with the class word");
 #define MPT_WL_NO_BUDGET 0x7FFFFFFFu  // budgets at or above this mean "run to completion"
 
 // ---- the step pieces k_wavelocal* and k_ordered share (scalars, pointers and const& only: by-value copies of the argument structs
@@ -760,7 +762,8 @@ struct WaveBudgets {
 #define MPT_WL_WAVES(ALL_LDS) MPT_WL_WAVES_N
 template <bool COUNT, bool ALL_LDS, bool LEAN = false>
 __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveRings& ring, const WaveBudgets& budgets, uint32_t wl_block, uint32_t wl_min,
-                                               uint32_t wl_div, const WlLean& lean = WlLean{0u, 0u, 0u}, const uint32_t* tile_classes = nullptr);
+                                               uint32_t wl_div, const WlLean& lean = WlLean{0u, 0u, 0u}, const uint32_t* tile_classes = nullptr,
+                                               uint32_t sky_resolve = 0u);
 template <bool COUNT, bool ALL_LDS>
 __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) void k_wavelocal(PassParams pp, WaveRings ring, WaveBudgets budgets,
                                                                                              uint32_t wl_block, uint32_t wl_min, uint32_t wl_div) {
@@ -790,14 +793,14 @@ void k_wavelocal_corun(PassParams pp, WaveRings ring, WaveBudgets budgets, uint3
 template <bool ALL_LDS>
 __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) void k_wavelocal_lean(PassParams pp, WaveRings ring, WaveBudgets budgets,
                                                                                                   uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean,
-                                                                                                  const uint32_t* tile_classes) {
-    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean, tile_classes);
+                                                                                                  const uint32_t* tile_classes, uint32_t sky_resolve) {
+    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean, tile_classes, sky_resolve);
 }
 template <bool ALL_LDS>
 __global__ __launch_bounds__(MPT_WL_THREADS(ALL_LDS), MPT_WL_WAVES(ALL_LDS)) __attribute__((amdgpu_num_sgpr(MPT_WL_CORUN_SGPRS)))
 void k_wavelocal_lean_corun(PassParams pp, WaveRings ring, WaveBudgets budgets, uint32_t wl_block, uint32_t wl_min, uint32_t wl_div, WlLean lean,
-                            const uint32_t* tile_classes) {
-    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean, tile_classes);
+                            const uint32_t* tile_classes, uint32_t sky_resolve) {
+    wavelocal_body<false, ALL_LDS, true>(pp, ring, budgets, wl_block, wl_min, wl_div, lean, tile_classes, sky_resolve);
 }
 // The class table of the lean ALL_LDS kernels (mpt_lean_tiles.h): one thread per word, word T = the class of tile T = ty * tiles_x + tx — the
 // index path_to_pixel<true> computes — and 0 behind the last tile (a rank's last tile index may lie up to nranks - 1 past it; no pixel is there).
@@ -933,7 +936,7 @@ __device__ __forceinline__ void cfg_stage_lean(float4* blk, const PassParams& pp
 }
 template <bool COUNT, bool ALL_LDS, bool LEAN>
 __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveRings& ring, const WaveBudgets& budgets, uint32_t wl_block, uint32_t wl_min,
-                                               uint32_t wl_div, const WlLean& lean, const uint32_t* tile_classes) {
+                                               uint32_t wl_div, const WlLean& lean, const uint32_t* tile_classes, uint32_t sky_resolve) {
     static_assert(!(LEAN && COUNT), "the lean body does not count");
     // the per-tile class words (mpt_lean_tiles.h) are read by the primary steps of the lean kernels whose whole tree is in LDS
     constexpr bool TILES = LEAN && ALL_LDS;
@@ -959,6 +962,8 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
         if (TILES) {   // the class table's address (null: every tile is general) — read back when a wave changes its tile, so that the step loop keeps no scalar register for it
             w[CFG_W_CLASSES_LO] = (uint32_t)(uintptr_t)tile_classes;
             w[CFG_W_CLASSES_HI] = (uint32_t)((uint64_t)(uintptr_t)tile_classes >> 32);
+            static_assert(MPT_WL_LEVELS < CFG_MAX_LEVELS, "configuration block: CFG_W_SKY_RESOLVE lies in the last ring's minimum");
+            w[CFG_W_SKY_RESOLVE] = tile_classes != nullptr ? sky_resolve : 0u;   // (read with the class word, at a tile change)
         }
         if (LEAN) cfg_stage_lean<ALL_LDS>(blk_raw, pp);
     }
@@ -1073,6 +1078,10 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                     if ((tlo | thi) != 0u) {
                         typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
                         tile_class_cached = ((ConstWords)(((uint64_t)thi << 32) | tlo))[tl * pp.nranks + pp.rank];
+                        // a sky tile of a pass whose resolve sums the sky itself: marked in the cached word (the pass's flag is read here,
+                        // with the word, and nowhere else)
+                        if (tile_class_cached == MPT_LEAN_TILES_SKIP && (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_SKY_RESOLVE]) != 0u)
+                            tile_class_cached = MPT_LEAN_TILES_SKIP | MPT_WL_TILE_ELIDED;
                     }
                 }
                 if (TILES) {   // (the tile's place: by every step, below)
@@ -1092,6 +1101,18 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 tile_xy = (T - ty * pp.tiles_x) | (ty << 16);
             }
             const uint32_t px = (tile_xy & 0xFFFFu) * 8u + (lane & 7u), py = (tile_xy >> 16) * 8u + (lane >> 3);
+            if (TILES && (tile_class_cached & MPT_WL_TILE_ELIDED) != 0u) {
+                // Every path of this tile ends in its primary step with the sky colour, a function of (pixel, sample, camera, seed), and the
+                // pass's resolve computes and adds those values itself (resolve_sky_sample): no ray, no slot.  The wave counts the steps as
+                // taken — this one and the tile's later samples inside its claim — and chooses its next step.  (No hit is carried into a
+                // primary step, so nothing of the step before is live.)
+                const uint32_t left = (end - cur) >> 6, more = pp.S - 1u - sidx < left ? pp.S - 1u - sidx : left;
+                const uint32_t elided = (uint32_t)__popcll(__ballot(px < pp.width && py < pp.height)) * (1u + more);
+                cur += more * 64u;
+                n_paths += elided;
+                n_rays += elided;
+                continue;
+            }
             const CamView cv = cfg_cam_view(blk);
             if (new_tile) pixel_uv(cv, px, py, uvx_cached, uvy_cached);
             if (px < pp.width && py < pp.height) {
@@ -1260,27 +1281,75 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
 // CU — 2 waves per SIMD next to the trace kernel's 6 and inside the VGPRs it leaves (launch bound 256 x 8: <= 64), so that both fit on every
 // CU whichever is dispatched first; a resolve with the chip to itself gets a workgroup per 256 pixels.  Four loads in flight per thread;
 // the additions stay in sample order.
-__global__ __launch_bounds__(256, 8) void k_resolve_sum(PassParams pp, float4* sum, uint32_t n_local_tiles) {
+//
+// Sky tiles (`sky_classes`: the pass's class table, mpt_lean_tiles.h, when its trace kernel elided them; else null).  A tile whose class
+// word is "skip, empty mask" holds no primary ray that hits anything: every path of it ends in its primary step with the sky colour, and
+// what that step would have stored depends on (pixel, sample, camera, seed) alone.  The trace kernel wrote no slot for such a tile and the
+// thread that owns the pixel computes the S values here, in sample order, with the device functions the step uses: the slot's 16 bytes
+// are neither written nor read back, and the step's plumbing is not run.  A tile is a wave here too, so the choice is wave-uniform.
+// The scalar registers of a resolve.  Beside k_wavelocal*_corun a SIMD has 128 of them left (the comment at MPT_WL_CORUN_SGPRS) and the
+// resolve's footprint is two waves per SIMD: 64 each, allocated in blocks of 16 after 6 more for the wave's own (vcc, flat_scratch, xnack)
+// — at most 58.  The slot loop alone took 36-38; with the camera and the Philox key of the sky loop the compiler takes 76-78 when it is
+// free to, and then only one of the two waves fits.
+#ifndef MPT_RESOLVE_SGPRS
+#define MPT_RESOLVE_SGPRS 56
+#endif
+__device__ __forceinline__ CamView resolve_cam_view(const PassParams& pp) {   // the bits cfg_stage_common / cfg_cam_view hand a lean primary step
+    return CamView{pp.cam, pp.first, pp.vu, pp.vv, pp.W, pp.H, cdiv_recip(pp.W), cdiv_recip(pp.H)};
+}
+__device__ __forceinline__ bool resolve_sky_tile(const PassParams& pp, const uint32_t* sky_classes, uint32_t tl) {
+    if (sky_classes == nullptr) return false;
+    const uint32_t T = (uint32_t)__builtin_amdgcn_readfirstlane((int)tl) * pp.nranks + pp.rank;   // as the primary step indexes the table
+    return sky_classes[T] == MPT_LEAN_TILES_SKIP;
+}
+#if defined(MPT_SKY_RESOLVE_CONTROL) && !defined(MPT_SKY_RESOLVE_TESTING)
+#error "MPT_SKY_RESOLVE_CONTROL makes the resolve's sky samples wrong on purpose: test builds only (-DMPT_SKY_RESOLVE_TESTING)"
+#endif
+__device__ __forceinline__ float4 resolve_sky_sample(const PassParams& pp, const CamView& cv, uint32_t px, uint32_t py, float uvx, float uvy, uint32_t s) {
+    PathState ps;
+    PathRngDev g;
+#if defined(MPT_SKY_RESOLVE_CONTROL)   // (the control of tests/test_gpu_sky_resolve.py: the next sample's value)
+    s += 1u;
+#endif
+    gen_primary<true>(pp, cv, px, py, uvx, uvy, pp.sample_begin + s, ps, g);
+    shade_bounce<true>(pp.scene, (LdsNodes)nullptr, pp.sp, g, ps, INFINITY, -1);   // (prim = -1: the sky, nothing of the scene is read)
+    return make_float4(clamp01(ps.L.x), clamp01(ps.L.y), clamp01(ps.L.z), clamp01(ps.La));
+}
+__device__ __forceinline__ void add_sample(float4& acc, const float4& v) {
+    acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+}
+__global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(MPT_RESOLVE_SGPRS))) void k_resolve_sum(PassParams pp, float4* sum, uint32_t n_local_tiles, const uint32_t* sky_classes) {
     const uint32_t n = n_local_tiles * 64u;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t tl = i >> 6, lane = i & 63u;
+        const bool sky = resolve_sky_tile(pp, sky_classes, tl);
         uint32_t px, py, s0;
         if (!path_to_pixel(pp, (tl * pp.S) * 64u + lane, px, py, s0)) continue;
         float4 acc = sum[py * pp.width + px];
         const uint32_t base = tl * pp.S;
         uint32_t s = 0;
+        if (sky) {   // two samples in flight; the additions stay in sample order
+            const CamView cv = resolve_cam_view(pp);
+            float uvx, uvy;
+            pixel_uv(cv, px, py, uvx, uvy);
+            for (; s + 2u <= pp.S; s += 2u) {
+                const float4 v0 = resolve_sky_sample(pp, cv, px, py, uvx, uvy, s), v1 = resolve_sky_sample(pp, cv, px, py, uvx, uvy, s + 1u);
+                add_sample(acc, v0);
+                add_sample(acc, v1);
+            }
+            if (s < pp.S) add_sample(acc, resolve_sky_sample(pp, cv, px, py, uvx, uvy, s));
+            sum[py * pp.width + px] = acc;
+            continue;
+        }
         for (; s + 4u <= pp.S; s += 4u) {
             const float4 v0 = load_slot(pp.slots, (base + s) * 64u + lane), v1 = load_slot(pp.slots, (base + s + 1u) * 64u + lane),
                          v2 = load_slot(pp.slots, (base + s + 2u) * 64u + lane), v3 = load_slot(pp.slots, (base + s + 3u) * 64u + lane);
-            acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-            acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
-            acc.x += v2.x; acc.y += v2.y; acc.z += v2.z; acc.w += v2.w;
-            acc.x += v3.x; acc.y += v3.y; acc.z += v3.z; acc.w += v3.w;
+            add_sample(acc, v0);
+            add_sample(acc, v1);
+            add_sample(acc, v2);
+            add_sample(acc, v3);
         }
-        for (; s < pp.S; ++s) {
-            const float4 v = load_slot(pp.slots, (base + s) * 64u + lane);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
+        for (; s < pp.S; ++s) add_sample(acc, load_slot(pp.slots, (base + s) * 64u + lane));
         sum[py * pp.width + px] = acc;
     }
 }
@@ -1291,23 +1360,44 @@ __device__ __forceinline__ void add_moments(float4& m, const float4& v) {
     const float l = (0.2126f * v.x + 0.7152f * v.y) + 0.0722f * v.z;
     m.x += v.x * v.x; m.y += v.y * v.y; m.z += v.z * v.z; m.w += l * l;
 }
-__global__ __launch_bounds__(256, 8) void k_resolve_sum_moments(PassParams pp, float4* sum, float4* m2, uint32_t n_local_tiles) {
+__global__ __launch_bounds__(256, 8) __attribute__((amdgpu_num_sgpr(MPT_RESOLVE_SGPRS))) void k_resolve_sum_moments(PassParams pp, float4* sum, float4* m2, uint32_t n_local_tiles, const uint32_t* sky_classes) {
     const uint32_t n = n_local_tiles * 64u;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t tl = i >> 6, lane = i & 63u;
+        const bool sky = resolve_sky_tile(pp, sky_classes, tl);
         uint32_t px, py, s0;
         if (!path_to_pixel(pp, (tl * pp.S) * 64u + lane, px, py, s0)) continue;
         float4 acc = sum[py * pp.width + px];
         float4 m = m2[py * pp.width + px];
         const uint32_t base = tl * pp.S;
         uint32_t s = 0;
+        if (sky) {   // (as k_resolve_sum)
+            const CamView cv = resolve_cam_view(pp);
+            float uvx, uvy;
+            pixel_uv(cv, px, py, uvx, uvy);
+            for (; s + 2u <= pp.S; s += 2u) {
+                const float4 v0 = resolve_sky_sample(pp, cv, px, py, uvx, uvy, s), v1 = resolve_sky_sample(pp, cv, px, py, uvx, uvy, s + 1u);
+                add_sample(acc, v0);
+                add_sample(acc, v1);
+                add_moments(m, v0);
+                add_moments(m, v1);
+            }
+            if (s < pp.S) {
+                const float4 v = resolve_sky_sample(pp, cv, px, py, uvx, uvy, s);
+                add_sample(acc, v);
+                add_moments(m, v);
+            }
+            sum[py * pp.width + px] = acc;
+            m2[py * pp.width + px] = m;
+            continue;
+        }
         for (; s + 4u <= pp.S; s += 4u) {
             const float4 v0 = load_slot(pp.slots, (base + s) * 64u + lane), v1 = load_slot(pp.slots, (base + s + 1u) * 64u + lane),
                          v2 = load_slot(pp.slots, (base + s + 2u) * 64u + lane), v3 = load_slot(pp.slots, (base + s + 3u) * 64u + lane);
-            acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
-            acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
-            acc.x += v2.x; acc.y += v2.y; acc.z += v2.z; acc.w += v2.w;
-            acc.x += v3.x; acc.y += v3.y; acc.z += v3.z; acc.w += v3.w;
+            add_sample(acc, v0);
+            add_sample(acc, v1);
+            add_sample(acc, v2);
+            add_sample(acc, v3);
             add_moments(m, v0);
             add_moments(m, v1);
             add_moments(m, v2);
@@ -1315,7 +1405,7 @@ __global__ __launch_bounds__(256, 8) void k_resolve_sum_moments(PassParams pp, f
         }
         for (; s < pp.S; ++s) {
             const float4 v = load_slot(pp.slots, (base + s) * 64u + lane);
-            acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+            add_sample(acc, v);
             add_moments(m, v);
         }
         sum[py * pp.width + px] = acc;

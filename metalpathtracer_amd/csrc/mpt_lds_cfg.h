@@ -30,6 +30,8 @@ enum : uint32_t {
     CFG_W_BUDGET = 0u,              // + level: trips of the walk's loop a step of that ring may make
     CFG_W_MIN_ACTIVE = 8u,          // + level: ... and it ends once fewer lanes than this are still walking
     CFG_W_INPLACE_MIN = 15u,        // k_ordered: lanes that must need the tree for a step to walk it in place
+    CFG_W_SKY_RESOLVE = 15u,        // lean ALL_LDS kernels of k_wavelocal (the same word: they have no such threshold and fewer than 8 rings): != 0 when
+                                    // the pass's resolve sums the sky tiles' samples itself, so that a primary step elides them (mpt_kernels.h)
     CFG_W_CLAIM_BLOCK = 16u,        // a claim of path ids: its upper bound,
     CFG_W_CLAIM_MIN = 17u,          // ... its lower bound,
     CFG_W_CLAIM_DIV = 18u,          // ... the claim divisor x the waves per claim range,
