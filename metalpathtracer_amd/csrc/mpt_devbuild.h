@@ -17,8 +17,10 @@
 #include <string.h>
 
 #include <thread>
+#include <type_traits>
 
 #include "mpt_accel.h"
+#include "mpt_build_scratch.h"
 #include "mpt_device.h"
 #include "mpt_lbvh.h"
 #include "mpt_own.h"
@@ -26,6 +28,7 @@
 
 namespace mpt_devbuild {
 using mpt_lbvh::Radix;
+using mpt_lbvh::Scan;
 using mpt_lbvh::Scratch;
 using mpt_sah::SahState;
 using mpt_sah::empty4;
@@ -599,9 +602,9 @@ __global__ void k_always(Scalars* sc, float4* dprims, const float4* refleaf, flo
     }
 }
 
-// Everything above, in order, on one stream.  Inputs: the caller's primitive and material arrays, ALREADY on the device
-// (d_prims_in: 3 float4 per primitive, d_mats_in: 2 float4 per primitive).  All outputs are allocated here and handed to
-// the caller (who takes `block`); scratch is freed on return.
+// ==== the host side: a scene build as a list of steps (build_pass, at the end) =================================================================
+// Inputs: the caller's primitive and material arrays, ALREADY on the device (d_prims_in: 3 float4 per primitive, d_mats_in: 2 float4 per
+// primitive).  All outputs are views into one block, handed to the caller (who takes `block`); scratch goes back to the pool on return.
 struct Built {
     // views into `block` (ONE allocation, sized from upper bounds before the first kernel: n_out <= 2n - 1 nodes, <= n leaves, <= n + 2 wide
     // nodes, <= n materials — ~390 bytes per primitive; until round 4 nine hipMallocs of the exact sizes sat on the build's critical path)
@@ -612,92 +615,85 @@ struct Built {
     uint32_t n_nodes = 0, n_prims = 0, n_mats = 0, n_acc_nodes = 0, n_always = 0, n_ref_leaves = 0, acc_depth = 0, n_spheres = 0;
     float tri_extent = 0.0f;
 };
-static size_t out_block_bytes(uint32_t n) {
-    const size_t nn = 2 * (size_t)n - 1, al = 256;
-    const size_t parts[9] = {nn * 32, (size_t)n * 4, (size_t)n * 48, (size_t)n * 32, nn * 32, ((size_t)n + 2) * MPT_OT_NODE_STRIDE * 16, (size_t)MPT_ACCEL_MAX_ALWAYS * 80,
-                             (size_t)n * 32, (size_t)n * 32};
-    size_t total = 0;
-    for (size_t b : parts) total += (b + al - 1) & ~(al - 1);
-    return total;
+// THE layout of the output block: its parts in order, each from a 256-byte boundary.  Returns the block's size; with `out`, points out's views
+// into the block at `base`.  (The order is part of what a build writes: a `spare` block is reused, and the recorded digests walk these arrays.)
+static size_t out_block_layout(uint32_t n, char* base, Built* out) {
+    const size_t nn = 2 * (size_t)n - 1;
+    size_t off = 0;
+    auto part = [&](auto Built::*view, size_t bytes) {
+        if (out) out->*view = (std::remove_reference_t<decltype(out->*view)>)(base + off);
+        off += (bytes + 255) & ~(size_t)255;
+    };
+    part(&Built::ref_bvh, nn * 32);
+    part(&Built::ref_idx, (size_t)n * 4);
+    part(&Built::prims, (size_t)n * 48);
+    part(&Built::refleaf, (size_t)n * 32);
+    part(&Built::nodes, nn * 32);
+    part(&Built::acc_nodes, ((size_t)n + 2) * MPT_OT_NODE_STRIDE * 16);
+    part(&Built::always, (size_t)MPT_ACCEL_MAX_ALWAYS * 80);
+    part(&Built::refbox, (size_t)n * 32);
+    part(&Built::mats, (size_t)n * 32);
+    return off;
+}
+// spare: a device allocation the caller has no more use for — taken for the outputs if it is large enough
+static hipError_t take_out_block(uint32_t n, mpt_own::DevMem<>* spare, Built& out) {
+    const size_t need = out_block_layout(n, nullptr, nullptr);
+    if (spare && spare->bytes() >= need) out.block = std::move(*spare);
+    else MPT_LB(out.block.alloc(need));
+    out_block_layout(n, (char*)out.block.get(), &out);
+    return hipSuccess;
 }
 
-// spare (in, out): a device allocation the caller has no more use for — taken for the outputs if it is large enough.
-// mats_host (may be null): the caller's material array in host memory, NOT yet copied to d_mats_in — the copy is then made here, on the side
-// stream by a helper thread (a copy from pageable memory keeps its host thread for its whole length: 1.1 ms for the 32 MB of 1 M
-// primitives), while this thread drives the tree build on the main stream.
-static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_mats_in, const float* mats_host, uint32_t n, int leaf_max, int builder,
-                             uint32_t n_spheres_hint, Built& out, mpt_lbvh::ScratchPool* pool, mpt_own::DevMem<>* spare, bool wide_mat_sort, bool* mat_collision) {
-    Scratch sc(pool);
-    // Two streams (round 5): the material chain (hash, sort, table: ~0.19 ms of small kernels for 1 M primitives) needs nothing of the tree until
-    // the leaves are written, and the threaded tree (depths, their sort, the emission: ~0.13 ms) nothing of the own tree's collapse — each runs
-    // on the pool's side stream beside the main one, forked and joined by events.  Without a pool: everything on `stream`, as before.
-    hipStream_t side = stream;
-    if (pool && getenv("MPT_BUILD_ONE_STREAM") == nullptr) MPT_LB(pool->side_stream(&side));
-    const bool two = side != stream;
-    struct SideGuard {   // (no scratch chunk goes back to the pool while the side stream may still use it: declared after `sc`, run before it)
-        hipStream_t s;
-        ~SideGuard() { if (s) hipStreamSynchronize(s); }
-    } side_guard{two ? side : nullptr};
-    struct Helper {   // (joined before the side stream is drained and the scratch goes back: declared after both)
-        std::thread t;
-        hipError_t err = hipSuccess;
-        ~Helper() { if (t.joinable()) t.join(); }
-    } helper;
-    auto hand_over = [&](hipStream_t from, hipStream_t to, int e) -> hipError_t {   // what `to` does next comes after what `from` has been given so far
+// Two streams (round 5): the material chain (hash, sort, table: ~0.19 ms of small kernels for 1 M primitives) needs nothing of the tree until
+// the leaves are written, and the threaded tree (depths, their sort, the emission: ~0.13 ms) nothing of the own tree's collapse — each runs
+// on the pool's side stream beside the main one, forked and joined by events.  MPT_BUILD_ONE_STREAM: everything on `main`.
+struct Streams {
+    hipStream_t main = nullptr, side = nullptr;
+    bool two = false;
+    hipEvent_t* ev = nullptr;
+    hipError_t open(hipStream_t stream, mpt_build::ScratchPool& pool, bool one_stream) {
+        main = side = stream;
+        if (!one_stream) MPT_LB(pool.side_stream(&side));
+        two = side != main;
+        ev = pool.ev;
+        return hipSuccess;
+    }
+    // what `to` does next comes after what `from` has been given so far
+    hipError_t hand_over(hipStream_t from, hipStream_t to, int e) const {
         if (!two) return hipSuccess;
-        MPT_LB(hipEventRecord(pool->ev[e], from));
-        return hipStreamWaitEvent(to, pool->ev[e], 0);
-    };
-    {
-        const size_t need = out_block_bytes(n);
-        if (spare && spare->bytes() >= need)
-            out.block = std::move(*spare);
-        else
-            MPT_LB(out.block.alloc(need));
-        char* q = (char*)out.block.get();
-        auto carve = [&](size_t bytes) {
-            char* r = q;
-            q += (bytes + 255) & ~(size_t)255;
-            return r;
-        };
-        const size_t nn_ = 2 * (size_t)n - 1;
-        out.ref_bvh = (float4*)carve(nn_ * 32);
-        out.ref_idx = (int*)carve((size_t)n * 4);
-        out.prims = (float4*)carve((size_t)n * 48);
-        out.refleaf = (float4*)carve((size_t)n * 32);
-        out.nodes = (float4*)carve(nn_ * 32);
-        out.acc_nodes = (float4*)carve(((size_t)n + 2) * MPT_OT_NODE_STRIDE * 16);
-        out.always = (float4*)carve((size_t)MPT_ACCEL_MAX_ALWAYS * 80);
-        out.refbox = (float4*)carve((size_t)n * 32);
-        out.mats = (float4*)carve((size_t)n * 32);
+        MPT_LB(hipEventRecord(ev[e], from));
+        return hipStreamWaitEvent(to, ev[e], 0);
     }
-    MPT_LB(sc.reserve((size_t)n * 720 + ((size_t)8 << 20)));   // (measured: ~620 bytes per primitive)
-    Radix R;
+    ~Streams() { if (two) hipStreamSynchronize(side); }   // on every exit path: what was given to the side stream has run
+};
+struct Helper {   // the thread that copies the materials from pageable memory and enqueues their chain
+    std::thread t;
+    hipError_t err = hipSuccess;
+    hipError_t join() { return t.joinable() ? (t.join(), err) : err; }
+    ~Helper() { join(); }
+};
+
+// The material table, on the side stream.  Everything the chain needs is reserved by the build's thread (the scratch allocator is not for
+// two); the chain itself — a copy of this struct — is enqueued by that thread or by the helper.
+struct MatChain {
+    hipStream_t side;
+    const float4* prims;
+    float4* mats;            // the caller's materials on the device ...
+    const float* mats_host;  // ... or (not null) in host memory, NOT yet copied there: the chain starts with the copy
+    uint32_t n, key_shift;
+    bool wide;               // sorted on all 64 bits of the hash (after a collision of the upper halves)
+    float4* table;           // (the de-duplicated table is written where it stays)
     Scalars* d_sc;
-    mpt_lbvh::PinnedWords pinned;   // read-backs of a few words go through pinned memory (a pageable target costs ~0.3 ms per copy)
-    MPT_LB(pinned.get(pool, 0));    // (words 64 .. 111: the level slots of mpt_sah::run_sah, 160 .. 175: the collapse's, 192 ..: the scalars read at the end)
-    uint32_t* pin = pinned.p;
-    MPT_LB(sc.alloc(&d_sc, 1));
-    MPT_LB(hipMemsetAsync(d_sc, 0, sizeof(Scalars), stream));
-    MPT_LB(hand_over(stream, side, 0));   // (the caller's uploads and the zeroed scalars)
-    const uint32_t B = 256, gn = (n + B - 1) / B;
-    // materials
-    unsigned long long *mk, *mk2;
-    uint32_t *mi, *mi2, *mhead, *mrank, *mat_of_prim;
-    float4* const mtable = out.mats;   // (the de-duplicated table is written where it stays)
-    mk = mk2 = nullptr;
-    if (wide_mat_sort) {
-        MPT_LB(sc.alloc(&mk, n));
-        MPT_LB(sc.alloc(&mk2, n));
-    }
-    MPT_LB(sc.alloc(&mi, n));
-    MPT_LB(sc.alloc(&mi2, n));
-    MPT_LB(sc.alloc(&mhead, n));
-    MPT_LB(sc.alloc(&mrank, n));
-    MPT_LB(sc.alloc(&mat_of_prim, n));
+    unsigned long long *mk = nullptr, *mk2 = nullptr;
+    uint32_t *mi, *mi2, *mhead, *mrank, *mat_of_prim, *mk32 = nullptr, *mk32s = nullptr;
+    char* sort_tmp = nullptr;
+    size_t sort_bytes = 0;
+    mpt_radix::RadixTemp RT;
+    char* scan_tmp = nullptr;   // (of the INCLUSIVE sum that numbers the runs: the one scan of the build that Scan does not fit)
+    size_t scan_bytes = 0;
     // Sorted on the upper 32 bits of the hash, as 32-bit keys, by four passes of the builders' own radix sort (mpt_radix.h: hipcub sorts
     // 1 M pairs by merging, 25 launches and ~0.2 ms whatever the key width).  The order is that of the full 64-bit sort unless two DIFFERENT materials share those 32 bits —
-    // k_mat_heads sees that (equal keys, other contents) and the caller builds again with wide_mat_sort (build() below).
+    // k_mat_heads sees that (equal keys, other contents) and the caller builds again with `wide` (build() below).
     // [hipcub::DeviceRadixSort::SortPairs over bits [32, 64) of the 64-bit keys themselves — the obvious way to do this — is WRONG on this
     // toolchain (ROCm 7.2.0, gfx950) from a few thousand items on: the keys it returns are not even a permutation of its input
     // (tests/experiments/hipcub_partial_bits.hip, run on MI355X: 4,971 / 99,362 / 1,000,003 items, its own queried temporary size, canaries
@@ -706,30 +702,26 @@ static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_m
     // s46_tests.log).  The same program finds every range the product uses right: [0, 64), [0, 63) (mpt_lbvh.h), [0, 13), [0, 8) on
     // 32-bit keys (docs/HISTORY.md).  The sort used here has a test of its own, tests/test_gpu_radix.py: full-width 32-bit keys of every
     // kind against numpy's stable sort; tests/test_gpu_materials.py runs this chain with up to 40,000 materials and with a real collision.]
-    uint32_t *mk32 = nullptr, *mk32s = nullptr;
-    if (!wide_mat_sort) {
-        MPT_LB(sc.alloc(&mk32, n));
-        MPT_LB(sc.alloc(&mk32s, n));
+    hipError_t reserve(Scratch& sc) {
+        MPT_LB(sc.allocs(n, &mi, &mi2, &mhead, &mrank, &mat_of_prim));
+        if (wide) {
+            MPT_LB(sc.allocs(n, &mk, &mk2));
+            MPT_LB(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, mk, mk2, mi, mi2, (int)n, 0, 64, side));
+            MPT_LB(sc.alloc(&sort_tmp, sort_bytes));
+        } else {
+            MPT_LB(sc.allocs(n, &mk32, &mk32s));
+            MPT_LB(mpt_radix::radix_reserve(sc, n, side, RT));
+        }
+        MPT_LB(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, mhead, mrank, (int)n, side));
+        return sc.alloc(&scan_tmp, scan_bytes);
     }
-    uint32_t key_shift = 0u;
-    if (const char* e = getenv("MPT_DEBUG_MAT_KEY_BITS")) key_shift = 32u - (uint32_t)std::min(std::max(atoi(e), 1), 32);
-    // (everything the chain needs is allocated here, by this thread: the scratch allocator is not for two)
-    char *sort_tmp = nullptr, *scan_tmp = nullptr;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    mpt_radix::RadixTemp RT;
-    if (wide_mat_sort) {
-        MPT_LB(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, mk, mk2, mi, mi2, (int)n, 0, 64, side));
-        MPT_LB(sc.alloc(&sort_tmp, sort_bytes));
-    } else {
-        MPT_LB(mpt_radix::radix_reserve(sc, n, side, RT));
-    }
-    MPT_LB(hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, mhead, mrank, (int)n, side));
-    MPT_LB(sc.alloc(&scan_tmp, scan_bytes));
-    auto mats_chain = [&]() -> hipError_t {
-        hipLaunchKernelGGL(k_tri_extent, dim3(std::min(gn, 1024u)), dim3(B), 0, side, (const float4*)d_prims_in, n, d_sc);   // (needed by k_leaves: joins with the materials)
-        hipLaunchKernelGGL(k_mat_hash, dim3(gn), dim3(B), 0, side, (const float4*)d_mats_in, n, mk, mk32, key_shift, mi);
+    hipError_t enqueue() const {
+        const uint32_t B = 256, gn = (n + B - 1) / B;
+        if (mats_host) MPT_LB(hipMemcpyAsync(mats, mats_host, (size_t)n * 32, hipMemcpyHostToDevice, side));
+        hipLaunchKernelGGL(k_tri_extent, dim3(std::min(gn, 1024u)), dim3(B), 0, side, prims, n, d_sc);   // (needed by k_leaves: joins with the materials)
+        hipLaunchKernelGGL(k_mat_hash, dim3(gn), dim3(B), 0, side, mats, n, mk, mk32, key_shift, mi);
         const uint32_t *ids_sorted = mi2, *keys32_sorted = nullptr;
-        if (wide_mat_sort) {
+        if (wide) {
             size_t bytes = sort_bytes;
             MPT_LB(hipcub::DeviceRadixSort::SortPairs(sort_tmp, bytes, mk, mk2, mi, mi2, (int)n, 0, 64, side));
         } else {
@@ -738,255 +730,272 @@ static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_m
             ids_sorted = second ? mi2 : mi;
             keys32_sorted = second ? mk32s : mk32;
         }
-        hipLaunchKernelGGL(k_mat_heads, dim3(gn), dim3(B), 0, side, (const float4*)d_mats_in, ids_sorted, keys32_sorted, n, mhead, d_sc);
+        hipLaunchKernelGGL(k_mat_heads, dim3(gn), dim3(B), 0, side, mats, ids_sorted, keys32_sorted, n, mhead, d_sc);
         size_t sb = scan_bytes;
         MPT_LB(hipcub::DeviceScan::InclusiveSum(scan_tmp, sb, mhead, mrank, (int)n, side));
-        hipLaunchKernelGGL(k_mat_scatter, dim3(gn), dim3(B), 0, side, (const float4*)d_mats_in, ids_sorted, (const uint32_t*)mhead, (const uint32_t*)mrank, n,
-                           mat_of_prim, mtable, d_sc);
+        hipLaunchKernelGGL(k_mat_scatter, dim3(gn), dim3(B), 0, side, mats, ids_sorted, mhead, mrank, n, mat_of_prim, table, d_sc);
         return hipGetLastError();
-    };
-    if (mats_host && two && (size_t)n * 32 >= ((size_t)1 << 20) && getenv("MPT_BUILD_NO_HELPER") == nullptr) {   // (below 1 MB the thread costs what the copy does)
+    }
+};
+struct Leaves {   // by node id of the radix tree (2n - 1 of them)
+    uint32_t *is_leaf, *leaf_id;   // flag, and its exclusive scan: leaf_id[2n - 1] = the number of leaves
+    uint32_t* pfirst;              // where the leaf's records start in the device primitive array
+    float4 *olo, *ohi;             // own box (k_leaves)
+    uint32_t n_sph;                // spheres of the scene
+    int use_always;                // ... few enough for the always list
+};
+struct OwnTree {   // the binary tree under the own 4-wide tree (node ids: a leaf's radix id; 2n - 1 + k = inner node k)
+    SahState* st;   // on the device: the root
+    int2* child;    // of inner node k
+    float4 *lo, *hi;
+    int dense;      // run_sah's (inner nodes 0 .. n_nodes - 1, all made); else the refitted one, whose unmade nodes hold child -1
+};
+static_assert(sizeof(Scalars) <= 4u * mpt_build::PIN_N_SCALARS, "Scalars must fit its region of the pinned block");
+
+// One pass of the build: what every step works with, the steps, and run() — the steps in order.  The first three members are destroyed last
+// to first, and that order IS the rule that keeps every exit path safe: no scratch chunk goes back to the pool (where the next build takes
+// it) while the side stream may still use it, and the side stream is not drained while the helper thread may still enqueue on it.
+struct Pass {
+    Scratch sc;      // 3. the scratch goes back to the pool
+    Streams st;      // 2. the side stream is drained
+    Helper helper;   // 1. the helper thread is joined
+    const mpt_build::Switches& env;
+    static constexpr uint32_t B = 256;
+    const uint32_t n, gn, gnn;   // primitives; grids of B threads over n and over the 2n - 1 node ids
+    const size_t nn;
+    hipStream_t stream = nullptr, side = nullptr;   // = st.main, st.side
+    Scalars* d_sc = nullptr;
+    uint32_t* pin = nullptr;     // the scene build's part of the pinned block: read-backs of a few words (a pageable target costs ~0.3 ms per copy)
+    Pass(mpt_build::ScratchPool& pool, const mpt_build::Switches& e, uint32_t n_)
+        : sc(pool), env(e), n(n_), gn((n_ + B - 1) / B), gnn((uint32_t)((2 * (size_t)n_ - 1 + B - 1) / B)), nn(2 * (size_t)n_ - 1) {}
+
+    hipError_t open(hipStream_t main) {
+        MPT_LB(st.open(main, sc.pool, env.one_stream));
+        stream = st.main, side = st.side;
+        MPT_LB(sc.reserve((size_t)n * 720 + ((size_t)8 << 20)));   // (measured: ~620 bytes per primitive)
+        MPT_LB(sc.pool.pinned(mpt_build::PIN_PART_SCENE, &pin));
+        MPT_LB(sc.alloc(&d_sc, 1));
+        return hipMemsetAsync(d_sc, 0, sizeof(Scalars), stream);
+    }
+    // Enqueues the material chain: with the materials still in host memory and two streams, from a helper thread (a copy from pageable memory
+    // keeps its host thread for its whole length: 1.1 ms for the 32 MB of 1 M primitives) while this thread drives the tree build.
+    hipError_t start_materials(const MatChain& C) {
+        if (!(C.mats_host && st.two && (size_t)n * 32 >= ((size_t)1 << 20) && !env.no_helper)) return C.enqueue();   // (below 1 MB the thread costs what the copy does)
         int dev = 0;
         MPT_LB(hipGetDevice(&dev));
-        helper.t = std::thread([&, dev]() {
-            helper.err = hipSetDevice(dev);
-            if (helper.err == hipSuccess) helper.err = hipMemcpyAsync(d_mats_in, mats_host, (size_t)n * 32, hipMemcpyHostToDevice, side);
-            if (helper.err == hipSuccess) helper.err = mats_chain();
+        Helper* const h = &helper;
+        h->t = std::thread([h, C, dev]() {
+            h->err = hipSetDevice(dev);
+            if (h->err == hipSuccess) h->err = C.enqueue();
         });
-    } else {
-        if (mats_host) MPT_LB(hipMemcpyAsync(d_mats_in, mats_host, (size_t)n * 32, hipMemcpyHostToDevice, side));
-        MPT_LB(mats_chain());
+        return hipSuccess;
     }
-    // the binary tree
-    MPT_LB(mpt_lbvh::build_radix(stream, sc, d_prims_in, n, leaf_max, builder, R));
-    const uint32_t n_out = R.n_out;
-    const size_t nn = 2 * (size_t)n - 1;
-    const uint32_t gnn = (uint32_t)((nn + B - 1) / B), go = (n_out + B - 1) / B;
-    MPT_LB(mpt_lbvh::emit_reference_format(stream, R, out.ref_bvh, out.ref_idx));
-    // leaves
-    uint32_t *is_leaf, *leaf_id;
-    float4 *olo, *ohi;
-    MPT_LB(sc.alloc(&is_leaf, nn + 1));
-    MPT_LB(sc.alloc(&leaf_id, nn + 1));
-    MPT_LB(sc.alloc(&olo, nn));
-    MPT_LB(sc.alloc(&ohi, nn));
-    hipLaunchKernelGGL(k_leaf_flags, dim3(gnn), dim3(B), 0, stream, (int)n, leaf_max, (const int2*)R.range, (const uint32_t*)R.keep, is_leaf);
-    MPT_LB(hipMemsetAsync(is_leaf + nn, 0, 4, stream));
-    {
-        size_t sb = 0;
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, is_leaf, leaf_id, (int)nn + 1, stream));
-        char* tmp;
-        MPT_LB(sc.alloc(&tmp, sb));
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(tmp, sb, is_leaf, leaf_id, (int)nn + 1, stream));
+    hipError_t mark_leaves(const Radix& R, uint32_t n_spheres_hint, Leaves& L) {
+        MPT_LB(sc.allocs(nn + 1, &L.is_leaf, &L.leaf_id));
+        MPT_LB(sc.allocs(nn, &L.olo, &L.ohi, &L.pfirst));
+        hipLaunchKernelGGL(k_leaf_flags, dim3(gnn), dim3(B), 0, stream, (int)n, R.leaf_max, R.range, R.keep, L.is_leaf);
+        MPT_LB(hipMemsetAsync(L.is_leaf + nn, 0, 4, stream));
+        MPT_LB(Scan::once(sc, L.is_leaf, L.leaf_id, nn + 1, stream));
+        // (n_spheres_hint = 0xFFFFFFFF: not counted by the caller — the top-down builder has counted them on the device)
+        L.n_sph = n_spheres_hint != 0xFFFFFFFFu ? n_spheres_hint : R.n_spheres;
+        if (L.n_sph == 0xFFFFFFFFu) return hipErrorInvalidValue;
+        L.use_always = L.n_sph <= MPT_ACCEL_MAX_ALWAYS ? 1 : 0;
+        return hipSuccess;
     }
-    // (n_spheres_hint = 0xFFFFFFFF: not counted by the caller — the top-down builder has counted them on the device)
-    const uint32_t n_sph = n_spheres_hint != 0xFFFFFFFFu ? n_spheres_hint : R.n_spheres;
-    if (n_sph == 0xFFFFFFFFu) return hipErrorInvalidValue;
-    const int use_always = n_sph <= MPT_ACCEL_MAX_ALWAYS ? 1 : 0;
-    // where each leaf's records go (see k_leaf_keys)
-    uint32_t* pfirst;
-    MPT_LB(sc.alloc(&pfirst, nn));
-    if (n >= MPT_AUTO_ORDERED_PRIMS) {
-        hipLaunchKernelGGL(k_pfirst_builder_order, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)R.range, (const uint32_t*)is_leaf, pfirst);
-    } else {
+    // where each leaf's records go (see k_leaf_keys): the builder's order for large scenes, else sorted by a key of the leaf's box area
+    hipError_t place_leaves(const Radix& R, const Leaves& L) {
+        if (n >= MPT_AUTO_ORDERED_PRIMS) {
+            hipLaunchKernelGGL(k_pfirst_builder_order, dim3(gnn), dim3(B), 0, stream, (int)n, R.range, L.is_leaf, L.pfirst);
+            return hipGetLastError();
+        }
+        const uint32_t n_out = R.n_out;
         uint32_t *key, *key_s, *node_of, *node_s, *cnt, *pos;
-        MPT_LB(sc.alloc(&key, n_out));
-        MPT_LB(sc.alloc(&key_s, n_out));
-        MPT_LB(sc.alloc(&node_of, n_out));
-        MPT_LB(sc.alloc(&node_s, n_out));
-        MPT_LB(sc.alloc(&cnt, n_out + 1));
-        MPT_LB(sc.alloc(&pos, n_out + 1));
-        MPT_LB(hipMemcpyAsync(pin, leaf_id + nn, 4, hipMemcpyDeviceToHost, stream));
+        MPT_LB(sc.allocs(n_out, &key, &key_s, &node_of, &node_s));
+        MPT_LB(sc.allocs(n_out + 1, &cnt, &pos));
+        MPT_LB(hipMemcpyAsync(pin + mpt_build::PIN_W_SMALL, L.leaf_id + nn, 4, hipMemcpyDeviceToHost, stream));
         MPT_LB(hipStreamSynchronize(stream));
-        const uint32_t nl = pin[0], gl = (nl + B - 1) / B;
-        hipLaunchKernelGGL(k_leaf_keys, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)R.range, (const uint32_t*)is_leaf, (const uint32_t*)leaf_id,
-                           (const uint32_t*)R.vals, (const float4*)d_prims_in, (const float4*)R.nlo, (const float4*)R.nhi, key, node_of);
-        size_t bytes = 0, sb = 0;
+        const uint32_t nl = pin[mpt_build::PIN_W_SMALL], gl = (nl + B - 1) / B;
+        hipLaunchKernelGGL(k_leaf_keys, dim3(gnn), dim3(B), 0, stream, (int)n, R.range, L.is_leaf, L.leaf_id, R.vals, R.prims, R.nlo, R.nhi, key, node_of);
+        size_t bytes = 0;
         MPT_LB(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, key, key_s, node_of, node_s, (int)nl, 0, 13, stream));
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, cnt, pos, (int)nl, stream));
-        char *tmp, *tmp2;
+        Scan scan;
+        MPT_LB(scan.reserve(sc, nl, stream));
+        char* tmp;
         MPT_LB(sc.alloc(&tmp, bytes));
-        MPT_LB(sc.alloc(&tmp2, sb));
         MPT_LB(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, key, key_s, node_of, node_s, (int)nl, 0, 13, stream));   // (stable: the builder's order among equals)
-        hipLaunchKernelGGL(k_leaf_counts, dim3(gl), dim3(B), 0, stream, (int)n, nl, (const int2*)R.range, (const uint32_t*)node_s, cnt);
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(tmp2, sb, cnt, pos, (int)nl, stream));
-        hipLaunchKernelGGL(k_pfirst_scatter, dim3(gl), dim3(B), 0, stream, nl, (const uint32_t*)node_s, (const uint32_t*)pos, pfirst);
+        hipLaunchKernelGGL(k_leaf_counts, dim3(gl), dim3(B), 0, stream, (int)n, nl, R.range, node_s, cnt);
+        MPT_LB(scan.run(cnt, pos, nl, stream));
+        hipLaunchKernelGGL(k_pfirst_scatter, dim3(gl), dim3(B), 0, stream, nl, node_s, pos, L.pfirst);
+        return hipGetLastError();
     }
-    if (helper.t.joinable()) helper.t.join();   // (the side stream has been GIVEN everything up to the material table)
-    MPT_LB(helper.err);
-    MPT_LB(hand_over(side, stream, 1));   // (mat_of_prim)
-    hipLaunchKernelGGL(k_leaves, dim3(gnn), dim3(B), 0, stream, (int)n, leaf_max, (const int2*)R.range, (const uint32_t*)is_leaf, (const uint32_t*)leaf_id,
-                       (const uint32_t*)R.vals, (const float4*)d_prims_in, (const uint32_t*)mat_of_prim, (const float4*)R.nlo, (const float4*)R.nhi,
-                       (const uint32_t*)pfirst, out.prims, out.refleaf, olo, ohi, d_sc, use_always);
-    // threaded tree, breadth-first — and the per-primitive leaf boxes: on the side stream, beside the own tree
-    MPT_LB(hand_over(stream, side, 2));   // (the leaves)
-    uint32_t *depth_c, *depth_s, *id_c, *order, *tpos;
-    int* skip;
-    MPT_LB(sc.alloc(&depth_c, n_out));
-    MPT_LB(sc.alloc(&depth_s, n_out));
-    MPT_LB(sc.alloc(&id_c, n_out));
-    MPT_LB(sc.alloc(&order, n_out));
-    MPT_LB(sc.alloc(&tpos, nn));
-    MPT_LB(sc.alloc(&skip, nn));
-    hipLaunchKernelGGL(k_depth_skip, dim3(gnn), dim3(B), 0, side, (int)n, (const uint32_t*)R.keep, (const uint32_t*)R.index, (const int2*)R.child,
-                       (const int*)R.parent, depth_c, id_c, skip);
-    {   // (one counting pass over the 8-bit depths, stable: breadth-first, the builder's order within a level)
-        mpt_radix::RadixTemp RT;
+    // the threaded tree, breadth-first — and the per-primitive leaf boxes: on the side stream, beside the own tree
+    hipError_t threaded_tree(const Radix& R, const Leaves& L, const Built& out) {
+        const uint32_t n_out = R.n_out, go = (n_out + B - 1) / B;
+        uint32_t *depth_c, *depth_s, *id_c, *order, *tpos;
+        int* skip;
+        MPT_LB(sc.allocs(n_out, &depth_c, &depth_s, &id_c, &order));
+        MPT_LB(sc.allocs(nn, &tpos, &skip));
+        hipLaunchKernelGGL(k_depth_skip, dim3(gnn), dim3(B), 0, side, (int)n, R.keep, R.index, R.child, R.parent, depth_c, id_c, skip);
+        mpt_radix::RadixTemp RT;   // (one counting pass over the 8-bit depths, stable: breadth-first, the builder's order within a level)
         MPT_LB(mpt_radix::radix_reserve(sc, n_out, side, RT));
         bool second = false;
         MPT_LB(mpt_radix::radix_sort_pairs(side, RT, depth_c, id_c, depth_s, order, n_out, 1, &second));
+        hipLaunchKernelGGL(k_positions, dim3(go), dim3(B), 0, side, n_out, order, tpos);
+        hipLaunchKernelGGL(k_emit_threaded, dim3(go), dim3(B), 0, side, n_out, (int)n, order, tpos, L.is_leaf, R.child, R.range, L.pfirst, skip, R.nlo, R.nhi, out.nodes);
+        hipLaunchKernelGGL(k_prim_refbox, dim3((n + 255u) / 256u), dim3(256), 0, side, out.prims, out.refleaf, n, out.refbox);
+        return hipGetLastError();
     }
-    hipLaunchKernelGGL(k_positions, dim3(go), dim3(B), 0, side, n_out, (const uint32_t*)order, tpos);
-    hipLaunchKernelGGL(k_emit_threaded, dim3(go), dim3(B), 0, side, n_out, (int)n, (const uint32_t*)order, (const uint32_t*)tpos, (const uint32_t*)is_leaf,
-                       (const int2*)R.child, (const int2*)R.range, (const uint32_t*)pfirst, (const int*)skip, (const float4*)R.nlo, (const float4*)R.nhi, out.nodes);
-    hipLaunchKernelGGL(k_prim_refbox, dim3((n + 255u) / 256u), dim3(256), 0, side, (const float4*)out.prims, (const float4*)out.refleaf, n, out.refbox);
-    MPT_LB(hipGetLastError());
-    // own tree: its binary tree (the builder's own SAH tree refitted, or a binned SAH over the leaves: mpt_sah.h), then the 4-wide collapse
-    const uint32_t max_items = n_out;   // (leaves <= output nodes)
-    SahState* d_st;
-    int2* s_child;
-    float4 *s_lo, *s_hi;
-    // (the builder's own tree serves when its SAH nodes hold no sphere — the builder hangs up to 16 spheres under the root,
-    //  mpt_lbvh.h — or when no always list is used; with spheres inside the SAH their boxes shape the top splits, which the own
-    //  tree leaves out: a second SAH over the leaves then.  MPT_OWN_TREE = refit | sah forces either way)
-    bool refit = builder == mpt_lbvh::BUILDER_SAH && n > 2 && (R.spheres_hoisted || n_sph == 0 || !use_always);
-    if (const char* e = getenv("MPT_OWN_TREE")) refit = builder == mpt_lbvh::BUILDER_SAH && n > 2 && strcmp(e, "refit") == 0;
-    if (refit) {
+    // The builder's own tree serves as the own tree's binary tree when its SAH nodes hold no sphere — the builder hangs up to 16 spheres
+    // under the root, mpt_lbvh.h — or when no always list is used; with spheres inside the SAH their boxes shape the top splits, which the
+    // own tree leaves out: a second SAH over the leaves then.  MPT_OWN_TREE = refit | sah forces either way.
+    bool own_tree_refits(int builder, const Radix& R, const Leaves& L) const {
+        if (builder != mpt_lbvh::BUILDER_SAH || n <= 2) return false;
+        if (env.own_tree != env.OWN_AUTO) return env.own_tree == env.OWN_REFIT;
+        return R.spheres_hoisted || L.n_sph == 0 || !L.use_always;
+    }
+    hipError_t own_tree_refit(const Radix& R, const Leaves& L, OwnTree& T) {
         int *eff, *arrived;
-        MPT_LB(sc.alloc(&d_st, 1));
-        MPT_LB(sc.alloc(&eff, nn));
-        MPT_LB(sc.alloc(&arrived, nn));
-        MPT_LB(sc.alloc(&s_child, n));
-        MPT_LB(sc.alloc(&s_lo, n));
-        MPT_LB(sc.alloc(&s_hi, n));
+        MPT_LB(sc.alloc(&T.st, 1));
+        MPT_LB(sc.allocs(nn, &eff, &arrived));
+        MPT_LB(sc.allocs(n, &T.child, &T.lo, &T.hi));
+        T.dense = 0;
         MPT_LB(hipMemsetAsync(arrived, 0, nn * 4, stream));
-        MPT_LB(hipMemsetAsync(d_st, 0xFF, sizeof(SahState), stream));   // root = -1
-        MPT_LB(hipMemsetAsync(s_child, 0xFF, (size_t)n * sizeof(int2), stream));   // (children -1: a node nobody made — k_collapse_picks)
+        MPT_LB(hipMemsetAsync(T.st, 0xFF, sizeof(SahState), stream));   // root = -1
+        MPT_LB(hipMemsetAsync(T.child, 0xFF, (size_t)n * sizeof(int2), stream));   // (children -1: a node nobody made — k_collapse_picks)
         // (the copy is valid when every leaf's own box is its reference box or, in the chain of hoisted items, empty: spheres hoisted or none
         //  — with spheres INSIDE the SAH's leaves and no always list the boxes agree too, but then nothing marks the chain: the walk)
-        const bool fast = (R.spheres_hoisted || n_sph == 0) && getenv("MPT_OWN_TREE_WALK") == nullptr;
+        const bool fast = (R.spheres_hoisted || L.n_sph == 0) && !env.own_tree_walk;
         if (fast) {
-            hipLaunchKernelGGL(k_own_copy, dim3((n + B - 1) / B), dim3(B), 0, stream, (int)n, (const int2*)R.child, (const uint32_t*)R.keep, (const uint32_t*)is_leaf,
-                               (const float4*)R.nlo, (const float4*)R.nhi, (const Scalars*)d_sc, s_lo, s_hi, s_child);
-            hipLaunchKernelGGL(k_own_chain, dim3(1), dim3(64), 0, stream, (int)n, (int)R.n_hoisted, (const int2*)R.child, (const uint32_t*)is_leaf, (const float4*)olo,
-                               (const float4*)ohi, (const Scalars*)d_sc, s_lo, s_hi, s_child, d_st);
+            hipLaunchKernelGGL(k_own_copy, dim3(gn), dim3(B), 0, stream, (int)n, R.child, R.keep, L.is_leaf, R.nlo, R.nhi, d_sc, T.lo, T.hi, T.child);
+            hipLaunchKernelGGL(k_own_chain, dim3(1), dim3(64), 0, stream, (int)n, (int)R.n_hoisted, R.child, L.is_leaf, L.olo, L.ohi, d_sc, T.lo, T.hi, T.child, T.st);
         }
-        hipLaunchKernelGGL(k_own_tree, dim3(gnn), dim3(B), 0, stream, (int)n, (const int*)R.parent, (const int2*)R.child, (const uint32_t*)is_leaf, (const float4*)olo,
-                           (const float4*)ohi, eff, s_lo, s_hi, s_child, arrived, d_st, fast ? (const Scalars*)d_sc : (const Scalars*)nullptr);
-    } else {
+        hipLaunchKernelGGL(k_own_tree, dim3(gnn), dim3(B), 0, stream, (int)n, R.parent, R.child, L.is_leaf, L.olo, L.ohi, eff, T.lo, T.hi, T.child, arrived, T.st,
+                           fast ? d_sc : (const Scalars*)nullptr);
+        return hipGetLastError();
+    }
+    hipError_t own_tree_sah(const Radix& R, const Leaves& L, OwnTree& T) {   // a binned SAH over the leaves (mpt_sah.h)
+        const uint32_t max_items = R.n_out;   // (leaves <= output nodes)
         uint32_t *flag_pos, *rank;
         float4 *it_lo_a, *it_hi_a;
-        MPT_LB(sc.alloc(&flag_pos, (size_t)n + 1));
-        MPT_LB(sc.alloc(&rank, (size_t)n + 1));
-        MPT_LB(sc.alloc(&it_lo_a, max_items));
-        MPT_LB(sc.alloc(&it_hi_a, max_items));
+        MPT_LB(sc.allocs((size_t)n + 1, &flag_pos, &rank));
+        MPT_LB(sc.allocs(max_items, &it_lo_a, &it_hi_a));
         MPT_LB(hipMemsetAsync(flag_pos, 0, ((size_t)n + 1) * 4, stream));
-        hipLaunchKernelGGL(k_item_flags, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)R.range, (const uint32_t*)is_leaf, (const float4*)olo, (const float4*)ohi,
-                           flag_pos);
-        size_t sb = 0;
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, flag_pos, rank, (int)n + 1, stream));
-        char* tmp;
-        MPT_LB(sc.alloc(&tmp, sb));
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(tmp, sb, flag_pos, rank, (int)n + 1, stream));
-        hipLaunchKernelGGL(k_items, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)R.range, (const uint32_t*)is_leaf, (const float4*)olo, (const float4*)ohi,
-                           (const uint32_t*)rank, it_lo_a, it_hi_a);
-        mpt_sah::SahTree T;
-        MPT_LB(mpt_sah::run_sah(stream, sc, pin, (int)(2 * n - 1), (const uint32_t*)(rank + n), 0u, max_items, it_lo_a, it_hi_a, T));
-        d_st = T.st;
-        s_child = T.child;
-        s_lo = T.lo;
-        s_hi = T.hi;
+        hipLaunchKernelGGL(k_item_flags, dim3(gnn), dim3(B), 0, stream, (int)n, R.range, L.is_leaf, L.olo, L.ohi, flag_pos);
+        MPT_LB(Scan::once(sc, flag_pos, rank, (size_t)n + 1, stream));
+        hipLaunchKernelGGL(k_items, dim3(gnn), dim3(B), 0, stream, (int)n, R.range, L.is_leaf, L.olo, L.ohi, rank, it_lo_a, it_hi_a);
+        mpt_sah::SahTree S;
+        MPT_LB(mpt_sah::run_sah(stream, sc, pin, (int)nn, (const uint32_t*)(rank + n), 0u, max_items, it_lo_a, it_hi_a, S));
+        T = OwnTree{S.st, S.child, S.lo, S.hi, 1};
+        return hipSuccess;
     }
-    const uint32_t cap = std::min(max_items, n) + 2u;   // wide nodes <= inner nodes of the SAH tree over the leaves (+ the root of a one-leaf tree)
-    {
+    // the collapse to the own 4-wide tree (the level loop described at CollapseLevel)
+    hipError_t collapse(const Radix& R, const Leaves& L, const OwnTree& T, const Built& out) {
+        const uint32_t cap = std::min(R.n_out, n) + 2u;   // wide nodes <= inner nodes of the SAH tree over the leaves (+ the root of a one-leaf tree)
         uint32_t *nint_a, *nint_b, *c_offs, *pn;
         int *wbin_a, *wbin_b;
         int4* picks;
         CollapseHead* head;
-        MPT_LB(sc.alloc(&nint_a, cap + 1));
-        MPT_LB(sc.alloc(&nint_b, cap + 1));
-        MPT_LB(sc.alloc(&c_offs, cap + 1));
-        MPT_LB(sc.alloc(&wbin_a, cap));
-        MPT_LB(sc.alloc(&wbin_b, cap));
-        MPT_LB(sc.alloc(&picks, n));
-        MPT_LB(sc.alloc(&pn, n));
+        MPT_LB(sc.allocs(cap + 1, &nint_a, &nint_b, &c_offs));
+        MPT_LB(sc.allocs(cap, &wbin_a, &wbin_b));
+        MPT_LB(sc.allocs(n, &picks, &pn));
         MPT_LB(sc.alloc(&head, 1));
-        const CollapseAcc A = {s_child, s_lo, s_hi, olo, ohi, (int)(2 * n - 1)};
-        size_t sb = 0;
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, nint_a, c_offs, (int)cap + 1, stream));
-        char* tmp;
-        MPT_LB(sc.alloc(&tmp, sb));
+        const CollapseAcc A = {T.child, T.lo, T.hi, L.olo, L.ohi, (int)nn};
+        Scan scan;
+        MPT_LB(scan.reserve(sc, (size_t)cap + 1, stream));
         static uint32_t s_epoch = 0;
         const uint32_t epoch = (++s_epoch & 0xFFFFu) << 16;
-        volatile unsigned long long* slots = (volatile unsigned long long*)(pin + 160);   // eight slots of (stamp << 32 | size of the next level), behind run_sah's (words 64 .. 111)
-        unsigned long long* d_slots = nullptr;
-        MPT_LB(hipHostGetDevicePointer((void**)&d_slots, pin + 160, 0));
-        for (int q = 0; q < 8; ++q) slots[q] = 0ull;
-        hipLaunchKernelGGL(k_collapse_picks, dim3((n + B - 1) / B), dim3(B), 0, stream, A, n, (const SahState*)d_st, refit ? 0 : 1, picks, pn);
-        hipLaunchKernelGGL(k_collapse_top, dim3(1), dim3(MPT_COLLAPSE_TOP), 0, stream, A, (int)n, (const int2*)R.range, (const uint32_t*)pfirst, (const SahState*)d_st,
-                           (const int4*)picks, (const uint32_t*)pn, head, wbin_a, nint_a, out.acc_nodes, cap, d_sc);
+        mpt_build::StampedSlots slots;   // one word a level: (stamp << 32 | size of the next level)
+        MPT_LB(slots.open(pin, mpt_build::PIN_W_COLLAPSE_SLOTS, 1u));
+        hipLaunchKernelGGL(k_collapse_picks, dim3(gn), dim3(B), 0, stream, A, n, T.st, T.dense, picks, pn);
+        hipLaunchKernelGGL(k_collapse_top, dim3(1), dim3(MPT_COLLAPSE_TOP), 0, stream, A, (int)n, R.range, L.pfirst, T.st, picks, pn, head, wbin_a, nint_a, out.acc_nodes, cap, d_sc);
         uint32_t bound = std::min(4u * MPT_COLLAPSE_TOP, cap);   // upper bound of the level about to be enqueued (the first: what k_collapse_top leaves)
         bool done = false;
-        for (uint32_t L = 0; L < 128u && !done; ++L) {
-            MPT_LB(hipcub::DeviceScan::ExclusiveSum(tmp, sb, nint_a, c_offs, (int)bound + 1, stream));
-            hipLaunchKernelGGL(k_collapse_level, dim3((bound + B - 1) / B), dim3(B), 0, stream, A, (int)n, (const int2*)R.range, (const uint32_t*)pfirst, head, L,
-                               (const int4*)picks, (const uint32_t*)pn, (const int*)wbin_a, (const uint32_t*)c_offs, wbin_b, nint_b, out.acc_nodes, cap, d_sc,
-                               d_slots + (L & 7u), epoch | (L + 1u));
+        for (uint32_t lv = 0; lv < 128u && !done; ++lv) {
+            MPT_LB(scan.run(nint_a, c_offs, (size_t)bound + 1, stream));
+            hipLaunchKernelGGL(k_collapse_level, dim3((bound + B - 1) / B), dim3(B), 0, stream, A, (int)n, R.range, L.pfirst, head, lv, picks, pn, wbin_a, c_offs, wbin_b, nint_b,
+                               out.acc_nodes, cap, d_sc, slots.dev_slot(lv), epoch | (lv + 1u));
             MPT_LB(hipGetLastError());
             uint32_t next_bound = (uint32_t)std::min<uint64_t>(4ull * bound, cap);
-            if (L >= 1u) {   // the size of level L (slot L - 1), which the device is at or past: nothing there = the tree is complete
-                volatile unsigned long long* sl = slots + ((L - 1u) & 7u);
-                const uint32_t want = epoch | L;
-                const auto t0 = std::chrono::steady_clock::now();
-                for (unsigned long long spin = 0; (uint32_t)(*sl >> 32) != want; ++spin)
-                    if ((spin & 0xFFFu) == 0xFFFu) {
-                        const hipError_t q = hipStreamQuery(stream);
-                        if (q != hipSuccess && q != hipErrorNotReady) return q;
-                        if (q == hipSuccess && (uint32_t)(*sl >> 32) != want) return hipErrorUnknown;   // the stream is drained and the stamp never came
-                        if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return hipErrorLaunchTimeOut;
-                    }
-                const uint32_t size_L = (uint32_t)*sl;
-                if (size_L == 0u) done = true;
-                next_bound = (uint32_t)std::min<uint64_t>(4ull * size_L, cap);
+            if (lv >= 1u) {   // the size of level lv (slot lv - 1), which the device is at or past: nothing there = the tree is complete
+                unsigned long long w;
+                MPT_LB(slots.wait(stream, lv - 1u, epoch | lv, 0u, &w));
+                const uint32_t size_lv = (uint32_t)w;
+                if (size_lv == 0u) done = true;
+                next_bound = (uint32_t)std::min<uint64_t>(4ull * size_lv, cap);
             }
             bound = std::max(next_bound, 1u);
             std::swap(nint_a, nint_b);
             std::swap(wbin_a, wbin_b);
         }
-        if (!done) return hipErrorUnknown;
+        return done ? hipSuccess : hipErrorUnknown;
     }
-    hipLaunchKernelGGL(k_always, dim3(1), dim3(64), 0, stream, d_sc, out.prims, (const float4*)out.refleaf, out.always);
-    MPT_LB(hipGetLastError());
-    MPT_LB(hand_over(side, stream, 3));
-    Scalars& h = *(Scalars*)(pin + 192);   // (pinned: a pageable target costs ~0.3 ms per copy)
-    static_assert(sizeof(Scalars) + 4 <= 256, "Scalars must fit the last quarter of the pinned block");
-    uint32_t& n_leaves = pin[192 + sizeof(Scalars) / 4];
-    MPT_LB(hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, stream));
-    MPT_LB(hipMemcpyAsync(&n_leaves, leaf_id + nn, 4, hipMemcpyDeviceToHost, stream));
-    MPT_LB(hipStreamSynchronize(stream));
-    const uint32_t acc_nodes_n = h.n_acc_nodes, acc_depth = h.acc_depth;
-    out.n_nodes = n_out;
-    out.n_prims = n;
-    out.n_mats = h.n_mats;
-    out.n_acc_nodes = acc_nodes_n;
-    out.acc_depth = acc_depth;
-    out.n_spheres = h.n_spheres;
-    out.n_always = h.n_spheres <= MPT_ACCEL_MAX_ALWAYS ? h.n_spheres : 0u;
-    out.n_ref_leaves = n_leaves;
-    memcpy(&out.tri_extent, &h.tri_extent, 4);
-    *mat_collision = h.mat_collision != 0u;
-    return hipSuccess;
+    hipError_t read_back(const Leaves& L, uint32_t n_out, Built& out, bool* mat_collision) {   // the counts of the finished scene, read once
+        Scalars& h = *(Scalars*)(pin + mpt_build::PIN_W_SCALARS);
+        uint32_t& n_leaves = pin[mpt_build::PIN_W_LEAF_COUNT];
+        MPT_LB(hipMemcpyAsync(&h, d_sc, sizeof h, hipMemcpyDeviceToHost, stream));
+        MPT_LB(hipMemcpyAsync(&n_leaves, L.leaf_id + nn, 4, hipMemcpyDeviceToHost, stream));
+        MPT_LB(hipStreamSynchronize(stream));
+        out.n_nodes = n_out;
+        out.n_prims = n;
+        out.n_mats = h.n_mats;
+        out.n_acc_nodes = h.n_acc_nodes;
+        out.acc_depth = h.acc_depth;
+        out.n_spheres = h.n_spheres;
+        out.n_always = h.n_spheres <= MPT_ACCEL_MAX_ALWAYS ? h.n_spheres : 0u;
+        out.n_ref_leaves = n_leaves;
+        memcpy(&out.tri_extent, &h.tri_extent, 4);
+        *mat_collision = h.mat_collision != 0u;
+        return hipSuccess;
+    }
+
+    // The steps in order, and the four points at which one stream is handed what the other has been given.
+    // mats_host (may be null): the caller's material array in host memory, NOT yet copied to d_mats_in (MatChain).
+    hipError_t run(hipStream_t main, float4* d_prims_in, float4* d_mats_in, const float* mats_host, int leaf_max, int builder, uint32_t n_spheres_hint, Built& out,
+                   mpt_own::DevMem<>* spare, bool wide_mat_sort, bool* mat_collision) {
+        MPT_LB(open(main));
+        MPT_LB(take_out_block(n, spare, out));
+        MPT_LB(st.hand_over(stream, side, 0));   // (the caller's uploads and the zeroed scalars)
+        MatChain mats = {side, d_prims_in, d_mats_in, mats_host, n, env.mat_key_shift, wide_mat_sort, out.mats, d_sc};
+        MPT_LB(mats.reserve(sc));
+        MPT_LB(start_materials(mats));
+        Radix R;
+        MPT_LB(mpt_lbvh::build_radix(stream, sc, d_prims_in, n, leaf_max, builder, env, R));
+        MPT_LB(mpt_lbvh::emit_reference_format(stream, R, out.ref_bvh, out.ref_idx));
+        Leaves L;
+        MPT_LB(mark_leaves(R, n_spheres_hint, L));
+        MPT_LB(place_leaves(R, L));
+        MPT_LB(helper.join());                   // (the side stream has been GIVEN everything up to the material table)
+        MPT_LB(st.hand_over(side, stream, 1));   // (mat_of_prim)
+        hipLaunchKernelGGL(k_leaves, dim3(gnn), dim3(B), 0, stream, (int)n, leaf_max, R.range, L.is_leaf, L.leaf_id, R.vals, d_prims_in, mats.mat_of_prim, R.nlo, R.nhi, L.pfirst,
+                           out.prims, out.refleaf, L.olo, L.ohi, d_sc, L.use_always);
+        MPT_LB(st.hand_over(stream, side, 2));   // (the leaves)
+        MPT_LB(threaded_tree(R, L, out));
+        OwnTree T;
+        if (own_tree_refits(builder, R, L)) MPT_LB(own_tree_refit(R, L, T));
+        else MPT_LB(own_tree_sah(R, L, T));
+        MPT_LB(collapse(R, L, T, out));
+        hipLaunchKernelGGL(k_always, dim3(1), dim3(64), 0, stream, d_sc, out.prims, out.refleaf, out.always);
+        MPT_LB(hipGetLastError());
+        MPT_LB(st.hand_over(side, stream, 3));   // (the threaded tree and the leaf boxes)
+        return read_back(L, R.n_out, out, mat_collision);
+    }
+};
+static hipError_t build_pass(hipStream_t stream, float4* d_prims_in, float4* d_mats_in, const float* mats_host, uint32_t n, int leaf_max, int builder,
+                             uint32_t n_spheres_hint, Built& out, mpt_build::ScratchPool& pool, mpt_own::DevMem<>* spare, const mpt_build::Switches& env,
+                             bool wide_mat_sort, bool* mat_collision) {
+    return Pass(pool, env, n).run(stream, d_prims_in, d_mats_in, mats_host, leaf_max, builder, n_spheres_hint, out, spare, wide_mat_sort, mat_collision);
 }
 static hipError_t build(hipStream_t stream, float4* d_prims_in, float4* d_mats_in, const float* mats_host, uint32_t n, int leaf_max, int builder, uint32_t n_spheres_hint,
-                        Built& out, mpt_lbvh::ScratchPool* pool = nullptr, mpt_own::DevMem<>* spare = nullptr) {
+                        Built& out, mpt_build::ScratchPool& pool, mpt_own::DevMem<>* spare = nullptr) {
+    const mpt_build::Switches env;
     bool collision = false;
-    MPT_LB(build_pass(stream, d_prims_in, d_mats_in, mats_host, n, leaf_max, builder, n_spheres_hint, out, pool, spare, false, &collision));
+    MPT_LB(build_pass(stream, d_prims_in, d_mats_in, mats_host, n, leaf_max, builder, n_spheres_hint, out, pool, spare, env, false, &collision));
     if (!collision) return hipSuccess;
     // two different materials share the upper half of their hashes (one scene in ~2^33 / materials^2): once more, sorted on all 64 bits,
     // into the same block (freed on return if the pass fails before it takes it)
     mpt_own::DevMem<> block = std::move(out.block);
     out = Built{};
-    return build_pass(stream, d_prims_in, d_mats_in, nullptr, n, leaf_max, builder, n_spheres_hint, out, pool, &block, true, &collision);   // (the materials are on the device by now)
+    return build_pass(stream, d_prims_in, d_mats_in, nullptr, n, leaf_max, builder, n_spheres_hint, out, pool, &block, env, true, &collision);   // (the materials are on the device by now)
 }
 
 }  // namespace mpt_devbuild

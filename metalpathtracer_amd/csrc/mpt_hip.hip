@@ -319,7 +319,7 @@ struct mpt_ctx : SceneState {
     int ot_occ = 0;                  // MPT_OT_OCC: 5 / 6 forces an operating point, 0 = by scene size (ordered_point)
     bool tile_order_forced = false;  // MPT_TILE_ORDER was given
     uint32_t ot_stack_depth = 8;     // LDS stack entries per lane (MPT_OT_STACK); deeper entries spill to global memory
-    mpt_lbvh::ScratchPool build_pool;  // scratch chunks of the GPU builders, kept between builds (<= 2 GiB)
+    mpt_build::ScratchPool build_pool;  // scratch chunks of the GPU builders, kept between builds (<= 2 GiB)
     // the block of the built scene before is kept as the next build's (install_scene), so a rebuild allocates nothing
     DevMem<> spare_block;
     DevMem<> in_block;                 // device staging of mpt_build_and_upload's input arrays, kept between builds
@@ -1765,8 +1765,9 @@ static int build_and_upload_impl(mpt_ctx* ctx, const float* prims, const float* 
     const uint32_t n = (uint32_t)n_prims;
     // (whether the always list can be used decides the own boxes of the leaves that hold spheres.  The default builder counts the spheres on
     //  the device, in a kernel it runs anyway; a pass of the host over the 48 MB of 1 M primitives was 0.4 ms of the call)
+    const int builder = gpu_builder();
     uint32_t n_spheres = 0xFFFFFFFFu;
-    if (!(gpu_builder() == mpt_lbvh::BUILDER_SAH && n > 2)) {
+    if (!(builder == mpt_lbvh::BUILDER_SAH && n > 2)) {
         n_spheres = 0;
         for (uint32_t i = 0; i < n; ++i) n_spheres += (int)prims[12 * (size_t)i + 3] != 1 ? 1u : 0u;
     }
@@ -1786,7 +1787,7 @@ static int build_and_upload_impl(mpt_ctx* ctx, const float* prims, const float* 
     hipEventRecord(e0.get(), ctx->stream);
     mpt_devbuild::Built b;
     // (the materials are copied by the build itself, on its second stream, beside the tree build: mpt_devbuild.h build_pass)
-    hipError_t e = mpt_devbuild::build(ctx->stream, d_p, d_m, mats, n, leaf_max, gpu_builder(), n_spheres, b, &ctx->build_pool, &ctx->spare_block);
+    hipError_t e = mpt_devbuild::build(ctx->stream, d_p, d_m, mats, n, leaf_max, builder, n_spheres, b, ctx->build_pool, &ctx->spare_block);
     if (e == hipSuccess) e = hipEventRecord(e1.get(), ctx->stream);
     if (e == hipSuccess) e = hipEventSynchronize(e1.get());
     float ms = 0.0f;
@@ -2345,7 +2346,7 @@ extern "C" int mpt_build_bvh(mpt_ctx* ctx, const float* prims, uint64_t n_prims,
         HIPCHK(hipSetDevice(ctx->device));
         float ms = 0.0f;
         const int leaf_max = gpu_leaf_max(n_prims);
-        hipError_t e = mpt_lbvh::build(ctx->stream, prims, (uint32_t)n_prims, leaf_max, gpu_builder(), bvh_out, n_nodes_out, prim_idx_out, &ms, &ctx->build_pool);
+        hipError_t e = mpt_lbvh::build(ctx->stream, prims, (uint32_t)n_prims, leaf_max, gpu_builder(), bvh_out, n_nodes_out, prim_idx_out, &ms, ctx->build_pool);
         if (e != hipSuccess) return fail(ctx, MPT_ERR_HIP, std::string("GPU BVH build: ") + hipGetErrorString(e));
         if (device_ms_out) *device_ms_out = ms;
         return MPT_OK;

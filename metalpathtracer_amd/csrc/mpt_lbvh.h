@@ -16,17 +16,21 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <algorithm>
 #include <vector>
 
+#include "mpt_build_scratch.h"
 #include "mpt_own.h"
 #include "mpt_sah.h"
 
 #define MPT_LBVH_LEAF_MAX 8u   // what the reference's builder allows (R/Scene/Scene.h:223) and a device leaf record holds twice over
 
 namespace mpt_lbvh {
+using mpt_build::Scratch;
+using mpt_build::Scan;
+using mpt_build::PIN_N_SMALL;
+using mpt_build::PIN_W_SMALL;
 
 __device__ __forceinline__ int f2ord(float f) {  // order-preserving float -> int (for atomicMin / atomicMax)
     int i = __float_as_int(f);
@@ -568,203 +572,185 @@ struct Radix {
 
 // the output nodes of a finished tree: flags, compact index, count (one stream synchronisation for the count)
 static hipError_t finish_radix(hipStream_t stream, Scratch& sc, Radix& R, uint32_t* pin) {
-    const uint32_t n = R.n;
-    const int leaf_max = R.leaf_max;
-    const size_t nn = 2 * (size_t)n - 1;
-    const uint32_t B = 256, gnn = (uint32_t)((nn + B - 1) / B);
-    hipLaunchKernelGGL(k_mark, dim3(gnn), dim3(B), 0, stream, (int)n, leaf_max, (const int*)R.parent, (const int2*)R.range, R.keep);
-    size_t scan_bytes = 0;
-    MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, R.keep, R.index, (int)nn + 1, stream));
-    char* tmp2;
-    MPT_LB(sc.alloc(&tmp2, scan_bytes));
+    const size_t nn = 2 * (size_t)R.n - 1;
+    hipLaunchKernelGGL(k_mark, dim3((uint32_t)((nn + 255) / 256)), dim3(256), 0, stream, (int)R.n, R.leaf_max, R.parent, R.range, R.keep);
+    Scan scan;
+    MPT_LB(scan.reserve(sc, nn + 1, stream));
     MPT_LB(hipMemsetAsync(R.keep + nn, 0, 4, stream));
-    MPT_LB(hipcub::DeviceScan::ExclusiveSum(tmp2, scan_bytes, R.keep, R.index, (int)nn + 1, stream));
+    MPT_LB(scan.run(R.keep, R.index, nn + 1, stream));
     MPT_LB(hipGetLastError());
-    MPT_LB(hipMemcpyAsync(pin, R.index + nn, 4, hipMemcpyDeviceToHost, stream));
+    MPT_LB(hipMemcpyAsync(pin + PIN_W_SMALL, R.index + nn, 4, hipMemcpyDeviceToHost, stream));
     MPT_LB(hipStreamSynchronize(stream));
-    R.n_out = pin[0];
+    R.n_out = pin[PIN_W_SMALL];
     return hipSuccess;
+}
+
+// what the three builders of build_radix share beside R's arrays
+struct RadixWork {
+    hipStream_t stream;
+    uint32_t* pin;        // the tree build's part of the pinned block
+    uint32_t n, gn, gnn;  // primitives; grids of 256 threads over n and over the 2n - 1 node ids
+    size_t nn;
+    int* arrived;
+    unsigned long long *keys, *keys2;   // Morton codes, and sorted
+    uint32_t *vals0, *vals_sorted;      // primitive ids beside them
+};
+// builder "sah" (n > 2): top-down binned SAH over the primitives (mpt_sah.h), then renumbered like the clustering's tree
+static hipError_t radix_top_down(Scratch& sc, const RadixWork& W, bool keep_spheres, Radix& R) {
+    const hipStream_t stream = W.stream;
+    const uint32_t n = W.n, B = 256, gn = W.gn, gnn = W.gnn;
+    const size_t nn = W.nn;
+    float4 *it_lo, *it_hi, *nlo0, *nhi0;
+    int2* child0;
+    int* parent0;
+    uint32_t *size, *first;
+    uint32_t *flag, *rank, *sph, *first_inner, *first_item;
+    HoistState* hoist;
+    MPT_LB(sc.allocs(n, &it_lo, &it_hi, &child0, &first_inner));
+    MPT_LB(sc.allocs(nn, &parent0, &nlo0, &nhi0, &size, &first, &first_item));
+    MPT_LB(sc.alloc(&flag, (size_t)n + 1));
+    MPT_LB(sc.alloc(&rank, (size_t)n + 2));   // (+ 1 word behind the scan's output: the sphere count, k_tri_flags)
+    MPT_LB(sc.alloc(&sph, MPT_LBVH_HOIST_MAX));
+    MPT_LB(sc.alloc(&hoist, 1));
+    MPT_LB(hipMemsetAsync(hoist, 0, sizeof(HoistState), stream));
+    hipLaunchKernelGGL(k_hoist_hist, dim3(std::min(gn, 512u)), dim3(B), 0, stream, (int)n, R.prims, R.blo, R.bhi, hoist);
+    hipLaunchKernelGGL(k_hoist_median, dim3(1), dim3(64), 0, stream, (int)n, hoist);
+    hipLaunchKernelGGL(k_tri_flags, dim3((n + 1 + B - 1) / B), dim3(B), 0, stream, (int)n, R.prims, R.blo, R.bhi, hoist, flag, rank + n + 1);
+    MPT_LB(Scan::once(sc, flag, rank, (size_t)n + 1, stream));
+    MPT_LB(hipMemcpyAsync(W.pin + PIN_W_SMALL, rank + n, 8, hipMemcpyDeviceToHost, stream));
+    MPT_LB(hipStreamSynchronize(stream));
+    const uint32_t nt = W.pin[PIN_W_SMALL], ns = n - nt;   // items that stay in the SAH / that would hang under the root
+    R.n_spheres = W.pin[PIN_W_SMALL + 1u];
+    mpt_sah::SahTree T;
+    T.first = mpt_sah::SahFirst{first_inner, first_item};
+    // the hoisting decision: a few spheres (and huge triangles) among at least three other items hang under the root, the SAH sees the rest
+    if (ns >= 1u && ns <= MPT_LBVH_HOIST_MAX && nt >= 3u && !keep_spheres) {
+        R.spheres_hoisted = true;
+        R.n_hoisted = ns;
+        hipLaunchKernelGGL(k_prim_items_hoisted, dim3(gn), dim3(B), 0, stream, (int)n, R.blo, R.bhi, flag, rank, it_lo, it_hi, W.vals0, sph);
+        MPT_LB(mpt_sah::run_sah(stream, sc, W.pin, (int)nn, nullptr, nt, nt, it_lo, it_hi, T));
+        hipLaunchKernelGGL(k_sah_to_radix_hoisted, dim3(gnn), dim3(B), 0, stream, (int)n, (int)ns, T.child, T.lo, T.hi, R.blo, R.bhi, sph, flag, rank, first_inner, first_item,
+                           child0, parent0, size, nlo0, nhi0, first);
+    } else {
+        hipLaunchKernelGGL(k_prim_items, dim3(gn), dim3(B), 0, stream, (int)n, R.blo, R.bhi, it_lo, it_hi, W.vals0);
+        MPT_LB(mpt_sah::run_sah(stream, sc, W.pin, (int)nn, nullptr, n, n, it_lo, it_hi, T));
+        hipLaunchKernelGGL(k_sah_to_radix, dim3(gnn), dim3(B), 0, stream, (int)n, T.child, T.lo, T.hi, R.blo, R.bhi, first_inner, first_item, child0, parent0, size, nlo0, nhi0,
+                           first);
+    }
+    hipLaunchKernelGGL(k_ploc_renumber<true>, dim3(gnn), dim3(B), 0, stream, (int)n, child0, parent0, size, first, nlo0, nhi0, W.vals0, R.child, R.parent, R.range, R.nlo, R.nhi,
+                       R.vals);
+    return hipGetLastError();
+}
+// builders "ploc" and "lbvh" start from the primitives sorted by the 63-bit Morton codes of their centroids
+static hipError_t radix_morton_sort(Scratch& sc, const RadixWork& W, const Radix& R) {
+    hipLaunchKernelGGL(k_morton, dim3(W.gn), dim3(256), 0, W.stream, R.blo, R.bhi, W.n, R.cb, W.keys, W.vals0);
+    size_t tmp_bytes = 0;
+    MPT_LB(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, W.keys, W.keys2, W.vals0, W.vals_sorted, (int)W.n, 0, 63, W.stream));
+    char* tmp;
+    MPT_LB(sc.alloc(&tmp, tmp_bytes));
+    return hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, W.keys, W.keys2, W.vals0, W.vals_sorted, (int)W.n, 0, 63, W.stream);
+}
+// builder "ploc" (n > 2), over the sorted Morton codes: clustering on scratch arrays in creation order, then the renumbered tree into R's arrays
+static hipError_t radix_ploc(Scratch& sc, const RadixWork& W, Radix& R) {
+    const hipStream_t stream = W.stream;
+    const uint32_t n = W.n, B = 256, gn = W.gn, gnn = W.gnn;
+    const size_t nn = W.nn;
+    int2* child0;
+    int* parent0;
+    float4 *nlo0, *nhi0;
+    uint32_t *C0, *C1, *size, *nn_, *merged, *valid, *mslot, *vpos, *first;
+    PlocState* st;
+    MPT_LB(sc.allocs(n, &child0, &C0, &C1, &nn_, &merged, &valid, &mslot, &vpos));
+    MPT_LB(sc.allocs(nn, &parent0, &nlo0, &nhi0, &size, &first));
+    MPT_LB(sc.alloc(&st, 1));
+    Scan scan;   // (both scans of a round, one after the other)
+    MPT_LB(scan.reserve(sc, n, stream));
+    hipLaunchKernelGGL(k_ploc_init, dim3(gn), dim3(B), 0, stream, (int)n, W.vals_sorted, R.blo, R.bhi, C0, size, nlo0, nhi0, parent0, st);
+    uint32_t alive = n;          // upper bound of the clusters alive (the exact count lives on the device)
+    for (int round = 0; round < 4096 && alive > 1u; ++round) {
+        const uint32_t g = (alive + B - 1) / B;
+        hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(B), 0, stream, st, C0, nlo0, nhi0, nn_);
+        hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(B), 0, stream, st, nn_, merged, valid);
+        MPT_LB(scan.run(merged, mslot, alive, stream));
+        MPT_LB(scan.run(valid, vpos, alive, stream));
+        hipLaunchKernelGGL(k_ploc_merge, dim3(g), dim3(B), 0, stream, st, C0, nn_, merged, valid, mslot, vpos, (int)n, C1, child0, parent0, size, nlo0, nhi0);
+        hipLaunchKernelGGL(k_ploc_advance, dim3(1), dim3(64), 0, stream, st, merged, mslot, valid, vpos);
+        std::swap(C0, C1);
+        // every round merges at least one pair; in practice the count falls by ~40 %: read it back every few rounds
+        if ((round & 3) == 3 || alive <= 4096u) {
+            static_assert(sizeof(PlocState) <= 4u * PIN_N_SMALL, "PlocState must fit the small read-back words");
+            PlocState& h = *(PlocState*)(W.pin + PIN_W_SMALL);
+            MPT_LB(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, stream));
+            MPT_LB(hipStreamSynchronize(stream));
+            alive = h.n_clusters;
+        }
+    }
+    if (alive != 1u) return hipErrorUnknown;
+    hipLaunchKernelGGL(k_ploc_first, dim3(gnn), dim3(B), 0, stream, (int)n, child0, parent0, size, first);
+    hipLaunchKernelGGL(k_ploc_renumber<false>, dim3(gnn), dim3(B), 0, stream, (int)n, child0, parent0, size, first, nlo0, nhi0, W.vals_sorted, R.child, R.parent, R.range, R.nlo,
+                       R.nhi, R.vals);
+    return hipGetLastError();
+}
+// builder "lbvh" (and every builder's tree of one or two primitives), over the sorted Morton codes: Karras' hierarchy and a bottom-up refit
+static hipError_t radix_karras(const RadixWork& W, Radix& R) {
+    const hipStream_t stream = W.stream;
+    const uint32_t n = W.n, B = 256;
+    MPT_LB(hipMemcpyAsync(R.vals, W.vals_sorted, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
+    if (n > 1) {
+        hipLaunchKernelGGL(k_hierarchy, dim3(W.gn), dim3(B), 0, stream, (const unsigned long long*)W.keys2, (int)n, R.child, R.parent, R.range);
+    } else {   // (the lone primitive: a tree of one node without a parent)
+        const int minus1 = -1;
+        MPT_LB(hipMemcpyAsync(R.parent, &minus1, 4, hipMemcpyHostToDevice, stream));
+    }
+    hipLaunchKernelGGL(k_refit, dim3(W.gn), dim3(B), 0, stream, R.vals, R.blo, R.bhi, (int)n, R.child, R.parent, R.nlo, R.nhi, W.arrived);
+    return hipGetLastError();
 }
 
 // d_prims: device, 3 float4 per primitive.  Leaves everything of Radix on the device; synchronises the stream once to
 // read the output node count (and once per round / level of the clustering or the SAH).
 enum { BUILDER_KARRAS = 0, BUILDER_PLOC = 1, BUILDER_SAH = 2 };
-static hipError_t build_radix(hipStream_t stream, Scratch& sc, float4* d_prims, uint32_t n, int leaf_max, int builder, Radix& R) {
-    int *arrived;
-    unsigned long long *keys, *keys2;
-    uint32_t *vals0, *vals_sorted;
-    PinnedWords pinned;   // the few words read back per round go through pinned memory (a pageable target costs ~0.3 ms per copy)
-    MPT_LB(pinned.get(sc.pool, 1));   // (words 64.. : the level slots of mpt_sah::run_sah)
+static hipError_t build_radix(hipStream_t stream, Scratch& sc, float4* d_prims, uint32_t n, int leaf_max, int builder, const mpt_build::Switches& env, Radix& R) {
     const size_t nn = 2 * (size_t)n - 1;
+    const uint32_t B = 256;
+    RadixWork W = {stream, nullptr, n, (n + B - 1) / B, (uint32_t)((nn + B - 1) / B), nn, nullptr, nullptr, nullptr, nullptr, nullptr};
+    MPT_LB(sc.pool.pinned(mpt_build::PIN_PART_TREE, &W.pin));
     R.n = n;
     R.leaf_max = leaf_max;
     R.prims = d_prims;
-    MPT_LB(sc.alloc(&R.blo, n));
-    MPT_LB(sc.alloc(&R.bhi, n));
-    MPT_LB(sc.alloc(&R.nlo, nn));
-    MPT_LB(sc.alloc(&R.nhi, nn));
+    MPT_LB(sc.allocs(n, &R.blo, &R.bhi, &W.arrived, &R.child, &R.range, &W.keys, &W.keys2, &W.vals0, &R.vals, &W.vals_sorted));
+    MPT_LB(sc.allocs(nn, &R.nlo, &R.nhi, &R.parent));
+    MPT_LB(sc.allocs(nn + 1, &R.keep, &R.index));
     MPT_LB(sc.alloc(&R.cb, 6));
-    MPT_LB(sc.alloc(&R.parent, nn));
-    MPT_LB(sc.alloc(&arrived, n));
-    MPT_LB(sc.alloc(&R.child, n));
-    MPT_LB(sc.alloc(&R.range, n));
-    MPT_LB(sc.alloc(&keys, n));
-    MPT_LB(sc.alloc(&keys2, n));
-    MPT_LB(sc.alloc(&vals0, n));
-    MPT_LB(sc.alloc(&R.vals, n));
-    MPT_LB(sc.alloc(&vals_sorted, n));
-    MPT_LB(sc.alloc(&R.keep, nn + 1));
-    MPT_LB(sc.alloc(&R.index, nn + 1));
-    const int init[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
     const bool top_down = n > 2 && builder == BUILDER_SAH;   // (needs neither the bounds of the centroids nor the refit's arrival counters)
+    const int init[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, (int)0x80000000, (int)0x80000000, (int)0x80000000};
     if (!top_down) {
         MPT_LB(hipMemcpyAsync(R.cb, init, sizeof init, hipMemcpyHostToDevice, stream));
-        MPT_LB(hipMemsetAsync(arrived, 0, (size_t)n * 4, stream));
+        MPT_LB(hipMemsetAsync(W.arrived, 0, (size_t)n * 4, stream));
     }
-    const uint32_t B = 256, gn = (n + B - 1) / B, gnn = (uint32_t)((nn + B - 1) / B);
-    hipLaunchKernelGGL(k_boxes, dim3(gn), dim3(B), 0, stream, (const float4*)d_prims, n, R.blo, R.bhi, top_down ? (int*)nullptr : R.cb);
+    hipLaunchKernelGGL(k_boxes, dim3(W.gn), dim3(B), 0, stream, d_prims, n, R.blo, R.bhi, top_down ? (int*)nullptr : R.cb);
     if (top_down) {
-        // top-down binned SAH over the primitives (mpt_sah.h), then renumbered like the clustering's tree
-        float4 *it_lo, *it_hi, *nlo0, *nhi0;
-        int2* child0;
-        int* parent0;
-        uint32_t *size, *first;
-        MPT_LB(sc.alloc(&it_lo, n));
-        MPT_LB(sc.alloc(&it_hi, n));
-        MPT_LB(sc.alloc(&child0, n));
-        MPT_LB(sc.alloc(&parent0, nn));
-        MPT_LB(sc.alloc(&nlo0, nn));
-        MPT_LB(sc.alloc(&nhi0, nn));
-        MPT_LB(sc.alloc(&size, nn));
-        MPT_LB(sc.alloc(&first, nn));
-        uint32_t *flag, *rank, *sph;
-        HoistState* hoist;
-        MPT_LB(sc.alloc(&flag, (size_t)n + 1));
-        MPT_LB(sc.alloc(&rank, (size_t)n + 2));   // (+ 1 word behind the scan's output: the sphere count, k_tri_flags)
-        MPT_LB(sc.alloc(&sph, MPT_LBVH_HOIST_MAX));
-        MPT_LB(sc.alloc(&hoist, 1));
-        MPT_LB(hipMemsetAsync(hoist, 0, sizeof(HoistState), stream));
-        hipLaunchKernelGGL(k_hoist_hist, dim3(std::min(gn, 512u)), dim3(B), 0, stream, (int)n, (const float4*)d_prims, (const float4*)R.blo, (const float4*)R.bhi, hoist);
-        hipLaunchKernelGGL(k_hoist_median, dim3(1), dim3(64), 0, stream, (int)n, hoist);
-        hipLaunchKernelGGL(k_tri_flags, dim3((n + 1 + B - 1) / B), dim3(B), 0, stream, (int)n, (const float4*)d_prims, (const float4*)R.blo, (const float4*)R.bhi, hoist,
-                           flag, rank + n + 1);
-        {
-            size_t sb = 0;
-            MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, flag, rank, (int)n + 1, stream));
-            char* stmp;
-            MPT_LB(sc.alloc(&stmp, sb));
-            MPT_LB(hipcub::DeviceScan::ExclusiveSum(stmp, sb, flag, rank, (int)n + 1, stream));
-        }
-        MPT_LB(hipMemcpyAsync(pinned.p, rank + n, 8, hipMemcpyDeviceToHost, stream));
-        MPT_LB(hipStreamSynchronize(stream));
-        const uint32_t nt = pinned.p[0], ns = n - nt;
-        R.n_spheres = pinned.p[1];
-        mpt_sah::SahTree T;
-        uint32_t *first_inner, *first_item;
-        MPT_LB(sc.alloc(&first_inner, n));
-        MPT_LB(sc.alloc(&first_item, nn));
-        T.first = mpt_sah::SahFirst{first_inner, first_item};
-        if (ns >= 1u && ns <= MPT_LBVH_HOIST_MAX && nt >= 3u && getenv("MPT_SAH_KEEP_SPHERES") == nullptr) {
-            R.spheres_hoisted = true;
-            R.n_hoisted = ns;
-            hipLaunchKernelGGL(k_prim_items_hoisted, dim3(gn), dim3(B), 0, stream, (int)n, (const float4*)R.blo, (const float4*)R.bhi, (const uint32_t*)flag,
-                               (const uint32_t*)rank, it_lo, it_hi, vals0, sph);
-            MPT_LB(mpt_sah::run_sah(stream, sc, pinned.p, (int)nn, nullptr, nt, nt, it_lo, it_hi, T));
-            hipLaunchKernelGGL(k_sah_to_radix_hoisted, dim3(gnn), dim3(B), 0, stream, (int)n, (int)ns, (const int2*)T.child, (const float4*)T.lo, (const float4*)T.hi,
-                               (const float4*)R.blo, (const float4*)R.bhi, (const uint32_t*)sph, (const uint32_t*)flag, (const uint32_t*)rank, (const uint32_t*)first_inner,
-                               (const uint32_t*)first_item, child0, parent0, size, nlo0, nhi0, first);
-        } else {
-            hipLaunchKernelGGL(k_prim_items, dim3(gn), dim3(B), 0, stream, (int)n, (const float4*)R.blo, (const float4*)R.bhi, it_lo, it_hi, vals0);
-            MPT_LB(mpt_sah::run_sah(stream, sc, pinned.p, (int)nn, nullptr, n, n, it_lo, it_hi, T));
-            hipLaunchKernelGGL(k_sah_to_radix, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)T.child, (const float4*)T.lo, (const float4*)T.hi, (const float4*)R.blo,
-                               (const float4*)R.bhi, (const uint32_t*)first_inner, (const uint32_t*)first_item, child0, parent0, size, nlo0, nhi0, first);
-        }
-        hipLaunchKernelGGL(k_ploc_renumber<true>, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)child0, (const int*)parent0, (const uint32_t*)size,
-                           (const uint32_t*)first, (const float4*)nlo0, (const float4*)nhi0, (const uint32_t*)vals0, R.child, R.parent, R.range, R.nlo, R.nhi, R.vals);
-        return finish_radix(stream, sc, R, pinned.p);
-    }
-    hipLaunchKernelGGL(k_morton, dim3(gn), dim3(B), 0, stream, (const float4*)R.blo, (const float4*)R.bhi, n, (const int*)R.cb, keys, vals0);
-    size_t tmp_bytes = 0;
-    MPT_LB(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, vals0, vals_sorted, (int)n, 0, 63, stream));
-    char* tmp;
-    MPT_LB(sc.alloc(&tmp, tmp_bytes));
-    MPT_LB(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys2, vals0, vals_sorted, (int)n, 0, 63, stream));
-    if (n > 2 && builder == BUILDER_PLOC) {
-        // clustering on scratch arrays in creation order, then the renumbered tree into R's arrays
-        int2 *child0;
-        int *parent0;
-        float4 *nlo0, *nhi0;
-        uint32_t *C0, *C1, *size, *nn_, *merged, *valid, *mslot, *vpos, *first;
-        PlocState* st;
-        MPT_LB(sc.alloc(&child0, n));
-        MPT_LB(sc.alloc(&parent0, nn));
-        MPT_LB(sc.alloc(&nlo0, nn));
-        MPT_LB(sc.alloc(&nhi0, nn));
-        MPT_LB(sc.alloc(&C0, n));
-        MPT_LB(sc.alloc(&C1, n));
-        MPT_LB(sc.alloc(&size, nn));
-        MPT_LB(sc.alloc(&nn_, n));
-        MPT_LB(sc.alloc(&merged, n));
-        MPT_LB(sc.alloc(&valid, n));
-        MPT_LB(sc.alloc(&mslot, n));
-        MPT_LB(sc.alloc(&vpos, n));
-        MPT_LB(sc.alloc(&first, nn));
-        MPT_LB(sc.alloc(&st, 1));
-        size_t sb = 0;
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, sb, merged, mslot, (int)n, stream));
-        char* stmp;
-        MPT_LB(sc.alloc(&stmp, sb));
-        hipLaunchKernelGGL(k_ploc_init, dim3(gn), dim3(B), 0, stream, (int)n, (const uint32_t*)vals_sorted, (const float4*)R.blo, (const float4*)R.bhi, C0, size,
-                           nlo0, nhi0, parent0, st);
-        uint32_t alive = n;          // upper bound of the clusters alive (the exact count lives on the device)
-        for (int round = 0; round < 4096 && alive > 1u; ++round) {
-            const uint32_t g = (alive + B - 1) / B;
-            hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(B), 0, stream, (const PlocState*)st, (const uint32_t*)C0, (const float4*)nlo0, (const float4*)nhi0, nn_);
-            hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(B), 0, stream, (const PlocState*)st, (const uint32_t*)nn_, merged, valid);
-            MPT_LB(hipcub::DeviceScan::ExclusiveSum(stmp, sb, merged, mslot, (int)alive, stream));
-            MPT_LB(hipcub::DeviceScan::ExclusiveSum(stmp, sb, valid, vpos, (int)alive, stream));
-            hipLaunchKernelGGL(k_ploc_merge, dim3(g), dim3(B), 0, stream, st, (const uint32_t*)C0, (const uint32_t*)nn_, (const uint32_t*)merged, (const uint32_t*)valid,
-                               (const uint32_t*)mslot, (const uint32_t*)vpos, (int)n, C1, child0, parent0, size, nlo0, nhi0);
-            hipLaunchKernelGGL(k_ploc_advance, dim3(1), dim3(64), 0, stream, st, (const uint32_t*)merged, (const uint32_t*)mslot, (const uint32_t*)valid, (const uint32_t*)vpos);
-            std::swap(C0, C1);
-            // every round merges at least one pair; in practice the count falls by ~40 %: read it back every few rounds
-            if ((round & 3) == 3 || alive <= 4096u) {
-                PlocState& h = *(PlocState*)pinned.p;
-                MPT_LB(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, stream));
-                MPT_LB(hipStreamSynchronize(stream));
-                alive = h.n_clusters;
-            }
-        }
-        if (alive != 1u) return hipErrorUnknown;
-        hipLaunchKernelGGL(k_ploc_first, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)child0, (const int*)parent0, (const uint32_t*)size, first);
-        hipLaunchKernelGGL(k_ploc_renumber<false>, dim3(gnn), dim3(B), 0, stream, (int)n, (const int2*)child0, (const int*)parent0, (const uint32_t*)size, (const uint32_t*)first,
-                           (const float4*)nlo0, (const float4*)nhi0, (const uint32_t*)vals_sorted, R.child, R.parent, R.range, R.nlo, R.nhi, R.vals);
+        MPT_LB(radix_top_down(sc, W, env.keep_spheres, R));
     } else {
-        MPT_LB(hipMemcpyAsync(R.vals, vals_sorted, (size_t)n * 4, hipMemcpyDeviceToDevice, stream));
-        if (n > 1) {
-            hipLaunchKernelGGL(k_hierarchy, dim3(gn), dim3(B), 0, stream, (const unsigned long long*)keys2, (int)n, R.child, R.parent, R.range);
-        } else {
-            const int minus1 = -1;
-            MPT_LB(hipMemcpyAsync(R.parent, &minus1, 4, hipMemcpyHostToDevice, stream));
-        }
-        hipLaunchKernelGGL(k_refit, dim3(gn), dim3(B), 0, stream, (const uint32_t*)R.vals, (const float4*)R.blo, (const float4*)R.bhi, (int)n,
-                           (const int2*)R.child, (const int*)R.parent, R.nlo, R.nhi, arrived);
+        MPT_LB(radix_morton_sort(sc, W, R));
+        if (n > 2 && builder == BUILDER_PLOC) MPT_LB(radix_ploc(sc, W, R));
+        else MPT_LB(radix_karras(W, R));
     }
-    return finish_radix(stream, sc, R, pinned.p);
+    return finish_radix(stream, sc, R, W.pin);
 }
 
 // the output tree in the reference's buffer format, on the device: d_bvh (2 float4 per output node), d_idx (n ints)
 static hipError_t emit_reference_format(hipStream_t stream, const Radix& R, float4* d_bvh, int* d_idx) {
     const size_t nn = 2 * (size_t)R.n - 1;
-    hipLaunchKernelGGL(k_emit, dim3((uint32_t)((nn + 255) / 256)), dim3(256), 0, stream, (int)R.n, R.leaf_max, (const int2*)R.child, (const int2*)R.range,
-                       (const uint32_t*)R.keep, (const uint32_t*)R.index, (const float4*)R.nlo, (const float4*)R.nhi, (const uint32_t*)R.vals, d_bvh, d_idx);
+    hipLaunchKernelGGL(k_emit, dim3((uint32_t)((nn + 255) / 256)), dim3(256), 0, stream, (int)R.n, R.leaf_max, R.child, R.range, R.keep, R.index, R.nlo, R.nhi, R.vals, d_bvh,
+                       d_idx);
     return hipGetLastError();
 }
 
 // prims: host, 12 floats per primitive (Scene::createTransformsBuffer).  bvh_out: host, room for 8 * (2n - 1) floats;
 // prim_idx_out: host, n ints.  Returns hipSuccess and the node count, or the failing HIP status.
 static hipError_t build(hipStream_t stream, const float* prims, uint32_t n, int leaf_max, int builder, float* bvh_out, uint64_t* n_nodes_out,
-                        int32_t* prim_idx_out, float* ms_out, ScratchPool* pool = nullptr) {
+                        int32_t* prim_idx_out, float* ms_out, mpt_build::ScratchPool& pool) {
+    const mpt_build::Switches env;
     Scratch sc(pool);
     MPT_LB(sc.reserve((size_t)n * 560 + ((size_t)8 << 20)));
     float4 *d_prims, *d_bvh;
@@ -778,7 +764,7 @@ static hipError_t build(hipStream_t stream, const float* prims, uint32_t n, int 
     MPT_LB(e1.create(hipEventCreate));
     MPT_LB(hipEventRecord(e0.get(), stream));
     Radix R;
-    MPT_LB(build_radix(stream, sc, d_prims, n, leaf_max, builder, R));
+    MPT_LB(build_radix(stream, sc, d_prims, n, leaf_max, builder, env, R));
     MPT_LB(emit_reference_format(stream, R, d_bvh, d_idx));
     MPT_LB(hipEventRecord(e1.get(), stream));
     MPT_LB(hipStreamSynchronize(stream));

@@ -14,7 +14,7 @@
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
-#include "mpt_sah.h"   // mpt_lbvh::Scratch, MPT_LB
+#include "mpt_build_scratch.h"
 
 namespace mpt_radix {
 #define MPT_RADIX_TILE 1024u   // items per wave
@@ -82,18 +82,15 @@ __global__ __launch_bounds__(64 * MPT_RADIX_WAVES) void k_radix_scatter(const ui
 
 struct RadixTemp {
     uint32_t *counts = nullptr, *first = nullptr;
-    char* scan_tmp = nullptr;
-    size_t scan_bytes = 0;
+    mpt_build::Scan scan;
     uint32_t tiles = 0;
 };
-static hipError_t radix_reserve(mpt_lbvh::Scratch& sc, uint32_t n, hipStream_t stream, RadixTemp& T) {
+static hipError_t radix_reserve(mpt_build::Scratch& sc, uint32_t n, hipStream_t stream, RadixTemp& T) {
     T.tiles = (n + MPT_RADIX_TILE - 1u) / MPT_RADIX_TILE;
     const size_t m = (size_t)256 * T.tiles;
     MPT_LB(sc.alloc(&T.counts, m));
     MPT_LB(sc.alloc(&T.first, m));
-    MPT_LB(hipcub::DeviceScan::ExclusiveSum(nullptr, T.scan_bytes, T.counts, T.first, (int)m, stream));
-    MPT_LB(sc.alloc(&T.scan_tmp, T.scan_bytes));
-    return hipSuccess;
+    return T.scan.reserve(sc, m, stream);
 }
 // Sorts on key bits [0, 8 * passes).  The pairs ping-pong between (keys, vals) and (keys2, vals2); *in_second tells where they ended.
 static hipError_t radix_sort_pairs(hipStream_t stream, const RadixTemp& T, uint32_t* keys, uint32_t* vals, uint32_t* keys2, uint32_t* vals2, uint32_t n, int passes,
@@ -102,11 +99,9 @@ static hipError_t radix_sort_pairs(hipStream_t stream, const RadixTemp& T, uint3
     bool second = false;
     for (int p = 0; p < passes; ++p) {
         uint32_t *ki = second ? keys2 : keys, *vi = second ? vals2 : vals, *ko = second ? keys : keys2, *vo = second ? vals : vals2;
-        hipLaunchKernelGGL(k_radix_count, dim3(g), dim3(64 * MPT_RADIX_WAVES), 0, stream, (const uint32_t*)ki, n, 8u * (uint32_t)p, T.tiles, T.counts);
-        size_t sb = T.scan_bytes;
-        MPT_LB(hipcub::DeviceScan::ExclusiveSum(T.scan_tmp, sb, T.counts, T.first, (int)(256u * T.tiles), stream));
-        hipLaunchKernelGGL(k_radix_scatter, dim3(g), dim3(64 * MPT_RADIX_WAVES), 0, stream, (const uint32_t*)ki, (const uint32_t*)vi, n, 8u * (uint32_t)p, T.tiles,
-                           (const uint32_t*)T.first, ko, vo);
+        hipLaunchKernelGGL(k_radix_count, dim3(g), dim3(64 * MPT_RADIX_WAVES), 0, stream, ki, n, 8u * (uint32_t)p, T.tiles, T.counts);
+        MPT_LB(T.scan.run(T.counts, T.first, (size_t)256 * T.tiles, stream));
+        hipLaunchKernelGGL(k_radix_scatter, dim3(g), dim3(64 * MPT_RADIX_WAVES), 0, stream, ki, vi, n, 8u * (uint32_t)p, T.tiles, T.first, ko, vo);
         second = !second;
     }
     *in_second = second;

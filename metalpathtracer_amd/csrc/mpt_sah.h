@@ -11,129 +11,11 @@
 
 #include <algorithm>
 #include <utility>
-#include <chrono>
-#include <vector>
 
-namespace mpt_lbvh {
-// Scratch memory of a build: a bump allocator over a few large chunks (a build makes ~90 arrays; one hipMalloc each cost a
-// third of the 1 M-primitive build), freed — or handed back to the pool they came from — on every exit path.  A ScratchPool
-// (one per context) keeps the chunks between builds: a rebuild allocates nothing.
-struct ScratchPool {
-    std::vector<std::pair<void*, size_t>> chunks;
-    size_t keep_bytes = (size_t)2 << 30;   // what stays allocated between builds at most
-    uint32_t* pin = nullptr;               // 2 KiB of pinned host memory for the builders' read-backs (hipHostMalloc per build: ~0.1 ms each)
-    hipStream_t side = nullptr;            // a second stream for the chains of a build that need nothing of one another (mpt_devbuild.h) ...
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // ... and the events that fork and join it
-    ~ScratchPool() { release(); }
-    void release() {
-        for (auto& c : chunks) hipFree(c.first);
-        chunks.clear();
-        if (pin) hipHostFree(pin);
-        pin = nullptr;
-        if (side) hipStreamDestroy(side);
-        side = nullptr;
-        for (auto& e : ev) {
-            if (e) hipEventDestroy(e);
-            e = nullptr;
-        }
-    }
-    hipError_t side_stream(hipStream_t* out) {
-        if (!side) {
-            hipError_t e = hipStreamCreateWithFlags(&side, hipStreamNonBlocking);
-            if (e != hipSuccess) return e;
-            for (auto& v : ev)
-                if ((e = hipEventCreateWithFlags(&v, hipEventDisableTiming)) != hipSuccess) return e;
-        }
-        *out = side;
-        return hipSuccess;
-    }
-};
-// 1 KiB of pinned host memory for one builder's read-backs: part `which` (0 / 1) of the pool's block, or the builder's own for the call
-struct PinnedWords {
-    uint32_t* p = nullptr;
-    bool own = false;
-    PinnedWords() = default;
-    PinnedWords(const PinnedWords&) = delete;
-    PinnedWords& operator=(const PinnedWords&) = delete;
-    ~PinnedWords() { if (own && p) hipHostFree(p); }
-    hipError_t get(ScratchPool* pool, int which) {
-        if (pool) {
-            if (!pool->pin) {
-                const hipError_t e = hipHostMalloc((void**)&pool->pin, 2048, hipHostMallocDefault);
-                if (e != hipSuccess) return e;
-            }
-            p = pool->pin + 256 * which;
-            return hipSuccess;
-        }
-        own = true;
-        return hipHostMalloc((void**)&p, 1024, hipHostMallocDefault);
-    }
-};
-struct Scratch {
-    ScratchPool* pool;
-    std::vector<std::pair<void*, size_t>> mine;
-    size_t off = 0;   // in the last chunk of mine
-    explicit Scratch(ScratchPool* p = nullptr) : pool(p) {}
-    Scratch(const Scratch&) = delete;
-    Scratch& operator=(const Scratch&) = delete;
-    ~Scratch() {
-        size_t kept = 0;
-        if (pool)
-            for (auto& c : pool->chunks) kept += c.second;
-        for (auto& c : mine) {
-            if (pool && kept + c.second <= pool->keep_bytes) {
-                pool->chunks.push_back(c);
-                kept += c.second;
-            } else {
-                hipFree(c.first);
-            }
-        }
-    }
-    // a chunk of at least `bytes` becomes the current one: the pool's smallest that fits, else a new allocation
-    hipError_t chunk(size_t bytes) {
-        if (pool) {
-            int best = -1;
-            for (int i = 0; i < (int)pool->chunks.size(); ++i)
-                if (pool->chunks[i].second >= bytes && (best < 0 || pool->chunks[i].second < pool->chunks[best].second)) best = i;
-            if (best >= 0) {
-                mine.push_back(pool->chunks[best]);
-                pool->chunks.erase(pool->chunks.begin() + best);
-                off = 0;
-                return hipSuccess;
-            }
-        }
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes);
-        if (e != hipSuccess) return e;
-        mine.emplace_back(q, bytes);
-        off = 0;
-        return hipSuccess;
-    }
-    // (call once with an estimate of everything the build will ask for: one chunk instead of several)
-    hipError_t reserve(size_t bytes) { return chunk(std::max<size_t>(bytes, (size_t)1 << 20)); }
-    template <class T>
-    hipError_t alloc(T** p, size_t count) {
-        const size_t bytes = (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
-        if (mine.empty() || off + bytes > mine.back().second) {
-            *p = nullptr;
-            hipError_t e = chunk(std::max<size_t>(bytes, (size_t)64 << 20));
-            if (e != hipSuccess) return e;
-        }
-        *p = (T*)((char*)mine.back().first + off);
-        off += bytes;
-        return hipSuccess;
-    }
-};
-
-#define MPT_LB(call)                       \
-    do {                                   \
-        hipError_t e_ = (call);            \
-        if (e_ != hipSuccess) return e_;   \
-    } while (0)
-}  // namespace mpt_lbvh
+#include "mpt_build_scratch.h"
 
 namespace mpt_sah {
-using mpt_lbvh::Scratch;
+using mpt_build::Scratch;
 
 // Item record, 32 bytes, moved along by every partition (the passes stream it, nothing is looked up through an index):
 //   lo = (box min, bits(id))   hi = (box max, bits(primitives in the item))
@@ -983,7 +865,7 @@ struct SahTree {
     SahFirst first = {nullptr, nullptr};   // (in: arrays the caller wants filled — SahFirst above)
 };
 // it_lo / it_hi: the items (device, consumed: the partitions ping-pong between them and two scratch arrays).  The item count
-// is *d_count if d_count is not null (a device word), else count_host; max_items bounds it.  pin: >= 1 KiB of pinned host memory.
+// is *d_count if d_count is not null (a device word), else count_host; max_items bounds it.  pin: the caller's part of the pinned block (mpt_build_scratch.h).
 //
 // No host wait inside the level loop (round 4; round 3 synchronised the stream once per level to read three counters: ~22 idle
 // gaps of 30-40 us for 1 M items).  The kernels of a level read their task counts from the device (SahState::cnt, sah_level_prologue) and
@@ -996,54 +878,30 @@ static hipError_t run_sah(hipStream_t stream, Scratch& sc, uint32_t* pin, int to
     float4 *it_lo_b, *it_hi_b;
     SahTask *tasks_a, *tasks_b, *big_a, *big_b, *small_a, *small_b;
     MPT_LB(sc.alloc(&T.st, 1));
-    MPT_LB(sc.alloc(&it_lo_b, max_items));
-    MPT_LB(sc.alloc(&it_hi_b, max_items));
-    MPT_LB(sc.alloc(&tasks_a, max_items + 2));
-    MPT_LB(sc.alloc(&tasks_b, max_items + 2));
-    MPT_LB(sc.alloc(&big_a, max_items / MPT_SAH_BIG + 2));
-    MPT_LB(sc.alloc(&big_b, max_items / MPT_SAH_BIG + 2));
-    MPT_LB(sc.alloc(&small_a, max_items / 2 + 2));
-    MPT_LB(sc.alloc(&small_b, max_items / 2 + 2));
+    MPT_LB(sc.allocs(max_items, &it_lo_b, &it_hi_b));
+    MPT_LB(sc.allocs(max_items + 2, &tasks_a, &tasks_b));
+    MPT_LB(sc.allocs(max_items / MPT_SAH_BIG + 2, &big_a, &big_b));
+    MPT_LB(sc.allocs(max_items / 2 + 2, &small_a, &small_b));
     const uint32_t max_big = max_items / MPT_SAH_BIG + 2;
     SahBig* bigs;
     uint32_t *coff, *chunk_left;
     MPT_LB(sc.alloc(&bigs, max_big));
     MPT_LB(sc.alloc(&coff, max_big + 1));
     MPT_LB(sc.alloc(&chunk_left, max_items / MPT_SAH_CHUNK + max_big + 1));
-    MPT_LB(sc.alloc(&T.child, max_items));
-    MPT_LB(sc.alloc(&T.lo, max_items));
-    MPT_LB(sc.alloc(&T.hi, max_items));
+    MPT_LB(sc.allocs(max_items, &T.child, &T.lo, &T.hi));
     // (k_sah_* take n with top = 2n - 1)
     const int n = (top + 1) / 2;
-    // eight slots of three 8-byte words (stamp << 32 | mid tasks, big tasks, small tasks) in pinned memory, behind the words other read-backs
-    // of the build use
+    // the levels' counts come back through stamped slots of three words: (stamp << 32 | mid tasks, big tasks, small tasks)
     static uint32_t s_epoch = 0;
     const uint32_t epoch = (++s_epoch & 0x7FFFu) << 16;
-    volatile unsigned long long* slots = (volatile unsigned long long*)(pin + 64);
-    unsigned long long* d_slots = nullptr;
-    MPT_LB(hipHostGetDevicePointer((void**)&d_slots, pin + 64, 0));
-    for (int q = 0; q < 24; ++q) slots[q] = 0ull;
+    mpt_build::StampedSlots slots;
+    MPT_LB(slots.open(pin, mpt_build::PIN_W_SAH_SLOTS, mpt_build::PIN_SAH_SLOT_WORDS64));
     hipLaunchKernelGGL(k_sah_init, dim3(1), dim3(64), 0, stream, d_count, count_host, T.st, tasks_a, big_a, small_a);
     const uint32_t cap_mid = max_items / (MPT_SAH_SMALL + 1u) + 2u, cap_small = max_items / 2u + 2u;
-    auto slot_ready = [&](int level) {   // all three words of the level's slot carry its stamp
-        volatile unsigned long long* sl = slots + 3 * (level & 7);
-        const uint32_t want = epoch | (uint32_t)(level + 1);
-        for (int q = 0; q < 3; ++q)
-            if (((uint32_t)(sl[q] >> 32) & ~MPT_SAH_STAMP_OVERFLOW) != want) return false;
-        return true;
-    };
+    auto slot_ready = [&](int level) { return slots.ready((uint32_t)level, epoch | (uint32_t)(level + 1), MPT_SAH_STAMP_OVERFLOW); };
     auto wait_slot = [&](int level, uint32_t out[3]) -> hipError_t {   // the counts of `level`, once its first kernel has started
-        volatile unsigned long long* sl = slots + 3 * (level & 7);
-        const auto t0 = std::chrono::steady_clock::now();
-        for (unsigned long long spin = 0; !slot_ready(level); ++spin) {
-            if ((spin & 0xFFFu) == 0xFFFu) {
-                const hipError_t q = hipStreamQuery(stream);
-                if (q != hipSuccess && q != hipErrorNotReady) return q;
-                if (q == hipSuccess && !slot_ready(level)) return hipErrorUnknown;   // the stream is drained and the stamp never came
-                if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) return hipErrorLaunchTimeOut;   // (a level takes < 1 ms: a kernel hangs)
-            }
-        }
-        unsigned long long w[3] = {sl[0], sl[1], sl[2]};
+        unsigned long long w[3];
+        MPT_LB(slots.wait(stream, (uint32_t)level, epoch | (uint32_t)(level + 1), MPT_SAH_STAMP_OVERFLOW, w));
         for (int q = 0; q < 3; ++q) {
             if ((uint32_t)(w[q] >> 32) & MPT_SAH_STAMP_OVERFLOW) return hipErrorLaunchOutOfResources;   // a level had more tasks than its grids covered (sah_level_prologue)
             out[q] = (uint32_t)w[q];
@@ -1051,12 +909,11 @@ static hipError_t run_sah(hipStream_t stream, Scratch& sc, uint32_t* pin, int to
         return hipSuccess;
     };
     uint32_t b_mid = 1u, b_big = 1u, b_small = 1u;   // upper bounds of the level about to be enqueued (level 0: the root task, of one kind)
-    int known = -1;                                   // the latest level whose exact counts the host has read
     bool done = false;
     int level = 0;
     for (; level < 4096 && !done; ++level) {
         // (the level's first kernel publishes its counts and zeroes the set of the level after: sah_level_prologue)
-        SahLevel first = {(uint32_t)level, epoch | (uint32_t)(level + 1), d_slots + 3 * (level & 7), {b_mid, b_big, b_small}};
+        SahLevel first = {(uint32_t)level, epoch | (uint32_t)(level + 1), slots.dev_slot((uint32_t)level), {b_mid, b_big, b_small}};
         const SahLevel rest = {(uint32_t)level, 0u, nullptr, {0u, 0u, 0u}};
         auto take = [&]() {   // the prologue goes to whichever kernel is launched first
             const SahLevel r = first;
@@ -1098,7 +955,6 @@ static hipError_t run_sah(hipStream_t stream, Scratch& sc, uint32_t* pin, int to
         if (slot_ready(level)) from = level;
         if (from >= 0) {
             MPT_LB(wait_slot(from, c));
-            known = from;
             if ((c[0] | c[1] | c[2]) == 0u) done = true;   // nothing was left at `from`: the levels behind it are empty too
             const uint32_t steps = (uint32_t)(level + 1 - from);   // 1 or 2 doublings
             const unsigned long long g = 1ull << steps, parents = (unsigned long long)c[0] + c[1];
@@ -1114,7 +970,6 @@ static hipError_t run_sah(hipStream_t stream, Scratch& sc, uint32_t* pin, int to
         std::swap(it_lo_a, it_lo_b);
         std::swap(it_hi_a, it_hi_b);
     }
-    (void)known;
     if (!done) return hipErrorUnknown;
     return hipGetLastError();
 }

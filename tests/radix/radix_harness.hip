@@ -1,7 +1,7 @@
 // radix_harness.hip — the builders' radix sort (mpt_radix.h) and material hash (mpt_devbuild.h k_mat_hash) behind a C entry point each, for
 // tests/test_gpu_radix.py and tests/test_gpu_materials.py.  Test infrastructure only: the kernels are the product's, included, not copied.
 //
-// radix_harness_sort sorts device copies of the caller's pairs on a stream of its own, with mpt_lbvh::Scratch (no pool) for the sort's
+// radix_harness_sort sorts device copies of the caller's pairs on a stream of its own, with a Scratch over a pool of the call's own for the sort's
 // temporaries, and puts RADIX_GUARD words of a known pattern behind each of the four pair buffers: a word of them that changed is an
 // error of its own (RADIX_ERR_GUARD), whatever the sorted arrays look like.
 //
@@ -53,7 +53,8 @@ extern "C" int radix_harness_sort(const uint32_t* keys, const uint32_t* vals, ui
     }
     bool second = false;
     {
-        mpt_lbvh::Scratch sc;
+        mpt_build::ScratchPool pool;   // (freed with the call)
+        mpt_build::Scratch sc(pool);
         mpt_radix::RadixTemp T;
         if (mpt_radix::radix_reserve(sc, n, g_stream, T) != hipSuccess) return RADIX_ERR_HIP;
         const hipError_t e = mpt_radix::radix_sort_pairs(g_stream, T, d[0].p, d[1].p, d[2].p, d[3].p, n, passes, &second);
