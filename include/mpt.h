@@ -943,6 +943,90 @@ int mpt_get_light_sampling(mpt_ctx* ctx, int32_t* mode);
 int mpt_set_light_candidates(mpt_ctx* ctx, uint32_t m);   /* 1..MPT_LIGHT_CANDIDATES_MAX; default 1 */
 int mpt_get_light_candidates(mpt_ctx* ctx, uint32_t* m);
 
+/* ---- spatial reservoir reuse (ReSTIR) in the direct pass -------------------------------------------------------------------------------
+ * mpt_direct_restir is the direct pass with m candidates per sample (m: the context's mpt_set_light_candidates setting, read at the
+ * start of the call; m = 1 runs the same candidate loop) in which a pixel does not forget its candidates: in every round it merges its
+ * one-sample reservoir with those of K nearby pixels that see the same surface (Bitterli et al. 2020, "Spatiotemporal reservoir
+ * resampling", the spatial part).  Only a reservoir whose sample was found visible carries weight.  A new call with state of its own: no
+ * other call, result or kernel changes.  tests/restir_ref.py restates the section in numpy.  float32, one IEEE operation at a time in the
+ * order written; dot, normalize, u01, sincos_2pi, philox and the origin o as in the direct-lighting section.
+ * OUT OF SCOPE: temporal reuse over a camera path (the reprojection of mpt_temporal_accumulate is what it would use), mpt_render_nee,
+ * cone sampling, the adaptive calls.  The pass samples lights by AREA only: under MPT_LIGHT_SAMPLING_CONE the call returns
+ * MPT_ERR_INVALID_ARG, because a direction drawn in one point's cone is not a sample for another point.
+ *
+ * Surface pixels, emitters, misses, o, n and the final rgba = ((albedo.c * 0.31830987f) * (S.c / (float)N), 1) are the direct pass's.
+ * A RESERVOIR of pixel q in round s is EMPTY or HOLDS (k, ua, ub, wsum_q, fac_q): the light, the two uniforms u01(r.y), u01(r.z) the kept
+ * candidate was formed from, the running weight, and the kept candidate's factor ((cos_s * cos_l) / d2) * inv_pdf[k] at q.  The uniforms
+ * are stored, not the point, so "sample y seen from another pixel" is the candidate's geometry with another (o, n).
+ *
+ * Per round s in [sample_begin, sample_begin + N), ascending:
+ * Step A (every surface pixel p, before any pixel's step B of the round).  The candidate loop of the light-candidates section for the
+ *   direct pass — blocks (pixel, s, 0xFFFFFFFD, j), j < m, area geometry — remembering k, ua, ub and fac of the kept candidate.  Nothing
+ *   taken: EMPTY, no ray.  Otherwise traced += 1, the ray is any-hit(o_p, wi_y, dist_y * 0.9990234375f); occluded: EMPTY; not occluded:
+ *   unoccluded += 1 and the reservoir HOLDS.
+ * Step B.  held = the own reservoir holds; if so y = its sample, Wp = wsum_p, own = true; else Wp = 0.  For i = 0 .. K-1, ascending:
+ *   r_i = philox4x32_10(counter = (py*W+px, s, 0xFFFFFFFC, i), key)          (word 2 = 0xFFFFFFFC is nobody else's)
+ *   dx = min((int)(u01(r_i.x) * (float)(2R+1)), 2R) - R, dy likewise from r_i.y;  q = (px + dx, py + dy)
+ *   neighbour i is ACCEPTED iff (dx, dy) != (0, 0), q lies inside the image, q is class 0, dot(n_p, n_q) >= normal_threshold and
+ *     |t_q - t_p| <= depth_tolerance * t_p
+ *   ACCEPTED and q HOLDS: the light sample of (k_q, ua_q, ub_q) is formed from (o_p, n_p) exactly as a candidate is; fac its factor;
+ *     w = wsum_q * (fac / fac_q); it COUNTS iff ok && w > 0 && w < +inf
+ *   it counts: Wp = Wp + w; it is TAKEN iff !held || u01(r_i.z) * Wp < w; taking sets y = q's sample, own = false; then held = true
+ *   Not held: the round adds nothing and traces nothing more.
+ * Step C.  own: y's visibility is known, no ray.  Otherwise traced += 1, the ray is any-hit(o_p, wi_y, dist_y * 0.9990234375f) with y
+ *   formed from (o_p, n_p); occluded: the round ends; not occluded: unoccluded += 1.
+ * Step D.  c = 1 (the pixel itself).  For every ACCEPTED neighbour i, ascending, holding or not: y formed from (o_q, n_q); if
+ *   ok && fac > 0 && fac < +inf:   MPT_RESTIR_BIASED: c += 1.   MPT_RESTIR_UNBIASED: traced += 1, the ray is
+ *   any-hit(o_q, wi, dist * 0.9990234375f); not occluded: unoccluded += 1, c += 1.
+ * Step E.  Fy = (Wp / (float)(m * c)) / l_y,  S += (Le_y.r * Fy, Le_y.g * Fy, Le_y.b * Fy)    (l_y as in the light-candidates section;
+ *   the geometry factor cancels between the target and the integrand, hence the RIS pass's shape)
+ *
+ * With K = 0, or when no neighbour is accepted, rgba, traced and unoccluded are bit for bit mpt_direct_lighting's for m >= 2.
+ * UNBIASED is the 1/Z weighting of Bitterli et al., Alg. 6: the visibility test is inside the count because step A discarded occluded
+ * samples, and the pixel's own candidates cover every y with f_p(y) != 0.  BIASED omits the K correction rays: it counts a neighbour that
+ * could not have seen y, so it is wrong exactly there and DARKENS the image at visibility edges (penumbrae, contact shadows).
+ *
+ * Parameters: neighbours K in 0..MPT_RESTIR_MAX_NEIGHBOURS (0: no reuse), radius R in 1..MPT_RESTIR_MAX_RADIUS pixels (0: the default),
+ * normal_threshold and depth_tolerance (<= 0: the defaults, the temporal stage's).
+ * The call waits for queued renders, refreshes stale guides and the stale light table, and writes no other stage's state — not the
+ * direct pass's, not mpt_stats.  Its result has the direct result's lifetime: dropped by mpt_resize, mpt_upload_scene and
+ * mpt_build_and_upload.  MPT_ERR_INVALID_ARG with nothing changed: null params, sample_count outside 1..MPT_DIRECT_MAX_SAMPLES, a bad
+ * walk or mode, K > 16, R > 64, a NaN threshold or tolerance, cone sampling in effect.  MPT_ERR_NOT_READY and MPT_ERR_BAD_SCENE as the
+ * direct pass.
+ * mpt_restir_info: traced summed over the image = rays_initial + rays_final + rays_correction; rays_occluded of all three kinds;
+ * neighbours_accepted counts step B's accepted neighbours over surface pixels and rounds, samples_from_neighbours the pixel-rounds whose
+ * step B ended with a neighbour's sample.
+ * Test hooks.  mpt_restir_image: the same kernels on caller guides, as mpt_direct_image (needs a scene and no size).
+ * mpt_read_restir_reservoirs: the LAST round's reservoirs, six words per pixel — k, the bits of ua, ub, wsum, fac, and flags (bit 0 =
+ * holds, bit 1 = own).  which = 0: after step A (bit 1 never set).  which = 1: the pick after step B — wsum is Wp, fac the sample's
+ * factor at this pixel.  A reservoir that does not hold is six zero words.                                                            */
+#define MPT_RESTIR_MAX_NEIGHBOURS 16u
+#define MPT_RESTIR_MAX_RADIUS 64u
+#define MPT_RESTIR_DEFAULT_RADIUS 4u   /* the smallest radius measured was the best at every K */
+#define MPT_RESTIR_DEFAULT_NORMAL_THRESHOLD 0.5f
+#define MPT_RESTIR_DEFAULT_DEPTH_TOLERANCE 0.05f
+enum { MPT_RESTIR_UNBIASED = 0, MPT_RESTIR_BIASED = 1 };
+typedef struct mpt_restir_params {
+    uint32_t sample_begin, sample_count;   /* rounds N: 1..MPT_DIRECT_MAX_SAMPLES                                                      */
+    uint32_t seed_lo, seed_hi;
+    int32_t walk;                          /* MPT_WALK_*                                                                               */
+    uint32_t neighbours;                   /* K: 0..MPT_RESTIR_MAX_NEIGHBOURS                                                          */
+    uint32_t radius;                       /* R: 1..MPT_RESTIR_MAX_RADIUS, 0 = MPT_RESTIR_DEFAULT_RADIUS                               */
+    int32_t mode;                          /* MPT_RESTIR_UNBIASED or MPT_RESTIR_BIASED                                                 */
+    float normal_threshold, depth_tolerance;   /* <= 0: the defaults                                                                   */
+} mpt_restir_params;
+typedef struct mpt_restir_info {
+    uint64_t pixels_surface, rays_initial, rays_final, rays_correction, rays_occluded, neighbours_accepted, samples_from_neighbours, lights;
+    double device_ms;                      /* HIP-event time of the rounds (guide refresh and table build not included)                */
+} mpt_restir_info;
+int mpt_direct_restir(mpt_ctx* ctx, const mpt_restir_params* params, mpt_restir_info* out /* may be NULL */);
+int mpt_read_restir(mpt_ctx* ctx, float* rgba /* W*H*4 */, uint32_t* traced /* W*H, may be NULL */, uint32_t* unoccluded /* may be NULL */);
+int mpt_restir_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);   /* the RGBA32F image, laid out as the HDR sum                */
+int mpt_restir_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* albedo_depth, const float* normal_class,
+                     const mpt_uniforms* cam_uniforms, const mpt_restir_params* params, float* rgba_out, uint32_t* traced_out,
+                     uint32_t* unoccluded_out);
+int mpt_read_restir_reservoirs(mpt_ctx* ctx, int32_t which, uint32_t* out /* W*H*6 */);
+
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);
 int mpt_kat_philox(mpt_ctx* ctx, const uint32_t* ctr4, const uint32_t* key2, uint64_t n, uint32_t* out4);

@@ -103,6 +103,11 @@ int mpt_renderer_ambient_occlusion(mpt_renderer* r, uint32_t samples, float radi
 /* mpt_direct_lighting + mpt_read_direct (include/mpt.h) for the renderer's camera: `samples` light samples per surface pixel numbered
  * from 0, keyed by the render parameters' seed, `walk` one of MPT_WALK_*.  rgba: W*H*4 floats.  out may be NULL.                     */
 int mpt_renderer_direct_lighting(mpt_renderer* r, uint32_t samples, int32_t walk, float* rgba, mpt_direct_info* out);
+/* mpt_direct_restir + mpt_read_restir (include/mpt.h) for the renderer's camera: mpt_renderer_direct_lighting with spatial reservoir
+ * reuse — `neighbours` 0..16 per round from within `radius` pixels (0 = the default), `mode` MPT_RESTIR_UNBIASED or MPT_RESTIR_BIASED,
+ * the default thresholds.  rgba: W*H*4 floats.  out may be NULL.                                                                       */
+int mpt_renderer_direct_restir(mpt_renderer* r, uint32_t samples, uint32_t neighbours, uint32_t radius, int32_t mode, int32_t walk, float* rgba,
+                               mpt_restir_info* out);
 /* mpt_render_nee (include/mpt.h) for the renderer's camera and render parameters: samples [0, spp) onto the HDR sum (read it with
  * mpt_renderer_read_sum) at max_depth `depth`, `walk` one of MPT_WALK_*, clamp <= 0 = no per-sample clamp.  out may be NULL.          */
 int mpt_renderer_render_nee(mpt_renderer* r, uint32_t spp, int32_t depth, int32_t walk, float clamp, mpt_nee_info* out);

@@ -40,6 +40,7 @@ SYMBOLS = (
     "mpt_light_info", "mpt_read_lights", "mpt_direct_lighting", "mpt_read_direct", "mpt_direct_buffer", "mpt_direct_image",
     "mpt_render_nee", "mpt_set_light_sampling", "mpt_get_light_sampling", "mpt_render_nee_adaptive",
     "mpt_set_light_candidates", "mpt_get_light_candidates",
+    "mpt_direct_restir", "mpt_read_restir", "mpt_restir_buffer", "mpt_restir_image", "mpt_read_restir_reservoirs",
 )
 
 # mpt_scene_digest's words: the nine device arrays (mpt_read_scene_array's `which`), then the seven counts
@@ -69,6 +70,10 @@ DIRECT_MAX_SAMPLES = 1024
 LIGHTS_MAX = 65536
 LIGHT_SAMPLING_AREA, LIGHT_SAMPLING_CONE = 0, 1
 LIGHT_CANDIDATES_MAX = 32
+RESTIR_UNBIASED, RESTIR_BIASED = 0, 1
+RESTIR_MAX_NEIGHBOURS, RESTIR_MAX_RADIUS = 16, 64
+# include/mpt.h MPT_RESTIR_DEFAULT_* (radius 0 / a threshold <= 0 selects them)
+RESTIR_DEFAULTS = dict(radius=4, normal_threshold=0.5, depth_tolerance=0.05)
 
 
 class MptError(RuntimeError):
@@ -244,6 +249,29 @@ def direct_params(samples=16, sample_begin=0, seed=(0, 0), walk=WALK_AUTO):
     return DirectParams(int(sample_begin), int(samples), int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF, int(walk))
 
 
+class RestirParams(C.Structure):
+    _fields_ = [("sample_begin", C.c_uint32), ("sample_count", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32),
+                ("walk", C.c_int32), ("neighbours", C.c_uint32), ("radius", C.c_uint32), ("mode", C.c_int32),
+                ("normal_threshold", C.c_float), ("depth_tolerance", C.c_float)]
+
+
+class RestirInfo(C.Structure):
+    _fields_ = [("pixels_surface", C.c_uint64), ("rays_initial", C.c_uint64), ("rays_final", C.c_uint64), ("rays_correction", C.c_uint64),
+                ("rays_occluded", C.c_uint64), ("neighbours_accepted", C.c_uint64), ("samples_from_neighbours", C.c_uint64),
+                ("lights", C.c_uint64), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def restir_params(samples=16, sample_begin=0, seed=(0, 0), walk=WALK_AUTO, neighbours=0, radius=0, mode=RESTIR_UNBIASED, normal_threshold=0.0,
+                  depth_tolerance=0.0):
+    """mpt_restir_params: `samples` rounds per surface pixel, numbered from sample_begin, each merged with `neighbours` reservoirs from
+    within `radius` pixels (0: the default radius; a threshold <= 0: its default)."""
+    return RestirParams(int(sample_begin), int(samples), int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF, int(walk), int(neighbours),
+                        int(radius), int(mode), float(normal_threshold), float(depth_tolerance))
+
+
 class NeeParams(C.Structure):
     _fields_ = [("walk", C.c_int32), ("clamp", C.c_float)]
 
@@ -398,6 +426,11 @@ def load():
     L.mpt_read_direct.argtypes = [vp, fp, up, up]
     L.mpt_direct_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.mpt_direct_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(DirectParams), fp, up, up]
+    L.mpt_direct_restir.argtypes = [vp, C.POINTER(RestirParams), C.POINTER(RestirInfo)]
+    L.mpt_read_restir.argtypes = [vp, fp, up, up]
+    L.mpt_restir_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_restir_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(RestirParams), fp, up, up]
+    L.mpt_read_restir_reservoirs.argtypes = [vp, C.c_int32, up]
     L.mpt_render_nee.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(NeeInfo)]
     L.mpt_render_nee_adaptive.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(AdaptiveParams),
                                           C.POINTER(AdaptiveInfo), C.POINTER(NeeInfo)]
@@ -721,6 +754,50 @@ class Context:
         p = direct_params(**kw)
         self._chk(self.L.mpt_direct_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), C.byref(p), _fp(rgba), _up(traced), _up(unocc)),
                   "mpt_direct_image")
+        return rgba, traced, unocc
+
+    def direct_restir(self, **kw):
+        """mpt_direct_restir over the context's guide buffers (restir_params' keywords): the direct pass with spatial reservoir reuse;
+        returns the info dict."""
+        p = restir_params(**kw)
+        info = RestirInfo()
+        self._chk(self.L.mpt_direct_restir(self.h, C.byref(p), C.byref(info)), "mpt_direct_restir")
+        return info.as_dict()
+
+    def read_restir(self):
+        """(rgba [H,W,4] float32, traced [H,W] uint32, unoccluded [H,W] uint32) of the last direct_restir."""
+        rgba = np.empty((self.height, self.width, 4), np.float32)
+        traced = np.empty((self.height, self.width), np.uint32)
+        unocc = np.empty((self.height, self.width), np.uint32)
+        self._chk(self.L.mpt_read_restir(self.h, _fp(rgba), _up(traced), _up(unocc)), "mpt_read_restir")
+        return rgba, traced, unocc
+
+    def restir_buffer(self):
+        """(device pointer, bytes) of the last direct_restir's RGBA32F image."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_restir_buffer(self.h, C.byref(p), C.byref(n)), "mpt_restir_buffer")
+        return p.value, n.value
+
+    def read_restir_reservoirs(self, which):
+        """The last round's reservoirs of the last direct_restir, [H,W,6] uint32: k, the bits of ua, ub, wsum, fac, flags (bit 0 holds,
+        bit 1 own).  which = 0: after step A; 1: the pick after step B."""
+        out = np.empty((self.height, self.width, 6), np.uint32)
+        self._chk(self.L.mpt_read_restir_reservoirs(self.h, int(which), _up(out)), "mpt_read_restir_reservoirs")
+        return out
+
+    def restir_image(self, albedo_depth, normal_class, cam, **kw):
+        """The kernels of direct_restir on caller guides [H,W,4] with the camera of `cam` (Uniforms); needs a scene."""
+        ad = np.ascontiguousarray(albedo_depth, np.float32)
+        nc = np.ascontiguousarray(normal_class, np.float32)
+        if ad.ndim != 3 or ad.shape[2] != 4 or nc.shape != ad.shape:
+            raise ValueError("restir_image: albedo_depth and normal_class must be [H, W, 4] arrays of one shape")
+        H, W = ad.shape[:2]
+        rgba = np.empty((H, W, 4), np.float32)
+        traced = np.empty((H, W), np.uint32)
+        unocc = np.empty((H, W), np.uint32)
+        p = restir_params(**kw)
+        self._chk(self.L.mpt_restir_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), C.byref(p), _fp(rgba), _up(traced), _up(unocc)),
+                  "mpt_restir_image")
         return rgba, traced, unocc
 
     def render_nee(self, walk=WALK_AUTO, clamp=0.0, **params):

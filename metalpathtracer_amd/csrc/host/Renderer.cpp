@@ -382,6 +382,19 @@ void Renderer::readDirectLighting(std::vector<float>& rgba) {
     rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
     check(mpt_read_direct(ctx_, rgba.data(), nullptr, nullptr), "mpt_read_direct");
 }
+mpt_restir_info Renderer::renderDirectRestir(uint32_t samples, uint32_t neighbours, uint32_t radius, int32_t mode, int32_t walk) {
+    uniforms_.primitiveCount = scene_->getPrimitiveCount();
+    uniforms_.triangleCount = scene_->getTriangleCount();
+    check(mpt_set_uniforms(ctx_, &uniforms_), "mpt_set_uniforms");
+    const mpt_restir_params p = {0u, samples, params_.seed_lo, params_.seed_hi, walk, neighbours, radius, mode, 0.0f, 0.0f};
+    mpt_restir_info info;
+    check(mpt_direct_restir(ctx_, &p, &info), "mpt_direct_restir");
+    return info;
+}
+void Renderer::readDirectRestir(std::vector<float>& rgba) {
+    rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_restir(ctx_, rgba.data(), nullptr, nullptr), "mpt_read_restir");
+}
 mpt_nee_info Renderer::renderNee(uint32_t spp, int32_t depth, int32_t walk, float clamp, uint32_t sampleBegin) {
     uniforms_.primitiveCount = scene_->getPrimitiveCount();
     uniforms_.triangleCount = scene_->getTriangleCount();

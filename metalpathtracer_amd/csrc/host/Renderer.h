@@ -87,6 +87,12 @@ public:
     // parameters' seed, one shadow ray each through `walk` (MPT_WALK_*); readDirectLighting = the W*H*4 floats of the pass's rgba
     mpt_direct_info renderDirectLighting(uint32_t samples, int32_t walk = MPT_WALK_AUTO);
     void readDirectLighting(std::vector<float>& rgba);
+    // mpt_direct_restir over the same guides: renderDirectLighting with spatial reservoir reuse — every round merges a pixel's
+    // reservoir with `neighbours` from within `radius` pixels (0: the default), `mode` MPT_RESTIR_UNBIASED or MPT_RESTIR_BIASED, the
+    // default thresholds; readDirectRestir = the W*H*4 floats of its rgba
+    mpt_restir_info renderDirectRestir(uint32_t samples, uint32_t neighbours, uint32_t radius = 0, int32_t mode = MPT_RESTIR_UNBIASED,
+                                       int32_t walk = MPT_WALK_AUTO);
+    void readDirectRestir(std::vector<float>& rgba);
     // mpt_render_nee: renderBatch's samples [sampleBegin, sampleBegin + spp) onto the HDR sum with a light sample and MIS at every Lambert
     // vertex, at max_depth `depth`, both kinds of ray through `walk` (MPT_WALK_*), per-sample clamp `clamp` (<= 0: none)
     mpt_nee_info renderNee(uint32_t spp, int32_t depth, int32_t walk = MPT_WALK_AUTO, float clamp = 0.0f, uint32_t sampleBegin = 0);

@@ -43,7 +43,7 @@ static void usage() {
         "           [--camera-pos x,y,z] [--camera-dir x,y,z] [--camera-up x,y,z] [--vfov degrees]\n"
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]] [--ao N [--ao-radius R]]\n"
-        "           [--direct N [--direct-walk reference|own|auto]]\n"
+        "           [--direct N [--direct-walk reference|own|auto] [--restir K [--restir-radius R] [--restir-biased]]]\n"
         "           [--nee [--nee-walk reference|own|auto] [--nee-clamp C]]\n"
         "           [--nee-adaptive THRESHOLD [--nee-walk ...] [--nee-clamp C] [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--light-sampling area|cone]\n"
@@ -118,6 +118,12 @@ static void usage() {
         "                    resampling: every file and every line is what it is without the flag.  The \"direct\" / \"nee\" JSON object gains\n"
         "                    \"light_candidates\"; a checkpoint of an --nee render with M > 1 has the header MPTNEE3 (its last fields the\n"
         "                    sampling and M) and is resumed only by a run with the same M and sampling.  With --nee-adaptive only M = 1\n"
+        "  --restir K        with --direct: spatial reservoir reuse (mpt_direct_restir, include/mpt.h) — in every one of the N rounds a pixel\n"
+        "                    keeps the sample its --light-candidates pick only if its shadow ray arrives, then merges that one-sample\n"
+        "                    reservoir with those of K pixels (0..16; 4 is a fair start) drawn within --restir-radius R pixels (1..64, default 4) that\n"
+        "                    see the same surface.  Unbiased by default: one more shadow ray per accepted neighbour; --restir-biased omits\n"
+        "                    those rays and darkens the image at visibility edges.  The JSON line gains a \"restir\" object.  Lights are\n"
+        "                    sampled by area: not with --light-sampling cone.  Without --restir every file and line is what it was\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
@@ -407,6 +413,9 @@ int main(int argc, char** argv) {
     bool haveLightSampling = false;   // --light-sampling was given
     int lightSampling = MPT_LIGHT_SAMPLING_AREA;
     bool haveLightCandidates = false;   // --light-candidates was given
+    bool haveRestir = false, haveRestirRadius = false, haveRestirOpt = false;   // --restir K; --restir-radius; it or --restir-biased were given
+    int restirK = 0, restirRadius = 0;
+    int32_t restirMode = MPT_RESTIR_UNBIASED;
     int lightCandidates = 1;
     bool display = false;   // a display flag was given: .ppm files come from mpt_display
     DisplayOut shown;
@@ -483,6 +492,18 @@ int main(int argc, char** argv) {
             }
             lightSampling = std::strcmp(v, "cone") == 0 ? MPT_LIGHT_SAMPLING_CONE : MPT_LIGHT_SAMPLING_AREA;
             haveLightSampling = true;
+        }
+        else if (a == "--restir") {
+            restirK = std::atoi(next());
+            haveRestir = true;
+        }
+        else if (a == "--restir-radius") {
+            restirRadius = std::atoi(next());
+            haveRestirRadius = haveRestirOpt = true;
+        }
+        else if (a == "--restir-biased") {
+            restirMode = MPT_RESTIR_BIASED;
+            haveRestirOpt = true;
         }
         else if (a == "--light-candidates") {
             lightCandidates = std::atoi(next());
@@ -610,6 +631,16 @@ int main(int argc, char** argv) {
                                          : "mpt_render: --light-candidates goes with --direct or --nee\n");
         return 2;
     }
+    if (haveRestir || haveRestirOpt) {
+        const char* why = !haveRestir ? "--restir-radius and --restir-biased go with --restir K" : !haveDirect ? "--restir goes with --direct"
+                          : restirK < 0 || restirK > static_cast<int>(MPT_RESTIR_MAX_NEIGHBOURS) ? "--restir takes a count in 0..16"
+                          : haveRestirRadius && (restirRadius < 1 || restirRadius > static_cast<int>(MPT_RESTIR_MAX_RADIUS)) ? "--restir-radius takes a radius in 1..64"
+                          : lightSampling == MPT_LIGHT_SAMPLING_CONE ? "--restir cannot be combined with --light-sampling cone" : nullptr;
+        if (why) {
+            std::fprintf(stderr, "mpt_render: %s\n", why);
+            return 2;
+        }
+    }
     if (!neeAdaptive && (nee || haveNeeOpt)) {
         const char* why = !nee ? "a run without --nee" : neeClamp != neeClamp ? "a --nee-clamp that is no number" : adaptive ? "--adaptive" : gpus > 1 ? "--gpus > 1"
                           : !cameraPath.empty() ? "--camera-path" : frames > 0 ? "--frames" : haveAo || haveAoRadius ? "--ao"
@@ -714,6 +745,21 @@ int main(int argc, char** argv) {
                           ao, static_cast<double>(aoRadius), (unsigned long long)info.pixels_surface, (unsigned long long)info.rays,
                           (unsigned long long)info.rays_occluded, info.device_ms);
             extraJson = buf;
+        } else if (direct > 0 && haveRestir) {   // the same, with spatial reservoir reuse
+            const mpt_restir_info info = r.renderDirectRestir(static_cast<uint32_t>(direct), static_cast<uint32_t>(restirK), static_cast<uint32_t>(restirRadius),
+                                                              restirMode, directWalk);
+            r.readDirectRestir(img);
+            char buf[640];
+            std::snprintf(buf, sizeof buf,
+                          ", \"restir\": {\"samples\": %d, \"neighbours\": %d, \"radius\": %d, \"mode\": \"%s\", \"pixels_surface\": %llu, \"rays_initial\": %llu, "
+                          "\"rays_final\": %llu, \"rays_correction\": %llu, \"rays_occluded\": %llu, \"neighbours_accepted\": %llu, "
+                          "\"samples_from_neighbours\": %llu, \"lights\": %llu, \"device_ms\": %.3f",
+                          direct, restirK, restirRadius ? restirRadius : static_cast<int>(MPT_RESTIR_DEFAULT_RADIUS),
+                          restirMode == MPT_RESTIR_BIASED ? "biased" : "unbiased", (unsigned long long)info.pixels_surface,
+                          (unsigned long long)info.rays_initial, (unsigned long long)info.rays_final, (unsigned long long)info.rays_correction,
+                          (unsigned long long)info.rays_occluded, (unsigned long long)info.neighbours_accepted,
+                          (unsigned long long)info.samples_from_neighbours, (unsigned long long)info.lights, info.device_ms);
+            extraJson = buf + samplingJson + "}";
         } else if (direct > 0) {   // the pass's rgba through the writer the radiance goes through
             const mpt_direct_info info = r.renderDirectLighting(static_cast<uint32_t>(direct), directWalk);
             r.readDirectLighting(img);

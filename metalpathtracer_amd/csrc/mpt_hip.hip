@@ -50,6 +50,7 @@
 #include "mpt_nee.h"
 #include "mpt_nee_adaptive.h"
 #include "mpt_ris.h"
+#include "mpt_restir.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -280,6 +281,16 @@ struct DirectState {
     uint64_t epoch = 0;            // the guide_epoch the result was written in (0 = none)
 };
 
+// Spatial reservoir reuse (mpt_restir.h): the result of the last mpt_direct_restir and what its rounds pass on, with the direct
+// result's lifetime.  Allocated by the first call; mpt_resize and the scene calls let go of it.
+struct RestirState {
+    DevMem<float4> out;            // RestirPass::out: W * H rgba, W * H traced, W * H unoccluded, the MPT_RS_TOTAL_WORDS words of totals
+    DevMem<float4> S;              // a pixel's sum across the rounds
+    DevMem<uint4> res[2];          // two uint4 per pixel: the last round's reservoirs after step A, its picks after step B
+    uint32_t W = 0, H = 0;
+    uint64_t epoch = 0;            // the guide_epoch the result was written in (0 = none)
+};
+
 // Next-event estimation (mpt_nee.h): what every mpt_render_nee call needs besides the sum — the four totals of mpt_nee_info on the device
 // and the pair of timing events.  Made by the first call, kept for the context's life (an allocation per call would cost a device
 // synchronisation each time).
@@ -381,6 +392,7 @@ struct mpt_ctx : SceneState {
     AoState ao;
     LightState lights;
     DirectState di;
+    RestirState rs;
     NeeState nee;
     int32_t light_sampling = MPT_LIGHT_SAMPLING_AREA;   // mpt_set_light_sampling: host state, read at the start of the three calls that sample lights
     uint32_t light_candidates = 1u;                     // mpt_set_light_candidates: host state with the same life, read at the same three places
@@ -563,7 +575,11 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
                           (const void*)k_nee_cone<MPT_AO_REF_ALL_LDS>, (const void*)k_nee_cone<MPT_AO_OWN>, (const void*)k_nee_adaptive<MPT_AO_REF>,
                           (const void*)k_nee_adaptive<MPT_AO_REF_ALL_LDS>, (const void*)k_nee_adaptive<MPT_AO_OWN>,
                           (const void*)k_nee_adaptive_cone<MPT_AO_REF>, (const void*)k_nee_adaptive_cone<MPT_AO_REF_ALL_LDS>,
-                          (const void*)k_nee_adaptive_cone<MPT_AO_OWN>})
+                          (const void*)k_nee_adaptive_cone<MPT_AO_OWN>, (const void*)k_restir_initial<MPT_AO_REF>,
+                          (const void*)k_restir_initial<MPT_AO_REF_ALL_LDS>, (const void*)k_restir_initial<MPT_AO_OWN>,
+                          (const void*)k_restir_merge<MPT_AO_REF, true>, (const void*)k_restir_merge<MPT_AO_REF_ALL_LDS, true>,
+                          (const void*)k_restir_merge<MPT_AO_OWN, true>, (const void*)k_restir_merge<MPT_AO_REF, false>,
+                          (const void*)k_restir_merge<MPT_AO_REF_ALL_LDS, false>, (const void*)k_restir_merge<MPT_AO_OWN, false>})
         hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = ctx.release();
     return MPT_OK;
@@ -636,6 +652,7 @@ static void install_scene(mpt_ctx* ctx, SceneState&& s) {
     ctx->guide_epoch++;
     ctx->ao = AoState{};   // (an AO result belongs to the scene it was traced in)
     ctx->di = DirectState{};
+    ctx->rs = RestirState{};
     ctx->lights = LightState{};   // (built again by the first call that needs it)
 }
 
@@ -728,6 +745,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->dp = DisplayState{};
     ctx->ao = AoState{};
     ctx->di = DirectState{};
+    ctx->rs = RestirState{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;

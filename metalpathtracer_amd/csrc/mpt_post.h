@@ -666,6 +666,172 @@ extern "C" int mpt_direct_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const floa
     return guarded(ctx, [&] { return direct_image_impl(ctx, w, h, albedo_depth, normal_class, cam, p, rgba_out, traced_out, unoccluded_out); });
 }
 
+// ---- spatial reservoir reuse (mpt_restir.h; the specification is in include/mpt.h) ---------------------------------------------------
+struct RestirResolved {
+    uint32_t M, K, R;
+    float normal_thr, depth_tol;
+};
+// The argument checks, in front of wait_impl: a refused call changes nothing and waits for nothing.
+static int restir_check(mpt_ctx* ctx, const mpt_restir_params* p, RestirResolved& r) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null restir params");
+    if (p->sample_count == 0 || p->sample_count > MPT_DIRECT_MAX_SAMPLES) return fail(ctx, MPT_ERR_INVALID_ARG, "restir: sample_count outside 1..1024");
+    if (!walk_valid(p->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "restir: bad walk");
+    if (p->mode != MPT_RESTIR_UNBIASED && p->mode != MPT_RESTIR_BIASED) return fail(ctx, MPT_ERR_INVALID_ARG, "restir: bad mode");
+    if (p->neighbours > MPT_RESTIR_MAX_NEIGHBOURS) return fail(ctx, MPT_ERR_INVALID_ARG, "restir: neighbours > 16");
+    if (p->radius > MPT_RESTIR_MAX_RADIUS) return fail(ctx, MPT_ERR_INVALID_ARG, "restir: radius > 64");
+    if (p->normal_threshold != p->normal_threshold || p->depth_tolerance != p->depth_tolerance)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "restir: a threshold is NaN");
+    if (ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "restir: lights are sampled by area only (mpt_set_light_sampling is MPT_LIGHT_SAMPLING_CONE)");
+    r.M = ctx->light_candidates;   // (read at the start)
+    r.K = p->neighbours;
+    r.R = p->radius ? p->radius : MPT_RESTIR_DEFAULT_RADIUS;
+    r.normal_thr = p->normal_threshold > 0.0f ? p->normal_threshold : MPT_RESTIR_DEFAULT_NORMAL_THRESHOLD;
+    r.depth_tol = p->depth_tolerance > 0.0f ? p->depth_tolerance : MPT_RESTIR_DEFAULT_DEPTH_TOLERANCE;
+    return MPT_OK;
+}
+static size_t restir_out_bytes(size_t n_pixels) { return n_pixels * 24 + MPT_RS_TOTAL_WORDS * 8; }
+static size_t restir_res_bytes(size_t n_pixels) { return n_pixels * 32; }
+// The rounds on ctx->stream over guides on the device, at the camera `key`, with the (built) light table: the sums, the counts, the
+// totals and the picks zeroed, then k_restir_initial and k_restir_merge once per sample.  out: restir_out_bytes(W * H); S: 16 bytes per
+// pixel; initial, pick: restir_res_bytes(W * H).
+static int restir_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad, const float4* nc, const float key[14], const mpt_restir_params* p,
+                         const RestirResolved& r, float4* out, float4* S, uint4* initial, uint4* pick) {
+    RestirPass P = {};
+    const size_t n = (size_t)W * H;
+    P.ad = ad;
+    P.nc = nc;
+    P.out = out;
+    P.n_pixels = W * H;
+    P.S = S;
+    P.initial = initial;
+    P.pick = pick;
+    HIPCHK(hipMemsetAsync(P.traced(), 0, n * 8 + MPT_RS_TOTAL_WORDS * 8, ctx->stream));
+    HIPCHK(hipMemsetAsync(S, 0, n * 16, ctx->stream));
+    HIPCHK(hipMemsetAsync(pick, 0, restir_res_bytes(n), ctx->stream));
+    P.lights = ctx->lights.rec.get();
+    P.cdf = ctx->lights.cdf.get();
+    P.n_lights = ctx->lights.n();
+    pass_frame(P, key, W, H, *p);
+    P.M = r.M;
+    P.K = r.K;
+    P.R = r.R;
+    P.normal_threshold = r.normal_thr;
+    P.depth_tolerance = r.depth_tol;
+    static const WalkKernel<RestirPass> initial_k[3] = {k_restir_initial<MPT_AO_REF>, k_restir_initial<MPT_AO_REF_ALL_LDS>, k_restir_initial<MPT_AO_OWN>},
+                                        unbiased[3] = {k_restir_merge<MPT_AO_REF, true>, k_restir_merge<MPT_AO_REF_ALL_LDS, true>,
+                                                       k_restir_merge<MPT_AO_OWN, true>},
+                                        biased[3] = {k_restir_merge<MPT_AO_REF, false>, k_restir_merge<MPT_AO_REF_ALL_LDS, false>,
+                                                     k_restir_merge<MPT_AO_OWN, false>};
+    for (uint32_t round = 0; round < p->sample_count; ++round) {
+        P.round = round;
+        int rc = tile_walk_launch(ctx, W, H, p->walk, initial_k, P);
+        if (rc || (rc = tile_walk_launch(ctx, W, H, p->walk, p->mode == MPT_RESTIR_UNBIASED ? unbiased : biased, P))) return rc;
+    }
+    return MPT_OK;
+}
+static StageResult rs_result(const mpt_ctx* c) {
+    return stage_result(c, stage_valid(c, c->rs), c->rs.out.get(), 16, "no mpt_direct_restir result for this scene and size");
+}
+static int direct_restir_impl(mpt_ctx* ctx, const mpt_restir_params* p, mpt_restir_info* out) {
+    if (!ctx) return MPT_ERR_INVALID_ARG;
+    RestirResolved r;
+    int rc = restir_check(ctx, p, r);
+    if (rc || (rc = settle_and_guide(ctx)) || (rc = ensure_lights(ctx))) return rc;
+    std::vector<unsigned long long> slots(MPT_RS_TOTAL_WORDS, 0ull);   // the totals, MPT_RS_SLOTS times (mpt_restir.h)
+    float ms = 0.0f;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    rc = stage_run(ctx, ctx->rs, restir_out_bytes(n), slots.data(), MPT_RS_TOTAL_WORDS, out ? &ms : nullptr, [&](const float* key, float4* o) -> int {
+        RestirState& s = ctx->rs;
+        if (!s.S) {   // (stage_run has made a fresh state of this size)
+            HIPCHK(s.S.alloc(n * 16));
+            HIPCHK(s.res[0].alloc(restir_res_bytes(n)));
+            HIPCHK(s.res[1].alloc(restir_res_bytes(n)));
+        }
+        return restir_launch(ctx, ctx->W, ctx->H, ctx->gd.ad.get(), ctx->gd.nc.get(), key, p, r, o, s.S.get(), s.res[0].get(), s.res[1].get());
+    });
+    if (rc) return rc;
+    if (out) {
+        unsigned long long totals[MPT_RS_TOTALS] = {};
+        for (uint32_t s = 0; s < MPT_RS_SLOTS; ++s)
+            for (int k = 0; k < MPT_RS_TOTALS; ++k) totals[k] += slots[s * MPT_RS_SLOT_WORDS + k];
+        const unsigned long long traced = totals[MPT_RS_INITIAL] + totals[MPT_RS_FINAL] + totals[MPT_RS_CORRECTION];
+        out->pixels_surface = totals[MPT_RS_SURFACE];
+        out->rays_initial = totals[MPT_RS_INITIAL];
+        out->rays_final = totals[MPT_RS_FINAL];
+        out->rays_correction = totals[MPT_RS_CORRECTION];
+        out->rays_occluded = traced - totals[MPT_RS_UNOCCLUDED];
+        out->neighbours_accepted = totals[MPT_RS_ACCEPTED];
+        out->samples_from_neighbours = totals[MPT_RS_FROM_NEIGHBOUR];
+        out->lights = ctx->lights.n();
+        out->device_ms = (double)ms;
+    }
+    return MPT_OK;
+}
+static int read_restir_impl(mpt_ctx* ctx, float* rgba, uint32_t* traced, uint32_t* unoccluded) {
+    if (!ctx || !rgba) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    const StageResult r = rs_result(ctx);
+    int rc = need(ctx, r);
+    const size_t n = (size_t)ctx->W * ctx->H;
+    if (rc || (rc = copy_out(ctx, rgba, r.p, r.bytes)) || (rc = copy_out(ctx, traced, (const char*)r.p + n * 16, n * 4)) ||
+        (rc = copy_out(ctx, unoccluded, (const char*)r.p + n * 20, n * 4)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+// six of a reservoir's eight words per pixel (RestirPass: the last two are padding)
+static int read_restir_reservoirs_impl(mpt_ctx* ctx, int32_t which, uint32_t* out) {
+    if (!ctx || !out || (which != 0 && which != 1)) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_read_restir_reservoirs: null argument or which not 0 or 1");
+    int rc = need(ctx, rs_result(ctx));
+    if (rc) return rc;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    std::vector<uint32_t> words(n * 8);
+    HIPCHK(hipMemcpyAsync(words.data(), ctx->rs.res[which].get(), n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) memcpy(out + 6 * i, &words[8 * i], 24);
+    return MPT_OK;
+}
+static int restir_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* ad, const float* nc, const mpt_uniforms* cam, const mpt_restir_params* p,
+                             float* rgba_out, uint32_t* traced_out, uint32_t* unocc_out) {
+    if (!ctx || !ad || !nc || !cam || !rgba_out || bad_image_size(W, H)) return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    RestirResolved r;
+    int rc = restir_check(ctx, p, r);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = ensure_lights(ctx))) return rc;
+    const size_t n = (size_t)W * H;
+    DevMem<float4> d_ad, d_nc, d_out, d_S;
+    DevMem<uint4> d_res[2];
+    HIPCHK(d_out.alloc(restir_out_bytes(n)));
+    HIPCHK(d_S.alloc(n * 16));
+    HIPCHK(d_res[0].alloc(restir_res_bytes(n)));
+    HIPCHK(d_res[1].alloc(restir_res_bytes(n)));
+    if ((rc = stage_in(ctx, d_ad, ad, n * 16)) || (rc = stage_in(ctx, d_nc, nc, n * 16))) return rc;
+    float key[14];
+    guide_key(*cam, key);
+    const char* o = (const char*)d_out.get();
+    if ((rc = restir_launch(ctx, W, H, d_ad.get(), d_nc.get(), key, p, r, d_out.get(), d_S.get(), d_res[0].get(), d_res[1].get())) ||
+        (rc = copy_out(ctx, rgba_out, o, n * 16)) || (rc = copy_out(ctx, traced_out, o + n * 16, n * 4)) ||
+        (rc = copy_out(ctx, unocc_out, o + n * 20, n * 4)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+extern "C" int mpt_direct_restir(mpt_ctx* ctx, const mpt_restir_params* p, mpt_restir_info* out) {
+    return guarded(ctx, [&] { return direct_restir_impl(ctx, p, out); });
+}
+extern "C" int mpt_read_restir(mpt_ctx* ctx, float* rgba, uint32_t* traced, uint32_t* unoccluded) {
+    return guarded(ctx, [&] { return read_restir_impl(ctx, rgba, traced, unoccluded); });
+}
+extern "C" int mpt_restir_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) { return result_buffer(ctx, rs_result, p, bytes); }
+extern "C" int mpt_restir_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* albedo_depth, const float* normal_class, const mpt_uniforms* cam,
+                                const mpt_restir_params* p, float* rgba_out, uint32_t* traced_out, uint32_t* unoccluded_out) {
+    return guarded(ctx, [&] { return restir_image_impl(ctx, w, h, albedo_depth, normal_class, cam, p, rgba_out, traced_out, unoccluded_out); });
+}
+extern "C" int mpt_read_restir_reservoirs(mpt_ctx* ctx, int32_t which, uint32_t* out) {
+    return guarded(ctx, [&] { return read_restir_reservoirs_impl(ctx, which, out); });
+}
+
 // ---- temporal accumulation (mpt_temporal.h; the specification is in include/mpt.h) ---------------------------------------------
 struct TpResolved {
     float max_history, depth_tol, normal_thr, min_weight;

@@ -26,7 +26,7 @@ SYMBOLS = (
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
-    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_render_nee", "mpt_renderer_set_light_sampling",
+    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_direct_restir", "mpt_renderer_render_nee", "mpt_renderer_set_light_sampling",
     "mpt_renderer_render_nee_adaptive", "mpt_renderer_set_light_candidates", "mpt_renderer_get_light_candidates",
 )
 
@@ -86,6 +86,8 @@ def load():
     L.mpt_write_ppm8.argtypes = [C.c_char_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]
     L.mpt_renderer_ambient_occlusion.argtypes = [vp, C.c_uint32, C.c_float, C.POINTER(C.c_float), C.POINTER(capi.AoInfo)]
     L.mpt_renderer_direct_lighting.argtypes = [vp, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.POINTER(capi.DirectInfo)]
+    L.mpt_renderer_direct_restir.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                             C.POINTER(capi.RestirInfo)]
     L.mpt_renderer_render_nee.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.NeeInfo)]
     L.mpt_renderer_set_light_sampling.argtypes = [vp, C.c_int32]
     L.mpt_renderer_set_light_candidates.argtypes = [vp, C.c_uint32]
@@ -411,6 +413,16 @@ class Renderer:
         out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
         info = capi.DirectInfo()
         self._chk(self.L.mpt_renderer_direct_lighting(self.h, int(samples), int(walk), _fp(out), C.byref(info)), "renderDirectLighting")
+        return out, info.as_dict()
+
+    def renderDirectRestir(self, samples, neighbours, radius=0, mode=capi.RESTIR_UNBIASED, walk=capi.WALK_AUTO):
+        """mpt_renderer_direct_restir: renderDirectLighting with spatial reservoir reuse — every round merges a pixel's reservoir with
+        `neighbours` from within `radius` pixels (0: the default).  Returns (rgba [H, W, 4] float32; the mpt_restir_info as a dict)."""
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
+        info = capi.RestirInfo()
+        self._chk(self.L.mpt_renderer_direct_restir(self.h, int(samples), int(neighbours), int(radius), int(mode), int(walk), _fp(out),
+                                                    C.byref(info)), "renderDirectRestir")
         return out, info.as_dict()
 
     def renderNee(self, spp, depth, walk=capi.WALK_AUTO, clamp=0.0):
