@@ -26,7 +26,7 @@ oracle:
 	$(MAKE) --no-print-directory -C oracle
 
 # test infrastructure: the librccl test double that lets the N > 1 collective path run on one GPU (tests/test_gpu_stub_rccl.py)
-teststub: tests/stub_rccl/_build/librccl.so.1 tests/holder/_build/libholdchip.so tests/radix/_build/libradixharness.so tests/lean_math/_build/libleanmath.so tests/lean_entry/_build/libleanentry.so tests/lean_tail/_build/libleantail.so tests/lean_tiles/_build/libleantiles.so
+teststub: tests/stub_rccl/_build/librccl.so.1 tests/holder/_build/libholdchip.so tests/radix/_build/libradixharness.so tests/lean_math/_build/libleanmath.so tests/lean_entry/_build/libleanentry.so tests/lean_tail/_build/libleantail.so tests/lean_tiles/_build/libleantiles.so tests/ring0_rule/_build/libmpt_hip_ringtest.so
 # ... and the foreign persistent kernel of the residency-gate test (tests/test_gpu_parity.py)
 tests/holder/_build/libholdchip.so: tests/holder/hold_chip.hip
 	@mkdir -p tests/holder/_build
@@ -61,7 +61,13 @@ tests/lean_tiles/_build/libleantiles.so: tests/lean_tiles/lean_tiles_harness.hip
 	@mkdir -p tests/lean_tiles/_build
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -fPIC -ffp-contract=off -Iinclude -I$(PKG)/csrc -Wno-unused-function -Wno-unused-value -Wno-unused-result -Wno-pass-failed -shared -o $@ $<
 
+# ... and the library itself with the lean kernels' ring constants read from the configuration block, so that a test can set any
+# (N0, budget) pair (tests/test_gpu_ring0_rule.py); the product's flags
+tests/ring0_rule/_build/libmpt_hip_ringtest.so: $(PKG)/csrc/mpt_hip.hip $(wildcard $(PKG)/csrc/*.h) include/mpt.h
+	@mkdir -p tests/ring0_rule/_build
+	$(HIPCC) $(HIPFLAGS) -DMPT_LEAN_RING_TESTING -shared -o $@ $<
+
 clean:
-	rm -rf $(LIBDIR) oracle/_build oracle/_ref tests/stub_rccl/_build tests/holder/_build tests/radix/_build tests/lean_math/_build tests/lean_entry/_build tests/lean_tail/_build tests/lean_tiles/_build
+	rm -rf $(LIBDIR) oracle/_build oracle/_ref tests/stub_rccl/_build tests/holder/_build tests/radix/_build tests/lean_math/_build tests/lean_entry/_build tests/lean_tail/_build tests/lean_tiles/_build tests/ring0_rule/_build
 
 .PHONY: all host oracle teststub clean

@@ -287,6 +287,7 @@ struct WorkCount {
 #ifdef MPT_DEBUG_WAVE_TIMES
     unsigned long long t_box, t_leaf;              // diagnostics build: shader-clock cycles spent in the two loops
     uint32_t wait_leaf, wait_done;                 // box-loop trips this lane idled holding a leaf / after finishing
+    uint32_t low_trips[3];                         // per WAVE: box-loop trips made with fewer than 8 / 16 / 24 lanes searching
 #endif
 #ifdef MPT_OT_TIMES
     unsigned long long ot_node_cycles, ot_leaf_cycles, ot_node_trips, ot_leaf_trips, ot_rounds;  // closest-first walk, per wave
@@ -322,7 +323,14 @@ struct BoxLoopIdle {
         if (holds_leaf) wc.wait_leaf += round_trips - my_trips;
         else wc.wait_done += round_trips - my_trips;   // finished, out of budget, or cut by the early leave
     }
+    // (by the lane that counts the wave's trips: the trip about to be made has `n_searching` lanes searching)
+    __device__ __forceinline__ static void low(uint32_t n_searching, WorkCount& wc) {
+        wc.low_trips[0] += n_searching < 8u ? 1u : 0u;
+        wc.low_trips[1] += n_searching < 16u ? 1u : 0u;
+        wc.low_trips[2] += n_searching < 24u ? 1u : 0u;
+    }
 #else
+    __device__ __forceinline__ static void low(uint32_t, WorkCount&) {}
     __device__ __forceinline__ void trip(bool) {}
     template <bool COUNT>
     __device__ __forceinline__ void book(bool, WorkCount&) const {}
@@ -535,7 +543,18 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         const uint32_t n_entered0 = (uint32_t)__popcll(search_mask), n_entered = max(n_entered0, 1u);
         BoxLoopIdle idle;
         uint32_t n_searching = n_entered0;
-        while (n_searching * MPT_LEAF_EARLY >= n_entered && (!BUDGETED || trips < budget)) {
+        // A budgeted step of the lean kernels (PAIRS).  The 1/8 rule is one bound for the round, n_searching >= max(ceil(n_entered / 8), 1):
+        // a compare per trip where there were a shift and a compare.  And the loop's control — population count, the two compares, the
+        // branch — runs every second trip: the second trip of a pair runs under the mask the first one left, so no lane tests a node
+        // it would not have tested, and since every exit rule of this loop is an economy, not semantics, the leaf phase or the park may
+        // come one trip later (an odd budget: one trip over).  (Also stopping the loop once fewer lanes than the ring-0 rule's N0
+        // search was built and priced: 0.06 ms slower, it starts leaf phases early — profiles/r28_ring0_rule.txt.)
+        constexpr bool PAIRS = LEAN && BUDGETED;
+        constexpr int TRIPS_PER_CHECK = PAIRS ? 2 : 1;
+        const uint32_t need = PAIRS ? max((n_entered0 + MPT_LEAF_EARLY - 1u) / MPT_LEAF_EARLY, 1u) : 0u;
+        while ((PAIRS ? n_searching >= need : n_searching * MPT_LEAF_EARLY >= n_entered) && (!BUDGETED || trips < budget)) {
+#pragma unroll
+          for (int rep = 0; rep < TRIPS_PER_CHECK; ++rep) {
             // LEAN: `searching` is the ballot the trip before (or the entry) took, handed back to the lanes — the compiler does not merge a
             // compare that feeds a ballot with the same compare feeding the exec mask, so the plain form issues it twice per trip
             // (priced: profiles/r17_lean_primary.txt)
@@ -572,13 +591,17 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
             if (COUNT) {
                 wc.node_visits += searching ? 1u : 0u;
                 wc.aabb_hits += (searching && box) ? 1u : 0u;
-                if (first_active_lane()) wc.node_iters++;
+                if (first_active_lane()) {
+                    wc.node_iters++;
+                    BoxLoopIdle::low(n_searching, wc);
+                }
             }
             const uint32_t next = box ? A : B;
             i = searching ? next : i;
             skip = searching ? B : skip;
             if (BUDGETED) trips++;
             search_mask = __ballot(i < n_nodes);
+          }
             n_searching = (uint32_t)__popcll(search_mask);
         }
         idle.template book<COUNT>((i & MPT_NODE_HOLD) != 0u, wc);
@@ -596,7 +619,13 @@ __device__ __forceinline__ bool closest_hit_resume(const SceneDev& sc, LdsNodes 
         if (going == 0ull) break;
         // ... and, in a budgeted step, while enough lanes are still working: the stragglers of a step are parked and
         // meet other stragglers in the next ring instead of holding 64 lanes for their long walks
-        if (BUDGETED && (uint32_t)__popcll(going) < min_active) break;
+        if (BUDGETED && (uint32_t)__popcll(going) < min_active) {
+#if defined(MPT_LEAN_RING_CONTROL)   // (a test's build: a ray this exit parks in a ring-0 step of the lean kernels — the one ring with a trip
+                                     //  budget — loses its walk and counts as finished: tests/test_gpu_ring0_rule.py must then fail)
+            if (LEAN && budget < 0x7FFFFFFFu && i < n_nodes) i = n_nodes;
+#endif
+            break;
+        }
     }
     }
     if (LEAN && ALL_LDS) {   // (the block is staged with the entry terms: wavelocal_body)

@@ -69,6 +69,8 @@ static WaveBudgets default_budgets() {
         w.b[k] = k + 1 < MPT_WL_LEVELS && k < 7 ? ladder[k] : MPT_WL_NO_BUDGET;
         // a step of ring 1.. also ends once fewer than 24 of its 64 lanes are still traversing (the stragglers are
         // parked and regrouped): 29.9 -> 28.5 ms; 16 or 32 lanes are about as good, 8 is not, ring 0 is better without
+        // (round 3, five rings, no carry rule.  The lean kernels, whose values are their own constants — mpt_lds_cfg.h — end a ring-0 step
+        //  below 8 lanes: swept again on them, profiles/r28_ring0_rule.txt.  The generic kernels were not swept and keep 0.)
         w.min_active[k] = k == 0 ? 0 : 24;
     }
     return w;
@@ -370,6 +372,8 @@ struct mpt_ctx : SceneState {
     // 128 / 256 / 512 / 1024 -> 16.79-16.86 / 16.70 / 16.62-16.65 / 16.65 / 17.87 ms, the 1/8 shard's serial step 2.54 / - / 2.71 / 3.36
     uint32_t wl_min = 0, wl_div = 32;
     bool wl_lean = true;               // MPT_WL_LEAN=0: every wave-local pass runs the generic kernels (development knob)
+    bool ring_knobs_set = false;       // MPT_BUDGETS / MPT_MIN_ACTIVE / MPT_LIGHT_BUDGET given: the generic kernels too, whose ring steps read `budgets`
+                                       // (the lean kernels' are constants, mpt_lds_cfg.h)
     bool lean_tiles = true;            // MPT_LEAN_TILES=0: the lean kernels get no class table, every tile is "general" (mpt_lean_tiles.h; development knob)
     bool lean_sky_resolve = true;      // MPT_LEAN_SKY_RESOLVE=0: the lean kernels trace the sky tiles and the resolve reads their slots (development knob)
     LeanCdivCache lean_cdiv;           // is the lean kernels' division by W and H exact at this context's size (mpt_lean_cdiv.h)
@@ -542,6 +546,9 @@ static int create_impl(int device_ordinal, mpt_ctx** out) {
         uint32_t b = (uint32_t)atoi(e);
         for (uint32_t k = 0; k + 1 < MPT_WL_LEVELS; ++k) ctx->budgets.b[k] = b > (1u << 28) ? b : std::min<uint64_t>((uint64_t)b << k, MPT_WL_NO_BUDGET);
     }
+#if !defined(MPT_LEAN_RING_TESTING)   // (a test's build of the lean kernels reads the values as the generic ones do)
+    ctx->ring_knobs_set = getenv("MPT_BUDGETS") || getenv("MPT_MIN_ACTIVE") || getenv("MPT_LIGHT_BUDGET");
+#endif
     if ((e = getenv("MPT_WL_MIN")) && atoi(e) >= 64) ctx->wl_min = (uint32_t)atoi(e) & ~63u;
     if ((e = getenv("MPT_TILE_ORDER"))) {
         ctx->tile_order_mode = atoi(e);
@@ -1154,7 +1161,8 @@ static int select_trace_kernel(mpt_ctx* ctx, Lane& L, const mpt_render_params* p
         // resolve of the render before it (k_wavelocal_corun); only then may the end of one pass overlap the start of the next (order_behind_previous_trace)
         g.corun = (ctx->lane_order & 4) && !ctx->sync_render && !count;
         // Philox + Lambert without counters, inside the ranges of the lean kernels' 24-bit index arithmetic: the lean variant of the same kernel
-        const bool lean = ctx->wl_lean &&
+        // ... and with the ring knobs untouched (the lean kernels' ring budgets are their own constants)
+        const bool lean = ctx->wl_lean && !ctx->ring_knobs_set &&
                           wl_lean_ok(ctx->n_prims, n_local_tiles, pp.tiles_x, ctx->W, ctx->H, pp.nranks, pp.S, pp.tile_magic, p->rng_mode, p->bsdf_mode, count, &g.lean_args) &&
                           lean_cdiv_ok(ctx->lean_cdiv, pp.W, pp.H, [&](float W, float H, uint32_t* bad) { return lean_cdiv_device_check(ctx, L.stream.get(), W, H, bad); });
         variant = (g.corun ? TK_CORUN : 0) | (lean ? TK_LEAN : 0);

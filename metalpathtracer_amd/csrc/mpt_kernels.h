@@ -853,6 +853,13 @@ struct WaveStepDiag {
         atomicAdd(lv + 5, 1ull);  // rays in the step
         if (wc.wait_leaf != wc0.wait_leaf) atomicAdd(lv + 7, (unsigned long long)(wc.wait_leaf - wc0.wait_leaf));
         if (done) atomicAdd(lv + 6, 1ull);
+        // rows 8.. of the block, per step kind: box trips made with fewer than 8 / 16 / 24 lanes searching, and the steps that made any
+        unsigned long long* lo = lv + 8ull * 8ull;
+        for (int q = 0; q < 3; ++q) {
+            const uint32_t n = wc.low_trips[q] - wc0.low_trips[q];
+            if (n != 0u) atomicAdd(lo + q, (unsigned long long)n);
+            if (__ballot(n != 0u) != 0ull && first_active_lane()) atomicAdd(lo + 3 + q, 1ull);
+        }
     }
     template <bool COUNT>
     __device__ __forceinline__ void traffic(const WaveRings& ring, uint32_t lane, unsigned long long am, unsigned long long pm, bool keep, bool alive, bool parked,
@@ -940,6 +947,12 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
     static_assert(!(LEAN && COUNT), "the lean body does not count");
     // the per-tile class words (mpt_lean_tiles.h) are read by the primary steps of the lean kernels whose whole tree is in LDS
     constexpr bool TILES = LEAN && ALL_LDS;
+    // the ring steps of the lean kernels run on the constants of mpt_lds_cfg.h (two rings: what those constants describe)
+#if defined(MPT_LEAN_RING_TESTING)
+    constexpr bool RING_CONSTS = false;
+#else
+    constexpr bool RING_CONSTS = LEAN && MPT_WL_LEVELS == 2u;
+#endif
     extern __shared__ float4 lds_nodes_raw[];
     // what only some steps need goes to LDS, behind the scene image (the 256-byte descriptor area of MPT_LDS_EXTRA), instead of
     // living in scalar registers across the whole step loop: the camera (14 words, primary steps) and the ring budgets (10 words,
@@ -1144,7 +1157,12 @@ __device__ __forceinline__ void wavelocal_body(const PassParams& pp, const WaveR
                 cnt[k] -= tk;
                 assigned += tk;
             }
-            if (level < (int)MPT_WL_LEVELS) {   // (a ring step: its budget and its minimum of working lanes, from the LDS copy)
+            if (RING_CONSTS) {   // (a ring step of the lean kernels: its budget and its minimum of working lanes are the kernel's, mpt_lds_cfg.h)
+                if (level < (int)MPT_WL_LEVELS) {
+                    budget = level == 0 ? MPT_LEAN_RING0_BUDGET : MPT_WL_NO_BUDGET;
+                    min_active = level == 0 ? MPT_LEAN_RING0_N0 : MPT_LEAN_RING1_N;
+                }
+            } else if (level < (int)MPT_WL_LEVELS) {   // (a ring step: its budget and its minimum of working lanes, from the LDS copy)
                 budget = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_BUDGET + level]);
                 min_active = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_cfg_u32[CFG_W_MIN_ACTIVE + level]);
             }

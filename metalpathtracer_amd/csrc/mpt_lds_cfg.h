@@ -51,6 +51,23 @@ enum : uint32_t {
     CFG_TAIL_W_LEAF = 4u * CFG_TAIL_LO + CFG_W_OF_F4,
     CFG_TAIL_W_PRIMARY = 4u * CFG_TAIL_HI + CFG_W_OF_F4,
 };
+// What the lean k_wavelocal kernels do NOT read from the block: the trip budget and the lane minimum of their ring steps are constants
+// of the kernels (the generic kernels read CFG_W_BUDGET / CFG_W_MIN_ACTIVE, which the environment can set; a context whose values differ
+// from these runs the generic kernels — select_trace_kernel).  Swept together on the bench step, profiles/r28_ring0_rule.txt.
+//   ring 0: a step makes at most MPT_LEAN_RING0_BUDGET box trips and ends — its unfinished rays parked in ring 1 — once fewer than
+//           MPT_LEAN_RING0_N0 of its lanes still walk (asked after every leaf phase, where the generic kernels ask their minimum)
+//   ring 1: no trip budget, and the step ends once fewer than MPT_LEAN_RING1_N lanes still walk (the generic kernels' default)
+// A -DMPT_LEAN_RING_TESTING build (tests/test_gpu_ring0_rule.py) reads the block instead, so that a test can set any pair.
+#ifndef MPT_LEAN_RING0_BUDGET
+#define MPT_LEAN_RING0_BUDGET 8u
+#endif
+#ifndef MPT_LEAN_RING0_N0
+#define MPT_LEAN_RING0_N0 8u
+#endif
+#define MPT_LEAN_RING1_N 24u
+#if defined(MPT_LEAN_RING_CONTROL) && !defined(MPT_LEAN_RING_TESTING)
+#error "MPT_LEAN_RING_CONTROL makes a parked ray forget what it had found: test builds only (-DMPT_LEAN_RING_TESTING)"
+#endif
 static_assert(CFG_W_BUDGET + CFG_MAX_LEVELS <= CFG_W_MIN_ACTIVE && CFG_W_MIN_ACTIVE + CFG_MAX_LEVELS - 1u <= CFG_W_INPLACE_MIN,
               "configuration block: the per-level words overlap (the last minimum shares its word with k_ordered's threshold: MPT_OT_MLEVELS < 8)");
 static_assert(4u * CFG_F4_WORDS + CFG_N_WORDS <= 4u * CFG_F4_ENTRY_LO, "configuration block: the word area runs into the entry terms");

@@ -76,6 +76,18 @@ if flags:
         print("  %-8s steps %9d  rays/step %5.1f  done %5.1f %%  box trips %7.1f util %4.1f %%  prim trips %6.1f util %4.1f %%  cost share %4.1f %%  box slots waiting with a leaf %4.1f %%" % (
             nm, st_, rays / st_, 100 * dn / max(1, rays), bt / st_, 100 * bw / max(1, 64 * bt), pt / st_, 100 * pw / max(1, 64 * pt),
             100 * (bt * 26 + pt * 70) / tot, 100 * wl / max(1, 64 * bt)))
+    # rows 8.. of the block, per step kind: the box trips made with fewer than 8 / 16 / 24 lanes searching and the steps that made any
+    all_trips = lv[:len(names), 1].sum()
+    print("box trips made with few lanes searching (per step kind; %% of the kind's trips, %% of all %d box trips of the launch):" % all_trips)
+    for i, nm in enumerate(names):
+        st_, bt = lv[i, 0], lv[i, 1]
+        if st_ == 0: continue
+        row = lv[8 + i]
+        J.setdefault("low_lane_trips", {})[nm] = {"fewer_than_%d" % n: {"trips": row[q], "steps": row[3 + q], "pct_of_kind_trips": 100 * row[q] / max(1, bt),
+                                                                      "pct_of_all_trips": 100 * row[q] / max(1, all_trips), "pct_of_kind_steps": 100 * row[3 + q] / st_}
+                                                  for q, n in enumerate((8, 16, 24))}
+        print("  %-8s" % nm + "".join("  < %2d: %9d trips (%4.1f %% / %4.1f %%) in %8d steps (%4.1f %%)" % (
+            n, row[q], 100 * row[q] / max(1, bt), 100 * row[q] / max(1, all_trips), row[3 + q], 100 * row[3 + q] / st_) for q, n in enumerate((8, 16, 24))))
     # rows 15 and 14 of the block, the ring traffic by record: hits that stayed in their lanes for the ring-0 step that followed
     # (the carry) against hits pushed to ring 0, and the rays parked in ring 1; a record is 48 bytes, 16 more if the path has
     # gathered light, 16 more (the walk state) for a parked ray
