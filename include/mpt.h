@@ -950,8 +950,8 @@ int mpt_get_light_candidates(mpt_ctx* ctx, uint32_t* m);
  * resampling", the spatial part).  Only a reservoir whose sample was found visible carries weight.  A new call with state of its own: no
  * other call, result or kernel changes.  tests/restir_ref.py restates the section in numpy.  float32, one IEEE operation at a time in the
  * order written; dot, normalize, u01, sincos_2pi, philox and the origin o as in the direct-lighting section.
- * OUT OF SCOPE: temporal reuse over a camera path (the reprojection of mpt_temporal_accumulate is what it would use), mpt_render_nee,
- * cone sampling, the adaptive calls.  The pass samples lights by AREA only: under MPT_LIGHT_SAMPLING_CONE the call returns
+ * OUT OF SCOPE: mpt_render_nee, cone sampling, the adaptive calls.  Temporal reuse over a camera path is a call of its own,
+ * mpt_direct_restir_temporal (the "temporal reservoir reuse" section below).  The pass samples lights by AREA only: under MPT_LIGHT_SAMPLING_CONE the call returns
  * MPT_ERR_INVALID_ARG, because a direction drawn in one point's cone is not a sample for another point.
  *
  * Surface pixels, emitters, misses, o, n and the final rgba = ((albedo.c * 0.31830987f) * (S.c / (float)N), 1) are the direct pass's.
@@ -1026,6 +1026,93 @@ int mpt_restir_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float*
                      const mpt_uniforms* cam_uniforms, const mpt_restir_params* params, float* rgba_out, uint32_t* traced_out,
                      uint32_t* unoccluded_out);
 int mpt_read_restir_reservoirs(mpt_ctx* ctx, int32_t which, uint32_t* out /* W*H*6 */);
+
+/* ---- temporal reservoir reuse in the direct pass over a camera path ---------------------------------------------------------------
+ * mpt_direct_restir_temporal is one FRAME of the direct pass in which a pixel does not forget last frame's candidates: one round, m
+ * candidates (the context's mpt_set_light_candidates setting, read at the start of the call; it may differ from frame to frame), the
+ * pixel's one-sample reservoir merged with the reservoir of the ONE nearest pixel of the previous frame that the pixel's surface point
+ * reprojects to (Bitterli et al. 2020, the temporal part).  The candidates of the frames before cost one reprojection and, UNBIASED, one
+ * ray.  A new call with state of its own: no other call, result or kernel changes; there is no spatial step in the same frame.
+ * tests/restir_temporal_ref.py restates the section in numpy.  float32, one IEEE operation at a time in the order written; dot, u01,
+ * philox, the light sample of (k, ua, ub) from any (o, n), its factor fac, l_y, Le and the origin o as in the direct-lighting,
+ * light-candidates and spatial sections.  Lights are sampled by AREA only, as there.
+ *
+ * State per context, two of each, ping-pong, with the lifetime of the mpt_temporal_* history: a reservoir per pixel — two uint4,
+ * (k, ua, ub, wsum) (fac, flags, Mh, 0); flags bit 0 = the reservoir HOLDS, bit 1 = the pick was the pixel's own sample; Mh = the count
+ * (uint32) of the candidates the reservoir stands for, 0 exactly at pixels that were no surface — the history guide of its frame ((normal
+ * facing the ray, t), t = +inf for a miss) and that frame's fourteen camera floats.  Allocated by the first call; dropped by mpt_resize,
+ * mpt_upload_scene, mpt_build_and_upload and mpt_restir_temporal_reset.  The scene is static while a history lives: that is why a ray
+ * from last frame's surface point may be traced in the current scene.
+ *
+ * C = max_history, primes mark the history's camera.  For every surface pixel p (class 0) of the frame:
+ * Step A.  The spatial step A with s = frame, for every pixel before any pixel's step T: the own reservoir HOLDS
+ *   (k, ua, ub, wsum_p, fac_p) iff something was taken and its shadow ray arrives.
+ * Step T, the tap.  No valid history: no tap.  The camera's fourteen floats equal the history's bit for bit: the tap is q = p and no
+ *   test applies (step 6 of the temporal section).  Otherwise steps 1-3 of mpt_temporal_accumulate with the hit rule give r, s, fx, fy
+ *   under the same conditions (s > 0, s finite, -1 <= fx < W, -1 <= fy < H; a NaN fails them); qx = (int)floor(fx + 0.5f), qy
+ *   likewise; the tap COUNTS iff q is inside the image (tested on the integers), the history guide at q is a hit,
+ *   |t_q - |r|| <= depth_tolerance * |r| and dot(n_p, n_q) >= normal_threshold.  The tap is ACCEPTED iff it counts and Mh_q > 0.
+ * Step B.  held = own = (the own reservoir holds); y = its sample; Wp = wsum_p if it holds, else 0.  ACCEPTED: Mc = min(Mh_q, C * m).
+ *   ACCEPTED and q HOLDS: the light sample of (k_q, ua_q, ub_q) formed from (o_p, n_p), fac its factor,
+ *     w = (wsum_q * (fac / fac_q)) * ((float)Mc / (float)Mh_q); it COUNTS iff ok && w > 0 && w < +inf
+ *   it counts: Wp = Wp + w; it is TAKEN iff !held || u01(r.z) * Wp < w, r = philox4x32_10(counter = (py*W+px, frame, 0xFFFFFFFB, 0), key)
+ *     (word 2 = 0xFFFFFFFB is nobody else's); taking sets y = q's sample, own = false, yfac = fac; then held = true
+ *   Not held: the frame adds nothing and traces nothing more.
+ * Step C.  The spatial step C: own: no ray.  Otherwise traced += 1, the ray is any-hit(o_p, wi_y, dist_y * 0.9990234375f) with y formed
+ *   from (o_p, n_p); occluded: the frame adds nothing, traces nothing more and the new reservoir does not hold; else unoccluded += 1.
+ * Step D.  Z = m.  ACCEPTED, q holding or not: y formed from (o_q', n_q'), last frame's point at q — the origin o evaluated with the
+ *   HISTORY's camera at the integer pixel q with the history guide's t and n: the bits frame f-1 used.  If ok && fac > 0 && fac < +inf:
+ *   MPT_RESTIR_BIASED: Z += Mc.  MPT_RESTIR_UNBIASED: traced += 1, the ray is any-hit(o_q', wi, dist * 0.9990234375f); not occluded:
+ *   unoccluded += 1, Z += Mc.
+ * Step E.  Fy = (Wp / (float)Z) / l_y, S = Le_y * Fy, rgba = ((albedo.c * 0.31830987f) * (S.c / 1.0f), 1).  Mnew = m + (ACCEPTED ? Mc : 0).
+ *   The frame went through: the new reservoir HOLDS (yk, yua, yub, Wp * ((float)Mnew / (float)Z), yfac), flags = 1 | own << 1,
+ *   Mh = Mnew.  Otherwise it is zeros with Mh = Mnew and S = 0.  A pixel that is no surface stores zeros and rgba = (0, 0, 0, 1).
+ *   The new history guide is the current guide, written for every pixel.
+ *
+ * With no accepted tap, rgba, traced and unoccluded are bit for bit mpt_direct_restir's with K = 0, N = 1, sample_begin = frame.
+ * UNBIASED is unbiased because a stored sample passed a shadow ray at its own pixel: the history's support is "visible from o_q' with a
+ * positive factor", which is what step D tests — the 1/Z weight of Alg. 6 with the temporal neighbour counted Mc times.  BIASED omits
+ * the ray and darkens where last frame's point could not see y.  Frames share samples over time: their noise is correlated, and feeding
+ * them to mpt_temporal_accumulate is out of scope, as are a spatial merge in the same frame, more than one round per frame,
+ * mpt_render_nee and moving geometry.
+ *
+ * The call waits for queued renders, refreshes stale guides and the stale light table, and writes no other stage's state.
+ * MPT_ERR_INVALID_ARG with nothing changed — the result and the history stay: null params, a bad walk or mode, a NaN threshold or
+ * tolerance, max_history > MPT_RESTIR_TEMPORAL_MAX_HISTORY, cone sampling in effect.  MPT_ERR_NOT_READY and MPT_ERR_BAD_SCENE as the
+ * direct pass.
+ * mpt_restir_temporal_info: traced summed over the image = rays_initial + rays_final + rays_correction; rays_occluded of all three
+ * kinds; history_accepted = surface pixels with an ACCEPTED tap, pixels_reset the other surface pixels; samples_from_history = the
+ * pixels whose step B ended with the history's sample.
+ * Read-backs and hooks.  mpt_read_restir_temporal_reservoirs: the frame's reservoirs, seven words per pixel — k, the bits of ua, ub,
+ * wsum, fac, then flags and Mh.  mpt_restir_temporal_image: the same kernels on caller arrays (needs a scene and no size; never touches
+ * the context's history): reservoirs_prev = W*H*7 words in that format, or NULL = no history (the three other *_prev arguments are
+ * ignored); a holding reservoir whose k is no light of the table is MPT_ERR_INVALID_ARG.                                              */
+#define MPT_RESTIR_TEMPORAL_DEFAULT_HISTORY 20u   /* Bitterli et al.'s cap */
+#define MPT_RESTIR_TEMPORAL_MAX_HISTORY 1024u
+typedef struct mpt_restir_temporal_params {
+    uint32_t frame;                        /* Philox counter word 1, where the spatial pass has s                                      */
+    uint32_t seed_lo, seed_hi;
+    int32_t walk;                          /* MPT_WALK_*                                                                               */
+    int32_t mode;                          /* MPT_RESTIR_UNBIASED or MPT_RESTIR_BIASED                                                 */
+    uint32_t max_history;                  /* C: 1..MPT_RESTIR_TEMPORAL_MAX_HISTORY, 0 = MPT_RESTIR_TEMPORAL_DEFAULT_HISTORY           */
+    float normal_threshold, depth_tolerance;   /* <= 0: MPT_RESTIR_DEFAULT_*                                                           */
+} mpt_restir_temporal_params;
+typedef struct mpt_restir_temporal_info {
+    uint64_t pixels_surface, rays_initial, rays_final, rays_correction, rays_occluded, history_accepted, samples_from_history, pixels_reset,
+        lights;
+    double device_ms;                      /* HIP-event time of the two launches (guide refresh and table build not included)          */
+} mpt_restir_temporal_info;
+int mpt_direct_restir_temporal(mpt_ctx* ctx, const mpt_restir_temporal_params* params, mpt_restir_temporal_info* out /* may be NULL */);
+int mpt_read_restir_temporal(mpt_ctx* ctx, float* rgba /* W*H*4 */, uint32_t* traced /* W*H, may be NULL */, uint32_t* unoccluded /* may be NULL */);
+int mpt_restir_temporal_buffer(mpt_ctx* ctx, void** device_ptr, uint64_t* bytes);   /* the RGBA32F image, laid out as the HDR sum      */
+int mpt_read_restir_temporal_reservoirs(mpt_ctx* ctx, uint32_t* out /* W*H*7 */);
+int mpt_restir_temporal_reset(mpt_ctx* ctx);
+int mpt_restir_temporal_image(mpt_ctx* ctx, uint32_t width, uint32_t height, const float* albedo_depth_cur, const float* normal_class_cur,
+                              const mpt_uniforms* cam_cur, const float* albedo_depth_prev, const float* normal_class_prev,
+                              const mpt_uniforms* cam_prev, const uint32_t* reservoirs_prev /* W*H*7, or NULL */,
+                              const mpt_restir_temporal_params* params, float* rgba_out, uint32_t* traced_out /* may be NULL */,
+                              uint32_t* unoccluded_out /* may be NULL */, uint32_t* reservoirs_out /* W*H*7, may be NULL */,
+                              mpt_restir_temporal_info* out /* may be NULL */);
 
 /* RNG known-answer hooks evaluated ON THE DEVICE (Random.h:6-16 and the philox / sincos spec).      */
 int mpt_kat_pcg(mpt_ctx* ctx, const uint32_t* seeds, uint64_t n, uint32_t* hash_out, float* float_out);

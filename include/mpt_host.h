@@ -108,6 +108,12 @@ int mpt_renderer_direct_lighting(mpt_renderer* r, uint32_t samples, int32_t walk
  * the default thresholds.  rgba: W*H*4 floats.  out may be NULL.                                                                       */
 int mpt_renderer_direct_restir(mpt_renderer* r, uint32_t samples, uint32_t neighbours, uint32_t radius, int32_t mode, int32_t walk, float* rgba,
                                mpt_restir_info* out);
+/* mpt_direct_restir_temporal + mpt_read_restir_temporal (include/mpt.h) for the renderer's camera: frame number `frame` of a camera
+ * path with the pending mpt_renderer_input applied, its reservoirs merged with the previous frame's — `max_history` 1..1024 (0 = the
+ * default), `mode` MPT_RESTIR_UNBIASED or MPT_RESTIR_BIASED, the default thresholds, the context's light candidates.  rgba: W*H*4
+ * floats.  out may be NULL.                                                                                                           */
+int mpt_renderer_direct_restir_temporal(mpt_renderer* r, uint32_t frame, uint32_t max_history, int32_t mode, int32_t walk, float* rgba,
+                                        mpt_restir_temporal_info* out);
 /* mpt_render_nee (include/mpt.h) for the renderer's camera and render parameters: samples [0, spp) onto the HDR sum (read it with
  * mpt_renderer_read_sum) at max_depth `depth`, `walk` one of MPT_WALK_*, clamp <= 0 = no per-sample clamp.  out may be NULL.          */
 int mpt_renderer_render_nee(mpt_renderer* r, uint32_t spp, int32_t depth, int32_t walk, float clamp, mpt_nee_info* out);

@@ -41,6 +41,8 @@ SYMBOLS = (
     "mpt_render_nee", "mpt_set_light_sampling", "mpt_get_light_sampling", "mpt_render_nee_adaptive",
     "mpt_set_light_candidates", "mpt_get_light_candidates",
     "mpt_direct_restir", "mpt_read_restir", "mpt_restir_buffer", "mpt_restir_image", "mpt_read_restir_reservoirs",
+    "mpt_direct_restir_temporal", "mpt_read_restir_temporal", "mpt_restir_temporal_buffer", "mpt_read_restir_temporal_reservoirs",
+    "mpt_restir_temporal_reset", "mpt_restir_temporal_image",
 )
 
 # mpt_scene_digest's words: the nine device arrays (mpt_read_scene_array's `which`), then the seven counts
@@ -74,6 +76,9 @@ RESTIR_UNBIASED, RESTIR_BIASED = 0, 1
 RESTIR_MAX_NEIGHBOURS, RESTIR_MAX_RADIUS = 16, 64
 # include/mpt.h MPT_RESTIR_DEFAULT_* (radius 0 / a threshold <= 0 selects them)
 RESTIR_DEFAULTS = dict(radius=4, normal_threshold=0.5, depth_tolerance=0.05)
+# include/mpt.h MPT_RESTIR_TEMPORAL_* (max_history 0 / a threshold <= 0 selects the defaults)
+RESTIR_TEMPORAL_MAX_HISTORY = 1024
+RESTIR_TEMPORAL_DEFAULTS = dict(max_history=20, normal_threshold=0.5, depth_tolerance=0.05)
 
 
 class MptError(RuntimeError):
@@ -272,6 +277,27 @@ def restir_params(samples=16, sample_begin=0, seed=(0, 0), walk=WALK_AUTO, neigh
                         int(radius), int(mode), float(normal_threshold), float(depth_tolerance))
 
 
+class RestirTemporalParams(C.Structure):
+    _fields_ = [("frame", C.c_uint32), ("seed_lo", C.c_uint32), ("seed_hi", C.c_uint32), ("walk", C.c_int32), ("mode", C.c_int32),
+                ("max_history", C.c_uint32), ("normal_threshold", C.c_float), ("depth_tolerance", C.c_float)]
+
+
+class RestirTemporalInfo(C.Structure):
+    _fields_ = [("pixels_surface", C.c_uint64), ("rays_initial", C.c_uint64), ("rays_final", C.c_uint64), ("rays_correction", C.c_uint64),
+                ("rays_occluded", C.c_uint64), ("history_accepted", C.c_uint64), ("samples_from_history", C.c_uint64),
+                ("pixels_reset", C.c_uint64), ("lights", C.c_uint64), ("device_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def restir_temporal_params(frame=0, seed=(0, 0), walk=WALK_AUTO, mode=RESTIR_UNBIASED, max_history=0, normal_threshold=0.0, depth_tolerance=0.0):
+    """mpt_restir_temporal_params: frame number `frame` of a camera path, its reservoirs merged with the previous frame's, which count
+    for at most `max_history` frames' candidates (0: the default; a threshold <= 0: its default)."""
+    return RestirTemporalParams(int(frame) & 0xFFFFFFFF, int(seed[0]) & 0xFFFFFFFF, int(seed[1]) & 0xFFFFFFFF, int(walk), int(mode),
+                                int(max_history), float(normal_threshold), float(depth_tolerance))
+
+
 class NeeParams(C.Structure):
     _fields_ = [("walk", C.c_int32), ("clamp", C.c_float)]
 
@@ -431,6 +457,13 @@ def load():
     L.mpt_restir_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.mpt_restir_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), C.POINTER(RestirParams), fp, up, up]
     L.mpt_read_restir_reservoirs.argtypes = [vp, C.c_int32, up]
+    L.mpt_direct_restir_temporal.argtypes = [vp, C.POINTER(RestirTemporalParams), C.POINTER(RestirTemporalInfo)]
+    L.mpt_read_restir_temporal.argtypes = [vp, fp, up, up]
+    L.mpt_restir_temporal_buffer.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.mpt_read_restir_temporal_reservoirs.argtypes = [vp, up]
+    L.mpt_restir_temporal_reset.argtypes = [vp]
+    L.mpt_restir_temporal_image.argtypes = [vp, C.c_uint32, C.c_uint32, fp, fp, C.POINTER(Uniforms), fp, fp, C.POINTER(Uniforms), up,
+                                            C.POINTER(RestirTemporalParams), fp, up, up, up, C.POINTER(RestirTemporalInfo)]
     L.mpt_render_nee.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(NeeInfo)]
     L.mpt_render_nee_adaptive.argtypes = [vp, C.POINTER(RenderParams), C.POINTER(NeeParams), C.POINTER(AdaptiveParams),
                                           C.POINTER(AdaptiveInfo), C.POINTER(NeeInfo)]
@@ -799,6 +832,66 @@ class Context:
         self._chk(self.L.mpt_restir_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), C.byref(p), _fp(rgba), _up(traced), _up(unocc)),
                   "mpt_restir_image")
         return rgba, traced, unocc
+
+    def direct_restir_temporal(self, **kw):
+        """mpt_direct_restir_temporal over the context's guide buffers (restir_temporal_params' keywords): one frame of the direct pass
+        whose reservoirs are merged with the previous frame's; returns the info dict."""
+        p = restir_temporal_params(**kw)
+        info = RestirTemporalInfo()
+        self._chk(self.L.mpt_direct_restir_temporal(self.h, C.byref(p), C.byref(info)), "mpt_direct_restir_temporal")
+        return info.as_dict()
+
+    def read_restir_temporal(self):
+        """(rgba [H,W,4] float32, traced [H,W] uint32, unoccluded [H,W] uint32) of the last direct_restir_temporal."""
+        rgba = np.empty((self.height, self.width, 4), np.float32)
+        traced = np.empty((self.height, self.width), np.uint32)
+        unocc = np.empty((self.height, self.width), np.uint32)
+        self._chk(self.L.mpt_read_restir_temporal(self.h, _fp(rgba), _up(traced), _up(unocc)), "mpt_read_restir_temporal")
+        return rgba, traced, unocc
+
+    def restir_temporal_buffer(self):
+        """(device pointer, bytes) of the last direct_restir_temporal's RGBA32F image."""
+        p, n = C.c_void_p(), C.c_uint64()
+        self._chk(self.L.mpt_restir_temporal_buffer(self.h, C.byref(p), C.byref(n)), "mpt_restir_temporal_buffer")
+        return p.value, n.value
+
+    def read_restir_temporal_reservoirs(self):
+        """The reservoirs the last direct_restir_temporal left for the next frame, [H,W,7] uint32: k, the bits of ua, ub, wsum, fac, flags
+        (bit 0 holds, bit 1 own) and the count Mh."""
+        out = np.empty((self.height, self.width, 7), np.uint32)
+        self._chk(self.L.mpt_read_restir_temporal_reservoirs(self.h, _up(out)), "mpt_read_restir_temporal_reservoirs")
+        return out
+
+    def restir_temporal_reset(self):
+        """mpt_restir_temporal_reset: the next direct_restir_temporal starts without a history."""
+        self._chk(self.L.mpt_restir_temporal_reset(self.h), "mpt_restir_temporal_reset")
+
+    def restir_temporal_image(self, albedo_depth, normal_class, cam, prev=None, **kw):
+        """The kernels of direct_restir_temporal on caller guides [H,W,4] with the camera of `cam` (Uniforms); needs a scene.  prev: None
+        (no history) or (albedo_depth, normal_class, cam, reservoirs [H,W,7]) of the previous frame.  Returns (rgba, traced, unoccluded,
+        reservoirs [H,W,7], info dict)."""
+        ad = np.ascontiguousarray(albedo_depth, np.float32)
+        nc = np.ascontiguousarray(normal_class, np.float32)
+        if ad.ndim != 3 or ad.shape[2] != 4 or nc.shape != ad.shape:
+            raise ValueError("restir_temporal_image: albedo_depth and normal_class must be [H, W, 4] arrays of one shape")
+        H, W = ad.shape[:2]
+        args_prev = (None, None, None, None)
+        if prev is not None:
+            ad_h = np.ascontiguousarray(prev[0], np.float32)
+            nc_h = np.ascontiguousarray(prev[1], np.float32)
+            res_h = np.ascontiguousarray(prev[3], np.uint32)
+            if ad_h.shape != ad.shape or nc_h.shape != ad.shape or res_h.shape != (H, W, 7):
+                raise ValueError("restir_temporal_image: the previous frame's arrays must be [H, W, 4], [H, W, 4] and [H, W, 7]")
+            args_prev = (_fp(ad_h), _fp(nc_h), C.byref(prev[2]), _up(res_h))
+        rgba = np.empty((H, W, 4), np.float32)
+        traced = np.empty((H, W), np.uint32)
+        unocc = np.empty((H, W), np.uint32)
+        res = np.empty((H, W, 7), np.uint32)
+        p = restir_temporal_params(**kw)
+        info = RestirTemporalInfo()
+        self._chk(self.L.mpt_restir_temporal_image(self.h, W, H, _fp(ad), _fp(nc), C.byref(cam), *args_prev, C.byref(p), _fp(rgba), _up(traced),
+                                                   _up(unocc), _up(res), C.byref(info)), "mpt_restir_temporal_image")
+        return rgba, traced, unocc, res, info.as_dict()
 
     def render_nee(self, walk=WALK_AUTO, clamp=0.0, **params):
         """mpt_render_nee: the samples of `params` (the keywords of render) with a light sample and MIS at every Lambert vertex, added

@@ -395,6 +395,20 @@ void Renderer::readDirectRestir(std::vector<float>& rgba) {
     rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
     check(mpt_read_restir(ctx_, rgba.data(), nullptr, nullptr), "mpt_read_restir");
 }
+mpt_restir_temporal_info Renderer::drawDirectRestirTemporal(OffscreenView* /*view*/, uint32_t frame, uint32_t maxHistory, int32_t mode, int32_t walk) {
+    updateCamera();   // (the frame's inputs; the frame counter and the seed protocol of draw() are not this pass's)
+    uniforms_.primitiveCount = scene_->getPrimitiveCount();
+    uniforms_.triangleCount = scene_->getTriangleCount();
+    check(mpt_set_uniforms(ctx_, &uniforms_), "mpt_set_uniforms");
+    const mpt_restir_temporal_params p = {frame, params_.seed_lo, params_.seed_hi, walk, mode, maxHistory, 0.0f, 0.0f};
+    mpt_restir_temporal_info info;
+    check(mpt_direct_restir_temporal(ctx_, &p, &info), "mpt_direct_restir_temporal");
+    return info;
+}
+void Renderer::readDirectRestirTemporal(std::vector<float>& rgba) {
+    rgba.resize(static_cast<size_t>(Camera::screenSize.x) * static_cast<size_t>(Camera::screenSize.y) * 4);
+    check(mpt_read_restir_temporal(ctx_, rgba.data(), nullptr, nullptr), "mpt_read_restir_temporal");
+}
 mpt_nee_info Renderer::renderNee(uint32_t spp, int32_t depth, int32_t walk, float clamp, uint32_t sampleBegin) {
     uniforms_.primitiveCount = scene_->getPrimitiveCount();
     uniforms_.triangleCount = scene_->getTriangleCount();

@@ -93,6 +93,12 @@ public:
     mpt_restir_info renderDirectRestir(uint32_t samples, uint32_t neighbours, uint32_t radius = 0, int32_t mode = MPT_RESTIR_UNBIASED,
                                        int32_t walk = MPT_WALK_AUTO);
     void readDirectRestir(std::vector<float>& rgba);
+    // mpt_direct_restir_temporal: frame number `frame` of a camera path — the frame's inputs applied as drawTemporal applies them, then
+    // one round of the direct pass whose reservoirs are merged with the previous frame's, which count for at most `maxHistory` frames'
+    // candidates (0: the default); readDirectRestirTemporal = the W*H*4 floats of its rgba
+    mpt_restir_temporal_info drawDirectRestirTemporal(OffscreenView* view, uint32_t frame, uint32_t maxHistory = 0, int32_t mode = MPT_RESTIR_UNBIASED,
+                                                      int32_t walk = MPT_WALK_AUTO);
+    void readDirectRestirTemporal(std::vector<float>& rgba);
     // mpt_render_nee: renderBatch's samples [sampleBegin, sampleBegin + spp) onto the HDR sum with a light sample and MIS at every Lambert
     // vertex, at max_depth `depth`, both kinds of ray through `walk` (MPT_WALK_*), per-sample clamp `clamp` (<= 0: none)
     mpt_nee_info renderNee(uint32_t spp, int32_t depth, int32_t walk = MPT_WALK_AUTO, float clamp = 0.0f, uint32_t sampleBegin = 0);

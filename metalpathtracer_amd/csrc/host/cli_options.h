@@ -24,6 +24,7 @@ inline void usage() {
         "           [--gpus N | --devices a,b,...] [--camera-path FILE [--out-dir runs]] [--bvh reference|binned|gpu|auto]\n"
         "           [--checkpoint FILE] [--resume FILE] [--denoise [--denoise-iterations N]] [--ao N [--ao-radius R]]\n"
         "           [--direct N [--direct-walk reference|own|auto] [--restir K [--restir-radius R] [--restir-biased]]]\n"
+        "           [--camera-path FILE --direct 1 --restir-temporal [--restir-history C] [--restir-biased]]\n"
         "           [--nee [--nee-walk reference|own|auto] [--nee-clamp C]]\n"
         "           [--nee-adaptive THRESHOLD [--nee-walk ...] [--nee-clamp C] [--adaptive-min N] [--adaptive-batch N] [--adaptive-floor F]]\n"
         "           [--light-sampling area|cone]\n"
@@ -104,6 +105,14 @@ inline void usage() {
         "                    see the same surface.  Unbiased by default: one more shadow ray per accepted neighbour; --restir-biased omits\n"
         "                    those rays and darkens the image at visibility edges.  The JSON line gains a \"restir\" object.  Lights are\n"
         "                    sampled by area: not with --light-sampling cone.  Without --restir every file and line is what it was\n"
+        "  --restir-temporal with --camera-path and --direct 1: temporal reservoir reuse (mpt_direct_restir_temporal, include/mpt.h) — every\n"
+        "                    frame of the path is one round of the direct pass in which a pixel merges the sample its --light-candidates\n"
+        "                    pick with the reservoir of the pixel its surface point had in the frame before, which counts for at most\n"
+        "                    --restir-history C frames' candidates (1..1024, default 20).  Unbiased by default: one more shadow ray per\n"
+        "                    accepted history; --restir-biased omits it.  The frame's direct lighting goes to <out-dir>/frame_NNNN.ppm through\n"
+        "                    the same writer, --out gets the last frame, the per-frame JSON line gains \"accepted\", \"from_history\" and\n"
+        "                    \"reset\".  Not with --restir K, --light-sampling cone, --temporal, --svgf, --denoise, the display flags,\n"
+        "                    --gpus > 1, --checkpoint or --resume.  Without it every file and line is what it was\n"
         "  --denoise         write the denoised image (mpt_denoise: first-hit guides + a-trous filter, include/mpt.h) to --out\n"
         "                    and to every --camera-path frame; with --gpus N the root's reduced sum; N levels (default 3, 0..8)\n"
         "  --bvh             tree builder: the reference's sweep SAH (default with --rng literal, --frames and --camera-path:\n"
@@ -156,6 +165,8 @@ struct Options {
     int lightSampling = MPT_LIGHT_SAMPLING_AREA, lightCandidates = 1;
     bool haveRestir = false, haveRestirRadius = false, restirBiased = false;
     int restirK = 0, restirRadius = 0;
+    bool restirTemporal = false, haveRestirHistory = false;   // --restir-temporal, --restir-history C
+    int restirHistory = 0;        // (0 = the default of include/mpt.h)
     bool display = false;         // a display flag was given: .ppm files come from mpt_display
     mpt_display_params shown = {};   // (clamp, srgb, and 0 = the defaults of include/mpt.h; source and samples are set per call)
 
@@ -336,6 +347,8 @@ static std::vector<Flag> flagTable(Options& o) {
         {"--restir", &o.restirK, &o.haveRestir},
         {"--restir-radius", &o.restirRadius, &o.haveRestirRadius},
         {"--restir-biased", &o.restirBiased},
+        {"--restir-temporal", &o.restirTemporal},
+        {"--restir-history", &o.restirHistory, &o.haveRestirHistory},
         {"--adaptive", &o.adp.threshold, &o.adaptive},
         {"--nee-adaptive", &o.adp.threshold, &o.neeAdaptive},
         {"--adaptive-min", &o.adp.min_samples},
@@ -437,7 +450,8 @@ static const Check
                   kLiteralRng, kScatterAll}},
     kDirectCheck = {"--direct", kDirect.holds,
                     {{[](const Options& o) { return o.direct < 1 || o.direct > static_cast<int>(MPT_DIRECT_MAX_SAMPLES); }, "a sample count outside 1..1024"},
-                     kOutNoPpm, kAo, kFrames, kCameraPath, kSeveralGpus, kAdaptive, kDenoise, kDisplayFlags, kTemporal, kSvgf, kCheckpoint, kResume}},
+                     {[](const Options& o) { return o.restirTemporal ? !o.out.empty() && !o.outPpm() : !o.outPpm(); }, kOutNoPpm.words}, kAo, kFrames,
+                     {[](const Options& o) { return !o.restirTemporal && kCameraPath.holds(o); }, kCameraPath.words}, kSeveralGpus, kAdaptive, kDenoise, kDisplayFlags, kTemporal, kSvgf, kCheckpoint, kResume}},
     kAoCheck = {"--ao", kAo.holds,
                 {{[](const Options& o) { return o.ao < 1 || o.ao > static_cast<int>(MPT_AO_MAX_SAMPLES); }, "a sample count outside 1..1024"},
                  kOutNoPpm, kFrames, kCameraPath, kSeveralGpus, kAdaptive, kDenoise, kDisplayFlags, kTemporal, kSvgf, kCheckpoint, kResume}},
@@ -448,11 +462,26 @@ static const Check
 
 // --restir's refusals are whole sentences of their own
 inline const char* restirRefusal(const Options& o) {
-    if (!o.haveRestir && !o.haveRestirRadius && !o.restirBiased) return nullptr;
+    if (!o.haveRestir && !o.haveRestirRadius && !(o.restirBiased && !o.restirTemporal)) return nullptr;   // (--restir-temporal takes --restir-biased too)
     return !o.haveRestir ? "--restir-radius and --restir-biased go with --restir K" : !o.haveDirect ? "--restir goes with --direct"
            : o.restirK < 0 || o.restirK > static_cast<int>(MPT_RESTIR_MAX_NEIGHBOURS) ? "--restir takes a count in 0..16"
            : o.haveRestirRadius && (o.restirRadius < 1 || o.restirRadius > static_cast<int>(MPT_RESTIR_MAX_RADIUS)) ? "--restir-radius takes a radius in 1..64"
            : o.lightSampling == MPT_LIGHT_SAMPLING_CONE ? "--restir cannot be combined with --light-sampling cone" : nullptr;
+}
+
+// ... and so are --restir-temporal's (before --direct's rows: with this flag the pass runs along a camera path)
+inline const char* restirTemporalRefusal(const Options& o) {
+    if (!o.restirTemporal) return o.haveRestirHistory ? "--restir-history goes with --restir-temporal" : nullptr;
+    return o.cameraPath.empty() ? "--restir-temporal goes with --camera-path" : !o.haveDirect ? "--restir-temporal goes with --direct 1"
+           : o.direct != 1 ? "--restir-temporal takes --direct 1: a frame is one round"
+           : o.haveRestir || o.haveRestirRadius ? "--restir-temporal cannot be combined with --restir K"
+           : o.lightSampling == MPT_LIGHT_SAMPLING_CONE ? "--restir-temporal cannot be combined with --light-sampling cone"
+           : o.temporal ? "--restir-temporal cannot be combined with --temporal" : o.svgf ? "--restir-temporal cannot be combined with --svgf"
+           : o.denoise ? "--restir-temporal cannot be combined with --denoise" : o.display ? "--restir-temporal cannot be combined with the display flags"
+           : o.gpus() > 1 ? "--restir-temporal cannot be combined with --gpus > 1" : !o.checkpoint.empty() ? "--restir-temporal cannot be combined with --checkpoint"
+           : !o.resume.empty() ? "--restir-temporal cannot be combined with --resume"
+           : o.haveRestirHistory && (o.restirHistory < 1 || o.restirHistory > static_cast<int>(MPT_RESTIR_TEMPORAL_MAX_HISTORY))
+               ? "--restir-history takes a count in 1..1024" : nullptr;
 }
 
 inline int refused(const char* sentence) {
@@ -474,6 +503,7 @@ inline int validate(const Options& o) {
     if (o.haveLightSampling && !o.nee && !o.haveDirect && !o.neeAdaptive) return refused("--light-sampling goes with --direct, --nee or --nee-adaptive");
     if (o.haveLightCandidates && (o.neeAdaptive ? o.lightCandidates > 1 : !o.nee && !o.haveDirect))
         return refused(o.neeAdaptive ? "--light-candidates above 1 cannot be combined with --nee-adaptive" : "--light-candidates goes with --direct or --nee");
+    if (const char* why = restirTemporalRefusal(o)) return refused(why);
     if (const char* why = restirRefusal(o)) return refused(why);
     for (const Check* c : {&kNeeCheck, &kDirectCheck, &kAoCheck, &kAdaptiveCheck, &kTemporalCheck, &kSvgfCheck})
         if (const int status = c->refuse(o)) return status;

@@ -354,6 +354,17 @@ int mpt_renderer_direct_restir(mpt_renderer* r, uint32_t samples, uint32_t neigh
         if (out) *out = info;
     });
 }
+int mpt_renderer_direct_restir_temporal(mpt_renderer* r, uint32_t frame, uint32_t max_history, int32_t mode, int32_t walk, float* rgba,
+                                        mpt_restir_temporal_info* out) {
+    if (!r || !rgba) return MPT_ERR_INVALID_ARG;
+    std::vector<float> img;
+    GUARD({
+        const mpt_restir_temporal_info info = r->r->drawDirectRestirTemporal(nullptr, frame, max_history, mode, walk);
+        r->r->readDirectRestirTemporal(img);
+        std::memcpy(rgba, img.data(), img.size() * sizeof(float));
+        if (out) *out = info;
+    });
+}
 int mpt_renderer_render_nee(mpt_renderer* r, uint32_t spp, int32_t depth, int32_t walk, float clamp, mpt_nee_info* out) {
     if (!r) return MPT_ERR_INVALID_ARG;
     GUARD({

@@ -264,9 +264,14 @@ static void playPathFrame(Renderer& r, OffscreenView& view, const Options& o, Di
     const char* ft = std::getenv("MPT_FRAME_TIMES");   // 1: the JSON line gains the host's milliseconds around render / read-back / file write
     const bool frameTimes = ft && std::atoi(ft);
     mpt_temporal_info ti = {};
+    mpt_restir_temporal_info ri = {};
     auto t0 = std::chrono::steady_clock::now();
     double renderMs = 0.0;
-    if (temporalSpp && o.svgf) {   // --svgf: the frame is the variance-filtered history
+    if (o.restirTemporal) {   // --direct 1 --restir-temporal: the frame is the direct pass's, its reservoirs merged with the frame's before
+        ri = r.drawDirectRestirTemporal(&view, static_cast<uint32_t>(frame), static_cast<uint32_t>(o.restirHistory), o.restirMode(), o.directWalk);
+        renderMs = msSince(t0);
+        r.readDirectRestirTemporal(view.rgba);
+    } else if (temporalSpp && o.svgf) {   // --svgf: the frame is the variance-filtered history
         const mpt_svgf_info si = r.drawSvgf(&view, temporalSpp);
         ti.pixels_reprojected = si.pixels_reprojected;
         ti.pixels_reset = si.pixels_reset;
@@ -304,6 +309,9 @@ static void playPathFrame(Renderer& r, OffscreenView& view, const Options& o, Di
     if (temporalSpp)
         tj += std::snprintf(temporalJson + tj, sizeof temporalJson - tj, ", \"reprojected\": %llu, \"reset\": %llu",
                             (unsigned long long)ti.pixels_reprojected, (unsigned long long)ti.pixels_reset);
+    if (o.restirTemporal)
+        tj += std::snprintf(temporalJson + tj, sizeof temporalJson - tj, ", \"accepted\": %llu, \"from_history\": %llu, \"reset\": %llu",
+                            (unsigned long long)ri.history_accepted, (unsigned long long)ri.samples_from_history, (unsigned long long)ri.pixels_reset);
     if (dp)
         tj += std::snprintf(temporalJson + tj, sizeof temporalJson - tj, ", \"scale\": %.9g, \"key_bin\": %lld, \"clipped\": %llu",
                             dp->info.scale, dp->info.key_bin == 0xFFFFFFFFu ? -1ll : (long long)dp->info.key_bin,
@@ -358,7 +366,8 @@ static Rendered runCameraPath(Renderer& r, OffscreenView& view, const Options& o
     }
     res.frames = playCameraPath(r, view, o, shown);
     if (res.frames < 0 || o.display) return res;   // (with the display flags: the last frame's bytes, which `shown` still holds)
-    if (o.svgf) r.readSvgf(view.rgba);
+    if (o.restirTemporal) r.readDirectRestirTemporal(view.rgba);
+    else if (o.svgf) r.readSvgf(view.rgba);
     else if (o.temporal && o.denoise) r.denoiseTemporal(o.dnp, view.rgba);   // the filtered history
     else if (o.temporal) r.readTemporal(view.rgba);
     else r.readFrame(&view);
@@ -507,6 +516,7 @@ int main(int argc, char** argv) {
         shown.params = o.shown;
         auto t0 = std::chrono::steady_clock::now();
         const auto run = o.ao > 0                            ? runAo
+                         : o.restirTemporal                  ? runCameraPath
                          : o.direct > 0                      ? runDirect
                          : o.adaptive || o.neeAdaptive       ? runAdaptive
                          : !o.cameraPath.empty()             ? runCameraPath

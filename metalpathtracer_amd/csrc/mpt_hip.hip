@@ -51,6 +51,7 @@
 #include "mpt_nee_adaptive.h"
 #include "mpt_ris.h"
 #include "mpt_restir.h"
+#include "mpt_restir_temporal.h"
 
 // =====================================================================================================
 // host side of the C ABI
@@ -293,6 +294,21 @@ struct RestirState {
     uint64_t epoch = 0;            // the guide_epoch the result was written in (0 = none)
 };
 
+// Temporal reservoir reuse (mpt_restir_temporal.h): the last frame's result block and, ping-pong as a History, every pixel's reservoir
+// with the guide and the camera of the frame it belongs to.  Not a History: that keeps 16 bytes per pixel and no result block; the
+// validity rule (stage_valid) and the camera key are the same.  Allocated by the first mpt_direct_restir_temporal; mpt_resize, the scene
+// calls and mpt_restir_temporal_reset let go of it.
+struct RestirTemporalState {
+    DevMem<float4> out;            // RestirPass::out of the last frame: W * H rgba, W * H traced, W * H unoccluded, the totals
+    DevMem<uint4> initial;         // the frame's reservoirs after step A
+    DevMem<uint4> res[2];          // two uint4 per pixel: (k, ua, ub, wsum) (fac, flags, Mh, 0)
+    DevMem<float4> guide[2];       // (normal facing the ray, t; +inf for a miss)
+    uint32_t W = 0, H = 0;
+    int cur = 0;                   // which of the two holds the history
+    uint64_t epoch = 0;            // the guide_epoch the history was written in (0 = no history)
+    float cam[14] = {};            // guide_key of the history's frame
+};
+
 // Next-event estimation (mpt_nee.h): what every mpt_render_nee call needs besides the sum — the four totals of mpt_nee_info on the device
 // and the pair of timing events.  Made by the first call, kept for the context's life (an allocation per call would cost a device
 // synchronisation each time).
@@ -397,6 +413,7 @@ struct mpt_ctx : SceneState {
     LightState lights;
     DirectState di;
     RestirState rs;
+    RestirTemporalState rt;
     NeeState nee;
     int32_t light_sampling = MPT_LIGHT_SAMPLING_AREA;   // mpt_set_light_sampling: host state, read at the start of the three calls that sample lights
     uint32_t light_candidates = 1u;                     // mpt_set_light_candidates: host state with the same life, read at the same three places
@@ -660,6 +677,7 @@ static void install_scene(mpt_ctx* ctx, SceneState&& s) {
     ctx->ao = AoState{};   // (an AO result belongs to the scene it was traced in)
     ctx->di = DirectState{};
     ctx->rs = RestirState{};
+    ctx->rt = RestirTemporalState{};
     ctx->lights = LightState{};   // (built again by the first call that needs it)
 }
 
@@ -753,6 +771,7 @@ static int resize_impl(mpt_ctx* ctx, uint32_t width, uint32_t height) {
     ctx->ao = AoState{};
     ctx->di = DirectState{};
     ctx->rs = RestirState{};
+    ctx->rt = RestirTemporalState{};
     ctx->W = width;
     ctx->H = height;
     ctx->cur_target = 0;

@@ -956,6 +956,233 @@ extern "C" int mpt_temporal_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const fl
     });
 }
 
+// ---- temporal reservoir reuse (mpt_restir_temporal.h; the specification is in include/mpt.h) -----------------------------------------
+// The spatial call's frame-to-frame counterpart.  It stands here, behind temporal accumulation, because it takes the camera arithmetic,
+// k_tp_pack and reset_state from there; the reservoirs, the totals and the result block are the spatial call's (restir_*_bytes, MPT_RS_*).
+struct RtResolved {
+    uint32_t M, C;
+    float normal_thr, depth_tol;
+};
+// The argument checks, in front of wait_impl: a refused call changes nothing and waits for nothing.
+static int rt_check(mpt_ctx* ctx, const mpt_restir_temporal_params* p, RtResolved& r) {
+    if (!p) return fail(ctx, MPT_ERR_INVALID_ARG, "null restir temporal params");
+    if (!walk_valid(p->walk)) return fail(ctx, MPT_ERR_INVALID_ARG, "restir temporal: bad walk");
+    if (p->mode != MPT_RESTIR_UNBIASED && p->mode != MPT_RESTIR_BIASED) return fail(ctx, MPT_ERR_INVALID_ARG, "restir temporal: bad mode");
+    if (p->max_history > MPT_RESTIR_TEMPORAL_MAX_HISTORY) return fail(ctx, MPT_ERR_INVALID_ARG, "restir temporal: max_history > 1024");
+    if (p->normal_threshold != p->normal_threshold || p->depth_tolerance != p->depth_tolerance)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "restir temporal: a threshold is NaN");
+    if (ctx->light_sampling == MPT_LIGHT_SAMPLING_CONE)
+        return fail(ctx, MPT_ERR_INVALID_ARG, "restir temporal: lights are sampled by area only (mpt_set_light_sampling is MPT_LIGHT_SAMPLING_CONE)");
+    r.M = ctx->light_candidates;   // (read at the start)
+    r.C = p->max_history ? p->max_history : MPT_RESTIR_TEMPORAL_DEFAULT_HISTORY;
+    r.normal_thr = p->normal_threshold > 0.0f ? p->normal_threshold : MPT_RESTIR_DEFAULT_NORMAL_THRESHOLD;
+    r.depth_tol = p->depth_tolerance > 0.0f ? p->depth_tolerance : MPT_RESTIR_DEFAULT_DEPTH_TOLERANCE;
+    return MPT_OK;
+}
+// One frame on ctx->stream over guides on the device, at the camera `key`, with the (built) light table: the counts and the totals
+// zeroed, then k_restir_initial and k_restir_temporal.  key_h = nullptr: no history (res_in and guide_in are not read).  out:
+// restir_out_bytes(W * H); initial, res_in, res_out: restir_res_bytes(W * H); the guides 16 bytes per pixel.
+static int rt_launch(mpt_ctx* ctx, uint32_t W, uint32_t H, const float4* ad, const float4* nc, const float key[14], const float* key_h,
+                     const mpt_restir_temporal_params* p, const RtResolved& r, float4* out, uint4* initial, const uint4* res_in, const float4* guide_in,
+                     uint4* res_out, float4* guide_out) {
+    RestirTemporalPass T = {};
+    RestirPass& P = T.base;
+    const size_t n = (size_t)W * H;
+    P.ad = ad;
+    P.nc = nc;
+    P.out = out;
+    P.n_pixels = W * H;
+    P.initial = initial;
+    HIPCHK(hipMemsetAsync(P.traced(), 0, n * 8 + MPT_RS_TOTAL_WORDS * 8, ctx->stream));
+    P.lights = ctx->lights.rec.get();
+    P.cdf = ctx->lights.cdf.get();
+    P.n_lights = ctx->lights.n();
+    const struct {
+        uint32_t sample_begin, sample_count, seed_lo, seed_hi;
+    } range = {p->frame, 1u, p->seed_lo, p->seed_hi};   // the frame is round 0 of a one-sample range that begins at its number
+    pass_frame(P, key, W, H, range);
+    P.M = r.M;
+    P.normal_threshold = r.normal_thr;
+    P.depth_tolerance = r.depth_tol;
+    T.res_in = res_in;
+    T.guide_in = guide_in;
+    T.res_out = res_out;
+    T.guide_out = guide_out;
+    T.cap = r.C * r.M;
+    T.mode = MPT_TP_NONE;
+    if (key_h) {   // (by the expressions of tp_frame_constants)
+        T.mode = memcmp(key, key_h, 14 * sizeof(float)) == 0 ? MPT_TP_SAME : MPT_TP_MOVED;
+        T.cam_h = RestirCamera{key_f3(key_h, KEY_CAM), key_f3(key_h, KEY_FIRST), key_f3(key_h, KEY_VU), key_f3(key_h, KEY_VV), (float)W, (float)H};
+        const F3 a = T.cam_h.vu, b = T.cam_h.vv;
+        T.nn = F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+        T.fc = F3{key_h[9] - key_h[0], key_h[10] - key_h[1], key_h[11] - key_h[2]};
+        T.fcnn = tp_dot(T.fc, T.nn);
+        T.uu = tp_dot(a, a);
+        T.vvl = tp_dot(b, b);
+    }
+    static const WalkKernel<RestirPass> initial_k[3] = {k_restir_initial<MPT_AO_REF>, k_restir_initial<MPT_AO_REF_ALL_LDS>, k_restir_initial<MPT_AO_OWN>};
+    static const WalkKernel<RestirTemporalPass> unbiased[3] = {k_restir_temporal<MPT_AO_REF, true>, k_restir_temporal<MPT_AO_REF_ALL_LDS, true>,
+                                                               k_restir_temporal<MPT_AO_OWN, true>},
+                                                biased[3] = {k_restir_temporal<MPT_AO_REF, false>, k_restir_temporal<MPT_AO_REF_ALL_LDS, false>,
+                                                             k_restir_temporal<MPT_AO_OWN, false>};
+    int rc = tile_walk_launch(ctx, W, H, p->walk, initial_k, P);
+    if (rc || (rc = tile_walk_launch(ctx, W, H, p->walk, p->mode == MPT_RESTIR_UNBIASED ? unbiased : biased, T))) return rc;
+    return MPT_OK;
+}
+// mpt_restir_temporal_info from the totals, MPT_RS_SLOTS times (mpt_restir.h)
+static void rt_info(const mpt_ctx* ctx, const unsigned long long* slots, float ms, mpt_restir_temporal_info* out) {
+    unsigned long long totals[MPT_RS_TOTALS] = {};
+    for (uint32_t s = 0; s < MPT_RS_SLOTS; ++s)
+        for (int k = 0; k < MPT_RS_TOTALS; ++k) totals[k] += slots[s * MPT_RS_SLOT_WORDS + k];
+    const unsigned long long traced = totals[MPT_RS_INITIAL] + totals[MPT_RS_FINAL] + totals[MPT_RS_CORRECTION];
+    out->pixels_surface = totals[MPT_RS_SURFACE];
+    out->rays_initial = totals[MPT_RS_INITIAL];
+    out->rays_final = totals[MPT_RS_FINAL];
+    out->rays_correction = totals[MPT_RS_CORRECTION];
+    out->rays_occluded = traced - totals[MPT_RS_UNOCCLUDED];
+    out->history_accepted = totals[MPT_RS_ACCEPTED];
+    out->samples_from_history = totals[MPT_RS_FROM_NEIGHBOUR];
+    out->pixels_reset = totals[MPT_RS_SURFACE] - totals[MPT_RS_ACCEPTED];
+    out->lights = ctx->lights.n();
+    out->device_ms = (double)ms;
+}
+static StageResult rt_result(const mpt_ctx* c) {
+    return stage_result(c, stage_valid(c, c->rt), c->rt.out.get(), 16, "no mpt_direct_restir_temporal result for this scene and size");
+}
+static int direct_restir_temporal_impl(mpt_ctx* ctx, const mpt_restir_temporal_params* p, mpt_restir_temporal_info* out) {
+    if (!ctx) return MPT_ERR_INVALID_ARG;
+    RtResolved r;
+    int rc = rt_check(ctx, p, r);
+    if (rc || (rc = settle_and_guide(ctx)) || (rc = ensure_lights(ctx))) return rc;
+    RestirTemporalState& s = ctx->rt;
+    const bool have = stage_valid(ctx, s);   // (asked before stage_run, which marks the state as being written)
+    float key_h[14];
+    memcpy(key_h, s.cam, sizeof key_h);
+    std::vector<unsigned long long> slots(MPT_RS_TOTAL_WORDS, 0ull);
+    float ms = 0.0f;
+    const size_t n = (size_t)ctx->W * ctx->H;
+    rc = stage_run(ctx, s, restir_out_bytes(n), slots.data(), MPT_RS_TOTAL_WORDS, out ? &ms : nullptr, [&](const float* key, float4* o) -> int {
+        if (!s.initial) {   // (stage_run has made a fresh state of this size)
+            int arc = scratch(ctx, restir_res_bytes(n), {&s.initial, &s.res[0], &s.res[1]});
+            if (arc || (arc = scratch(ctx, n * 16, {&s.guide[0], &s.guide[1]}))) return arc;
+            s.cur = 0;
+        }
+        return rt_launch(ctx, ctx->W, ctx->H, ctx->gd.ad.get(), ctx->gd.nc.get(), key, have ? key_h : nullptr, p, r, o, s.initial.get(),
+                         s.res[s.cur].get(), s.guide[s.cur].get(), s.res[s.cur ^ 1].get(), s.guide[s.cur ^ 1].get());
+    });
+    if (rc) return rc;
+    s.cur ^= 1;   // the frame's reservoirs are the history
+    guide_key(ctx->u, s.cam);
+    if (out) rt_info(ctx, slots.data(), ms, out);
+    return MPT_OK;
+}
+static int read_restir_temporal_impl(mpt_ctx* ctx, float* rgba, uint32_t* traced, uint32_t* unoccluded) {
+    if (!ctx || !rgba) return fail(ctx, MPT_ERR_INVALID_ARG, "null argument");
+    const StageResult r = rt_result(ctx);
+    int rc = need(ctx, r);
+    const size_t n = (size_t)ctx->W * ctx->H;
+    if (rc || (rc = copy_out(ctx, rgba, r.p, r.bytes)) || (rc = copy_out(ctx, traced, (const char*)r.p + n * 16, n * 4)) ||
+        (rc = copy_out(ctx, unoccluded, (const char*)r.p + n * 20, n * 4)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return MPT_OK;
+}
+// seven of a reservoir's eight words per pixel (RestirTemporalPass: the last one is padding), after the wait
+static int rt_words_out(mpt_ctx* ctx, const uint4* res, size_t n, uint32_t* out) {
+    std::vector<uint32_t> words(n * 8);
+    HIPCHK(hipMemcpyAsync(words.data(), res, n * 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < n; ++i) memcpy(out + 7 * i, &words[8 * i], 28);
+    return MPT_OK;
+}
+static int read_restir_temporal_reservoirs_impl(mpt_ctx* ctx, uint32_t* out) {
+    if (!ctx || !out) return fail(ctx, MPT_ERR_INVALID_ARG, "mpt_read_restir_temporal_reservoirs: null argument");
+    const int rc = need(ctx, rt_result(ctx));
+    if (rc) return rc;
+    return rt_words_out(ctx, ctx->rt.res[ctx->rt.cur].get(), (size_t)ctx->W * ctx->H, out);
+}
+static int restir_temporal_image_impl(mpt_ctx* ctx, uint32_t W, uint32_t H, const float* ad, const float* nc, const mpt_uniforms* cam, const float* ad_h,
+                                      const float* nc_h, const mpt_uniforms* cam_h, const uint32_t* res_h, const mpt_restir_temporal_params* p,
+                                      float* rgba_out, uint32_t* traced_out, uint32_t* unocc_out, uint32_t* res_out, mpt_restir_temporal_info* out) {
+    if (!ctx || !ad || !nc || !cam || !rgba_out || bad_image_size(W, H)) return fail(ctx, MPT_ERR_INVALID_ARG, "bad argument");
+    if (res_h && (!ad_h || !nc_h || !cam_h)) return fail(ctx, MPT_ERR_INVALID_ARG, "restir temporal: reservoirs without their guides or camera");
+    RtResolved r;
+    int rc = rt_check(ctx, p, r);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    if ((rc = ensure_lights(ctx))) return rc;
+    const size_t n = (size_t)W * H;
+    std::vector<uint32_t> words;
+    if (res_h) {   // seven words per pixel -> the two uint4; a light the table does not have would be read out of bounds
+        words.assign(n * 8, 0u);
+        for (size_t i = 0; i < n; ++i) {
+            memcpy(&words[8 * i], res_h + 7 * i, 28);
+            if ((words[8 * i + 5] & 1u) && words[8 * i] >= ctx->lights.n())
+                return fail(ctx, MPT_ERR_INVALID_ARG, "restir temporal: a reservoir holds a light the table does not have");
+        }
+    }
+    DevMem<float4> d_ad, d_nc, d_adh, d_nch, d_out, d_guide[2];
+    DevMem<uint4> d_initial, d_res[2];
+    HIPCHK(d_out.alloc(restir_out_bytes(n)));
+    if ((rc = scratch(ctx, restir_res_bytes(n), {&d_initial, &d_res[1]})) || (rc = scratch(ctx, n * 16, {&d_guide[1]})) ||
+        (rc = stage_in(ctx, d_ad, ad, n * 16)) || (rc = stage_in(ctx, d_nc, nc, n * 16)))
+        return rc;
+    float key[14], key_h[14];
+    guide_key(*cam, key);
+    if (res_h) {
+        if ((rc = scratch(ctx, n * 16, {&d_guide[0]})) || (rc = stage_in(ctx, d_res[0], words.data(), n * 32)) ||
+            (rc = stage_in(ctx, d_adh, ad_h, n * 16)) || (rc = stage_in(ctx, d_nch, nc_h, n * 16)))
+            return rc;
+        hipLaunchKernelGGL(k_tp_pack, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_adh.get(), d_nch.get(), (uint32_t)n, d_guide[0].get());
+        HIPCHK(hipGetLastError());
+        guide_key(*cam_h, key_h);
+    }
+    Event e0, e1;
+    HIPCHK(e0.create(hipEventCreate));
+    HIPCHK(e1.create(hipEventCreate));
+    HIPCHK(hipEventRecord(e0.get(), ctx->stream));
+    if ((rc = rt_launch(ctx, W, H, d_ad.get(), d_nc.get(), key, res_h ? key_h : nullptr, p, r, d_out.get(), d_initial.get(), d_res[0].get(),
+                        d_guide[0].get(), d_res[1].get(), d_guide[1].get())))
+        return rc;
+    HIPCHK(hipEventRecord(e1.get(), ctx->stream));
+    const char* o = (const char*)d_out.get();
+    std::vector<unsigned long long> slots(MPT_RS_TOTAL_WORDS, 0ull);
+    if ((rc = copy_out(ctx, rgba_out, o, n * 16)) || (rc = copy_out(ctx, traced_out, o + n * 16, n * 4)) ||
+        (rc = copy_out(ctx, unocc_out, o + n * 20, n * 4)) || (rc = copy_out(ctx, slots.data(), o + n * 24, MPT_RS_TOTAL_WORDS * 8)))
+        return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (res_out && (rc = rt_words_out(ctx, d_res[1].get(), n, res_out))) return rc;
+    if (out) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, e0.get(), e1.get()));
+        rt_info(ctx, slots.data(), ms, out);
+    }
+    return MPT_OK;
+}
+extern "C" int mpt_direct_restir_temporal(mpt_ctx* ctx, const mpt_restir_temporal_params* p, mpt_restir_temporal_info* out) {
+    return guarded(ctx, [&] { return direct_restir_temporal_impl(ctx, p, out); });
+}
+extern "C" int mpt_read_restir_temporal(mpt_ctx* ctx, float* rgba, uint32_t* traced, uint32_t* unoccluded) {
+    return guarded(ctx, [&] { return read_restir_temporal_impl(ctx, rgba, traced, unoccluded); });
+}
+extern "C" int mpt_restir_temporal_buffer(mpt_ctx* ctx, void** p, uint64_t* bytes) { return result_buffer(ctx, rt_result, p, bytes); }
+extern "C" int mpt_read_restir_temporal_reservoirs(mpt_ctx* ctx, uint32_t* out) {
+    return guarded(ctx, [&] { return read_restir_temporal_reservoirs_impl(ctx, out); });
+}
+extern "C" int mpt_restir_temporal_reset(mpt_ctx* ctx) {
+    return guarded(ctx, [&] { return reset_state(ctx, &mpt_ctx::rt); });
+}
+extern "C" int mpt_restir_temporal_image(mpt_ctx* ctx, uint32_t w, uint32_t h, const float* albedo_depth_cur, const float* normal_class_cur,
+                                         const mpt_uniforms* cam_cur, const float* albedo_depth_prev, const float* normal_class_prev,
+                                         const mpt_uniforms* cam_prev, const uint32_t* reservoirs_prev, const mpt_restir_temporal_params* p,
+                                         float* rgba_out, uint32_t* traced_out, uint32_t* unoccluded_out, uint32_t* reservoirs_out,
+                                         mpt_restir_temporal_info* out) {
+    return guarded(ctx, [&] {
+        return restir_temporal_image_impl(ctx, w, h, albedo_depth_cur, normal_class_cur, cam_cur, albedo_depth_prev, normal_class_prev, cam_prev,
+                                          reservoirs_prev, p, rgba_out, traced_out, unoccluded_out, reservoirs_out, out);
+    });
+}
+
 // ---- SVGF (mpt_svgf.h; the specification is in include/mpt.h) -------------------------------------------------------------------
 struct SvResolved {
     TpResolved tp;

@@ -26,7 +26,7 @@ SYMBOLS = (
     "mpt_write_ppm", "mpt_renderer_denoise", "mpt_renderer_render_adaptive",
     "mpt_renderer_draw_temporal", "mpt_renderer_read_temporal", "mpt_renderer_denoise_temporal",
     "mpt_renderer_draw_svgf", "mpt_renderer_read_svgf", "mpt_renderer_display", "mpt_write_ppm8",
-    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_direct_restir", "mpt_renderer_render_nee", "mpt_renderer_set_light_sampling",
+    "mpt_renderer_ambient_occlusion", "mpt_renderer_direct_lighting", "mpt_renderer_direct_restir", "mpt_renderer_direct_restir_temporal", "mpt_renderer_render_nee", "mpt_renderer_set_light_sampling",
     "mpt_renderer_render_nee_adaptive", "mpt_renderer_set_light_candidates", "mpt_renderer_get_light_candidates",
 )
 
@@ -88,6 +88,8 @@ def load():
     L.mpt_renderer_direct_lighting.argtypes = [vp, C.c_uint32, C.c_int32, C.POINTER(C.c_float), C.POINTER(capi.DirectInfo)]
     L.mpt_renderer_direct_restir.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
                                              C.POINTER(capi.RestirInfo)]
+    L.mpt_renderer_direct_restir_temporal.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_float),
+                                                      C.POINTER(capi.RestirTemporalInfo)]
     L.mpt_renderer_render_nee.argtypes = [vp, C.c_uint32, C.c_int32, C.c_int32, C.c_float, C.POINTER(capi.NeeInfo)]
     L.mpt_renderer_set_light_sampling.argtypes = [vp, C.c_int32]
     L.mpt_renderer_set_light_candidates.argtypes = [vp, C.c_uint32]
@@ -423,6 +425,17 @@ class Renderer:
         info = capi.RestirInfo()
         self._chk(self.L.mpt_renderer_direct_restir(self.h, int(samples), int(neighbours), int(radius), int(mode), int(walk), _fp(out),
                                                     C.byref(info)), "renderDirectRestir")
+        return out, info.as_dict()
+
+    def drawDirectRestirTemporal(self, frame, max_history=0, mode=capi.RESTIR_UNBIASED, walk=capi.WALK_AUTO):
+        """mpt_renderer_direct_restir_temporal: frame number `frame` of a camera path with the pending input() — one round of the direct
+        pass whose reservoirs are merged with the previous frame's, which count for at most `max_history` frames' candidates (0: the
+        default).  Returns (rgba [H, W, 4] float32; the mpt_restir_temporal_info as a dict)."""
+        u = self.uniforms()
+        out = np.empty((int(u.screenSize[1]), int(u.screenSize[0]), 4), np.float32)
+        info = capi.RestirTemporalInfo()
+        self._chk(self.L.mpt_renderer_direct_restir_temporal(self.h, int(frame), int(max_history), int(mode), int(walk), _fp(out), C.byref(info)),
+                  "drawDirectRestirTemporal")
         return out, info.as_dict()
 
     def renderNee(self, spp, depth, walk=capi.WALK_AUTO, clamp=0.0):
